@@ -208,9 +208,11 @@ def cpu_leg(rung: int, cpu_steps: int) -> dict:
 
 # ---- the GPU measurement of one rung ---------------------------------------------------------------------------------
 def measure(rung: int, cms: np.ndarray, *, envs: int, steps: int, warmup: int, rounds: int, groups: int, gather_kind: str,
-            rank: int, local_rank: int, world: int, dist, spec=None, generic: bool = False, specialize="auto") -> dict:
+            rank: int, local_rank: int, world: int, dist, spec=None, generic: bool = False, specialize="auto",
+            dump_dir: str | None = None) -> dict:
     """spec: another game on the rung's maps (the run-time specialisation leg); generic: the kernels any program gets — no
-    build-time preset instance, no generated handlers (MGX_NO_GEN / MGX_OBS_GENERIC at mgx_create), no run-time code objects."""
+    build-time preset instance, no generated handlers (MGX_NO_GEN / MGX_OBS_GENERIC at mgx_create), no run-time code objects;
+    dump_dir: write what the last timed step computed there (dump_outputs), on rank 0."""
     import torch
     from mettagrid_amd.compiler import compile_spec
     from mettagrid_amd.dist import GatherToRoot, shard_seeds
@@ -307,6 +309,8 @@ def measure(rung: int, cms: np.ndarray, *, envs: int, steps: int, warmup: int, r
     bits, first = grp.poll_errors()
     if bits:
         raise SystemExit(f"engine reported env error bits {bits} (first env {first})")
+    if dump_dir is not None and rank == 0:
+        dump_outputs(grp, dump_dir)
     per_round = []
     for i in range(rounds):
         n_i = bounds[i + 1] - bounds[i]
@@ -365,6 +369,42 @@ def measure(rung: int, cms: np.ndarray, *, envs: int, steps: int, warmup: int, r
                    "obs_tokens": T, "gather": gather_kind, "parallelism": f"env-shard x{world}",
                    "env_groups_per_gpu": G, "envs_per_launch": E // G},
     }
+
+
+DUMP_OBS_BYTES = 24 << 20   # float32 observation rows of the sampled envs
+DUMP_ROWS = 1 << 20          # per-agent arrays: every row up to this many (65 536 envs x 16 agents), else sampled envs
+
+
+def dump_outputs(grp, out_dir: str) -> None:
+    """What a caller of the timed path holds after its last step, as float32 DIR/<name>.npy (under 64 MB in all):
+    rewards, terminals, truncations, action_success and episode_rewards [rows] (row = env * A + agent), and the
+    observation tokens obs_sample [rows of the sampled envs, T, 3] — all envs would be E*A*T*3 bytes (629 MB at the
+    default size), so a fixed seeded sample of envs, listed in obs_envs (float64 env indices).  The per-agent arrays are
+    cut to sampled envs too (listed in row_envs) where E*A exceeds DUMP_ROWS."""
+    import torch
+    E, A, T = grp.E, grp.A, grp.T
+    rng = np.random.RandomState(0)
+    obs_envs = np.sort(rng.choice(E, min(E, max(1, DUMP_OBS_BYTES // (A * T * 3 * 4))), replace=False))
+    row_envs = np.arange(E) if E * A <= DUMP_ROWS else np.sort(rng.choice(E, DUMP_ROWS // A, replace=False))
+
+    def rows(envs):
+        return (envs[:, None] * A + np.arange(A)).ravel()
+
+    grp.sync()
+    torch.cuda.synchronize()
+    per_agent = {"rewards": grp.rewards.cpu().numpy(), "terminals": grp.terminals.cpu().numpy(),
+                 "truncations": grp.truncations.cpu().numpy(),
+                 "action_success": np.concatenate([eng.action_success() for eng in grp.engines]),
+                 "episode_rewards": np.concatenate([eng.episode_rewards() for eng in grp.engines])}
+    idx = torch.as_tensor(rows(obs_envs), device=grp.obs.device)
+    out = {k: v[rows(row_envs)] for k, v in per_agent.items()}
+    out["obs_sample"] = grp.obs.index_select(0, idx).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v.astype(np.float32))
+    np.save(os.path.join(out_dir, "obs_envs.npy"), obs_envs.astype(np.float64))
+    if E * A > DUMP_ROWS:
+        np.save(os.path.join(out_dir, "row_envs.npy"), row_envs.astype(np.float64))
 
 
 def env_wrapper_throughput(envs: int, steps: int, local_rank: int) -> dict:
@@ -489,10 +529,15 @@ def main() -> None:
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="headline only: skip the rung-4 object and the env-wrapper throughput")
     ap.add_argument("--rung4-steps", type=int, default=100)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of the headline, write what its last step computed as DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of the observations; rank 0's envs): same arguments, same inputs")
     ap.add_argument("--stub", action="store_true",
                     help="launcher self-test (tests/test_bench_launcher.py): the ranks rendezvous over gloo and do no GPU work; "
                          "rank 0 prints a line whose n_gpus is the communicator's size and whose value is null")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by hand: start the N ranks ourselves (what torch.distributed.run does for the driver).
@@ -540,7 +585,8 @@ def main() -> None:
             raise SystemExit(f"bench.py: --gpus {args.gpus} but the RCCL communicator has {dist.get_world_size()} ranks")
 
     common = dict(envs=args.envs, groups=args.groups, gather_kind=args.gather, rank=rank, local_rank=local_rank, world=world, dist=dist)
-    head = measure(args.rung, cms, steps=args.steps, warmup=args.warmup, rounds=args.rounds, **common)
+    head = measure(args.rung, cms, steps=args.steps, warmup=args.warmup, rounds=args.rounds, dump_dir=args.dump_outputs,
+                   **common)
     r4 = wrap = gen = jit_leg = long_run = None
     if extras:
         # the headline workload over the reference harness' protocol length whatever --steps says

@@ -118,6 +118,55 @@ def compare_snapshots(a: dict, b: dict, where: str) -> None:
             raise AssertionError(f"{where}: '{k}' differs.{detail}")
 
 
+SNAPSHOT_KEYS = ("obs", "rewards", "terminals", "truncations", "action_success", "episode_rewards")
+_DIGEST_DTYPES = {"obs": np.uint8, "rewards": np.float32, "terminals": np.uint8, "truncations": np.uint8,
+                  "action_success": np.uint8, "episode_rewards": np.float32}
+
+
+def snapshot_digests(snap: dict) -> np.ndarray:
+    """uint32 [6]: per caller-visible buffer (SNAPSHOT_KEYS order) the first 4 bytes of the SHA-256 of its shape and its
+    values in the engine's dtype, -0.0 folded into 0.0 so that equal digests mean what np.array_equal means.  The form in
+    which tests/golden/vs_reference/traces.npz holds the reference's per-step outputs."""
+    import hashlib
+    out = np.empty(len(SNAPSHOT_KEYS), np.uint32)
+    for i, k in enumerate(SNAPSHOT_KEYS):
+        v = np.ascontiguousarray(np.asarray(snap[k]).astype(_DIGEST_DTYPES[k]))
+        if v.dtype.kind == "f":
+            v = v + v.dtype.type(0.0)
+        h = hashlib.sha256(repr(v.shape).encode())
+        h.update(v.tobytes())
+        out[i] = int.from_bytes(h.digest()[:4], "little")
+    return out
+
+
+# initial inventories whose observation token order is libstdc++ unordered_map order (SURVEY.md §7.3.2)
+INVENTORY_ORDER = ({"a": 1, "d": 2, "b": 3}, {"d": 5, "c": 1, "a": 9, "b": 2}, {"b": 1}, {"c": 3, "a": 0, "d": 4})
+# (action, vibe action) of every agent per step: indices far outside the action table
+INVALID_INDEX_STEPS = ((1000, 0), (-500, 0), (1000, 2 ** 31 - 1), (None, -5))   # None: len(action_names) + 40
+INVALID_INDEX_SEED = 3
+
+
+def inventory_order_case(initial: dict):
+    """(spec, cells) of one INVENTORY_ORDER case: one agent and one box, both starting with ``initial``."""
+    spec = S.GameSpec(resource_names=["a", "b", "c", "d"],
+                      agents=[S.AgentSpec(inventory=S.Inventory(initial=dict(initial)))],
+                      objects={"wall": S.ObjectSpec("wall", kind="wall"),
+                               "box": S.ObjectSpec("box", inventory=S.Inventory(initial=dict(initial)))},
+                      obs=S.ObsSpec(5, 5, 60))
+    cells = np.array([["wall"] * 5, ["wall", "agent.agent", "box", "empty", "wall"], ["wall"] * 5])
+    return spec, cells
+
+
+def invalid_index_case():
+    """(spec, cells, prog, [(actions, vibe actions)] of INVALID_INDEX_STEPS) on rung 1, map seed 0."""
+    spec_f, map_f, _, _ = SCENARIOS["rung1"]
+    spec, cells = spec_f(), map_f(0)
+    prog = compile_scenario("rung1", spec, *cells.shape)
+    n, A = len(prog.action_names), prog.num_agents
+    steps = [(np.full(A, n + 40 if a is None else a, np.int32), np.full(A, v, np.int32)) for a, v in INVALID_INDEX_STEPS]
+    return spec, cells, prog, steps
+
+
 def payload_from_raw(prog, raw_objects, current_stat_reward, raw_stats, snap, steps, seed) -> dict:
     return sg.payload(sg.objects_from_raw(prog, raw_objects, current_stat_reward), sg.stats_dicts(prog, *raw_stats),
                       snap["action_success"], snap["episode_rewards"], steps, seed)
