@@ -311,6 +311,32 @@ int32_t mgx_dispatch_pairs(const mgx_engine* e);
  * them (mgx_get_stats, the episode records, mgx_state_digests) — chosen at mgx_create when no game value or mutation of the
  * program touches those stats.  0, 1 or 3.  Same results.  Diagnostic. */
 int32_t mgx_integer_bookkeeping(const mgx_engine* e);
+/* Every code path mgx_create chose for this program, one bit per choice (MGX_PATH_*); the environment switch named beside
+ * a bit forces its fallback side.  Same results on either side of every bit.  Diagnostic: reading it changes nothing. */
+enum {
+  MGX_PATH_X = 1 << 0,               /* extended kernels (= mgx_is_extended) */
+  MGX_PATH_PROG_LDS = 1 << 1,        /* world kernels copy the program into LDS; clear: read from HBM (MGX_PROG_LDS=0) */
+  MGX_PATH_AOE_LOCAL = 1 << 2,       /* extended: lane-per-agent area-effect kernel; clear: serial AoE in the world kernel
+                                        (MGX_AOE_SERIAL) */
+  MGX_PATH_TICK_IN_AOE = 1 << 3,     /* per-agent on_tick folded into the area-effect kernel (MGX_TICK_SERIAL) */
+  MGX_PATH_COV_IN_AOE = 1 << 4,      /* coverage tracking folded into the area-effect kernel (MGX_TICK_SERIAL) */
+  MGX_PATH_AOE_PROG_LDS = 1 << 5,    /* hot program range of the area-effect kernel in its LDS (MGX_AOE_PROG_HBM) */
+  MGX_PATH_X_AOE_LDS = 1 << 6,       /* extended world kernel stages the scratch of its in-kernel AoE phase */
+  MGX_PATH_FLAT_TOP = 1 << 7,        /* extended action-phase handlers on the register VM; clear: LDS VM (MGX_NO_FLAT_TOP) */
+  MGX_PATH_TICK_SPLIT = 1 << 8,      /* lean on_tick split over the helper lanes (MGX_NO_TICK_SPLIT) */
+  MGX_PATH_ACT_PAR = 1 << 9,         /* = mgx_act_variant 1 (MGX_ACT_SERIAL) */
+  MGX_PATH_DUO = 1 << 10,            /* = mgx_dispatch_pairs (MGX_NO_DUO) */
+  MGX_PATH_ACT_MAP = 1 << 11,        /* lane-per-agent dispatch keeps a cell map of the conflict lookup (MGX_ACT_NO_MAP) */
+  MGX_PATH_SHADOW = 1 << 12,         /* = mgx_integer_bookkeeping != 0 (MGX_NO_SHADOW) */
+  MGX_PATH_REWARDS_EARLY = 1 << 13,  /* lean reward expressions evaluated beside the token-cache phase */
+  MGX_PATH_REWARDS_MID = 1 << 14,    /* extended reward expressions evaluated during the encode phase (MGX_REWARDS_LATE) */
+  MGX_PATH_REWARDS_EXT = 1 << 15,    /* reward expressions with query operands: evaluated after the observation kernel */
+  MGX_PATH_OBS_512 = 1 << 16,        /* 512-thread observation kernel; clear: 256 threads (MGX_OBS_256) */
+  MGX_PATH_WORLD_LDS_64K = 1 << 17,  /* world kernel needs more than 64 KB of LDS (the opt-in attribute) */
+  MGX_PATH_GEN = 1 << 18,            /* = mgx_handler_variant != 0 (MGX_NO_GEN) */
+  MGX_PATH_COUNT = 19
+};
+int32_t mgx_create_paths(const mgx_engine* e);
 int32_t mgx_num_envs(const mgx_engine* e);
 int32_t mgx_num_agents(const mgx_engine* e);   /* per env */
 int32_t mgx_num_tokens(const mgx_engine* e);

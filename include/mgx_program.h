@@ -22,7 +22,13 @@
 
 #define MGX_MAX_RESOURCES 13 /* inventory order list = 4-bit ids in one u64, 0xF terminator; see DESIGN.md */
 #define MGX_TAG_WORDS 8      /* 256 tags = 8 x u32 (reference kMaxTags, core/types.hpp:62) */
-#define MGX_MAX_AGENTS 256
+#define MGX_MAX_AGENTS 254   /* per env: agent ids are u8 with 0xFF = none (the world kernel's LDS staging allows fewer) */
+#define MGX_MAX_OBJECT_SLOTS 65534 /* per env: the handler VM packs slot ids as (id + 2) & 0xFFFF */
+#define MGX_MAX_HANDLER_NESTING 6      /* VM frames of a handler chain (tree levels, + the move handler's levels for an
+                                          on_use / on_after_use tree reached by UseTarget): the LDS VM's MGX_VM_FRAMES */
+#define MGX_MAX_HANDLER_NESTING_REG 4  /* ... on the register VM (lean programs, extended flat_top): its four frames */
+#define MGX_VALUE_STACK 8              /* game-value expression stack (MgxValueStack) */
+#define MGX_MAX_QUERY_DEPTH 3          /* query nesting (the device's eval_query<3> at the top) */
 #define MGX_INVALID_WINDOW 16 /* action.invalid_index.<k> is a fixed stat column for k in [-16,-1] and [n_actions, n_actions+15] */
 #define MGX_INVALID_EXTRA 4   /* ... and one of this many (k, count) pairs per agent and episode for any other k */
 

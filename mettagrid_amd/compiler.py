@@ -156,6 +156,7 @@ class _Compiler:
         self.pending_class_refs: list = []
         self.query_depth = 0
         self._qdepth = 0          # nesting level of the query currently being emitted (filters/values inherit it)
+        self._hdepth: dict = {}   # handler index -> levels of its tree (leaf = 1)
         self.dynamic_tags = False
         self.tag_mutations = False       # AddTag / RemoveTag / RemoveTagsWithPrefix somewhere in the program
         # Records emitted once per distinct content: the reference's converter builds one config per agent
@@ -169,7 +170,7 @@ class _Compiler:
         if len(sp.resource_names) > K.MAX_RESOURCES:
             raise UnsupportedFeature(f"at most {K.MAX_RESOURCES} resources are supported (got {len(sp.resource_names)})")
         if len(sp.agents) == 0 or len(sp.agents) > K.MAX_AGENTS:
-            raise ValueError("need 1..256 agents")
+            raise ValueError(f"need 1..{K.MAX_AGENTS} agents")
         self.res_id = {n: i for i, n in enumerate(sp.resource_names)}
         vibes = list(sp.vibe_names)
         self.vibe_id = {n: i for i, n in enumerate(vibes)}
@@ -310,8 +311,8 @@ class _Compiler:
         for ins in code:
             depth += -1 if ins[0] in (K.GOP_ADD_TERM, K.GOP_RATIO, K.GOP_MAX2, K.GOP_MIN2) else 1
             peak = max(peak, depth)
-        if peak > 8:
-            raise UnsupportedFeature("game value expression nests deeper than 8 stack entries")
+        if peak > K.VALUE_STACK:
+            raise UnsupportedFeature(f"game value expression nests deeper than {K.VALUE_STACK} stack entries")
         start = self.counts[K.SEC_GV_CODE]
         for ins in code:
             self.emit(K.SEC_GV_CODE, ins)
@@ -334,6 +335,8 @@ class _Compiler:
 
     def _query(self, q, depth: int) -> int:
         self.query_depth = max(self.query_depth, depth)
+        if depth > K.MAX_QUERY_DEPTH:
+            raise UnsupportedFeature(f"queries nest deeper than {K.MAX_QUERY_DEPTH} levels")
         if isinstance(q, str):
             q = S.TagQuery(q)
         if isinstance(q, S.MaterializedQuery):
@@ -568,16 +571,23 @@ class _Compiler:
             mstart = self.counts[K.SEC_MUTS]
             for rec in muts:
                 self.emit(K.SEC_MUTS, (rec + [0, 0])[:K.MU_WORDS])
-            return self.emit(K.SEC_HANDLERS, [K.HK_LEAF, fpc, mstart, len(muts), 0, 0, 0, 0])
+            hid = self.emit(K.SEC_HANDLERS, [K.HK_LEAF, fpc, mstart, len(muts), 0, 0, 0, 0])
+            self._hdepth[hid] = 1
+            return hid
         if isinstance(h, (S.FirstMatch, S.AllOf)):
             kids = [k for k in (self.handler(c) for c in h.handlers) if k >= 0]
             if not kids:
                 return -1
+            depth = 1 + max(self._hdepth[k] for k in kids)
+            if depth > K.MAX_HANDLER_NESTING:   # (the engine's VM frames; UseTarget and tag handlers nest at run time)
+                raise UnsupportedFeature(f"handlers nest deeper than {K.MAX_HANDLER_NESTING} levels")
             cstart = self.counts[K.SEC_CHILDREN]
             for k in kids:
                 self.emit(K.SEC_CHILDREN, [k])
             kind = K.HK_FIRST_MATCH if isinstance(h, S.FirstMatch) else K.HK_ALL
-            return self.emit(K.SEC_HANDLERS, [kind, K.PC_PASS, 0, 0, cstart, len(kids), 0, 0])
+            hid = self.emit(K.SEC_HANDLERS, [kind, K.PC_PASS, 0, 0, cstart, len(kids), 0, 0])
+            self._hdepth[hid] = depth
+            return hid
         raise TypeError(f"Expected Handler, FirstMatch, or AllOf, got {type(h)}")
 
     # ---- inventory configs -----------------------------------------------------------------------------------
@@ -1071,8 +1081,8 @@ def compile_spec(spec: S.GameSpec, height: int, width: int, max_objects: int | N
     if height > 255 or width > 255:
         raise UnsupportedFeature("maps larger than 255x255 are not supported yet")
     slots = max_objects if max_objects is not None else height * width
-    if slots > 65535:
-        raise UnsupportedFeature("more than 65535 object slots")
+    if slots > K.MAX_OBJECT_SLOTS:
+        raise UnsupportedFeature(f"more than {K.MAX_OBJECT_SLOTS} object slots")
     h[K.H_MAX_OBJECTS] = slots
     words: list[int] = list(h)
     for s in range(K.SEC_COUNT):

@@ -683,10 +683,68 @@ int mgx_create(const int32_t* program, size_t program_words, const uint16_t* cla
       (size_t)program[MGX_H_TOTAL_WORDS] != program_words)
     return fail(MGX_ERR_PROGRAM, "mgx_create: not a version-" + std::to_string(MGX_VERSION) + " mgx program");
   const int32_t* P = program;
-  if (P[MGX_H_NUM_RESOURCES] > MGX_MAX_RESOURCES || P[MGX_H_NUM_AGENTS] >= 255 || P[MGX_H_HEIGHT] > 255 ||
+  if (P[MGX_H_NUM_RESOURCES] > MGX_MAX_RESOURCES || P[MGX_H_NUM_AGENTS] > MGX_MAX_AGENTS || P[MGX_H_HEIGHT] > 255 ||
       P[MGX_H_WIDTH] > 255 || P[MGX_H_NUM_AGENTS] < 1 || P[MGX_H_TOKEN_BASE] < 2 || P[MGX_H_TOKEN_BASE] > 256 ||
       P[MGX_H_NUM_TOKENS] < 1 || P[MGX_H_OBS_HEIGHT] > 15 || P[MGX_H_OBS_WIDTH] > 15)
     return fail(MGX_ERR_PROGRAM, "mgx_create: program exceeds engine limits (resources<=13, agents<255, map<=255x255)");
+  // the handler VM's context slots hold object slot ids as (id + 2) & 0xFFFF (mgx_world.h ctx_store): ids up to 65533
+  if (P[MGX_H_MAX_OBJECTS] < 1 || P[MGX_H_MAX_OBJECTS] > MGX_MAX_OBJECT_SLOTS)
+    return fail(MGX_ERR_PROGRAM, "mgx_create: max_objects must be 1.." + std::to_string(MGX_MAX_OBJECT_SLOTS));
+  // Nesting the device evaluates in fixed storage: queries (eval_query<3>), the game-value stack (MgxValueStack) and the
+  // levels of a handler tree (VM frames; the register VM has fewer, settled below once the kernels are known).
+  if (P[MGX_H_QUERY_DEPTH] > MGX_MAX_QUERY_DEPTH)
+    return fail(MGX_ERR_PROGRAM, "mgx_create: queries nest deeper than " + std::to_string(MGX_MAX_QUERY_DEPTH) + " levels");
+  {
+    const int n_code = mgx_sec_cnt(P, MGX_SEC_GV_CODE);
+    const int32_t* code = P + mgx_sec_off(P, MGX_SEC_GV_CODE);
+    auto stack_ok = [&](int start, int count) {
+      if (start < 0 || count < 0 || start + count > n_code) return false;
+      int depth = 0;
+      for (int i = start; i < start + count; i++) {
+        const int op = code[i * MGX_GV_WORDS + MGX_GV_OP];
+        depth += (op == MGX_GOP_ADD_TERM || op == MGX_GOP_RATIO || op == MGX_GOP_MAX2 || op == MGX_GOP_MIN2) ? -1 : 1;
+        if (depth > MGX_VALUE_STACK) return false;
+      }
+      return true;
+    };
+    bool ok = true;
+    for (int k = 0; k < mgx_sec_cnt(P, MGX_SEC_OBS_VALUES) && ok; k++) {
+      const int32_t* V = P + mgx_sec_off(P, MGX_SEC_OBS_VALUES) + k * MGX_OV_WORDS;
+      ok = stack_ok(V[MGX_OV_GV_START], V[MGX_OV_GV_COUNT]);
+    }
+    for (int k = 0; k < mgx_sec_cnt(P, MGX_SEC_REWARDS) && ok; k++) {
+      const int32_t* R = P + mgx_sec_off(P, MGX_SEC_REWARDS) + k * MGX_RW_WORDS;
+      ok = stack_ok(R[MGX_RW_GV_START], R[MGX_RW_GV_COUNT]);
+    }
+    if (!ok)
+      return fail(MGX_ERR_PROGRAM, "mgx_create: a game value expression needs more than " + std::to_string(MGX_VALUE_STACK) + " stack entries");
+  }
+  int hnest = 0;   // VM frames the deepest handler tree needs (children are laid out before their parent)
+  {
+    const int n_hd = mgx_sec_cnt(P, MGX_SEC_HANDLERS);
+    std::vector<int> lv(n_hd, 1);
+    for (int h = 0; h < n_hd; h++) {
+      const int32_t* hd = P + mgx_sec_off(P, MGX_SEC_HANDLERS) + h * MGX_HD_WORDS;
+      if (hd[MGX_HD_KIND] != MGX_HK_LEAF)
+        for (int i = 0; i < hd[MGX_HD_CHILD_COUNT]; i++) {
+          const int k = P[mgx_sec_off(P, MGX_SEC_CHILDREN) + hd[MGX_HD_CHILD_START] + i];
+          lv[h] = std::max(lv[h], k >= 0 && k < h ? lv[k] + 1 : MGX_MAX_HANDLER_NESTING + 1);
+        }
+      hnest = std::max(hnest, lv[h]);
+    }
+    // an on_use / on_after_use tree runs on frames above the move handler whose UseTarget reached it
+    auto level = [&](int h) { return h >= 0 && h < n_hd ? lv[h] : 0; };
+    int mv = 0, use = 0;
+    for (int k = 0; k < P[MGX_H_NUM_MOVE_HANDLERS]; k++)
+      mv = std::max(mv, level(P[mgx_sec_off(P, MGX_SEC_MOVE_HANDLERS) + k * MGX_MH_WORDS + MGX_MH_HANDLER]));
+    for (int c = 0; c < P[MGX_H_NUM_CLASSES]; c++) {
+      const int32_t* C = P + mgx_sec_off(P, MGX_SEC_CLASSES) + c * MGX_C_WORDS;
+      use = std::max(use, std::max(level(C[MGX_C_ON_USE]), level(C[MGX_C_ON_AFTER_USE])));
+    }
+    if (use > 0) hnest = std::max(hnest, mv + use);
+    if (hnest > MGX_MAX_HANDLER_NESTING)
+      return fail(MGX_ERR_PROGRAM, "mgx_create: handlers nest deeper than " + std::to_string(MGX_MAX_HANDLER_NESTING) + " levels");
+  }
   {
     const size_t hw = (size_t)P[MGX_H_HEIGHT] * P[MGX_H_WIDTH];
     for (size_t i = 0; i < (size_t)num_envs * hw; i++)
@@ -773,6 +831,24 @@ int mgx_create(const int32_t* program, size_t program_words, const uint16_t* cla
     e->aoe_local = mgx_aoe_is_target_local(P) && !getenv("MGX_AOE_SERIAL");
     d.X = (any_aoe || d.NT > 0 || d.n_schedule > 0 || d.n_matq > 0 || d.game_on_tick >= 0 || P[MGX_H_DYNAMIC_TAGS] ||
            mgx_sec_cnt(P, MGX_SEC_QUERIES) > 0) ? 1 : 0;
+  }
+  {  // The world kernel stages per agent and env 17 B (lean, 64 envs per workgroup) or 15 B (extended, 32 envs), plus per
+     // env 144 B of VM words and, when the AoE phase runs in the world kernel, 176 B of scratch (extended) — at most 160 KB:
+     // the agents an env may have depend on the program.  Refused here, before anything is allocated (the size is settled
+     // below, where the program copy is added only when it fits).
+    const bool aoe_lds = d.X && !(e->aoe_local && (d.NF > 0 || d.NM > 0 || d.NT > 0));
+    const size_t lds = d.X ? mgx_world_x_lds_bytes(d.A, aoe_lds) : mgx_world_fast_lds_bytes(d.A);
+    if (!d.X && hnest > MGX_MAX_HANDLER_NESTING_REG) {   // lean programs run every handler on the register VM
+      mgx_destroy(e);
+      return fail(MGX_ERR_PROGRAM, "mgx_create: handlers of a lean program nest deeper than " +
+                                       std::to_string(MGX_MAX_HANDLER_NESTING_REG) + " levels (the register VM's frames)");
+    }
+    if (lds > 160 * 1024) {
+      mgx_destroy(e);
+      return fail(MGX_ERR_PROGRAM, "mgx_create: " + std::to_string(d.A) + " agents per env are too many for the " +
+                                       (d.X ? "extended" : "lean") + " world kernel's LDS staging (" + std::to_string(lds) +
+                                       " B > 160 KB per workgroup)");
+    }
   }
   const size_t E = d.E, HW = (size_t)d.H * d.W, S = d.S, A = d.A, rows = E * A;
   int rc = MGX_OK;
@@ -1029,7 +1105,7 @@ int mgx_create(const int32_t* program, size_t program_words, const uint16_t* cla
     d.shadow = !counters ? 0 : coverage ? 3 : 1;   // (settled below, once the dispatch is known)
   }
   if (d.X) {  // can the action phase's top-level handlers run on the register VM?  (mgx_world.h apply_top)
-    bool flat = !getenv("MGX_NO_FLAT_TOP");
+    bool flat = !getenv("MGX_NO_FLAT_TOP") && hnest <= MGX_MAX_HANDLER_NESTING_REG;   // (the register VM has four frames)
     const int n_atoms = mgx_sec_cnt(P, MGX_SEC_ATOMS);
     std::vector<char> hseen(mgx_sec_cnt(P, MGX_SEC_HANDLERS), 0);
     std::vector<int> todo;
@@ -1302,8 +1378,8 @@ int mgx_create(const int32_t* program, size_t program_words, const uint16_t* cla
       if (arc != MGX_OK) { mgx_destroy(e); return arc; }
     }
   }
-  // The world kernel stages 17 (+ extended: 176) bytes per agent and env in LDS, 64 envs per workgroup: up to 160 KB,
-  // i.e. about 147 agents per env in the lean variant.  Past 64 KB the kernels need the opt-in attribute.
+  // The world kernel's LDS staging (see above): up to 160 KB, i.e. 148 agents per env in the lean variant (refused above
+  // already).  Past 64 KB the kernels need the opt-in attribute.
   if (e->lds_world > 160 * 1024) {
     mgx_destroy(e);
     return fail(MGX_ERR_PROGRAM, "mgx_create: too many agents per env for the world kernel's LDS staging (160 KB per 64 envs)");
@@ -2389,6 +2465,33 @@ int32_t mgx_world_prog_in_lds(const mgx_engine* e) { return e && e->prog_in_lds 
 int32_t mgx_is_extended(const mgx_engine* e) { return e && e->d.X ? 1 : 0; }
 int32_t mgx_dispatch_pairs(const mgx_engine* e) { return e && e->d.duo ? 1 : 0; }
 int32_t mgx_integer_bookkeeping(const mgx_engine* e) { return e ? e->d.shadow : 0; }
+int32_t mgx_create_paths(const mgx_engine* e) {
+  if (!e) return 0;
+  const MgxDev& d = e->d;
+  const bool aoe_kernel = d.X && e->aoe_local && (d.NF > 0 || d.NM > 0 || d.NT > 0);   // (mgx_create: `split`)
+  int32_t p = 0;
+  auto set = [&](int bit, bool on) { if (on) p |= bit; };
+  set(MGX_PATH_X, d.X != 0);
+  set(MGX_PATH_PROG_LDS, e->prog_in_lds);
+  set(MGX_PATH_AOE_LOCAL, aoe_kernel);
+  set(MGX_PATH_TICK_IN_AOE, d.tick_in_aoe != 0);
+  set(MGX_PATH_COV_IN_AOE, d.cov_in_aoe != 0);
+  set(MGX_PATH_AOE_PROG_LDS, aoe_kernel && e->aoe_prog_lds);
+  set(MGX_PATH_X_AOE_LDS, d.x_aoe_lds != 0);
+  set(MGX_PATH_FLAT_TOP, d.X && d.flat_top);
+  set(MGX_PATH_TICK_SPLIT, d.tick_split != 0);
+  set(MGX_PATH_ACT_PAR, d.act_par != 0);
+  set(MGX_PATH_DUO, d.duo != 0);
+  set(MGX_PATH_ACT_MAP, d.act_par && d.act_map);
+  set(MGX_PATH_SHADOW, d.shadow != 0);
+  set(MGX_PATH_REWARDS_EARLY, e->rewards_early);
+  set(MGX_PATH_REWARDS_MID, e->rewards_mid);
+  set(MGX_PATH_REWARDS_EXT, e->rewards_ext);
+  set(MGX_PATH_OBS_512, e->obs_threads == 512);
+  set(MGX_PATH_WORLD_LDS_64K, e->lds_world > 64 * 1024);
+  set(MGX_PATH_GEN, d.gen_prog != 0);
+  return p;
+}
 int32_t mgx_num_envs(const mgx_engine* e) { return e ? e->d.E : 0; }
 int32_t mgx_num_agents(const mgx_engine* e) { return e ? e->d.A : 0; }
 int32_t mgx_num_tokens(const mgx_engine* e) { return e ? e->d.T : 0; }

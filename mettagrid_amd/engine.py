@@ -97,13 +97,20 @@ def load_lib():
         L.mgx_pack_result.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i32), vp]
         L.mgx_unpack_rows.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     for name in ("mgx_num_envs", "mgx_num_agents", "mgx_num_tokens", "mgx_obs_variant", "mgx_act_variant", "mgx_handler_variant",
-                 "mgx_world_prog_in_lds", "mgx_is_extended", "mgx_dispatch_pairs", "mgx_integer_bookkeeping"):
+                 "mgx_world_prog_in_lds", "mgx_is_extended", "mgx_dispatch_pairs", "mgx_integer_bookkeeping",
+                 "mgx_create_paths"):
         getattr(L, name).argtypes = [vp]
         getattr(L, name).restype = i32
     L.mgx_state_bytes.argtypes = [vp]
     L.mgx_state_bytes.restype = i64
     _lib = L
     return L
+
+
+# bit i of mgx_create_paths (include/mgx.h MGX_PATH_*, in bit order)
+PATH_BITS = ("X", "prog_lds", "aoe_local", "tick_in_aoe", "cov_in_aoe", "aoe_prog_lds", "x_aoe_lds", "flat_top", "tick_split",
+             "act_par", "duo", "act_map", "shadow", "rewards_early", "rewards_mid", "rewards_ext", "obs_512", "world_lds_64k",
+             "gen")
 
 
 def exported_symbols() -> list:
@@ -688,6 +695,13 @@ class BatchedMettaGrid:
     def integer_bookkeeping(self) -> int:
         """1: the per-action bookkeeping counters live as integers beside the stat rows (written into them before any read)."""
         return int(self.L.mgx_integer_bookkeeping(self.h))
+
+    @property
+    def paths(self) -> dict:
+        """Every code path mgx_create chose for this program (include/mgx.h MGX_PATH_*): {name: bool}, names in
+        PATH_BITS.  Diagnostic; the results are the same on either side of every entry."""
+        bits = int(self.L.mgx_create_paths(self.h))
+        return {name: bool(bits >> i & 1) for i, name in enumerate(PATH_BITS)}
 
     @property
     def state_bytes(self) -> int:

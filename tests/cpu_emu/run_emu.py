@@ -5,7 +5,8 @@ after another (tests/cpu_emu/hip/hip_runtime.h).  It has NO observation kernel (
 compared after every step is the world state: every object (class, position, vibe, inventory in iteration order, tags),
 every stat key/value except the ones the observation phase writes, and action_success.
 
-  python tests/cpu_emu/run_emu.py [scenario ...]        (default: all scenarios of tests/helpers.py)
+  python tests/cpu_emu/run_emu.py [scenario ...]        (default: all scenarios of tests/helpers.py SCENARIOS; the
+                                                         names of LIMIT_SCENARIOS are accepted too)
 """
 from __future__ import annotations
 
@@ -68,7 +69,7 @@ def compare(prog, a: dict, b: dict, where: str) -> None:
 
 
 def run(name: str, E: int = 3, steps=None) -> None:
-    spec_f, map_f, nsteps, invalid = hp.SCENARIOS[name]
+    spec_f, map_f, nsteps, invalid = hp.scenario(name)
     steps = nsteps if steps is None else steps
     spec = spec_f()
     maps = [map_f(s) for s in range(E)]

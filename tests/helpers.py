@@ -545,3 +545,300 @@ def reference_infos(prog, o) -> dict:
         agent[n] = v / A
     return {"game": sd["game"], "agent": agent, "per_agent": {str(i): dict(s) for i, s in enumerate(sd["agent"])},
             "episode_rewards": o.snapshot()["episode_rewards"], "steps": o.current_step}
+
+
+# ---- capacity limits (tests/test_gpu_limits.py, tests/test_gpu_paths.py, tests/cpu_emu/run_emu.py) ----------------------
+# Kept apart from SCENARIOS so that the parametrised suites above do not multiply over them.  Every number here is the
+# largest size mgx_create accepts for that program; one more is refused (test_gpu_limits.py).
+LEAN_MAX_AGENTS = 148   # rung-3 rules: the lean world kernel's LDS staging (17 B per agent and env, 64 envs per workgroup)
+EXT_MAX_AGENTS = 254    # rung-4 rules: MGX_MAX_AGENTS (the extended kernel stages 32 envs per workgroup: 126 528 B here)
+MAP_MAX_DEFAULT = 98    # largest square map at the default max_objects = H*W (observation kernel's LDS staging)
+MAX_SLOTS_AT_255 = 1863   # the most object slots the observation kernel's LDS staging takes at 255x255 (rung-3 rules)
+MAP_MAX_FEW = (255, 255)   # with a small explicit max_objects the cell count binds: the largest map accepted
+MAP_FEW_OBJECTS = 64
+
+
+def teams_spec(base: S.GameSpec, n: int, teams: int) -> S.GameSpec:
+    """``base`` with ``n`` agents spread over its first ``teams`` teams (copies of each team's first agent)."""
+    import copy
+    firsts = []
+    for a in base.agents:
+        if a.team_id not in [f.team_id for f in firsts]:
+            firsts.append(a)
+    firsts = firsts[:teams]
+    per = [n // teams + (1 if i < n % teams else 0) for i in range(teams)]
+    base.agents = [copy.deepcopy(firsts[t]) for t in range(teams) for _ in range(per[t])]
+    return base
+
+
+def team_counts(n: int, names: list) -> dict:
+    return {name: n // len(names) + (1 if i < n % len(names) else 0) for i, name in enumerate(names)}
+
+
+def lean_agents_spec(n: int = 0) -> S.GameSpec:
+    return teams_spec(presets.rung3_spec(), n or LEAN_MAX_AGENTS, 2)
+
+
+def lean_agents_map(seed: int, n: int = 0) -> np.ndarray:
+    return random_map(40, 40, {"wall": 60, "extractor": 30, "chest": 12}, team_counts(n or LEAN_MAX_AGENTS, ["red", "blue"]), seed)
+
+
+def ext_agents_spec(n: int = 0) -> S.GameSpec:
+    sp = teams_spec(presets.rung4_spec(), n or EXT_MAX_AGENTS, 4)
+    sp.obs.width = sp.obs.height = 5   # (crowded: a wider window overflows the token budget, an error in the reference)
+    return sp
+
+
+def ext_agents_map(seed: int, n: int = 0) -> np.ndarray:
+    objs = {k: max(1, v // 4) for k, v in presets.RUNG4_OBJECTS.items()}
+    return random_map(56, 56, objs, team_counts(n or EXT_MAX_AGENTS, presets.RUNG4_TEAMS), seed)
+
+
+def edge_map(height: int, width: int, seed: int) -> np.ndarray:
+    """Rung-3 cells on a borderless ``height`` x ``width`` map: the 16 agents on the four corners, the last row and the
+    last column (so that moves run into the map's edge), extractors and chests beside them, a few walls."""
+    rng = np.random.RandomState(seed)
+    g = np.full((height, width), "empty", dtype="<U50")
+    H, W = height - 1, width - 1
+    spots = [(0, 0), (0, W), (H, 0), (H, W), (H, W // 2), (H, W - 2), (H, 2), (H // 2, W), (H - 2, W), (2, W),
+             (H, W // 3), (H // 3, W), (H - 1, W - 1), (0, W // 2), (H // 2, 0), (H - 1, 1)]
+    order = rng.permutation(len(spots))
+    for k, i in enumerate(order):
+        g[spots[i]] = "agent.red" if k < 8 else "agent.blue"
+    for r, c, name in ((H, W - 1, "extractor"), (H - 1, W, "chest"), (H, 1, "extractor"), (1, W, "chest"),
+                       (H - 1, W // 2, "extractor"), (H // 2, W - 1, "wall"), (H - 2, W - 1, "wall")):
+        if g[r, c] == "empty":
+            g[r, c] = name
+    return g
+
+
+WINDOW15_FULL = (58, 21)   # (env, step) of run_parity where an agent's observation fills the whole budget
+
+
+def window15_spec() -> S.GameSpec:
+    """Rung-3 rules through the largest window (15x15): row offsets up to 14 in the packed location byte, 225 cells per
+    agent, and a token budget of 185 — not a multiple of four (ragged row tail) and exactly the most tokens any agent of
+    run_parity's 65 envs is given (env 58 at step 21: the last token lands in the last slot).  One more token is an
+    error in the reference (mettagrid_c.cpp throws), not a drop: tokens_dropped stays 0."""
+    sp = teams_spec(presets.rung3_spec(), 12, 2)
+    sp.obs = S.ObsSpec(width=15, height=15, num_tokens=185)
+    return sp
+
+
+def window15_map(seed: int) -> np.ndarray:
+    return random_map(14, 14, {"wall": 30, "extractor": 12, "chest": 8}, {"red": 6, "blue": 6}, seed)
+
+
+def ceiling_spec(base: int) -> S.GameSpec:
+    """Inventories at the uint16_t ceiling (core/types.hpp InventoryQuantity): limits of 65535, deltas and transfers
+    that overshoot above 65535 or below 0, and observation values of 65535 in token value base ``base``."""
+    A, T = S.ACTOR, S.TARGET
+    big = S.Inventory(initial={"gold": 65530, "dust": 3, "ore": 65535}, default_limit=65535,
+                      limits=[S.Limit(["gold"], base=65535), S.Limit(["dust"], base=60000, max=65535, modifiers={"ore": 1})])
+    agent_use = S.FirstMatch([
+        S.Handler([S.ResourceFilter(A, "gold", 65535)], [S.ResourceDelta(A, "gold", -70000), S.ResourceDelta(T, "dust", 65535)], "drain"),
+        S.Handler([], [S.ResourceTransfer(T, A, "gold", 40000), S.ResourceTransfer(A, T, "dust", 65535)], "swap_goods"),
+    ])
+    return S.GameSpec(
+        resource_names=["gold", "dust", "ore"],
+        agents=[S.AgentSpec(team_id=0, inventory=big, on_use=agent_use,
+                            rewards=[S.RewardSpec(S.InventoryValue("gold")), S.RewardSpec(S.InventoryValue("dust"), per_tick=True)])
+                for _ in range(4)],
+        objects={
+            "wall": S.ObjectSpec("wall", kind="wall"),
+            "vault": S.ObjectSpec("vault", inventory=S.Inventory(initial={"gold": 65535, "ore": 65535}, default_limit=65535),
+                                  on_use=S.Handler([], [S.ResourceTransfer(T, A, "gold", 65535), S.ResourceDelta(A, "ore", 65535),
+                                                        S.ResourceDelta(T, "gold", 65535)], "loot")),
+            "sink": S.ObjectSpec("sink", inventory=S.Inventory(initial={"dust": 1}, default_limit=65535),
+                                 on_use=S.Handler([], [S.ResourceTransfer(A, T, "gold", 65535), S.ResourceDelta(A, "dust", -65535),
+                                                       S.ResourceDelta(A, "ore", 70000)], "dump")),
+        },
+        move_directions=["north", "south", "west", "east"],
+        obs=S.ObsSpec(width=5, height=5, num_tokens=600 if base == 2 else 300, token_value_base=base),
+        max_steps=0)
+
+
+def ceiling_map(seed: int) -> np.ndarray:
+    return random_map(7, 8, {"wall": 2, "vault": 5, "sink": 4}, 4, seed)
+
+
+def tags_spec(on_class: int = 63) -> S.GameSpec:
+    """More than 64 unique tags (ids past 63 and across the 31/32 and 63/64 tag-word boundaries) reaching Tag /
+    TagPrefix / SharedTagPrefix filters and observations, and ``on_class`` tags on one class (63 = the most one class
+    may carry)."""
+    A, T = S.ACTOR, S.TARGET
+    names = [f"t{i:03d}" for i in range(90)]
+    pillar_tags = names[:on_class - 1]   # + the type tag every class carries (type:pillar)
+    agent_use = S.FirstMatch([
+        S.Handler([S.SharedTagPrefixFilter("z:")], [S.ResourceDelta(T, "ore", 1)], "shared_z"),
+        S.Handler([S.TagPrefixFilter(T, "y:")], [S.ResourceDelta(A, "ore", 2)], "prefix_y"),
+    ])
+    pillar_use = S.FirstMatch([
+        S.Handler([S.TagPrefixFilter(T, "t08")], [S.ResourceDelta(A, "ore", 3)], "t08x"),   # t080..t089: ids past 63
+        S.Handler([S.TagPrefixFilter(A, "z:")], [S.ResourceDelta(A, "gem", 1)], "z_agent"),
+    ])
+    return S.GameSpec(
+        resource_names=["ore", "gem"],
+        agents=[S.AgentSpec(team_id=0, tags=["z:a", "t031", "t032", "t063", "t064"], on_use=agent_use,
+                            inventory=S.Inventory(initial={"ore": 1})),
+                S.AgentSpec(team_id=1, tags=["z:a", "y:b", "t085"], on_use=agent_use),
+                S.AgentSpec(team_id=2, tags=["y:c", "t089"], on_use=agent_use)],
+        objects={"wall": S.ObjectSpec("wall", kind="wall"),
+                 "pillar": S.ObjectSpec("pillar", tags=pillar_tags, on_use=pillar_use),
+                 "post": S.ObjectSpec("post", tags=["t080", "t081", "t070", "y:post"], on_use=pillar_use)},
+        tags=names + ["z:a", "y:b", "y:c", "y:post"],
+        move_directions=["north", "south", "west", "east"],
+        obs=S.ObsSpec(width=7, height=7, num_tokens=800),
+        max_steps=0)
+
+
+def tags_map(seed: int) -> np.ndarray:
+    from mettagrid_amd.mapgen import random_map as rm
+    return rm(9, 10, {"wall": 4, "pillar": 4, "post": 4}, {"team_0": 1, "team_1": 1, "team_2": 1}, seed)
+
+
+def nested_handler(levels: int, tag: str = "n") -> object:
+    """A handler tree of exactly ``levels`` levels, FirstMatch and AllOf alternating, whose deepest leaf runs whenever the
+    actor holds fewer gems than the level's gate (so that random play reaches every level)."""
+    A, T = S.ACTOR, S.TARGET
+    if levels == 1:
+        return S.Handler([], [S.ResourceDelta(A, "ore", 1), S.ResourceDelta(T, "ore", -1)], f"{tag}_leaf")
+    inner = nested_handler(levels - 1, tag)
+    if levels % 2:
+        return S.AllOf([S.Handler([], [S.ResourceDelta(A, "gem", 1)], f"{tag}_add{levels}"), inner])
+    return S.FirstMatch([S.Handler([S.ResourceFilter(A, "gem", 3 + levels)], [S.ResourceDelta(A, "gem", -levels)], f"{tag}_gate{levels}"),
+                         inner])
+
+
+def stack_value(peak: int):
+    """A game value whose evaluation needs exactly ``peak`` stack entries (nested SumValues around an inventory read)."""
+    v = S.InventoryValue("ore")
+    for i in range(peak - 1):
+        v = S.SumValue([S.InventoryValue("gem"), v], [1.0, 0.5 + 0.125 * (i % 3)])
+    return v
+
+
+def query_of_depth(depth: int):
+    """A query nested exactly ``depth`` levels (FilteredQuery around FilteredQuery ... around a TagQuery)."""
+    T = S.TARGET
+    q = S.TagQuery("type:box")
+    for i in range(depth - 1):
+        q = S.FilteredQuery(q, [S.ResourceFilter(T, "ore", 1 + i)])
+    return q
+
+
+def nesting_spec(levels: int = 6, extended: bool = True, peak: int = 8, qdepth: int = 0) -> S.GameSpec:
+    """Boxes whose on_use is a handler tree of ``levels`` levels (run on ``levels`` + 1 VM frames: the move handler whose
+    UseTarget reaches it takes the first); a reward, an observation value and a GameValueFilter that
+    need ``peak`` value-stack entries; ``extended``: a timestep event (extended kernels); ``qdepth``: an observation value,
+    a per-tick reward and an event target that are queries nested ``qdepth`` levels."""
+    A, T = S.ACTOR, S.TARGET
+    deep = stack_value(peak)
+    box_use = S.FirstMatch([
+        S.Handler([S.GameValueFilter(A, deep, S.ConstValue(4000.0))], [S.ResourceDelta(A, "gem", 1)], "rich"),
+        nested_handler(levels - 1)])   # (+ this FirstMatch: ``levels`` levels)
+    rewards = [S.RewardSpec(deep), S.RewardSpec(S.InventoryValue("gem"), per_tick=True)]
+    values = {"deep": deep}
+    events = {}
+    if extended:
+        events["gift"] = S.EventSpec(S.TagQuery("type:agent"), [3, 9, 15, 21, 27], [], [S.ResourceDelta(T, "gem", 2)])
+    if qdepth:
+        q = query_of_depth(qdepth)
+        values["boxes"] = S.QueryCountValue(q)
+        rewards.append(S.RewardSpec(S.QueryInventoryValue("ore", q), per_tick=True))
+        events["drain"] = S.EventSpec(q, [5, 12, 20, 30], [], [S.ResourceDelta(T, "ore", -1)])
+    return S.GameSpec(
+        resource_names=["ore", "gem"],
+        agents=[S.AgentSpec(team_id=i % 2, inventory=S.Inventory(initial={"ore": 2, "gem": i % 4}), rewards=rewards)
+                for i in range(6)],
+        objects={"wall": S.ObjectSpec("wall", kind="wall"),
+                 "box": S.ObjectSpec("box", inventory=S.Inventory(initial={"ore": 40}, default_limit=1000), on_use=box_use)},
+        move_directions=["north", "south", "west", "east"],
+        obs=S.ObsSpec(width=5, height=5, num_tokens=120, values=values),
+        events=events, max_steps=0)
+
+
+def nesting_map(seed: int) -> np.ndarray:
+    return random_map(9, 9, {"wall": 3, "box": 18}, {"red": 3, "blue": 3}, seed)
+
+
+LIMIT_SCENARIOS = {
+    # name: (spec factory, map factory(seed), steps, allow invalid action indices) as in SCENARIOS
+    "agents_lean_max": (lean_agents_spec, lean_agents_map, 20, False),
+    "agents_ext_max": (ext_agents_spec, ext_agents_map, 20, False),
+    "map_max_default": (presets.rung3_spec, lambda s: edge_map(MAP_MAX_DEFAULT, MAP_MAX_DEFAULT, s), 24, True),
+    "map_max_few": (presets.rung3_spec, lambda s: edge_map(*MAP_MAX_FEW, s), 24, True),
+    "window15": (window15_spec, window15_map, 30, False),
+    "ceiling_b2": (lambda: ceiling_spec(2), ceiling_map, 40, False),
+    "ceiling_b10": (lambda: ceiling_spec(10), ceiling_map, 40, False),
+    "ceiling_b256": (lambda: ceiling_spec(256), ceiling_map, 40, False),
+    "tags": (tags_spec, tags_map, 40, False),
+    # handler chains at the register VM's 4 frames (lean; extended flat_top) and the LDS VM's 6: the move handler's frame
+    # + an on_use tree of 3 / 5 levels; value stack 8, queries 3
+    "nest4_lean": (lambda: nesting_spec(3, extended=False), nesting_map, 40, False),
+    "nest4_x": (lambda: nesting_spec(3), nesting_map, 40, False),
+    "nest6_x": (lambda: nesting_spec(5), nesting_map, 40, False),
+    "query3": (lambda: nesting_spec(3, qdepth=3), nesting_map, 40, False),
+}
+MAX_OBJECTS["map_max_few"] = MAP_FEW_OBJECTS
+
+
+def scenario(name: str) -> tuple:
+    """The SCENARIOS or LIMIT_SCENARIOS entry of ``name``."""
+    return SCENARIOS[name] if name in SCENARIOS else LIMIT_SCENARIOS[name]
+
+
+def run_parity(name: str, E: int, check_envs, steps: int | None = None) -> dict:
+    """Step ``E`` envs of scenario ``name`` (SCENARIOS or LIMIT_SCENARIOS) on the engine and the oracle with the same
+    seeded actions; after every step the caller-visible buffers of ``check_envs`` must be equal (compare_snapshots), at
+    the end their signature payloads, and no env may report an error bit.  Returns the final stats of check_envs[0]."""
+    from mettagrid_amd.engine import BatchedMettaGrid
+    import oracle_py as op
+    spec_f, map_f, nsteps, invalid = scenario(name)
+    steps = nsteps if steps is None else steps
+    spec = spec_f()
+    maps = [map_f(s) for s in range(E)]
+    prog = compile_scenario(name, spec, *maps[0].shape)
+    cms = np.stack([prog.class_map(m) for m in maps])
+    seeds = np.arange(E, dtype=np.uint32) * 7 + 3
+    eng = BatchedMettaGrid(prog, cms, seeds, buffers="host")
+    try:
+        oracles = {i: op.OracleSim(prog, cms[i], int(seeds[i])) for i in check_envs}
+        for o in oracles.values():
+            o.reinit_buffers()
+        acts = [make_actions(prog, i, steps, invalid) for i in range(E)]
+        A = prog.num_agents
+
+        def check(t):
+            snap = eng.snapshot()
+            for i, o in oracles.items():
+                compare_snapshots(o.snapshot(), {k: v[i * A:(i + 1) * A] for k, v in snap.items()}, f"{name} env {i} step {t}")
+
+        check(0)
+        for t in range(steps):
+            eng.actions[:] = np.concatenate([acts[i][0][t] for i in range(E)])
+            eng.vibe_actions[:] = np.concatenate([acts[i][1][t] for i in range(E)])
+            eng.step()
+            for i, o in oracles.items():
+                o.step(acts[i][0][t], acts[i][1][t])
+            check(t + 1)
+        bits, first = eng.poll_errors()
+        assert bits == 0, f"{name}: env error bits {bits} (first env {first})"
+        snap = eng.snapshot()
+        for i, o in oracles.items():
+            mine = {k: v[i * A:(i + 1) * A] for k, v in snap.items()}
+            pa = payload_from_raw(prog, o.raw_objects(), o.current_stat_reward(), o.raw_stats(), o.snapshot(), steps, int(seeds[i]))
+            pb = payload_from_raw(prog, eng.raw_objects(i), eng.current_stat_reward(i), eng.raw_stats(i), mine, steps, int(seeds[i]))
+            assert pa == pb, f"{name} env {i}: signature payload differs: {diff_payload(pa, pb)}"
+        return eng.get_episode_stats(check_envs[0])
+    finally:
+        eng.close()
+
+
+def create_one(name: str, **compile_kw):
+    """An engine with E = 1 for scenario ``name`` (map seed 0), or the exception mgx_create raised."""
+    from mettagrid_amd.engine import BatchedMettaGrid
+    spec_f, map_f, _, _ = scenario(name)
+    grid = map_f(0)
+    prog = compile_spec(spec_f(), *grid.shape, max_objects=compile_kw.get("max_objects", MAX_OBJECTS.get(name)))
+    return BatchedMettaGrid(prog, prog.class_map(grid)[None], np.zeros(1, np.uint32), buffers="host")
