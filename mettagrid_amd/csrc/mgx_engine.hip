@@ -18,6 +18,7 @@
 #include "mgx_world.h"
 #include "mgx_aoe_local.h"
 #include "mgx_episode.h"
+#include "mgx_plan.h"       // mgx_create's host-only half: validation and every create-time decision
 
 
 // Territory ownership map (TerritoryTracker::compute_cell_ownership, core/territory_tracker.cpp:215-252) of every cell,
@@ -208,16 +209,14 @@ static int fail(int code, const std::string& msg) {
       return fail(MGX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));                 \
   } while (0)
 
-struct mgx_engine {
-  int num_tags = 0;  // MGX_H_NUM_TAGS
-  MgxDev d{};
+struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layout) + the resources behind it
+  MgxSwitches sw{};            // the create-time switches, for the rest of the engine's life
   MgxDev* d_dev = nullptr;     // copy of `d` in device memory for the kernels that take it by pointer (extended path)
   MgxDev d_dev_host{};         // what d_dev holds
   bool d_dev_valid = false;
   MgxDev* d_hot = nullptr;     // the extended world kernel's copy: sec[] of the hot program range relative to its LDS copy
   MgxDev d_hot_host{};
   bool d_hot_valid = false;
-  int hot_lo = 0, hot_hi = 0;  // [hot_lo, hot_hi): program words of that range
   int device = 0;
   hipStream_t stream = nullptr;
   std::vector<void*> allocs;
@@ -233,40 +232,9 @@ struct mgx_engine {
   float* h_rew = nullptr;
   int32_t *h_act = nullptr, *h_vact = nullptr;
   bool external = false;
-  size_t lds_world = 0, lds_obs = 0, lds_act = 0;
-  int obs_threads = MGX_OBS_THREADS, obs_ew = MGX_OBS_THREADS / MGX_WAVE;
-  int obs_variant = 0;   // 0: generic observation kernel; 3: the instance specialised for the shape of BASELINE.json configs[2]
   int box_dtype = 0, box_C = 0;   // mgx_set_box_output: the observation kernel writes the dense box instead of token rows
   void* box_out = nullptr;
-  int pool_tokens = 0;   // capacity of the LDS token pool (entries), including the class-tag prefix
-  int pool_prefix = 0;   // entries of the per-class static tag table at the head of the pool
-  bool prog_in_lds = false;
-  int prog_lds_words = 0;   // program words in front of the schedule section (what the world kernels copy into LDS)
-  int obs_blk_start = 0, obs_blk_words = 0;  // program block the observation kernel interprets
-  bool obs_blk_lds = false;
-  std::vector<int> class_list_tokens;  // worst-case per-step token list length per class (0: static class)
-  bool pool_from_maps = false;         // pool sized from the class maps (no run-time object creation / tag changes)
-  // max over the selected envs of the summed worst-case list lengths of the objects on their class maps
-  long long list_tokens_bound(const uint16_t* class_maps, size_t first, size_t count, const uint8_t* mask) const {
-    const size_t hw = (size_t)d.H * d.W;
-    const int nc = (int)class_list_tokens.size();
-    long long best = 0;
-    for (size_t env = first; env < first + count; env++) {
-      if (mask && !mask[env]) continue;
-      const uint16_t* cm = class_maps + env * hw;
-      long long t = 0;
-      for (size_t i = 0; i < hw; i++) {
-        const int k = cm[i];
-        if (k > 0 && k <= nc) t += class_list_tokens[k - 1];
-      }
-      best = std::max(best, t);
-    }
-    return best;
-  }
-  bool verbose = false;
-  bool rewards_early = false;  // reward expressions have no stat operands: evaluated beside the token-cache phase
   bool terr_fresh = false;     // the territory ownership maps were refreshed in this step and nothing behind that can change them
-  bool rewards_mid = false;    // extended games: ... read nothing the observation kernel writes: evaluated during its encode phase
   int slot = 0;                // constant-memory slot of the lean world kernel (mgx_world_fast.hip, MGX_SLOT)
   uint32_t* h_act_err = nullptr;      // pinned + mapped [4]: mgx_set_joint_actions' range check: flags, lowest bad row, its value
   uint32_t* h_act_err_dev = nullptr;
@@ -274,10 +242,6 @@ struct mgx_engine {
   int32_t* d_vibe_ids = nullptr;  // mgx_set_joint_actions: action index of each vibe action
   int32_t vibe_ids_host[256] = {};
   int n_vibe_ids = 0;
-  bool aoe_local = false;      // area effects only touch their target: one lane per agent (mgx_aoe_kernel)
-  bool aoe_prog_lds = false;   // ... with the hot program range copied into its LDS
-  int hot_words = 0;           // words of the hot program range, rounded up to 4
-  bool rewards_ext = false;    // reward expressions have query operands: evaluated by mgx_values_kernel after the obs kernel
   uint16_t* dmaps = nullptr;
   uint32_t* dseeds = nullptr;
   uint8_t* dmask = nullptr;
@@ -308,7 +272,6 @@ struct mgx_engine {
     bool dev_valid = false;
     int epg = 0, threads = 0;
   } jit_world, jit_obs, jit_actx;
-  unsigned long long handler_fp = 0;  // FNV-1a of the handler tables (gen_handlers.py fingerprint())
   int32_t* d_done_list = nullptr;   // [E] the envs of d_next_mask in ascending order (mgx_episode_end_kernel) ...
   uint32_t* d_done_n = nullptr;     // [1] ... and how many: what the restart and episode-statistics kernels walk
   // episode-end statistics (mgx_set_episode_stats; csrc/mgx_episode.h)
@@ -365,44 +328,12 @@ struct mgx_engine {
   }
 };
 
-// Dynamic LDS of the observation kernel for the current pool capacity (mgx_create; mgx_reset_envs when new maps need
-// a larger pool).
-static int size_obs_lds(mgx_engine* e) {
-  const MgxDev& d = e->d;
-  const int xmode = mgx_obs_xmode(d.X != 0, d.X && d.aoe_mask_feat != 0 && d.NT > 0, d.S, e->num_tags);
-  // extended games with many agents per env: 512 threads, of which EW wavefronts encode (4 staging rows each).  Fewer
-  // encode wavefronts = fewer rows in LDS: the largest EW of 4, 3, 2 that lets three workgroups share a CU's 160 KB is
-  // taken (rung 4, T = 200: EW 4, 52.8 KB, 4.3 ms; all eight wavefronts encoding: 66.6 KB, two workgroups, 5.2 ms;
-  // T = 256: EW 3, 52.6 KB, 4.8 ms against 6.1 ms for EW 4 at two workgroups; 1 024 threads 8.6 ms; 256 threads 7.25 ms;
-  // the lean kernel with 512 threads 1.14 instead of 0.67 ms)
-  e->obs_threads = (d.X && d.A >= 48 && !getenv("MGX_OBS_256")) ? 512 : MGX_OBS_THREADS;
-  e->obs_ew = e->obs_threads / MGX_WAVE;
-  auto lds_for = [&](int ew) {
-    return (size_t)mgx_obs_lds_layout(d.H * d.W, d.NOFF, d.S, d.A, d.T, e->pool_tokens, xmode, d.n_obs_values,
-                                      e->obs_blk_lds ? e->obs_blk_words : 0, mgx_obs_gt(d.n_obs_values, d.base, d.flags),
-                                      e->rewards_early, ew).total;
-  };
-  if (e->obs_threads == 512) {
-    e->obs_ew = 4;
-    for (int ew : {4, 3, 2})
-      if (lds_for(ew) <= 53760) { e->obs_ew = ew; break; }
-  }
-  e->lds_obs = lds_for(e->obs_ew);
-  if (const char* pad = getenv("MGX_OBS_LDS_PAD")) e->lds_obs += (size_t)atoi(pad);   // (occupancy experiments: unused LDS behind the layout)
-  const bool keep_jit = e->obs_variant == 9 && e->jit_obs.mod && e->lds_obs <= 64 * 1024;   // (the shape does not depend on the pool size)
-  e->obs_variant = 0;
-  if (keep_jit) e->obs_variant = 9;
-  else if (!getenv("MGX_OBS_GENERIC")) {
-    if (!d.X && e->obs_blk_lds && mgx_obs_shape_matches<MgxObsShapeR3>(d, e->obs_blk_words, (e->rewards_early ? 1 : e->rewards_mid ? 2 : 0))) e->obs_variant = 3;
-    else if (!d.X && e->obs_blk_lds && mgx_obs_shape_matches<MgxObsShapeR3AnyLength>(d, e->obs_blk_words, (e->rewards_early ? 1 : e->rewards_mid ? 2 : 0))) e->obs_variant = 5;   // same shape, max_steps set
-    // (an instance for the shape of configs[3], MgxObsShapeR4, was measured too: 5.07 ms against the generic kernel's 5.01 —
-    // the extended kernel's time is barrier and LDS latency, not scalar arithmetic; it is not built)
-  }
-  if (e->lds_obs > 160 * 1024)
-    return fail(MGX_ERR_PROGRAM, "map/object count too large for the LDS staging of the observation kernel");
-  if (e->verbose || getenv("MGX_VERBOSE"))
+// Raise the observation kernels' dynamic LDS limit to the engine's lds_obs (mgx_create; fit_maps when new maps need a
+// larger pool).
+static int raise_obs_lds(mgx_engine* e) {
+  if (e->sw.verbose)
     fprintf(stderr, "[mgx] obs: lds=%zu B pool=%d tokens (prefix %d) blk_lds=%d rewards_early=%d threads=%d encode wavefronts=%d (4 would need %zu B)\n",
-            e->lds_obs, e->pool_tokens, e->pool_prefix, (int)e->obs_blk_lds, (e->rewards_early ? 1 : e->rewards_mid ? 2 : 0), e->obs_threads, e->obs_ew, lds_for(4));
+            e->lds_obs, e->pool_tokens, e->pool_prefix, (int)e->obs_blk_lds, e->rmode, e->obs_threads, e->obs_ew, e->obs_lds_bytes(4));
   // The attribute is per kernel and process-wide: keep one maximum and only ever raise it, so that a second engine
   // with a smaller requirement cannot lower the limit under a live one.
   static std::mutex mu;
@@ -450,9 +381,9 @@ static void launch_obs_t(mgx_engine* e, bool with_rewards, const uint8_t* mask, 
   if (PL)  // the interpreted sections are addressed relative to their LDS copy
     for (int k = MGX_SEC_INV_FEATURES; k < MGX_SEC_WORDLIST; k++) dd.sec[k] -= e->obs_blk_start;
   if (with_rewards)
-    hipLaunchKernelGGL((mgx_obs_kernel<true, X, PL, NTH, EW, K>), grid, block, e->lds_obs, e->stream, dd, e->pool_tokens, e->pool_prefix, mask, e->obs_blk_start, e->obs_blk_words, (e->rewards_early ? 1 : e->rewards_mid ? 2 : 0), (void*)nullptr, (const float*)nullptr, 0, 0, ll, ln, l.passes);
+    hipLaunchKernelGGL((mgx_obs_kernel<true, X, PL, NTH, EW, K>), grid, block, e->lds_obs, e->stream, dd, e->pool_tokens, e->pool_prefix, mask, e->obs_blk_start, e->obs_blk_words, e->rmode, (void*)nullptr, (const float*)nullptr, 0, 0, ll, ln, l.passes);
   else
-    hipLaunchKernelGGL((mgx_obs_kernel<false, X, PL, NTH, EW, K>), grid, block, e->lds_obs, e->stream, dd, e->pool_tokens, e->pool_prefix, mask, e->obs_blk_start, e->obs_blk_words, (e->rewards_early ? 1 : e->rewards_mid ? 2 : 0), (void*)nullptr, (const float*)nullptr, 0, 0, ll, ln, l.passes);
+    hipLaunchKernelGGL((mgx_obs_kernel<false, X, PL, NTH, EW, K>), grid, block, e->lds_obs, e->stream, dd, e->pool_tokens, e->pool_prefix, mask, e->obs_blk_start, e->obs_blk_words, e->rmode, (void*)nullptr, (const float*)nullptr, 0, 0, ll, ln, l.passes);
 }
 // The observation kernel of a run-time code object: same arguments as mgx_obs_kernel, through hipModuleLaunchKernel.
 static int launch_obs_jit(mgx_engine* e, bool with_rewards, const uint8_t* mask, const MgxList& l) {
@@ -460,7 +391,7 @@ static int launch_obs_jit(mgx_engine* e, bool with_rewards, const uint8_t* mask,
   MgxDev dd = e->d;
   for (int k = MGX_SEC_INV_FEATURES; k < MGX_SEC_WORDLIST; k++) dd.sec[k] -= e->obs_blk_start;   // (PL: relative to the LDS copy)
   int pool_tokens = e->pool_tokens, pool_prefix = e->pool_prefix, blk_start = e->obs_blk_start, blk_words = e->obs_blk_words;
-  int rmode = e->rewards_early ? 1 : e->rewards_mid ? 2 : 0, zero = 0, passes = l.passes;
+  int rmode = e->rmode, zero = 0, passes = l.passes;
   void* box = nullptr;
   const float* scale = nullptr;
   const uint8_t* m = listed ? nullptr : mask;
@@ -487,8 +418,7 @@ static int launch_world_jit(mgx_engine* e, int prog_words) {
 }
 // The extended games' lane-per-agent dispatch of a run-time code object (same geometry as mgx_launch_act_x).
 static int launch_act_x_jit(mgx_engine* e, const MgxDev* dp, int prog_words) {
-  int ap = 1;
-  while (ap < e->d.A) ap <<= 1;
+  const int ap = mgx_pow2_at_least(e->d.A);
   const int epg = e->jit_actx.epg;
   void* params[] = {&dp, &prog_words};
   HIP_TRY(hipModuleLaunchKernel(e->jit_actx.f0, (unsigned)((e->d.E + epg - 1) / epg), 1, 1, (unsigned)(epg * ap), 1, 1, (unsigned)e->lds_act, e->stream,
@@ -556,7 +486,7 @@ static int launch_obs(mgx_engine* e, bool with_rewards, const uint8_t* mask = nu
     if (pl)
       for (int k = MGX_SEC_INV_FEATURES; k < MGX_SEC_WORDLIST; k++) dd.sec[k] -= e->obs_blk_start;
     if (!mgx_launch_obs_box(e->stream, dd, e->lds_obs, e->pool_tokens, e->pool_prefix, mask, e->obs_blk_start, e->obs_blk_words,
-                            (e->rewards_early ? 1 : e->rewards_mid ? 2 : 0), with_rewards, e->d.X != 0, pl, e->obs_threads, e->obs_ew, e->box_out, e->d_scale,
+                            e->rmode, with_rewards, e->d.X != 0, pl, e->obs_threads, e->obs_ew, e->box_out, e->d_scale,
                             e->box_C, e->box_dtype, with_rewards ? nullptr : l.list, l.n, (int)list_grid(e, l, 128, 2048), l.passes))
       return fail(MGX_ERR_PROGRAM, "mgx_step: no dense-output instance of the observation kernel for this configuration");
     HIP_TRY(hipGetLastError());
@@ -676,186 +606,48 @@ const char* mgx_last_error(void) { return g_err.c_str(); }
 static std::mutex g_live_mu;
 static std::vector<mgx_engine*> g_live;  // engines between mgx_create and mgx_destroy
 
+static int hip_rc(hipError_t he, const char* what) {
+  return he == hipSuccess ? MGX_OK : fail(MGX_ERR_HIP, std::string(what) + ": " + hipGetErrorString(he));
+}
+// MGX_VERBOSE: the paths mgx_create chose
+static void report_plan(const mgx_engine* e, size_t program_words) {
+  const MgxDev& d = e->d;
+  if (e->aoe_kernel)
+    fprintf(stderr, "[mgx] aoe kernel: %d agent stats staged per lane, %d B of LDS per workgroup\n", d.aoe_nstat, mgx_aoe_lds_bytes(d.aoe_nstat));
+  fprintf(stderr, "[mgx] E=%d A=%d S=%d program=%zu B world: X=%d prog_in_lds=%d lds=%zu B\n", d.E, d.A, d.S, program_words * 4, d.X,
+          (int)e->prog_in_lds, e->lds_world);
+  if (d.X) fprintf(stderr, "[mgx] action-phase handlers on the %s VM\n", d.flat_top ? "register" : "LDS");
+  fprintf(stderr, "[mgx] handler code: %s\n", d.gen_prog ? "generated for this program at build()" : "interpreter");
+  fprintf(stderr, "[mgx] lean dispatch: %s\n", d.duo ? "two agents of an env at a time (disjoint footprints)" : "one agent at a time");
+  fprintf(stderr, "[mgx] action dispatch: one lane per %s\n", d.act_par ? "agent (conflict-ordered rounds)" : "env");
+  if (d.X) fprintf(stderr, "[mgx] extended world kernel: %zu bytes of private memory per lane\n", mgx_world_x_private_bytes());
+}
+
 int mgx_create(const int32_t* program, size_t program_words, const uint16_t* class_maps, const uint32_t* seeds,
                int32_t num_envs, int32_t device, mgx_engine** out) {
   if (!program || !class_maps || !seeds || !out || num_envs <= 0) return fail(MGX_ERR_BAD_ARG, "mgx_create: null/empty argument");
-  if (program_words < MGX_H_WORDS || program[MGX_H_MAGIC] != MGX_MAGIC || program[MGX_H_VERSION] != MGX_VERSION ||
-      (size_t)program[MGX_H_TOTAL_WORDS] != program_words)
-    return fail(MGX_ERR_PROGRAM, "mgx_create: not a version-" + std::to_string(MGX_VERSION) + " mgx program");
-  const int32_t* P = program;
-  if (P[MGX_H_NUM_RESOURCES] > MGX_MAX_RESOURCES || P[MGX_H_NUM_AGENTS] > MGX_MAX_AGENTS || P[MGX_H_HEIGHT] > 255 ||
-      P[MGX_H_WIDTH] > 255 || P[MGX_H_NUM_AGENTS] < 1 || P[MGX_H_TOKEN_BASE] < 2 || P[MGX_H_TOKEN_BASE] > 256 ||
-      P[MGX_H_NUM_TOKENS] < 1 || P[MGX_H_OBS_HEIGHT] > 15 || P[MGX_H_OBS_WIDTH] > 15)
-    return fail(MGX_ERR_PROGRAM, "mgx_create: program exceeds engine limits (resources<=13, agents<255, map<=255x255)");
-  // the handler VM's context slots hold object slot ids as (id + 2) & 0xFFFF (mgx_world.h ctx_store): ids up to 65533
-  if (P[MGX_H_MAX_OBJECTS] < 1 || P[MGX_H_MAX_OBJECTS] > MGX_MAX_OBJECT_SLOTS)
-    return fail(MGX_ERR_PROGRAM, "mgx_create: max_objects must be 1.." + std::to_string(MGX_MAX_OBJECT_SLOTS));
-  // Nesting the device evaluates in fixed storage: queries (eval_query<3>), the game-value stack (MgxValueStack) and the
-  // levels of a handler tree (VM frames; the register VM has fewer, settled below once the kernels are known).
-  if (P[MGX_H_QUERY_DEPTH] > MGX_MAX_QUERY_DEPTH)
-    return fail(MGX_ERR_PROGRAM, "mgx_create: queries nest deeper than " + std::to_string(MGX_MAX_QUERY_DEPTH) + " levels");
-  {
-    const int n_code = mgx_sec_cnt(P, MGX_SEC_GV_CODE);
-    const int32_t* code = P + mgx_sec_off(P, MGX_SEC_GV_CODE);
-    auto stack_ok = [&](int start, int count) {
-      if (start < 0 || count < 0 || start + count > n_code) return false;
-      int depth = 0;
-      for (int i = start; i < start + count; i++) {
-        const int op = code[i * MGX_GV_WORDS + MGX_GV_OP];
-        depth += (op == MGX_GOP_ADD_TERM || op == MGX_GOP_RATIO || op == MGX_GOP_MAX2 || op == MGX_GOP_MIN2) ? -1 : 1;
-        if (depth > MGX_VALUE_STACK) return false;
-      }
-      return true;
-    };
-    bool ok = true;
-    for (int k = 0; k < mgx_sec_cnt(P, MGX_SEC_OBS_VALUES) && ok; k++) {
-      const int32_t* V = P + mgx_sec_off(P, MGX_SEC_OBS_VALUES) + k * MGX_OV_WORDS;
-      ok = stack_ok(V[MGX_OV_GV_START], V[MGX_OV_GV_COUNT]);
-    }
-    for (int k = 0; k < mgx_sec_cnt(P, MGX_SEC_REWARDS) && ok; k++) {
-      const int32_t* R = P + mgx_sec_off(P, MGX_SEC_REWARDS) + k * MGX_RW_WORDS;
-      ok = stack_ok(R[MGX_RW_GV_START], R[MGX_RW_GV_COUNT]);
-    }
-    if (!ok)
-      return fail(MGX_ERR_PROGRAM, "mgx_create: a game value expression needs more than " + std::to_string(MGX_VALUE_STACK) + " stack entries");
-  }
-  int hnest = 0;   // VM frames the deepest handler tree needs (children are laid out before their parent)
-  {
-    const int n_hd = mgx_sec_cnt(P, MGX_SEC_HANDLERS);
-    std::vector<int> lv(n_hd, 1);
-    for (int h = 0; h < n_hd; h++) {
-      const int32_t* hd = P + mgx_sec_off(P, MGX_SEC_HANDLERS) + h * MGX_HD_WORDS;
-      if (hd[MGX_HD_KIND] != MGX_HK_LEAF)
-        for (int i = 0; i < hd[MGX_HD_CHILD_COUNT]; i++) {
-          const int k = P[mgx_sec_off(P, MGX_SEC_CHILDREN) + hd[MGX_HD_CHILD_START] + i];
-          lv[h] = std::max(lv[h], k >= 0 && k < h ? lv[k] + 1 : MGX_MAX_HANDLER_NESTING + 1);
-        }
-      hnest = std::max(hnest, lv[h]);
-    }
-    // an on_use / on_after_use tree runs on frames above the move handler whose UseTarget reached it
-    auto level = [&](int h) { return h >= 0 && h < n_hd ? lv[h] : 0; };
-    int mv = 0, use = 0;
-    for (int k = 0; k < P[MGX_H_NUM_MOVE_HANDLERS]; k++)
-      mv = std::max(mv, level(P[mgx_sec_off(P, MGX_SEC_MOVE_HANDLERS) + k * MGX_MH_WORDS + MGX_MH_HANDLER]));
-    for (int c = 0; c < P[MGX_H_NUM_CLASSES]; c++) {
-      const int32_t* C = P + mgx_sec_off(P, MGX_SEC_CLASSES) + c * MGX_C_WORDS;
-      use = std::max(use, std::max(level(C[MGX_C_ON_USE]), level(C[MGX_C_ON_AFTER_USE])));
-    }
-    if (use > 0) hnest = std::max(hnest, mv + use);
-    if (hnest > MGX_MAX_HANDLER_NESTING)
-      return fail(MGX_ERR_PROGRAM, "mgx_create: handlers nest deeper than " + std::to_string(MGX_MAX_HANDLER_NESTING) + " levels");
-  }
-  {
-    const size_t hw = (size_t)P[MGX_H_HEIGHT] * P[MGX_H_WIDTH];
-    for (size_t i = 0; i < (size_t)num_envs * hw; i++)
-      if (class_maps[i] > P[MGX_H_NUM_CLASSES])
-        return fail(MGX_ERR_BAD_ARG, "mgx_create: class map holds id " + std::to_string(class_maps[i]) + " but the program has " +
-                                         std::to_string(P[MGX_H_NUM_CLASSES]) + " classes");
-  }
+  // ---- plan (mgx_plan.h): every refusal of the program or the maps happens here, before any HIP call ----
+  const MgxSwitches sw = mgx_read_switches();
+  MgxPlan plan;
+  std::string why;
+  int rc = mgx_plan(program, program_words, class_maps, num_envs, sw, plan, why);
+  if (rc != MGX_OK) return fail(rc, why);
   HIP_TRY(hipSetDevice(device));
   mgx_engine* e = new mgx_engine();
+  static_cast<MgxPlan&>(*e) = std::move(plan);
+  e->sw = sw;
   e->device = device;
   e->prog.assign(program, program + program_words);
-  hipError_t se = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
-  if (se != hipSuccess) { delete e; return fail(MGX_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(se)); }
-
+  if (sw.verbose) report_plan(e, program_words);
   MgxDev& d = e->d;
-  d.E = num_envs; d.H = P[MGX_H_HEIGHT]; d.W = P[MGX_H_WIDTH]; d.A = P[MGX_H_NUM_AGENTS]; d.S = P[MGX_H_MAX_OBJECTS];
-  d.R = P[MGX_H_NUM_RESOURCES] > 0 ? P[MGX_H_NUM_RESOURCES] : 1;
-  d.T = P[MGX_H_NUM_TOKENS];
-  d.NS = P[MGX_H_NUM_AGENT_STATS]; d.NG = P[MGX_H_NUM_GAME_STATS];
-  d.NSW = (d.NS + 31) / 32; d.NGW = (d.NG + 31) / 32;
-  d.NSP = d.NSW * 32;
-  d.SEENW = (d.H * d.W + 31) / 32;
-  d.NOFF = P[MGX_H_NUM_OBS_OFFSETS];
-  d.base = P[MGX_H_TOKEN_BASE];
-  d.max_steps = P[MGX_H_MAX_STEPS]; d.truncates = P[MGX_H_EPISODE_TRUNCATES]; d.max_priority = P[MGX_H_MAX_PRIORITY];
-  d.nact = P[MGX_H_NUM_ACTIONS]; d.flags = P[MGX_H_GLOBAL_FLAGS]; d.hp_res = P[MGX_H_HP_RESOURCE];
-  if (d.nact > 32000) { mgx_destroy(e); return fail(MGX_ERR_PROGRAM, "mgx_create: more than 32000 actions"); }
-  d.n_obs_values = P[MGX_H_NUM_OBS_VALUES]; d.n_move_handlers = P[MGX_H_NUM_MOVE_HANDLERS];
-  for (int i = 0; i < 14; i++) d.feat[i] = P[MGX_H_FEAT_BASE + i];
-  d.feat[14] = P[MGX_H_OBS_HEIGHT] >> 1;
-  d.feat[15] = P[MGX_H_OBS_WIDTH] >> 1;
-  for (int i = 0; i < 32; i++) d.wk[i] = P[MGX_H_STAT_BASE + i];
-  for (int s = 0; s < MGX_SEC_COUNT; s++) d.sec[s] = mgx_sec_off(P, s);
-  int nrw = 1;
-  for (int c = 0; c < P[MGX_H_NUM_CLASSES]; c++)
-    nrw = std::max(nrw, (int)P[d.sec[MGX_SEC_CLASSES] + c * MGX_C_WORDS + MGX_C_REWARD_COUNT]);
-  d.NRW = nrw;
-  d.any_on_tick = 0;
-  for (int c = 0; c < P[MGX_H_NUM_CLASSES]; c++)
-    if (P[d.sec[MGX_SEC_CLASSES] + c * MGX_C_WORDS + MGX_C_ON_TICK] >= 0) d.any_on_tick = 1;
-
-  // ---- extended (rung 4) features: capacities come from a host scan of the class maps ----
-  d.n_events = P[MGX_H_NUM_EVENTS]; d.n_schedule = P[MGX_H_NUM_SCHEDULE]; d.n_matq = P[MGX_H_NUM_MATQ];
-  d.NT = P[MGX_H_NUM_TERRITORIES]; d.game_on_tick = P[MGX_H_GAME_ON_TICK]; d.NL = P[MGX_H_NUM_INDEXED_TAGS];
-  d.aoe_mask_feat = P[MGX_H_FEAT_BASE + MGX_F_AOE_MASK];
-  e->num_tags = P[MGX_H_NUM_TAGS];
-  d.QD = std::max(1, (int)P[MGX_H_QUERY_DEPTH]) + 1;
-  d.QB = 3 + 2 * (d.QD + 1);
-  d.AW = (d.A + 31) / 32;
-  d.SW = (d.S + 31) / 32;
-  {
-    const int nc = P[MGX_H_NUM_CLASSES];
-    std::vector<int> cf(nc), cm(nc), ct(nc);
-    bool any_aoe = false;
-    for (int c = 0; c < nc; c++) {
-      const int32_t* C = P + d.sec[MGX_SEC_CLASSES] + c * MGX_C_WORDS;
-      for (int i = 0; i < C[MGX_C_AOE_COUNT]; i++) {
-        bool st = P[d.sec[MGX_SEC_AOES] + (C[MGX_C_AOE_START] + i) * MGX_AO_WORDS + MGX_AO_STATIC] != 0;
-        (st ? cf[c] : cm[c])++;
-        any_aoe = true;
-      }
-      ct[c] = C[MGX_C_TERR_COUNT];
-    }
-    int nf = 0, nm = 0, nts = 0;
-    const size_t hw = (size_t)d.H * d.W;
-    if (any_aoe || d.NT > 0)
-      for (int env = 0; env < num_envs; env++) {
-        int f = 0, m = 0, t = 0;
-        const uint16_t* cmap = class_maps + (size_t)env * hw;
-        for (size_t i = 0; i < hw; i++) {
-          int k = cmap[i];
-          if (k > 0 && k <= nc) { f += cf[k - 1]; m += cm[k - 1]; t += ct[k - 1]; }
-        }
-        nf = std::max(nf, f); nm = std::max(nm, m); nts = std::max(nts, t);
-      }
-    if (P[MGX_H_SPAWNS]) {  // spawned objects may bring AoEs: leave room for one set per object slot
-      int per_f = 0, per_m = 0;
-      for (int c = 0; c < nc; c++) { per_f = std::max(per_f, cf[c]); per_m = std::max(per_m, cm[c]); }
-      nf += per_f ? std::min<int>(d.S * per_f, 4096) : 0;
-      nm += per_m ? std::min<int>(d.S * per_m, 4096) : 0;
-    }
-    d.NF = nf; d.NM = nm; d.NTS = nts;
-    d.FW = std::max(1, (nf + 31) / 32); d.MW = std::max(1, (nm + 31) / 32);
-    e->aoe_local = mgx_aoe_is_target_local(P) && !getenv("MGX_AOE_SERIAL");
-    d.X = (any_aoe || d.NT > 0 || d.n_schedule > 0 || d.n_matq > 0 || d.game_on_tick >= 0 || P[MGX_H_DYNAMIC_TAGS] ||
-           mgx_sec_cnt(P, MGX_SEC_QUERIES) > 0) ? 1 : 0;
-  }
-  {  // The world kernel stages per agent and env 17 B (lean, 64 envs per workgroup) or 15 B (extended, 32 envs), plus per
-     // env 144 B of VM words and, when the AoE phase runs in the world kernel, 176 B of scratch (extended) — at most 160 KB:
-     // the agents an env may have depend on the program.  Refused here, before anything is allocated (the size is settled
-     // below, where the program copy is added only when it fits).
-    const bool aoe_lds = d.X && !(e->aoe_local && (d.NF > 0 || d.NM > 0 || d.NT > 0));
-    const size_t lds = d.X ? mgx_world_x_lds_bytes(d.A, aoe_lds) : mgx_world_fast_lds_bytes(d.A);
-    if (!d.X && hnest > MGX_MAX_HANDLER_NESTING_REG) {   // lean programs run every handler on the register VM
-      mgx_destroy(e);
-      return fail(MGX_ERR_PROGRAM, "mgx_create: handlers of a lean program nest deeper than " +
-                                       std::to_string(MGX_MAX_HANDLER_NESTING_REG) + " levels (the register VM's frames)");
-    }
-    if (lds > 160 * 1024) {
-      mgx_destroy(e);
-      return fail(MGX_ERR_PROGRAM, "mgx_create: " + std::to_string(d.A) + " agents per env are too many for the " +
-                                       (d.X ? "extended" : "lean") + " world kernel's LDS staging (" + std::to_string(lds) +
-                                       " B > 160 KB per workgroup)");
-    }
-  }
+  const int32_t* P = program;
   const size_t E = d.E, HW = (size_t)d.H * d.W, S = d.S, A = d.A, rows = E * A;
-  int rc = MGX_OK;
-  int32_t* dprog = nullptr;
-  uint16_t* dmaps = nullptr;
-  uint32_t* dseeds = nullptr;
 #define A_(call) if (rc == MGX_OK) rc = (call)
+#define H_(call, what) if (rc == MGX_OK) rc = hip_rc((call), what)
+  H_(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate");
+
+  // ---- allocate: per-env state (env-major, cleared by restarts), the plan's tables, caller-visible buffers ----
+  int32_t* dprog = nullptr;
   A_(e->alloc(&dprog, program_words));
   A_(e->alloc_env(&d.grid, HW));
   A_(e->alloc_env(&d.obj_cls, S, 0xFF));
@@ -904,10 +696,10 @@ int mgx_create(const int32_t* program, size_t program_words, const uint16_t* cla
     if (d.NL) { A_(e->alloc_env(&d.tl_items, d.NL * S)); A_(e->alloc_env(&d.tl_count, (size_t)d.NL)); }
     if (d.NF) { A_(e->alloc_env(&d.fx_obj, (size_t)d.NF)); A_(e->alloc_env(&d.fx_aoe, (size_t)d.NF)); A_(e->alloc_env(&d.fx_rc, (size_t)d.NF));
                 A_(e->alloc_env(&d.fx_inside, A * (size_t)d.FW)); A_(e->alloc_env(&d.fx_count, 1));
-                if (e->aoe_local) A_(e->alloc(&d.fx_pack, E * (size_t)d.NF)); }
+                if (e->aoe_kernel) A_(e->alloc(&d.fx_pack, E * (size_t)d.NF)); }
     if (d.NM) { A_(e->alloc_env(&d.mb_obj, (size_t)d.NM)); A_(e->alloc_env(&d.mb_aoe, (size_t)d.NM));
                 A_(e->alloc_env(&d.mb_inside, A * (size_t)d.MW)); A_(e->alloc_env(&d.mb_count, 1));
-                if (e->aoe_local) A_(e->alloc(&d.mb_pack, E * (size_t)d.NM)); }
+                if (e->aoe_kernel) A_(e->alloc(&d.mb_pack, E * (size_t)d.NM)); }
     if (d.NTS) { A_(e->alloc_env(&d.ts_obj, (size_t)d.NTS)); A_(e->alloc_env(&d.ts_ctrl, (size_t)d.NTS)); A_(e->alloc_env(&d.ts_rc, (size_t)d.NTS));
                  A_(e->alloc_env(&d.ts_count, 1)); }
     A_(e->alloc_env(&d.terr_prev, A * std::max(1, d.NT)));
@@ -918,519 +710,69 @@ int mgx_create(const int32_t* program, size_t program_words, const uint16_t* cla
     A_(e->alloc(&d.qws, E * d.QB * S));
     A_(e->alloc(&d.qvis, E * (d.QD + 1) * d.SW));
   }
+  int16_t* dids = nullptr;
+  uint8_t* dmap = nullptr;
+  if (e->aoe_kernel) { A_(e->alloc(&dids, std::max<size_t>(1, e->aoe_stat_ids.size()))); A_(e->alloc(&dmap, 256)); }
+  uint32_t* dinfo = nullptr;
+  uint16_t* dtoks = nullptr;
+  A_(e->alloc(&dinfo, e->cls_tokinfo.size()));
+  A_(e->alloc(&dtoks, e->cls_tok.size()));
+  if (e->obsval) A_(e->alloc(&d.obsval, E * A * (size_t)d.n_obs_values));
   A_(e->alloc(&e->d_dev, 1));
   A_(e->alloc(&e->d_hot, 1));
-  A_(e->alloc(&dmaps, E * HW));
-  A_(e->alloc(&dseeds, E));
+  A_(e->alloc(&e->dmaps, E * HW));
+  A_(e->alloc(&e->dseeds, E));
   A_(e->alloc(&e->dmask, E));
-#undef A_
-  if (rc != MGX_OK) { mgx_destroy(e); return rc; }
   d.P = dprog;
+  d.aoe_stat_ids = dids; d.aoe_stat_map = dmap;
+  d.cls_tokinfo = dinfo; d.cls_tok = dtoks;
   d.obs = e->own_obs; d.terminals = e->own_term; d.truncations = e->own_trunc; d.rewards = e->own_rew;
   d.actions = e->own_act; d.vibe_actions = e->own_vact;
 
-  e->verbose = getenv("MGX_VERBOSE") != nullptr;
-  {
-    const bool split = d.X && e->aoe_local && (d.NF > 0 || d.NM > 0 || d.NT > 0);
-    d.tick_in_aoe = (split && d.any_on_tick && mgx_aoe_on_tick_local(P) && !getenv("MGX_TICK_SERIAL")) ? 1 : 0;
-    d.cov_in_aoe = (split && d.game_on_tick < 0 && !getenv("MGX_TICK_SERIAL")) ? 1 : 0;
-  }
-  d.x_aoe_lds = (d.X && !(e->aoe_local && (d.NF > 0 || d.NM > 0 || d.NT > 0))) ? 1 : 0;
-  if (d.X && e->aoe_local && (d.NF > 0 || d.NM > 0 || d.NT > 0)) {
-    // the agent stats the lane-per-agent area-effect kernel keeps in LDS (mgx_aoe_local.h)
-    std::vector<int16_t> ids;
-    mgx_aoe_collect_stats(P, d.tick_in_aoe != 0, d.cov_in_aoe != 0, ids);
-    if (getenv("MGX_AOE_NO_STAT_CELLS")) ids.clear();   // (debug: every stat access of the kernel goes to HBM)
-    std::vector<uint8_t> map(256, 0xFF);
-    for (size_t k = 0; k < ids.size(); k++) map[(size_t)ids[k]] = (uint8_t)k;
-    int16_t* dids = nullptr;
-    uint8_t* dmap = nullptr;
-    int arc = e->alloc(&dids, std::max<size_t>(1, ids.size()));
-    if (arc == MGX_OK) arc = e->alloc(&dmap, 256);
-    if (arc != MGX_OK) { mgx_destroy(e); return arc; }
-    hipError_t ce = hipSuccess;
-    if (!ids.empty()) ce = hipMemcpyAsync(dids, ids.data(), ids.size() * 2, hipMemcpyHostToDevice, e->stream);
-    if (ce == hipSuccess) ce = hipMemcpyAsync(dmap, map.data(), 256, hipMemcpyHostToDevice, e->stream);
-    if (ce == hipSuccess) ce = hipStreamSynchronize(e->stream);   // `ids` / `map` are locals
-    if (ce != hipSuccess) { mgx_destroy(e); return fail(MGX_ERR_HIP, std::string("aoe stat table upload: ") + hipGetErrorString(ce)); }
-    d.aoe_nstat = (int)ids.size();
-    d.aoe_stat_ids = dids;
-    d.aoe_stat_map = dmap;
-    // hot program range in the kernel's LDS when it leaves room for three workgroups per CU
-    e->hot_words = ((d.sec[MGX_SEC_TAG_LISTS] - (d.sec[MGX_SEC_LIMITS] & ~3)) + 3) & ~3;
-    e->aoe_prog_lds = (size_t)mgx_aoe_lds_bytes(d.aoe_nstat) + (size_t)e->hot_words * 4 <= 52 * 1024 && !getenv("MGX_AOE_PROG_HBM");
-#ifdef MGX_CPU_EMU
-    e->aoe_prog_lds = false;  // the LDS copy needs a workgroup barrier; the sanitizer build runs work-items one by one
-#endif
-    if (!mgx_aoe_set_lds(d.aoe_nstat, e->aoe_prog_lds ? e->hot_words : 0)) { mgx_destroy(e); return fail(MGX_ERR_HIP, "mgx_create: cannot raise the area-effect kernel's dynamic LDS limit"); }
-    if (getenv("MGX_VERBOSE")) fprintf(stderr, "[mgx] aoe kernel: %d agent stats staged per lane, %d B of LDS per workgroup\n", d.aoe_nstat, mgx_aoe_lds_bytes(d.aoe_nstat));
-  }
-  e->lds_world = d.X ? mgx_world_x_lds_bytes(d.A, d.x_aoe_lds != 0) : mgx_world_fast_lds_bytes(d.A);
-  // The world kernels copy the program — everything in front of the schedule, the last and only section that grows with
-  // the episode length — into LDS when it leaves room for 4 (lean) / 3 (extended) workgroups per CU (160 KB LDS).
-  // (Rung 4, measured: the copy at 2 workgroups per CU is slower than the program in HBM at 3: 9.8 against 8.4 ms.)
-  e->prog_lds_words = (int)((d.sec[MGX_SEC_SCHEDULE] + 3) & ~3);
-  if (d.X) {  // extended kernel: only the sections the handler VM walks (LIMITS .. TERR_CONTROLS); the class table — one
-              // record per agent — and the tag-list index are read from HBM / L2 (mgx_world.h MGX_HOT_PROG)
-    e->hot_lo = d.sec[MGX_SEC_LIMITS] & ~3;
-    e->hot_hi = d.sec[MGX_SEC_TAG_LISTS];
-    e->prog_lds_words = ((e->hot_hi - e->hot_lo) + 3) & ~3;
-  }
-  e->prog_in_lds = (size_t)e->prog_lds_words * 4 + e->lds_world <= (size_t)(d.X ? 53 : 40) * 1024;
-  if (const char* o = getenv("MGX_PROG_LDS")) e->prog_in_lds = e->prog_in_lds && atoi(o) != 0;
-#ifdef MGX_CPU_EMU
-  e->prog_in_lds = false;  // the LDS copy needs a workgroup barrier; the sanitizer build runs work-items one by one
-#endif
-  if (e->prog_in_lds) e->lds_world += (size_t)e->prog_lds_words * 4;
-  if (getenv("MGX_VERBOSE"))
-    fprintf(stderr, "[mgx] E=%d A=%d S=%d program=%zu B world: X=%d prog_in_lds=%d lds=%zu B\n", d.E, d.A, d.S,
-            program_words * 4, d.X, (int)e->prog_in_lds, e->lds_world);
-  {  // per-class static tag tokens (ascending tag id, core/grid_object.cpp:181-186)
-    std::vector<uint32_t> info(P[MGX_H_NUM_CLASSES]);
-    std::vector<uint16_t> toks;
-    for (int c = 0; c < P[MGX_H_NUM_CLASSES]; c++) {
-      const int32_t* C = P + d.sec[MGX_SEC_CLASSES] + c * MGX_C_WORDS;
-      uint32_t start = (uint32_t)toks.size();
-      int nt = 0;
-      for (int t = 0; t < 256; t++)
-        if (((uint32_t)C[MGX_C_TAGS + (t >> 5)] >> (t & 31)) & 1u) { toks.push_back((uint16_t)(d.feat[MGX_F_TAG] | (t << 8))); nt++; }
-      if (nt > 63 || start > 0xFFFF) { mgx_destroy(e); return fail(MGX_ERR_PROGRAM, "mgx_create: more than 63 tags on one class"); }
-      info[c] = start | ((uint32_t)(C[MGX_C_GROUP] & 0xFF) << 16) | ((uint32_t)nt << 24) |
-                (C[MGX_C_KIND] == MGX_KIND_AGENT ? 0x40000000u : 0u) | (C[MGX_C_STATIC] ? 0x80000000u : 0u);
-    }
-    if (toks.empty()) toks.push_back(0);
-    uint32_t* dinfo = nullptr;
-    uint16_t* dtoks = nullptr;
-    rc = e->alloc(&dinfo, info.size());
-    if (rc == MGX_OK) rc = e->alloc(&dtoks, toks.size());
-    if (rc != MGX_OK) { mgx_destroy(e); return rc; }
-    hipError_t ce = hipMemcpyAsync(dinfo, info.data(), info.size() * 4, hipMemcpyHostToDevice, e->stream);
-    if (ce == hipSuccess) ce = hipMemcpyAsync(dtoks, toks.data(), toks.size() * 2, hipMemcpyHostToDevice, e->stream);
-    if (ce == hipSuccess) ce = hipStreamSynchronize(e->stream);
-    if (ce != hipSuccess) { mgx_destroy(e); return fail(MGX_ERR_HIP, std::string("class token upload: ") + hipGetErrorString(ce)); }
-    d.cls_tokinfo = dinfo;
-    d.cls_tok = dtoks;
-    e->pool_prefix = (int)toks.size();
-  }
-  {  // LDS token pool = class-tag prefix + room for the per-step lists (objects of non-static classes).  Worst case
-     // per class from the program: tags + vibe + R * digits + 2.  Without run-time object creation the class maps
-     // bound it exactly (sum over the env's objects, max over envs); otherwise one worst-case list per slot.
-    int digits = 1;
-    for (unsigned v = 65535u / (unsigned)d.base; v > 0; v /= (unsigned)d.base) digits++;
-    const int nc = P[MGX_H_NUM_CLASSES];
-    e->class_list_tokens.assign(nc, 0);
-    int max_per_obj = 1;
-    for (int c = 0; c < nc; c++) {
-      const int32_t* C = P + d.sec[MGX_SEC_CLASSES] + c * MGX_C_WORDS;
-      int n = 0;
-      for (int w = 0; w < MGX_TAG_WORDS; w++) n += __builtin_popcount((unsigned)C[MGX_C_TAGS + w]);
-      if (!C[MGX_C_STATIC]) n += 1 + P[MGX_H_NUM_RESOURCES] * digits + (C[MGX_C_KIND] == MGX_KIND_AGENT ? 2 : 0) +
-                                 P[MGX_H_NUM_MATQ_TAGS];  // + the tags materialized queries may add
-      max_per_obj = std::max(max_per_obj, n);
-      e->class_list_tokens[c] = C[MGX_C_STATIC] ? 0 : n;
-    }
-    // without run-time object creation and without tag mutations the class maps bound the lists exactly
-    e->pool_from_maps = !P[MGX_H_SPAWNS] && !P[MGX_H_TAG_MUTATIONS];
-    long long bound = e->pool_from_maps ? e->list_tokens_bound(class_maps, 0, (size_t)E, nullptr) : (long long)S * max_per_obj;
-    e->pool_tokens = (e->pool_prefix + (int)std::min<long long>(bound, 16384) + 7) & ~7;
-  }
-  {  // sections INV_FEATURES..OBS_VALUES are contiguous (sections are laid out in id order); small block -> LDS copy
-    const int b0 = d.sec[MGX_SEC_INV_FEATURES], b1 = d.sec[MGX_SEC_WORDLIST];
-    const bool ordered = b0 <= d.sec[MGX_SEC_GV_CODE] && d.sec[MGX_SEC_GV_CODE] <= d.sec[MGX_SEC_REWARDS] &&
-                         d.sec[MGX_SEC_REWARDS] <= d.sec[MGX_SEC_OBS_VALUES] && d.sec[MGX_SEC_OBS_VALUES] <= b1;
-    e->obs_blk_start = b0;
-    e->obs_blk_words = b1 - b0;
-    e->obs_blk_lds = !d.X && ordered && (b0 & 3) == 0 && (e->obs_blk_words & 3) == 0 && e->obs_blk_words * 4 <= 8 * 1024;
-  }
-  {  // Per-action bookkeeping stats can be applied at the end of the tick unless some game value reads agent stats
-     // (a filter or SetStat evaluated mid-tick could then see them early or late).
-    bool reads_agent_stats = false;
-    const int n_code = P[MGX_H_SECTION_BASE + 2 * MGX_SEC_GV_CODE + 1];
-    const int32_t* code = P + d.sec[MGX_SEC_GV_CODE];
-    std::vector<char> reward_only(n_code, 0);  // reward expressions run in the observation kernel, after the flush
-    const int32_t* rwr = P + d.sec[MGX_SEC_REWARDS];
-    for (int k = 0; k < P[MGX_H_SECTION_BASE + 2 * MGX_SEC_REWARDS + 1]; k++)
-      for (int i = 0; i < rwr[k * MGX_RW_WORDS + MGX_RW_GV_COUNT]; i++) {
-        const int at = rwr[k * MGX_RW_WORDS + MGX_RW_GV_START] + i;
-        if (at >= 0 && at < n_code) reward_only[at] = 1;
-      }
-    // ... and then only when it reads one of the counters the deferred pass writes: the per-kind success / failed
-    // counters, action.failed and max_steps_without_motion (a game that counts zone entries in an agent stat and adds
-    // to it from a territory handler does not care when `action.move.success` is brought up to date)
-    auto booked = [&](int id) {
-      for (int k : {MGX_S_NOOP_SUCCESS, MGX_S_MOVE_SUCCESS, MGX_S_VIBE_SUCCESS})
-        if (id == d.wk[k] || id == d.wk[k + 1]) return true;
-      return id == d.wk[MGX_S_ACTION_FAILED] || id == d.wk[MGX_S_MAX_STEPS_WITHOUT_MOTION];
-    };
-    for (int i = 0; i < n_code; i++)
-      if (!reward_only[i] && code[i * MGX_GV_WORDS + MGX_GV_OP] == MGX_GOP_STAT && code[i * MGX_GV_WORDS + MGX_GV_A0] != 1 &&
-          booked(code[i * MGX_GV_WORDS + MGX_GV_A1]))
-        reads_agent_stats = true;
-    // ... or a handler WRITES one of them mid-tick (SetStat / a game-value mutation on a StatValue): set-then-deferred-add
-    // would end on a different value than the reference's add-then-set
-    bool writes_booked = false;
-    const int n_mut = mgx_sec_cnt(P, MGX_SEC_MUTS);
-    for (int i = 0; i < n_mut; i++) {
-      const int32_t* m = P + d.sec[MGX_SEC_MUTS] + i * MGX_MU_WORDS;
-      if (m[MGX_MU_OP] == MGX_MOP_STATS && m[MGX_MU_A0] != 0 && booked(m[MGX_MU_A2])) writes_booked = true;
-      if (m[MGX_MU_OP] == MGX_MOP_GAME_VALUE && m[MGX_MU_A1] >= 0) {
-        const int32_t* V = P + d.sec[MGX_SEC_OBS_VALUES] + m[MGX_MU_A1] * MGX_OV_WORDS;
-        const int32_t* c0 = P + d.sec[MGX_SEC_GV_CODE] + V[MGX_OV_GV_START] * MGX_GV_WORDS;
-        if (V[MGX_OV_GV_COUNT] > 0 && c0[MGX_GV_OP] == MGX_GOP_STAT && c0[MGX_GV_A0] != 1 && booked(c0[MGX_GV_A1])) writes_booked = true;
-      }
-    }
-    d.defer_book = (reads_agent_stats || writes_booked) ? 0 : 1;  // (flushed at the end of the launch that runs the action phase)
-    // ... and can be kept as integers beside the stat rows (mgx_world.h tail_shadow) when nothing on the device reads the
-    // cells between two flushes: no game value at all — rewards and observation values included — reads one of them or a
-    // coverage stat, and no mutation writes a coverage stat.  Lean lane-per-env dispatch only.
-    bool counters = d.defer_book && !getenv("MGX_NO_SHADOW"), coverage = true;
-#ifdef MGX_CPU_EMU
-    counters = false;   // (the sanitizer build has no flush kernel)
-#endif
-    auto covers = [&](int id) { return id == d.wk[MGX_S_CELL_UNIQUE] || id == d.wk[MGX_S_CELL_MAXDIST]; };
-    for (int i = 0; i < n_code; i++)
-      if (code[i * MGX_GV_WORDS + MGX_GV_OP] == MGX_GOP_STAT && code[i * MGX_GV_WORDS + MGX_GV_A0] != 1) {
-        if (booked(code[i * MGX_GV_WORDS + MGX_GV_A1])) counters = false;
-        if (covers(code[i * MGX_GV_WORDS + MGX_GV_A1])) coverage = false;
-      }
-    for (int i = 0; i < n_mut; i++) {
-      const int32_t* m = P + d.sec[MGX_SEC_MUTS] + i * MGX_MU_WORDS;
-      if (m[MGX_MU_OP] == MGX_MOP_STATS && m[MGX_MU_A0] != 0 && covers(m[MGX_MU_A2])) coverage = false;
-      if (m[MGX_MU_OP] == MGX_MOP_GAME_VALUE && m[MGX_MU_A1] >= 0) {
-        const int32_t* V = P + d.sec[MGX_SEC_OBS_VALUES] + m[MGX_MU_A1] * MGX_OV_WORDS;
-        const int32_t* c0 = P + d.sec[MGX_SEC_GV_CODE] + V[MGX_OV_GV_START] * MGX_GV_WORDS;
-        if (V[MGX_OV_GV_COUNT] > 0 && c0[MGX_GV_OP] == MGX_GOP_STAT && c0[MGX_GV_A0] != 1 && covers(c0[MGX_GV_A1])) coverage = false;
-      }
-    }
-    d.shadow = !counters ? 0 : coverage ? 3 : 1;   // (settled below, once the dispatch is known)
-  }
-  if (d.X) {  // can the action phase's top-level handlers run on the register VM?  (mgx_world.h apply_top)
-    bool flat = !getenv("MGX_NO_FLAT_TOP") && hnest <= MGX_MAX_HANDLER_NESTING_REG;   // (the register VM has four frames)
-    const int n_atoms = mgx_sec_cnt(P, MGX_SEC_ATOMS);
-    std::vector<char> hseen(mgx_sec_cnt(P, MGX_SEC_HANDLERS), 0);
-    std::vector<int> todo;
-    auto push = [&](int h) { if (h >= 0 && h < (int)hseen.size() && !hseen[h]) { hseen[h] = 1; todo.push_back(h); } };
-    const int32_t* mh = P + d.sec[MGX_SEC_MOVE_HANDLERS];
-    for (int k = 0; k < d.n_move_handlers; k++) push(mh[k * MGX_MH_WORDS + MGX_MH_HANDLER]);
-    for (int c = 0; c < P[MGX_H_NUM_CLASSES]; c++) {
-      const int32_t* C = P + d.sec[MGX_SEC_CLASSES] + c * MGX_C_WORDS;
-      push(C[MGX_C_ON_USE]); push(C[MGX_C_ON_AFTER_USE]); push(C[MGX_C_ON_TICK]);
-    }
-    push(d.game_on_tick);
-    while (!todo.empty() && flat) {
-      const int32_t* hd = P + d.sec[MGX_SEC_HANDLERS] + todo.back() * MGX_HD_WORDS;
-      todo.pop_back();
-      if (hd[MGX_HD_KIND] != MGX_HK_LEAF) {
-        const int32_t* kids = P + d.sec[MGX_SEC_CHILDREN] + hd[MGX_HD_CHILD_START];
-        for (int i = 0; i < hd[MGX_HD_CHILD_COUNT]; i++) push(kids[i]);
-        continue;
-      }
-      for (int i = 0; i < hd[MGX_HD_MUT_COUNT] && flat; i++) {
-        switch (P[d.sec[MGX_SEC_MUTS] + (hd[MGX_HD_MUT_START] + i) * MGX_MU_WORDS + MGX_MU_OP]) {
-          case MGX_MOP_RESOURCE_DELTA: case MGX_MOP_RESOURCE_TRANSFER: case MGX_MOP_CLEAR_INVENTORY: case MGX_MOP_ATTACK: case MGX_MOP_STATS:
-          case MGX_MOP_CHANGE_VIBE: case MGX_MOP_RELOCATE: case MGX_MOP_SWAP: case MGX_MOP_USE_TARGET: case MGX_MOP_GAME_VALUE: break;
-          default: flat = false;   // tag mutations (lifecycle handlers), query recomputation, push / spawn / query inventory
-        }
-      }
-      std::vector<int> pcs{hd[MGX_HD_FILTER_PC]};   // filters: no atom that evaluates a query (check_filters<0>)
-      std::vector<char> aseen(n_atoms, 0);
-      while (!pcs.empty() && flat) {
-        const int pc = pcs.back();
-        pcs.pop_back();
-        if (pc < 0 || pc >= n_atoms || aseen[pc]) continue;
-        aseen[pc] = 1;
-        const int32_t* a = P + d.sec[MGX_SEC_ATOMS] + pc * MGX_AT_WORDS;
-        if (a[MGX_AT_OP] == MGX_FOP_QUERY_RESOURCE || (a[MGX_AT_OP] == MGX_FOP_MAX_DISTANCE && a[MGX_AT_A2] >= 0)) flat = false;
-        if (a[MGX_AT_OP] == MGX_FOP_GAME_VALUE)
-          for (int rec : {a[MGX_AT_A1], a[MGX_AT_A2]})
-            if (rec >= 0) {
-              const int32_t* V = P + d.sec[MGX_SEC_OBS_VALUES] + rec * MGX_OV_WORDS;
-              for (int q = 0; q < V[MGX_OV_GV_COUNT]; q++) {
-                const int op = P[d.sec[MGX_SEC_GV_CODE] + (V[MGX_OV_GV_START] + q) * MGX_GV_WORDS + MGX_GV_OP];
-                if (op == MGX_GOP_QUERY_INVENTORY || op == MGX_GOP_QUERY_COUNT) flat = false;
-              }
-            }
-        pcs.push_back(a[MGX_AT_ON_TRUE]);
-        pcs.push_back(a[MGX_AT_ON_FALSE]);
-      }
-    }
-    d.flat_top = flat ? 1 : 0;
-    if (getenv("MGX_VERBOSE")) fprintf(stderr, "[mgx] action-phase handlers on the %s VM\n", flat ? "register" : "LDS");
-  }
-  {  // Do the handler tables equal a preset the build generated straight-line handler code for (mgx_handlers_gen.h)?
-    unsigned long long h = 0xCBF29CE484222325ull;   // FNV-1a over 32-bit words: mettagrid_amd/gen_handlers.py fingerprint()
-    auto mix = [&](int32_t v) { h = (h ^ (unsigned long long)(uint32_t)v) * 0x100000001B3ull; };
-    const int secs[5] = {MGX_SEC_HANDLERS, MGX_SEC_CHILDREN, MGX_SEC_ATOMS, MGX_SEC_MUTS, MGX_SEC_MOVE_HANDLERS};
-    const int words[5] = {MGX_HD_WORDS, 1, MGX_AT_WORDS, MGX_MU_WORDS, MGX_MH_WORDS};
-    for (int k = 0; k < 5; k++) {
-      const int n = mgx_sec_cnt(P, secs[k]);
-      mix(n);
-      for (int i = 0; i < n * words[k]; i++) mix(P[d.sec[secs[k]] + i]);
-    }
-    mix(P[MGX_H_NUM_CLASSES]);
-    for (int c = 0; c < P[MGX_H_NUM_CLASSES]; c++) {
-      const int32_t* C = P + d.sec[MGX_SEC_CLASSES] + c * MGX_C_WORDS;
-      mix(C[MGX_C_ON_USE]); mix(C[MGX_C_ON_AFTER_USE]); mix(C[MGX_C_ON_TICK]);
-    }
-    mix(P[MGX_H_GAME_ON_TICK]);
-    e->handler_fp = h;
-    d.gen_prog = getenv("MGX_NO_GEN") ? 0 : (!d.X && h == MGX_GEN_R3_FP) ? 3 : (d.X && h == MGX_GEN_R4_FP) ? 4 : 0;
-    if (getenv("MGX_VERBOSE")) fprintf(stderr, "[mgx] handler code: %s\n", d.gen_prog ? "generated for this program at build()" : "interpreter");
-  }
-  {  // Can the action dispatch run with one lane per AGENT (mgx_act.h)?  Every handler an action reaches must stay with
-     // its actor and target, look at no game-wide state, and the order of game-stat SETs must be recoverable.
-    bool par = !getenv("MGX_ACT_SERIAL");
-    int ap = 1;
-    while (ap < d.A) ap <<= 1;
-    if (d.A > 64) par = false;
-    if (!d.X && 16 * ap > 256) par = false;   // mgx_act_fast.hip: 16 envs per workgroup of at most 256 lanes
-    // Measured (MI355X, 65 536 envs): 64 agents per env 4.92 -> 2.0 ms; 16 agents per env 0.445 -> 0.52 ms — four envs share
-    // a wavefront there and a round costs what 2.4 serial steps cost, so lean games stay lane per env unless asked.
-    if (!d.X && !getenv("MGX_ACT_LEAN")) par = false;
-    if (d.X && !d.flat_top) par = false;      // tag mutations, query recomputation / filters: lane-per-env VM
-    if (d.X && !e->prog_in_lds) par = false;  // mgx_act_x.hip is built for the hot program range in LDS only
-    const int32_t* mh = P + d.sec[MGX_SEC_MOVE_HANDLERS];
-    for (int k = 0; k < d.n_move_handlers; k++)
-      if (mh[k * MGX_MH_WORDS + MGX_MH_MAX_RANGE] != 1) par = false;   // footprint = own cell + the cell ahead
-    for (int c = 0; c < P[MGX_H_NUM_CLASSES]; c++) {
-      const int32_t* C = P + d.sec[MGX_SEC_CLASSES] + c * MGX_C_WORDS;
-      if (d.X && C[MGX_C_KIND] == MGX_KIND_AGENT && C[MGX_C_TERR_COUNT] > 0) par = false;   // a moving territory source re-registers
-    }
-    std::vector<int> gset;
-    const int n_code = mgx_sec_cnt(P, MGX_SEC_GV_CODE), n_vals = mgx_sec_cnt(P, MGX_SEC_OBS_VALUES);
-    auto pure_value = [&](int rec) {   // reads inventories, agent-scope stats and constants only
-      if (rec < 0) return true;
-      if (rec >= n_vals) return false;
-      const int32_t* V = P + d.sec[MGX_SEC_OBS_VALUES] + rec * MGX_OV_WORDS;
-      for (int q = 0; q < V[MGX_OV_GV_COUNT]; q++) {
-        const int at = V[MGX_OV_GV_START] + q;
-        if (at < 0 || at >= n_code) return false;
-        const int32_t* g = P + d.sec[MGX_SEC_GV_CODE] + at * MGX_GV_WORDS;
-        if (g[MGX_GV_OP] == MGX_GOP_QUERY_INVENTORY || g[MGX_GV_OP] == MGX_GOP_QUERY_COUNT) return false;
-        if (g[MGX_GV_OP] == MGX_GOP_STAT && g[MGX_GV_A0] == 1) return false;
-      }
-      return true;
-    };
-    const int n_atoms = mgx_sec_cnt(P, MGX_SEC_ATOMS), n_hd = mgx_sec_cnt(P, MGX_SEC_HANDLERS);
-    bool saw_use_target = false;
-    auto local = [&](std::vector<int> todo, bool may_move) {   // every handler reachable from `todo`
-      std::vector<char> hseen(n_hd, 0);
-      std::vector<int> stack;
-      auto push = [&](int h) { if (h >= 0 && h < n_hd && !hseen[h]) { hseen[h] = 1; stack.push_back(h); } };
-      for (int h : todo) push(h);
-      bool use_target = false;
-      while (!stack.empty()) {
-        const int32_t* hd = P + d.sec[MGX_SEC_HANDLERS] + stack.back() * MGX_HD_WORDS;
-        stack.pop_back();
-        if (hd[MGX_HD_KIND] != MGX_HK_LEAF) {
-          const int32_t* kids = P + d.sec[MGX_SEC_CHILDREN] + hd[MGX_HD_CHILD_START];
-          for (int i = 0; i < hd[MGX_HD_CHILD_COUNT]; i++) push(kids[i]);
-          continue;
-        }
-        for (int i = 0; i < hd[MGX_HD_MUT_COUNT]; i++) {
-          const int32_t* m = P + d.sec[MGX_SEC_MUTS] + (hd[MGX_HD_MUT_START] + i) * MGX_MU_WORDS;
-          switch (m[MGX_MU_OP]) {
-            case MGX_MOP_RESOURCE_DELTA: case MGX_MOP_CLEAR_INVENTORY: case MGX_MOP_ATTACK: case MGX_MOP_CHANGE_VIBE: break;
-            case MGX_MOP_RESOURCE_TRANSFER: if (d.X && m[MGX_MU_A4]) return false; break;   // may remove the emptied object
-            case MGX_MOP_RELOCATE: case MGX_MOP_SWAP: if (!may_move) return false; break;
-            case MGX_MOP_USE_TARGET: use_target = true; break;
-            case MGX_MOP_STATS:
-              if (!pure_value(m[MGX_MU_A3])) return false;
-              if (m[MGX_MU_A0] == 0 && std::find(gset.begin(), gset.end(), m[MGX_MU_A2]) == gset.end()) gset.push_back(m[MGX_MU_A2]);
-              break;
-            case MGX_MOP_GAME_VALUE: {
-              if (!pure_value(m[MGX_MU_A1]) || !pure_value(m[MGX_MU_A2])) return false;   // (a game-scope target is impure too)
-              break;
-            }
-            default: return false;
-          }
-        }
-        std::vector<int> pcs{hd[MGX_HD_FILTER_PC]};
-        std::vector<char> aseen(n_atoms, 0);
-        while (!pcs.empty()) {
-          const int pc = pcs.back();
-          pcs.pop_back();
-          if (pc < 0 || pc >= n_atoms || aseen[pc]) continue;
-          aseen[pc] = 1;
-          const int32_t* a = P + d.sec[MGX_SEC_ATOMS] + pc * MGX_AT_WORDS;
-          switch (a[MGX_AT_OP]) {
-            case MGX_FOP_VIBE: case MGX_FOP_RESOURCE: case MGX_FOP_SHARED_TAG: case MGX_FOP_TAG: case MGX_FOP_TARGET_LOC_EMPTY:
-            case MGX_FOP_TARGET_IS_USABLE: case MGX_FOP_PERIODIC: case MGX_FOP_TRUE: break;
-            case MGX_FOP_GAME_VALUE: if (!pure_value(a[MGX_AT_A1]) || !pure_value(a[MGX_AT_A2])) return false; break;
-            case MGX_FOP_MAX_DISTANCE: if (a[MGX_AT_A2] >= 0) return false; break;
-            default: return false;
-          }
-          pcs.push_back(a[MGX_AT_ON_TRUE]);
-          pcs.push_back(a[MGX_AT_ON_FALSE]);
-        }
-      }
-      saw_use_target = use_target;   // UseTarget applies the target's on_use / the actor's on_after_use: roots of the action phase
-      return true;
-    };
-    std::vector<int> act_roots, tick_roots;
-    for (int k = 0; k < d.n_move_handlers; k++) act_roots.push_back(mh[k * MGX_MH_WORDS + MGX_MH_HANDLER]);
-    for (int c = 0; c < P[MGX_H_NUM_CLASSES]; c++) {
-      const int32_t* C = P + d.sec[MGX_SEC_CLASSES] + c * MGX_C_WORDS;
-      act_roots.push_back(C[MGX_C_ON_USE]);
-      act_roots.push_back(C[MGX_C_ON_AFTER_USE]);
-      tick_roots.push_back(C[MGX_C_ON_TICK]);
-    }
-    // Two agents of an env side by side in the lean lane-per-env kernel (MgxDev::duo, mgx_world.h): the same conditions as the
-    // lane-per-agent dispatch — every handler an action reaches stays with actor and target, move handlers look one cell
-    // ahead, at most four game-scope stats are SET — without that kernel's shape limits.
-    bool duo = !d.X && !getenv("MGX_NO_DUO") && d.A >= 2;
-    std::vector<int> duo_gset;
-    {
-      for (int k = 0; k < d.n_move_handlers; k++)
-        if (mh[k * MGX_MH_WORDS + MGX_MH_MAX_RANGE] != 1) duo = false;
-      const std::vector<int> gset_saved = gset;
-      gset.clear();
-      if (duo && !local(act_roots, true)) duo = false;
-      duo_gset = gset;
-      gset = gset_saved;
-      saw_use_target = false;
-      if (duo_gset.size() > 4) duo = false;
-    }
-    {   // on_tick handlers that stay with their agent (no game-scope stat, no UseTarget, nothing that moves): the helper lanes
-        // of the lean kernel may run them for half of the agents (MgxDev::tick_split)
-      const std::vector<int> gset_saved = gset;
-      const bool ok = d.any_on_tick && !d.X && local(tick_roots, false) && !saw_use_target && gset.size() == gset_saved.size();
-      gset = gset_saved;
-      saw_use_target = false;
-      d.tick_split = (ok && !getenv("MGX_NO_TICK_SPLIT")) ? 1 : 0;
-    }
-    if (par && !local(act_roots, true)) par = false;
-    bool tick = false;
-    if (par && !d.X) {   // the lean kernel is the whole world update: its on_tick handlers must be lane-local as well
-      if (d.any_on_tick && (!local(tick_roots, false) || saw_use_target)) par = false;   // (an on_tick handler that uses itself: lane per env)
-      tick = par;
-    }
-    if (gset.size() > 4) par = false;
-#ifdef MGX_CPU_EMU
-    par = false;   // wavefront-cooperative (ballot / readlane): not part of the sanitizer build
-#endif
-    d.act_par = par ? 1 : 0;
-    // integer bookkeeping: counters and coverage stats in the lean lane-per-env kernel (all or nothing: one fused pass),
-    // counters only in the lane-per-agent dispatch kernels (bookkeeping_flush_one), none in the extended lane-per-env kernel
-    if (d.act_par) d.shadow &= 1;
-    else if (d.X || d.shadow != 3) d.shadow = 0;
-    d.act_replay = getenv("MGX_ACT_SHUFFLE_REPLAY") ? 1 : 0;
-    d.act_tick = (par && tick) ? 1 : 0;
-    d.act_ngset = par ? (int)gset.size() : 0;
-    for (int k = 0; k < 4; k++) d.act_gset_ids[k] = (par && k < (int)gset.size()) ? gset[k] : -1;
-    d.duo = (duo && !par) ? 1 : 0;
-    if (d.duo) {   // the paired dispatch orders game-stat SETs through the same per-env cells
-      d.act_ngset = (int)duo_gset.size();
-      for (int k = 0; k < 4; k++) d.act_gset_ids[k] = k < (int)duo_gset.size() ? duo_gset[k] : -1;
-    }
-    if (getenv("MGX_VERBOSE")) fprintf(stderr, "[mgx] lean dispatch: %s\n", d.duo ? "two agents of an env at a time (disjoint footprints)" : "one agent at a time");
-    if (getenv("MGX_VERBOSE")) fprintf(stderr, "[mgx] action dispatch: one lane per %s\n", par ? "agent (conflict-ordered rounds)" : "env");
-  }
-  {  // reward code made only of inventory / constant arithmetic reads nothing the observation kernel writes
-    bool pure = !d.X;
-    const int32_t* rw = P + d.sec[MGX_SEC_REWARDS];
-    const int n_rw = P[MGX_H_SECTION_BASE + 2 * MGX_SEC_REWARDS + 1];
-    for (int k = 0; k < n_rw && pure; k++) {
-      const int32_t* code = P + d.sec[MGX_SEC_GV_CODE] + rw[k * MGX_RW_WORDS + MGX_RW_GV_START] * MGX_GV_WORDS;
-      for (int i = 0; i < rw[k * MGX_RW_WORDS + MGX_RW_GV_COUNT]; i++) {
-        const int op = code[i * MGX_GV_WORDS + MGX_GV_OP];
-        if (op == MGX_GOP_STAT || op == MGX_GOP_QUERY_INVENTORY || op == MGX_GOP_QUERY_COUNT) pure = false;
-      }
-    }
-    e->rewards_early = pure;
-    // Extended games: the reward expressions may still be evaluated before the kernel's end — by a wavefront that has no
-    // share of the encode — when no operand is something this kernel writes (the cell.visited agent stat, the token game
-    // stats) and none is a query (those go through mgx_values_kernel).
-    {
-      bool safe = d.X != 0;
-      for (int k = 0; k < n_rw && safe; k++) {
-        const int32_t* code = P + d.sec[MGX_SEC_GV_CODE] + rw[k * MGX_RW_WORDS + MGX_RW_GV_START] * MGX_GV_WORDS;
-        for (int i = 0; i < rw[k * MGX_RW_WORDS + MGX_RW_GV_COUNT]; i++) {
-          const int32_t* ins = code + i * MGX_GV_WORDS;
-          const int op = ins[MGX_GV_OP];
-          if (op == MGX_GOP_QUERY_INVENTORY || op == MGX_GOP_QUERY_COUNT) safe = false;
-          if (op == MGX_GOP_STAT) {
-            const int id = ins[MGX_GV_A1];
-            if (ins[MGX_GV_A0] != 1 && id == d.wk[MGX_S_CELL_VISITED]) safe = false;
-            if (ins[MGX_GV_A0] == 1 && (id == d.wk[MGX_S_GAME_TOKENS_WRITTEN] || id == d.wk[MGX_S_GAME_TOKENS_FREE] ||
-                                        id == d.wk[MGX_S_GAME_TOKENS_DROPPED])) safe = false;
-          }
-        }
-      }
-      e->rewards_mid = safe && !getenv("MGX_REWARDS_LATE");
-    }
-    auto has_query = [&](int start, int count) {
-      for (int i = 0; i < count; i++) {
-        const int op = P[d.sec[MGX_SEC_GV_CODE] + (start + i) * MGX_GV_WORDS + MGX_GV_OP];
-        if (op == MGX_GOP_QUERY_INVENTORY || op == MGX_GOP_QUERY_COUNT) return true;
-      }
-      return false;
-    };
-    for (int k = 0; k < n_rw; k++)
-      if (has_query(rw[k * MGX_RW_WORDS + MGX_RW_GV_START], rw[k * MGX_RW_WORDS + MGX_RW_GV_COUNT])) e->rewards_ext = true;
-    bool obsval_ext = false;
-    for (int i = 0; i < d.n_obs_values; i++) {
-      const int32_t* V = P + d.sec[MGX_SEC_OBS_VALUES] + i * MGX_OV_WORDS;
-      if (has_query(V[MGX_OV_GV_START], V[MGX_OV_GV_COUNT])) obsval_ext = true;
-    }
-    if (obsval_ext) {
-      int arc = e->alloc(&d.obsval, (size_t)d.E * d.A * d.n_obs_values);
-      if (arc != MGX_OK) { mgx_destroy(e); return arc; }
-    }
-  }
-  // The world kernel's LDS staging (see above): up to 160 KB, i.e. 148 agents per env in the lean variant (refused above
-  // already).  Past 64 KB the kernels need the opt-in attribute.
-  if (e->lds_world > 160 * 1024) {
-    mgx_destroy(e);
-    return fail(MGX_ERR_PROGRAM, "mgx_create: too many agents per env for the world kernel's LDS staging (160 KB per 64 envs)");
-  }
-  {
+  // ---- raise the kernels' dynamic LDS limits (past 64 KB they need the opt-in attribute) ----
+  if (rc == MGX_OK) {  // constant-memory slot of the lean world kernel: engines take them round-robin
     static std::mutex mu;
     static int next_slot = 0;
     std::lock_guard<std::mutex> lock(mu);
     e->slot = next_slot;
     if (!d.X) next_slot = (next_slot + 1) % MGX_FAST_SLOTS;
   }
-  if (!(d.X ? mgx_world_x_set_lds(e->lds_world)
-            : (e->slot == 0 ? mgx_world_fast_set_lds_s0(e->lds_world) : mgx_world_fast_set_lds_s1(e->lds_world)))) {
-    mgx_destroy(e);
-    return fail(MGX_ERR_HIP, "mgx_create: cannot raise the world kernel's dynamic LDS limit");
+  if (rc == MGX_OK && e->aoe_kernel && !mgx_aoe_set_lds(d.aoe_nstat, e->aoe_prog_lds ? e->prog_lds_words : 0))
+    rc = fail(MGX_ERR_HIP, "mgx_create: cannot raise the area-effect kernel's dynamic LDS limit");
+  if (rc == MGX_OK && !(d.X ? mgx_world_x_set_lds(e->lds_world)
+                            : (e->slot == 0 ? mgx_world_fast_set_lds_s0(e->lds_world) : mgx_world_fast_set_lds_s1(e->lds_world))))
+    rc = fail(MGX_ERR_HIP, "mgx_create: cannot raise the world kernel's dynamic LDS limit");
+  if (rc == MGX_OK && d.act_par && !(d.X ? mgx_act_x_set_lds(e->lds_act) : mgx_act_fast_set_lds_s0(e->lds_act)))
+    rc = fail(MGX_ERR_HIP, "mgx_create: cannot raise the action kernel's dynamic LDS limit");
+  A_(raise_obs_lds(e));
+
+  // ---- upload: the program, the plan's tables, maps and seeds ----
+  H_(hipMemcpyAsync(dprog, program, program_words * 4, hipMemcpyHostToDevice, e->stream), "mgx_create upload");
+  if (e->aoe_kernel) {
+    if (!e->aoe_stat_ids.empty())
+      H_(hipMemcpyAsync(dids, e->aoe_stat_ids.data(), e->aoe_stat_ids.size() * 2, hipMemcpyHostToDevice, e->stream), "aoe stat table upload");
+    H_(hipMemcpyAsync(dmap, e->aoe_stat_map.data(), 256, hipMemcpyHostToDevice, e->stream), "aoe stat table upload");
   }
-  if (d.act_par) {
-    {  // footprint table + (maps up to 64 x 64) the cell map of the conflict lookup, per workgroup
-      int ap = 1;
-      while (ap < d.A) ap <<= 1;
-      const int epg = d.X ? mgx_act_x_epg() : mgx_act_fast_epg();
-      d.act_map = (d.H * d.W <= 4096 && !getenv("MGX_ACT_NO_MAP")) ? 1 : 0;
-      d.act_lds_extra = ((4 * ap * epg + 15) & ~15) + (d.act_map ? epg * ((d.H * d.W + 15) & ~15) : 0);
-    }
-    e->lds_act = (d.X ? mgx_act_x_lds_bytes(d.A, d.x_aoe_lds != 0, d.act_lds_extra) : mgx_act_fast_lds_bytes(d.A, d.act_lds_extra)) +
-                 (e->prog_in_lds ? (size_t)e->prog_lds_words * 4 : 0);
-    if (!(d.X ? mgx_act_x_set_lds(e->lds_act) : mgx_act_fast_set_lds_s0(e->lds_act))) {
-      mgx_destroy(e);
-      return fail(MGX_ERR_HIP, "mgx_create: cannot raise the action kernel's dynamic LDS limit");
-    }
+  H_(hipMemcpyAsync(dinfo, e->cls_tokinfo.data(), e->cls_tokinfo.size() * 4, hipMemcpyHostToDevice, e->stream), "class token upload");
+  H_(hipMemcpyAsync(dtoks, e->cls_tok.data(), e->cls_tok.size() * 2, hipMemcpyHostToDevice, e->stream), "class token upload");
+  H_(hipMemcpyAsync(e->dmaps, class_maps, E * HW * 2, hipMemcpyHostToDevice, e->stream), "mgx_create upload");
+  H_(hipMemcpyAsync(e->dseeds, seeds, E * 4, hipMemcpyHostToDevice, e->stream), "mgx_create upload");
+
+  // ---- construct: the init kernel, then ctor -> _make_buffers -> set_buffers -> _init_buffers (mettagrid_c.cpp:190, 271-292) ----
+  if (rc == MGX_OK) {
+    MGX_LAUNCH_INIT(e->stream, dev_copy(e), (const uint16_t*)e->dmaps, (const int32_t*)nullptr, (const uint32_t*)e->dseeds,
+                    (const uint8_t*)nullptr, MgxList());
+    rc = hip_rc(hipGetLastError(), "mgx_init_kernel");
   }
-  if (e->verbose && d.X)
-    fprintf(stderr, "[mgx] extended world kernel: %zu bytes of private memory per lane\n", mgx_world_x_private_bytes());
-  rc = size_obs_lds(e);
-  if (rc != MGX_OK) { mgx_destroy(e); return rc; }
-  hipError_t he = hipSuccess;
-  if (he == hipSuccess) he = hipMemcpyAsync(dprog, program, program_words * 4, hipMemcpyHostToDevice, e->stream);
-  if (he == hipSuccess) he = hipMemcpyAsync(dmaps, class_maps, E * HW * 2, hipMemcpyHostToDevice, e->stream);
-  if (he == hipSuccess) he = hipMemcpyAsync(dseeds, seeds, E * 4, hipMemcpyHostToDevice, e->stream);
-  if (he != hipSuccess) { mgx_destroy(e); return fail(MGX_ERR_HIP, std::string("mgx_create upload: ") + hipGetErrorString(he)); }
-  e->dmaps = dmaps;
-  e->dseeds = dseeds;
-  MGX_LAUNCH_INIT(e->stream, dev_copy(e), (const uint16_t*)dmaps,
-                     (const int32_t*)nullptr, (const uint32_t*)dseeds, (const uint8_t*)nullptr, MgxList());
-  he = hipGetLastError();
-  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-  if (he != hipSuccess) { mgx_destroy(e); return fail(MGX_ERR_HIP, std::string("mgx_init_kernel: ") + hipGetErrorString(he)); }
-  MGX_TRACE_POINT(e, "init kernel");
-  for (int i = 0; i <= MGX_T_COUNT; i++) (void)hipEventCreate(&e->ev[i]);
-  (void)hipEventCreateWithFlags(&e->world_done, hipEventDisableTiming);
-  rc = init_buffers(e);  // ctor -> _make_buffers -> set_buffers -> _init_buffers (mettagrid_c.cpp:190, 271-292)
+  H_(hipStreamSynchronize(e->stream), "mgx_init_kernel");
+#undef A_
+#undef H_
+  if (rc == MGX_OK) {
+    MGX_TRACE_POINT(e, "init kernel");
+    for (int i = 0; i <= MGX_T_COUNT; i++) (void)hipEventCreate(&e->ev[i]);
+    (void)hipEventCreateWithFlags(&e->world_done, hipEventDisableTiming);
+    rc = init_buffers(e);
+  }
   if (rc != MGX_OK) { mgx_destroy(e); return rc; }
   { std::lock_guard<std::mutex> g(g_live_mu); g_live.push_back(e); }
   *out = e;
@@ -1570,39 +912,27 @@ static int validate_maps(const mgx_engine* e, const uint16_t* maps, size_t n_map
 static int fit_maps(mgx_engine* e, const uint16_t* maps, size_t first, size_t count, const uint8_t* mask, const char* who) {
   const MgxDev& d = e->d;
   const int32_t* P = e->prog.data();
-  const int nc = P[MGX_H_NUM_CLASSES];
   const size_t hw = (size_t)d.H * d.W;
   if (d.X && (d.NF || d.NM || d.NTS || mgx_sec_cnt(P, MGX_SEC_AOES) > 0 || d.NT > 0)) {
-    std::vector<int> cf(nc, 0), cm(nc, 0), ct(nc, 0);
-    for (int c = 0; c < nc; c++) {
-      const int32_t* C = P + d.sec[MGX_SEC_CLASSES] + c * MGX_C_WORDS;
-      for (int i = 0; i < C[MGX_C_AOE_COUNT]; i++)
-        (P[d.sec[MGX_SEC_AOES] + (C[MGX_C_AOE_START] + i) * MGX_AO_WORDS + MGX_AO_STATIC] ? cf[c] : cm[c])++;
-      ct[c] = C[MGX_C_TERR_COUNT];
-    }
-    const int spare_f = P[MGX_H_SPAWNS] ? 0 : 0;
-    (void)spare_f;
+    const std::vector<MgxSources> cls = mgx_class_sources(P);
     for (size_t m = first; m < first + count; m++) {
       if (mask && !mask[m]) continue;
-      int f = 0, mo = 0, t = 0;
-      for (size_t i = 0; i < hw; i++) {
-        const int k = maps[m * hw + i];
-        if (k > 0 && k <= nc) { f += cf[k - 1]; mo += cm[k - 1]; t += ct[k - 1]; }
-      }
-      if (f > d.NF || mo > d.NM || t > d.NTS)
-        return fail(MGX_ERR_PROGRAM, std::string(who) + ": a map holds more AoE / territory sources (" + std::to_string(f) + " fixed, " +
-                                         std::to_string(mo) + " mobile, " + std::to_string(t) + " territory) than any map given to "
+      const MgxSources s = mgx_map_sum(cls, maps + m * hw, hw);
+      if (s.f > d.NF || s.m > d.NM || s.t > d.NTS)
+        return fail(MGX_ERR_PROGRAM, std::string(who) + ": a map holds more AoE / territory sources (" + std::to_string(s.f) + " fixed, " +
+                                         std::to_string(s.m) + " mobile, " + std::to_string(s.t) + " territory) than any map given to "
                                          "mgx_create (capacity " + std::to_string(d.NF) + " / " + std::to_string(d.NM) + " / " +
                                          std::to_string(d.NTS) + "): create the engine with a map that has the maximum");
     }
   }
   if (e->pool_from_maps) {  // new maps may hold more non-static objects than any map seen so far
-    const long long bound = e->list_tokens_bound(maps, first, count, mask);
-    const int need = (e->pool_prefix + (int)std::min<long long>(bound, 16384) + 7) & ~7;
+    const int need = mgx_pool_tokens(e->pool_prefix, e->list_tokens_bound(maps, first, count, mask));
     if (need > e->pool_tokens) {
+      const bool jit = e->obs_variant == 9 && e->jit_obs.mod;
       e->pool_tokens = need;
-      int rcl = size_obs_lds(e);
-      if (rcl) return rcl;
+      if (!e->size_obs(e->sw)) return fail(MGX_ERR_PROGRAM, MGX_OBS_LDS_REFUSAL);
+      if (jit && e->lds_obs <= 64 * 1024) e->obs_variant = 9;   // (the code object's shape does not depend on the pool size)
+      return raise_obs_lds(e);
     }
   }
   return MGX_OK;
@@ -1832,7 +1162,7 @@ int mgx_attach_code(mgx_engine* e, int32_t kind, const char* path) {
     if (info[1] != (long long)sizeof(MgxDev) || info[4] != MGX_VERSION) return refuse("built against other headers than this libmgx");
     if (!e->obs_blk_lds || e->box_dtype != MGX_BOX_OFF) return refuse("the engine does not run the lean token-row kernel with the program block in LDS");
     const long long* K = info + 5;   // H, W, A, S, T, NOFF, BASE, NOV, NT, NRW, FLAGS, MAX_STEPS, BLKW, MASK_FEAT, REWARDS_EARLY
-    const int rmode = e->rewards_early ? 1 : e->rewards_mid ? 2 : 0;
+    const int rmode = e->rmode;
     const bool same = d.H == K[0] && d.W == K[1] && d.A == K[2] && d.S == K[3] && d.T == K[4] && d.NOFF == K[5] && d.base == K[6] &&
                       d.n_obs_values == K[7] && d.NT == K[8] && d.NRW == K[9] && d.flags == K[10] && (K[11] < 0 || d.max_steps == K[11]) &&
                       e->obs_blk_words == K[12] && d.aoe_mask_feat == K[13] && rmode == K[14];
@@ -2005,7 +1335,7 @@ int mgx_step(mgx_engine* e) {
         else mgx_launch_world_fast_s1(e->prog_in_lds, e->lds_world, e->stream, e->d, pw);
       }
       MGX_MARK(1); MGX_MARK(2); MGX_MARK(3);
-    } else if (e->aoe_local && (d.NF > 0 || d.NM > 0 || d.NT > 0)) {
+    } else if (e->aoe_kernel) {
       if (d.act_par) {
         if (e->jit_actx.mod) { int jrc = launch_act_x_jit(e, dev_copy_world_x(e), pw); if (jrc) return jrc; }
         else mgx_launch_act_x(e->prog_in_lds, e->lds_act, e->stream, e->d, dev_copy_world_x(e), pw);
@@ -2017,7 +1347,7 @@ int mgx_step(mgx_engine* e) {
       MGX_MARK(1);
       int trc = launch_terr(e);  // the per-agent territory effects read the ownership map
       if (trc) return trc;
-      mgx_launch_aoe(e->stream, e->d, dev_copy(e), e->aoe_prog_lds ? dev_copy_hot(e) : nullptr, e->aoe_prog_lds ? e->hot_words : 0);
+      mgx_launch_aoe(e->stream, e->d, dev_copy(e), e->aoe_prog_lds ? dev_copy_hot(e) : nullptr, e->aoe_prog_lds ? e->prog_lds_words : 0);
       MGX_TRACE_POINT(e, "aoe kernel");
       MGX_MARK(2);
       if (!d.cov_in_aoe) mgx_launch_world_x(e->prog_in_lds, e->lds_world, e->stream, e->d, dev_copy_world_x(e), pw, MGX_PH_TAIL);
@@ -2468,24 +1798,23 @@ int32_t mgx_integer_bookkeeping(const mgx_engine* e) { return e ? e->d.shadow : 
 int32_t mgx_create_paths(const mgx_engine* e) {
   if (!e) return 0;
   const MgxDev& d = e->d;
-  const bool aoe_kernel = d.X && e->aoe_local && (d.NF > 0 || d.NM > 0 || d.NT > 0);   // (mgx_create: `split`)
   int32_t p = 0;
   auto set = [&](int bit, bool on) { if (on) p |= bit; };
   set(MGX_PATH_X, d.X != 0);
   set(MGX_PATH_PROG_LDS, e->prog_in_lds);
-  set(MGX_PATH_AOE_LOCAL, aoe_kernel);
+  set(MGX_PATH_AOE_LOCAL, e->aoe_kernel);
   set(MGX_PATH_TICK_IN_AOE, d.tick_in_aoe != 0);
   set(MGX_PATH_COV_IN_AOE, d.cov_in_aoe != 0);
-  set(MGX_PATH_AOE_PROG_LDS, aoe_kernel && e->aoe_prog_lds);
+  set(MGX_PATH_AOE_PROG_LDS, e->aoe_prog_lds);
   set(MGX_PATH_X_AOE_LDS, d.x_aoe_lds != 0);
-  set(MGX_PATH_FLAT_TOP, d.X && d.flat_top);
+  set(MGX_PATH_FLAT_TOP, d.flat_top != 0);
   set(MGX_PATH_TICK_SPLIT, d.tick_split != 0);
   set(MGX_PATH_ACT_PAR, d.act_par != 0);
   set(MGX_PATH_DUO, d.duo != 0);
-  set(MGX_PATH_ACT_MAP, d.act_par && d.act_map);
+  set(MGX_PATH_ACT_MAP, d.act_map != 0);
   set(MGX_PATH_SHADOW, d.shadow != 0);
-  set(MGX_PATH_REWARDS_EARLY, e->rewards_early);
-  set(MGX_PATH_REWARDS_MID, e->rewards_mid);
+  set(MGX_PATH_REWARDS_EARLY, e->rmode == 1);
+  set(MGX_PATH_REWARDS_MID, e->rmode == 2);
   set(MGX_PATH_REWARDS_EXT, e->rewards_ext);
   set(MGX_PATH_OBS_512, e->obs_threads == 512);
   set(MGX_PATH_WORLD_LDS_64K, e->lds_world > 64 * 1024);
