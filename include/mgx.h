@@ -33,6 +33,9 @@ enum {
   MGX_ENV_DEPTH = 4,            /* handler / inventory-limit recursion deeper than the engine supports */
   MGX_ENV_TOO_MANY_OBJECTS = 8, /* map holds more objects than MGX_H_MAX_OBJECTS slots */
   MGX_ENV_TOKEN_POOL = 16,      /* per-env LDS token cache of the observation kernel exhausted */
+  MGX_ENV_PROXY_INVENTORY = 32, /* a handler gave a territory proxy cell an inventory */
+  MGX_ENV_AGENT_LIFECYCLE = 64, /* a handler spawned or removed an agent */
+  MGX_ENV_BAD_STATE = 128,      /* mgx_load_envs / mgx_copy_envs: the env's record has another magic or format; the env is untouched */
   MGX_ENV_INTERNAL = 0x8000     /* set by mgx_state_digests: a per-agent mirror (cell, class) differs from the object row — an engine bug */
 };
 
@@ -337,6 +340,34 @@ enum {
   MGX_PATH_COUNT = 19
 };
 int32_t mgx_create_paths(const mgx_engine* e);
+
+/* ---- Saving, loading and copying envs' state (csrc/mgx_env_state.h; DESIGN.md "Env state") ----
+ * An env's state is one RECORD of record_bytes bytes: a header (include/mgx_program.h MGX_ES_*) and the env's episode-owned
+ * arrays — world, agents, stats, the Mersenne-Twister state, its rows of the bound observation / reward / terminal /
+ * truncation buffers and its auto-reset words.  Not in it: what belongs to the slot (its seed for later restarts, its map-pool
+ * schedule, the create maps, the bound buffers) — a loaded or copied env finishes the saved episode as it would have, and
+ * its NEXT episode is the slot's.  The format word hashes the program, every capacity and the integer bookkeeping path
+ * (mgx_integer_bookkeeping); engines of equal format load each other's records.
+ * mgx_env_state_layout: the info of an engine that mgx_create would make from the program and n_maps class maps (host-only,
+ * no GPU call).  The save / load / copy calls enqueue on the engine's stream and return without waiting for the device
+ * (MGX_MEM_HOST buffers: the restored rows are copied into them before return); env lists are host memory.
+ * Load refuses with MGX_ERR_BAD_ARG, before touching anything: another format, n <= 0, an index out of range, a destination
+ * listed twice, box output on (mgx_set_box_output; save and copy refuse it too).  A record whose own header does not match
+ * leaves its env untouched and sets MGX_ENV_BAD_STATE.  saved->pool_tokens above the engine's grows the observation kernel's token pool.
+ * Copy acts as if every source were read before any destination is written ([0, 1] -> [1, 0] swaps). */
+struct mgx_env_state_info {   /* (a struct tag: the name is also the entry point that fills one) */
+  int64_t record_bytes;
+  uint64_t format;
+  int32_t version, pool_tokens, n_segments, reserved;
+};
+typedef struct mgx_env_state_info mgx_env_state_info_t;
+int mgx_env_state_layout(const int32_t* program, size_t program_words, const uint16_t* class_maps, int32_t n_maps,
+                         mgx_env_state_info_t* out);
+int mgx_env_state_info(mgx_engine* e, mgx_env_state_info_t* out);
+int mgx_save_envs(mgx_engine* e, const int32_t* envs, int32_t n, void* dst);   /* dst: device memory, n * record_bytes */
+int mgx_load_envs(mgx_engine* e, const int32_t* envs, int32_t n, const void* src, const mgx_env_state_info_t* saved);
+int mgx_copy_envs(mgx_engine* e, const int32_t* src_envs, const int32_t* dst_envs, int32_t n);
+
 int32_t mgx_num_envs(const mgx_engine* e);
 int32_t mgx_num_agents(const mgx_engine* e);   /* per env */
 int32_t mgx_num_tokens(const mgx_engine* e);

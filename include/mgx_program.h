@@ -28,6 +28,13 @@
                                           on_use / on_after_use tree reached by UseTarget): the LDS VM's MGX_VM_FRAMES */
 #define MGX_MAX_HANDLER_NESTING_REG 4  /* ... on the register VM (lean programs, extended flat_top): its four frames */
 #define MGX_VALUE_STACK 8              /* game-value expression stack (MgxValueStack) */
+
+/* Saved env state (include/mgx.h mgx_save_envs; mettagrid_amd/csrc/mgx_env_state.h): every record starts with a header of
+ * MGX_ES_HEADER_BYTES: u32 magic | u32 layout version | u64 format word | u32 step | u32 slot saved from | u32 record bytes | u32 0 */
+#define MGX_ES_MAGIC 0x5345584D /* "MXES" little-endian */
+#define MGX_ES_VERSION 1
+#define MGX_ES_HEADER_BYTES 32
+#define MGX_ES_ALIGN 16         /* every segment of a record starts on this boundary */
 #define MGX_MAX_QUERY_DEPTH 3          /* query nesting (the device's eval_query<3> at the top) */
 #define MGX_INVALID_WINDOW 16 /* action.invalid_index.<k> is a fixed stat column for k in [-16,-1] and [n_actions, n_actions+15] */
 #define MGX_INVALID_EXTRA 4   /* ... and one of this many (k, count) pairs per agent and episode for any other k */

@@ -19,6 +19,7 @@
 #include "mgx_aoe_local.h"
 #include "mgx_episode.h"
 #include "mgx_plan.h"       // mgx_create's host-only half: validation and every create-time decision
+#include "mgx_env_state.h"  // what an env's state is (the one list of its arrays) and the save / load kernel
 
 
 // Territory ownership map (TerritoryTracker::compute_cell_ownership, core/territory_tracker.cpp:215-252) of every cell,
@@ -290,6 +291,15 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
   bool ep_pending = false;          // a snapshot has been requested and not fetched yet
   int ep_tw() const { return MGX_EP_TOT_HDR + 2 * (ep.NG + ep.NS); }
   unsigned long long* d_digest = nullptr;   // [E] mgx_state_digests
+  // saved env state (mgx_env_state.h): the record layout, the device segment table, the staging of mgx_copy_envs
+  MgxEnvStateLayout es;
+  std::vector<MgxSeg> es_segs_host;   // what d_es_segs holds
+  MgxSeg* d_es_segs = nullptr;
+  uint8_t* d_es_buf = nullptr;        // mgx_copy_envs: records of the sources
+  size_t es_buf_bytes = 0;
+  std::vector<uint8_t> es_lists;      // host side of the env lists uploaded through d_stage ...
+  hipEvent_t es_ev = nullptr;         // ... recorded behind that upload: the vector is reused once it has completed
+  bool es_ev_pending = false;
   int32_t* d_objs = nullptr;        // mgx_get_objects_batch: env list | counts | packed records
   size_t objs_cap = 0;              // envs the buffer holds
   float* d_scale = nullptr;         // per-feature scale of the token decode (mgx_decode_obs)
@@ -306,24 +316,28 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
         // some engine waits on world_done // this engine's world kernels wait for that engine's most recent world_done
   hipEvent_t ev[MGX_T_COUNT + 1] = {};  // boundaries of the timing segments of the most recent step (profiling only)
 
-  template <class T>
-  int alloc_env(T** p, size_t per_env, int fill = 0) {  // env-major array: remembered for episode restarts
-    int rc = alloc(p, per_env * (size_t)d.E, fill);
-    if (rc == MGX_OK && per_env) rows_state.push_back({(void*)*p, per_env * sizeof(T), fill});
+  int alloc_env_bytes(void** p, size_t per_env, int fill) {  // env-major array: remembered for episode restarts
+    int rc = alloc_bytes(p, per_env * (size_t)d.E, fill);
+    if (rc == MGX_OK && per_env) rows_state.push_back({*p, per_env, fill});
     return rc;
   }
   template <class T>
   int alloc(T** p, size_t count, int fill = 0) {
     void* q = nullptr;
-    size_t bytes = count * sizeof(T);
-    if (bytes == 0) bytes = sizeof(T);
+    int rc = alloc_bytes(&q, count ? count * sizeof(T) : sizeof(T), fill);
+    if (rc == MGX_OK) *p = (T*)q;
+    return rc;
+  }
+  int alloc_bytes(void** p, size_t bytes, int fill = 0) {
+    void* q = nullptr;
+    if (bytes == 0) bytes = 16;
     hipError_t e = hipMalloc(&q, bytes);
     if (e != hipSuccess) return fail(MGX_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
     e = hipMemsetAsync(q, fill, bytes, stream);
     if (e != hipSuccess) return fail(MGX_ERR_HIP, std::string("hipMemset: ") + hipGetErrorString(e));
     allocs.push_back(q);
     state_bytes += (int64_t)bytes;
-    *p = (T*)q;
+    *p = q;
     return MGX_OK;
   }
 };
@@ -646,67 +660,28 @@ int mgx_create(const int32_t* program, size_t program_words, const uint16_t* cla
 #define H_(call, what) if (rc == MGX_OK) rc = hip_rc((call), what)
   H_(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate");
 
-  // ---- allocate: per-env state (env-major, cleared by restarts), the plan's tables, caller-visible buffers ----
+  // ---- allocate: the env state arrays (mgx_env_state.h: ONE list serves allocation, the restart table rows_state and the
+  // records of mgx_save_envs), the derived per-env arrays, the plan's tables, caller-visible buffers ----
   int32_t* dprog = nullptr;
   A_(e->alloc(&dprog, program_words));
-  A_(e->alloc_env(&d.grid, HW));
-  A_(e->alloc_env(&d.obj_cls, S, 0xFF));
-  A_(e->alloc_env(&d.obj_rc, S));
-  A_(e->alloc_env(&d.obj_vibe, S));
-  A_(e->alloc_env(&d.obj_agent, S, 0xFF));
-  A_(e->alloc_env(&d.obj_visited, S));
-  A_(e->alloc_env(&d.obj_inv, S * MGX_INV_PITCH));
-  A_(e->alloc_env(&d.obj_order, S, 0xFF));
-  A_(e->alloc_env(&d.num_objs, 1));
-  A_(e->alloc_env(&d.ag_obj, A));
-  A_(e->alloc_env(&d.ag_prev, A));
-  A_(e->alloc_env(&d.ag_spawn, A));
-  A_(e->alloc_env(&d.ag_rc, A));
-  A_(e->alloc_env(&d.ag_rwinfo, A));
-  A_(e->alloc_env(&d.ag_cls, A));
-  A_(e->alloc_env(&d.ag_stepprev, A));
-  A_(e->alloc_env(&d.ag_covrc, A, 0xFF));
-  A_(e->alloc_env(&d.ag_invk, A * MGX_INVALID_EXTRA));
-  A_(e->alloc_env(&d.ag_invn, A * MGX_INVALID_EXTRA));
-  A_(e->alloc_env(&d.ag_swm, A));
-  A_(e->alloc_env(&d.ag_cnt, A * 8));
-  A_(e->alloc_env(&d.ag_maxdist, A));
-  A_(e->alloc_env(&d.ag_unique, A));
-  A_(e->alloc_env(&d.ag_seen, A * d.SEENW));
-  A_(e->alloc_env(&d.ag_rprev, A * d.NRW));
-  A_(e->alloc_env(&d.ag_stats, A * d.NSP));
-  A_(e->alloc_env(&d.ag_touched, A * d.NSW));
-  A_(e->alloc_env(&d.game_stats, (size_t)d.NG));
-  A_(e->alloc_env(&d.game_touched, (size_t)d.NGW));
-  A_(e->alloc(&d.step, E));
-  A_(e->alloc(&d.err, E));
-  A_(e->alloc_env(&d.executed, A));
-  A_(e->alloc_env(&d.success, A));
-  A_(e->alloc_env(&d.episode_rewards, A));
-  A_(e->alloc(&d.mt, 624 * E));
-  A_(e->alloc(&d.mt_idx, E));
+  e->es = mgx_env_state_layout_of(d, P, program_words);
+  for (const MgxSegDef& s : e->es.segs) {
+    if (s.kind == MGX_SEG_ROW) {
+      A_(e->alloc_env_bytes(mgx_seg_ptr(d, s), s.bytes, s.fill));
+    } else if (s.kind == MGX_SEG_WORD || s.kind == MGX_SEG_MT) {
+      A_(e->alloc_bytes(mgx_seg_ptr(d, s), (size_t)s.bytes * E, s.fill));
+    }
+  }
   A_(e->alloc(&e->own_obs, rows * d.T * 3, 0xFF));
   A_(e->alloc(&e->own_term, rows));
   A_(e->alloc(&e->own_trunc, rows));
   A_(e->alloc(&e->own_rew, rows));
   A_(e->alloc(&e->own_act, rows));
   A_(e->alloc(&e->own_vact, rows));
-  if (d.X) {
-    if (P[MGX_H_DYNAMIC_TAGS]) A_(e->alloc_env(&d.obj_tags, S * MGX_TAG_WORDS));
-    if (d.NL) { A_(e->alloc_env(&d.tl_items, d.NL * S)); A_(e->alloc_env(&d.tl_count, (size_t)d.NL)); }
-    if (d.NF) { A_(e->alloc_env(&d.fx_obj, (size_t)d.NF)); A_(e->alloc_env(&d.fx_aoe, (size_t)d.NF)); A_(e->alloc_env(&d.fx_rc, (size_t)d.NF));
-                A_(e->alloc_env(&d.fx_inside, A * (size_t)d.FW)); A_(e->alloc_env(&d.fx_count, 1));
-                if (e->aoe_kernel) A_(e->alloc(&d.fx_pack, E * (size_t)d.NF)); }
-    if (d.NM) { A_(e->alloc_env(&d.mb_obj, (size_t)d.NM)); A_(e->alloc_env(&d.mb_aoe, (size_t)d.NM));
-                A_(e->alloc_env(&d.mb_inside, A * (size_t)d.MW)); A_(e->alloc_env(&d.mb_count, 1));
-                if (e->aoe_kernel) A_(e->alloc(&d.mb_pack, E * (size_t)d.NM)); }
-    if (d.NTS) { A_(e->alloc_env(&d.ts_obj, (size_t)d.NTS)); A_(e->alloc_env(&d.ts_ctrl, (size_t)d.NTS)); A_(e->alloc_env(&d.ts_rc, (size_t)d.NTS));
-                 A_(e->alloc_env(&d.ts_count, 1)); }
-    A_(e->alloc_env(&d.terr_prev, A * std::max(1, d.NT)));
-    if (d.NT > 0 && d.NTS > 0) { A_(e->alloc(&d.terr_owner, E * (size_t)d.NT * HW, 0xFF)); A_(e->alloc_env(&d.terr_dirty, 1, 1)); }
-    A_(e->alloc_env(&d.next_event, 1));
-    A_(e->alloc_env(&d.obj_flags, S));
-    if (P[MGX_H_SPAWNS]) { A_(e->alloc_env(&d.def_aoe, S)); A_(e->alloc_env(&d.def_count, 1)); }
+  if (d.X) {   // derived per-env arrays: rebuilt from the state before they are read (DESIGN.md "Env state")
+    if (d.NF && e->aoe_kernel) A_(e->alloc(&d.fx_pack, E * (size_t)d.NF));
+    if (d.NM && e->aoe_kernel) A_(e->alloc(&d.mb_pack, E * (size_t)d.NM));
+    if (d.NT > 0 && d.NTS > 0) A_(e->alloc(&d.terr_owner, E * (size_t)d.NT * HW, 0xFF));
     A_(e->alloc(&d.qws, E * d.QB * S));
     A_(e->alloc(&d.qvis, E * (d.QD + 1) * d.SW));
   }
@@ -792,6 +767,8 @@ void mgx_destroy(mgx_engine* e) {
   if (e->d_pool) (void)hipFree(e->d_pool);
   if (e->d_stage) (void)hipFree(e->d_stage);
   if (e->d_objs) (void)hipFree(e->d_objs);
+  if (e->d_es_buf) (void)hipFree(e->d_es_buf);
+  if (e->es_ev) (void)hipEventDestroy(e->es_ev);
   if (e->h_flags) (void)hipHostFree(e->h_flags);
   if (e->h_act_err) (void)hipHostFree(e->h_act_err);
   if (e->jit_world.mod) (void)hipModuleUnload(e->jit_world.mod);
@@ -907,6 +884,15 @@ static int validate_maps(const mgx_engine* e, const uint16_t* maps, size_t n_map
   }
   return MGX_OK;
 }
+// A larger LDS token pool for the observation kernel (new maps, or a loaded state from an engine that saw denser maps).
+static int grow_pool(mgx_engine* e, int need) {
+  if (need <= e->pool_tokens) return MGX_OK;
+  const bool jit = e->obs_variant == 9 && e->jit_obs.mod;
+  e->pool_tokens = need;
+  if (!e->size_obs(e->sw)) return fail(MGX_ERR_PROGRAM, MGX_OBS_LDS_REFUSAL);
+  if (jit && e->lds_obs <= 64 * 1024) e->obs_variant = 9;   // (the code object's shape does not depend on the pool size)
+  return raise_obs_lds(e);
+}
 // AoE / territory source counts of a set of maps against the capacities sized at mgx_create, and the observation kernel's
 // token pool against their object lists.
 static int fit_maps(mgx_engine* e, const uint16_t* maps, size_t first, size_t count, const uint8_t* mask, const char* who) {
@@ -925,16 +911,8 @@ static int fit_maps(mgx_engine* e, const uint16_t* maps, size_t first, size_t co
                                          std::to_string(d.NTS) + "): create the engine with a map that has the maximum");
     }
   }
-  if (e->pool_from_maps) {  // new maps may hold more non-static objects than any map seen so far
-    const int need = mgx_pool_tokens(e->pool_prefix, e->list_tokens_bound(maps, first, count, mask));
-    if (need > e->pool_tokens) {
-      const bool jit = e->obs_variant == 9 && e->jit_obs.mod;
-      e->pool_tokens = need;
-      if (!e->size_obs(e->sw)) return fail(MGX_ERR_PROGRAM, MGX_OBS_LDS_REFUSAL);
-      if (jit && e->lds_obs <= 64 * 1024) e->obs_variant = 9;   // (the code object's shape does not depend on the pool size)
-      return raise_obs_lds(e);
-    }
-  }
+  if (e->pool_from_maps)  // new maps may hold more non-static objects than any map seen so far
+    return grow_pool(e, mgx_pool_tokens(e->pool_prefix, e->list_tokens_bound(maps, first, count, mask)));
   return MGX_OK;
 }
 
@@ -1639,6 +1617,184 @@ int mgx_state_digests(mgx_engine* e, uint64_t* out) {
   hipLaunchKernelGGL(mgx_digest_kernel, dim3((unsigned)e->d.E), dim3(MGX_WAVE), 0, e->stream, dev_copy(e), e->d_digest);
   HIP_TRY(hipGetLastError());
   return d2h(e, out, e->d_digest, (size_t)e->d.E * 8);
+}
+
+// ---- saved env state (mgx_env_state.h) ------------------------------------------------------------------------------------
+static void es_info(const MgxEnvStateLayout& L, int pool_tokens, mgx_env_state_info_t* out) {
+  out->record_bytes = L.record_bytes;
+  out->format = L.format;
+  out->version = MGX_ES_VERSION;
+  out->pool_tokens = pool_tokens;
+  out->n_segments = (int32_t)L.segs.size();
+  out->reserved = 0;
+}
+int mgx_env_state_layout(const int32_t* program, size_t program_words, const uint16_t* class_maps, int32_t n_maps,
+                         mgx_env_state_info_t* out) {
+  if (!program || !class_maps || !out || n_maps <= 0) return fail(MGX_ERR_BAD_ARG, "mgx_env_state_layout: null/empty argument");
+  MgxPlan plan;
+  std::string why;
+  const int rc = mgx_plan(program, program_words, class_maps, n_maps, mgx_read_switches(), plan, why);
+  if (rc != MGX_OK) return fail(rc, why);
+  es_info(mgx_env_state_layout_of(plan.d, program, program_words), plan.pool_tokens, out);
+  return MGX_OK;
+}
+int mgx_env_state_info(mgx_engine* e, mgx_env_state_info_t* out) {
+  if (!e || !out) return fail(MGX_ERR_BAD_ARG, "mgx_env_state_info: null argument");
+  es_info(e->es, e->pool_tokens, out);
+  return MGX_OK;
+}
+// The device segment table for the current pointers (the bound caller buffers and the lazily allocated auto-reset words
+// change after mgx_create).
+static int es_upload_segs(mgx_engine* e) {
+  MgxDev& d = e->d;
+  std::vector<MgxSeg> t;
+  for (size_t i = 0; i < e->es.segs.size(); i++) {
+    const MgxSegDef& s = e->es.segs[i];
+    if (!s.bytes) continue;
+    void* base = nullptr;
+    if (s.kind != MGX_SEG_AUTO) base = *mgx_seg_ptr(d, s);
+    else if (s.off == MGX_AUTO_NEXT_MASK) base = e->d_next_mask;
+    else if (s.off == MGX_AUTO_EPISODES) base = e->d_episodes;
+    else if (s.off == MGX_AUTO_MAP_INDEX) base = e->d_map_index;
+    else base = e->d_early;
+    t.push_back({(uint8_t*)base, (unsigned long long)s.bytes, (unsigned long long)e->es.offs[i], s.kind == MGX_SEG_MT ? 1 : 0, 0});
+  }
+  if (t.size() == e->es_segs_host.size() && memcmp(t.data(), e->es_segs_host.data(), t.size() * sizeof(MgxSeg)) == 0) return MGX_OK;
+  if (!e->d_es_segs) { int rc = e->alloc(&e->d_es_segs, e->es.segs.size()); if (rc) return rc; }
+  HIP_TRY(hipMemcpyAsync(e->d_es_segs, t.data(), t.size() * sizeof(MgxSeg), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));   // `t` is a local
+  e->es_segs_host = t;
+  return MGX_OK;
+}
+// Host-side checks shared by the three calls: a positive count, indices in range, no destination twice (dst_unique).
+static int es_check_list(const mgx_engine* e, const int32_t* envs, int32_t n, bool dst_unique, const char* who) {
+  if (!envs || n <= 0) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": empty env list");
+  if (e->box_dtype != MGX_BOX_OFF) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": box output is on (mgx_set_box_output): states hold observation rows");
+  std::vector<uint8_t> seen(dst_unique ? (size_t)e->d.E : 0, 0);
+  for (int32_t k = 0; k < n; k++) {
+    if (envs[k] < 0 || envs[k] >= e->d.E)
+      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": env index " + std::to_string(envs[k]) + " out of range [0, " + std::to_string(e->d.E) + ")");
+    if (dst_unique && seen[envs[k]]++) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": destination env " + std::to_string(envs[k]) + " listed twice");
+  }
+  return MGX_OK;
+}
+// Upload env lists through d_stage: [list 0 | list 1 | n], each list n int32 on a 16-byte boundary.  The host vector is
+// reused only once the previous upload from it has completed (the calls return without waiting for the device).
+static int es_stage_lists(mgx_engine* e, const int32_t* a, const int32_t* b, int32_t n, const int32_t** da, const int32_t** db,
+                          const uint32_t** dn) {
+  const size_t L = ((size_t)n * 4 + 15) & ~(size_t)15, total = 2 * L + 16;
+  int rc = stage(e, total);
+  if (rc) return rc;
+  if (!e->es_ev) HIP_TRY(hipEventCreateWithFlags(&e->es_ev, hipEventDisableTiming));
+  if (e->es_ev_pending) HIP_TRY(hipEventSynchronize(e->es_ev));
+  e->es_lists.assign(total, 0);
+  memcpy(e->es_lists.data(), a, (size_t)n * 4);
+  if (b) memcpy(e->es_lists.data() + L, b, (size_t)n * 4);
+  const uint32_t n32 = (uint32_t)n;
+  memcpy(e->es_lists.data() + 2 * L, &n32, 4);
+  HIP_TRY(hipMemcpyAsync(e->d_stage, e->es_lists.data(), total, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipEventRecord(e->es_ev, e->stream));
+  e->es_ev_pending = true;
+  const uint8_t* st = (const uint8_t*)e->d_stage;
+  *da = (const int32_t*)st; *db = (const int32_t*)(st + L); *dn = (const uint32_t*)(st + 2 * L);
+  return MGX_OK;
+}
+static void es_launch(mgx_engine* e, const int32_t* list, int32_t n, uint8_t* buf, int dir) {
+  hipLaunchKernelGGL(mgx_env_state_kernel, dim3((unsigned)((n + MGX_ES_EPG - 1) / MGX_ES_EPG)), dim3(256), 0, e->stream,
+                     (const MgxSeg*)e->d_es_segs, (int)e->es_segs_host.size(), list, (int)n, buf, (unsigned long long)e->es.record_bytes,
+                     (unsigned long long)e->es.format, dir, e->d.E, (const uint32_t*)e->d.step, e->d.err, e->d.terr_dirty);
+}
+// After envs were written: the auto-reset done list follows their restart-pending words; MGX_MEM_HOST: their caller rows
+// go to the bound host buffers.
+static int es_after_write(mgx_engine* e, const int32_t* envs, int32_t n) {
+  const MgxDev& d = e->d;
+  if (e->auto_reset && e->d_next_mask && e->d_done_list) {
+    e->step_seq++;   // (mgx_step skips the restart launches only once this kernel has published the new count)
+    hipLaunchKernelGGL(mgx_es_done_list_kernel, dim3(1), dim3(256), 0, e->stream, (const uint8_t*)e->d_next_mask, d.E, e->d_done_list,
+                       e->d_done_n, (volatile uint32_t*)e->h_flags_dev, e->step_seq);
+    HIP_TRY(hipGetLastError());
+  }
+  if (e->mem_kind == MGX_MEM_HOST) {   // one copy per run of consecutive envs
+    std::vector<int32_t> idx(envs, envs + n);
+    std::sort(idx.begin(), idx.end());
+    const size_t A = d.A;
+    for (size_t k = 0; k < idx.size();) {
+      size_t j = k;
+      while (j + 1 < idx.size() && idx[j + 1] == idx[j] + 1) j++;
+      const size_t r0 = (size_t)idx[k] * A, rows = (size_t)(idx[j] - idx[k] + 1) * A;
+      HIP_TRY(hipMemcpyAsync(e->h_obs + r0 * d.T * 3, d.obs + r0 * d.T * 3, rows * d.T * 3, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipMemcpyAsync(e->h_term + r0, d.terminals + r0, rows, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipMemcpyAsync(e->h_trunc + r0, d.truncations + r0, rows, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipMemcpyAsync(e->h_rew + r0, d.rewards + r0, rows * 4, hipMemcpyDeviceToHost, e->stream));
+      k = j + 1;
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+  }
+  return MGX_OK;
+}
+int mgx_save_envs(mgx_engine* e, const int32_t* envs, int32_t n, void* dst) {
+  if (!e || !dst) return fail(MGX_ERR_BAD_ARG, "mgx_save_envs: null argument");
+  int rc = es_check_list(e, envs, n, false, "mgx_save_envs");
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  rc = es_upload_segs(e);
+  const int32_t *dl = nullptr, *unused = nullptr;
+  const uint32_t* dn = nullptr;
+  if (!rc) rc = es_stage_lists(e, envs, nullptr, n, &dl, &unused, &dn);
+  if (!rc) rc = flush_shadow(e, dl, dn, (unsigned)(((long long)n * e->d.A + 255) / 256));   // the records' stat cells are current
+  if (rc) return rc;
+  es_launch(e, dl, n, (uint8_t*)dst, MGX_ES_SAVE);
+  HIP_TRY(hipGetLastError());
+  return MGX_OK;
+}
+int mgx_load_envs(mgx_engine* e, const int32_t* envs, int32_t n, const void* src, const mgx_env_state_info_t* saved) {
+  if (!e || !src || !saved) return fail(MGX_ERR_BAD_ARG, "mgx_load_envs: null argument");
+  if (saved->format != e->es.format || saved->record_bytes != e->es.record_bytes || saved->version != MGX_ES_VERSION) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "mgx_load_envs: the state has format %016llx, this engine %016llx (other program, capacities or "
+             "integer bookkeeping)", (unsigned long long)saved->format, (unsigned long long)e->es.format);
+    return fail(MGX_ERR_BAD_ARG, buf);
+  }
+  int rc = es_check_list(e, envs, n, true, "mgx_load_envs");
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  rc = grow_pool(e, saved->pool_tokens);
+  if (!rc) rc = es_upload_segs(e);
+  if (!rc) rc = consume_out_fence(e);   // the caller rows are written
+  const int32_t *dl = nullptr, *unused = nullptr;
+  const uint32_t* dn = nullptr;
+  if (!rc) rc = es_stage_lists(e, envs, nullptr, n, &dl, &unused, &dn);
+  if (rc) return rc;
+  es_launch(e, dl, n, (uint8_t*)src, MGX_ES_LOAD);
+  HIP_TRY(hipGetLastError());
+  return es_after_write(e, envs, n);
+}
+int mgx_copy_envs(mgx_engine* e, const int32_t* src_envs, const int32_t* dst_envs, int32_t n) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_copy_envs: null engine");
+  int rc = es_check_list(e, src_envs, n, false, "mgx_copy_envs");
+  if (!rc) rc = es_check_list(e, dst_envs, n, true, "mgx_copy_envs");
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t bytes = (size_t)n * (size_t)e->es.record_bytes;
+  if (bytes > e->es_buf_bytes) {   // sources are saved here first: every source is read before any destination is written
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->d_es_buf) (void)hipFree(e->d_es_buf);
+    e->d_es_buf = nullptr;
+    e->es_buf_bytes = 0;
+    HIP_TRY(hipMalloc((void**)&e->d_es_buf, bytes));
+    e->es_buf_bytes = bytes;
+  }
+  rc = es_upload_segs(e);
+  if (!rc) rc = consume_out_fence(e);
+  const int32_t *ds = nullptr, *dd = nullptr;
+  const uint32_t* dn = nullptr;
+  if (!rc) rc = es_stage_lists(e, src_envs, dst_envs, n, &ds, &dd, &dn);
+  if (!rc) rc = flush_shadow(e, ds, dn, (unsigned)(((long long)n * e->d.A + 255) / 256));
+  if (rc) return rc;
+  es_launch(e, ds, n, e->d_es_buf, MGX_ES_SAVE);
+  es_launch(e, dd, n, e->d_es_buf, MGX_ES_LOAD);
+  HIP_TRY(hipGetLastError());
+  return es_after_write(e, dst_envs, n);
 }
 
 // joint action id -> (primary, vibe) action indices (mettagrid_puffer_env.py:331-381), one thread per agent row

@@ -28,10 +28,92 @@ OBJ_RECORD_WORDS = 42
 
 ENV_TOKEN_OVERFLOW, ENV_INVALID_KEY_RANGE, ENV_DEPTH, ENV_TOO_MANY_OBJECTS, ENV_TOKEN_POOL = 1, 2, 4, 8, 16
 ENV_PROXY_INVENTORY, ENV_AGENT_LIFECYCLE = 32, 64   # territory proxy given an inventory / an agent spawned or removed
+ENV_BAD_STATE = 128   # load_envs / copy_envs: a record of another layout; the env was left untouched
 
 
 class MgxError(RuntimeError):
     pass
+
+
+class EnvStateInfo(C.Structure):
+    """include/mgx.h mgx_env_state_info: what decides whether a saved env state can be loaded."""
+    _fields_ = [("record_bytes", C.c_int64), ("format", C.c_uint64), ("version", C.c_int32), ("pool_tokens", C.c_int32),
+                ("n_segments", C.c_int32), ("reserved", C.c_int32)]
+
+    def to_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def env_state_layout(prog: Program, class_maps) -> dict:
+    """The env-state info an engine created from ``prog`` and ``class_maps`` [n, H, W] would report (host-only)."""
+    cm = np.ascontiguousarray(class_maps, dtype=np.uint16)
+    if cm.ndim == 2:
+        cm = cm[None]
+    words = np.ascontiguousarray(prog.words, dtype=np.int32)
+    info = EnvStateInfo()
+    _check(load_lib().mgx_env_state_layout(words.ctypes.data, words.size, cm.ctypes.data, cm.shape[0], C.byref(info)))
+    return info.to_dict()
+
+
+class EnvState:
+    """Saved state of some envs (include/mgx.h mgx_save_envs): ``data`` uint8 [n, record_bytes] — a torch tensor on the
+    engine's device, or numpy after ``.cpu()`` / ``from_dict`` —, the layout info it was saved with and ``envs``, the slots
+    it was saved from.  ``to_dict()`` holds only numpy arrays and ints (``torch.save`` / ``np.savez``)."""
+
+    INFO = ("record_bytes", "format", "version", "pool_tokens", "n_segments", "reserved")
+
+    def __init__(self, data, info: dict, envs, extra: dict | None = None) -> None:
+        self.data = data
+        self.info = {k: int(info[k]) for k in self.INFO}
+        self.envs = np.asarray(envs, dtype=np.int64).reshape(-1)
+        self.extra = dict(extra or {})   # host-side companions (MettaGridBatchedEnv: episode counters)
+        if tuple(data.shape) != (len(self.envs), self.info["record_bytes"]):
+            raise ValueError(f"state data has shape {tuple(data.shape)}, expected {(len(self.envs), self.info['record_bytes'])}")
+
+    def __len__(self) -> int:
+        return len(self.envs)
+
+    def cpu(self) -> "EnvState":
+        d = self.data
+        return EnvState(d if isinstance(d, np.ndarray) else d.cpu().numpy(), self.info, self.envs, self.extra)
+
+    def to(self, device) -> "EnvState":
+        import torch
+        d = torch.as_tensor(self.data) if isinstance(self.data, np.ndarray) else self.data
+        return EnvState(d.to(device).contiguous(), self.info, self.envs, self.extra)
+
+    def to_dict(self) -> dict:
+        out = {"data": np.ascontiguousarray(self.cpu().data), "envs": self.envs.copy()}
+        out.update({f"info_{k}": np.array(v, dtype=np.uint64 if k == "format" else np.int64) for k, v in self.info.items()})
+        out.update({f"extra_{k}": np.asarray(v) for k, v in self.extra.items()})
+        return out
+
+    @classmethod
+    def from_dict(cls, d) -> "EnvState":
+        info = {k: int(np.asarray(d[f"info_{k}"])) for k in cls.INFO}
+        extra = {k[6:]: np.asarray(d[k]) for k in d.keys() if k.startswith("extra_")}
+        return cls(np.ascontiguousarray(np.asarray(d["data"], dtype=np.uint8)), info, np.asarray(d["envs"]), extra)
+
+    def info_struct(self) -> EnvStateInfo:
+        return EnvStateInfo(**self.info)
+
+
+def env_list(envs, E: int, what: str, unique: bool = False) -> np.ndarray:
+    """``envs`` (None = all) as a contiguous int32 array of valid env indices, else ValueError."""
+    if envs is None:
+        return np.arange(E, dtype=np.int32)
+    a = np.asarray(envs)
+    if a.ndim == 0:
+        a = a.reshape(1)
+    if a.ndim != 1 or a.size == 0:
+        raise ValueError(f"{what}: needs a non-empty 1-d list of env indices")
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{what}: env indices must be integers, not {a.dtype}")
+    if a.min() < 0 or a.max() >= E:
+        raise ValueError(f"{what}: env index out of range [0, {E}): {a.tolist()}")
+    if unique and len(np.unique(a)) != a.size:
+        raise ValueError(f"{what}: a destination env is listed twice: {a.tolist()}")
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 def load_lib():
@@ -103,6 +185,11 @@ def load_lib():
         getattr(L, name).restype = i32
     L.mgx_state_bytes.argtypes = [vp]
     L.mgx_state_bytes.restype = i64
+    L.mgx_env_state_layout.argtypes = [vp, C.c_size_t, vp, i32, C.POINTER(EnvStateInfo)]
+    L.mgx_env_state_info.argtypes = [vp, C.POINTER(EnvStateInfo)]
+    L.mgx_save_envs.argtypes = [vp, vp, i32, vp]
+    L.mgx_load_envs.argtypes = [vp, vp, i32, vp, C.POINTER(EnvStateInfo)]
+    L.mgx_copy_envs.argtypes = [vp, vp, vp, i32]
     _lib = L
     return L
 
@@ -706,6 +793,70 @@ class BatchedMettaGrid:
     @property
     def state_bytes(self) -> int:
         return int(self.L.mgx_state_bytes(self.h))
+
+    # ---- saving, loading and copying envs' state (include/mgx.h mgx_save_envs; DESIGN.md "Env state") ----
+    def env_state_info(self) -> dict:
+        info = EnvStateInfo()
+        _check(self.L.mgx_env_state_info(self.h, C.byref(info)))
+        return info.to_dict()
+
+    def _box_check(self, what: str) -> None:
+        if getattr(self, "_box", None) is not None:
+            raise ValueError(f"{what}: box output is on (set_box_output): states hold observation rows")
+
+    def save_envs(self, envs=None) -> EnvState:
+        """Save the state of ``envs`` (default: all) into a new ``EnvState`` (device tensor; numpy for host engines).
+        Ordered after everything enqueued before; the caller's stream waits for the copy."""
+        lst = env_list(envs, self.E, "save_envs")
+        self._box_check("save_envs")
+        info = self.env_state_info()
+        import torch
+        buf = torch.empty((len(lst), info["record_bytes"]), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        if self.kind == "device":
+            self.wait_for_caller()
+        _check(self.L.mgx_save_envs(self.h, lst.ctypes.data, len(lst), C.c_void_p(buf.data_ptr())))
+        if self.kind == "device":
+            self.caller_waits()
+            return EnvState(buf, info, lst)
+        self.sync()
+        return EnvState(buf.cpu().numpy(), info, lst)
+
+    def load_envs(self, state: EnvState, envs=None) -> None:
+        """Put the records of ``state`` into the slots ``envs`` (default: the slots they were saved from): each env then
+        continues its saved episode bit for bit; its next episode is the slot's (seed, map pool schedule)."""
+        lst = env_list(state.envs if envs is None else envs, self.E, "load_envs", unique=True)
+        if len(lst) != len(state):
+            raise ValueError(f"load_envs: {len(lst)} destination envs for {len(state)} records")
+        self._box_check("load_envs")
+        import torch
+        data = state.data
+        if isinstance(data, np.ndarray) or data.device != torch.device("cuda", self.device):
+            data = torch.as_tensor(np.ascontiguousarray(data) if isinstance(data, np.ndarray) else data).to(
+                torch.device("cuda", self.device))
+        data = data.contiguous()
+        if self.kind == "device":
+            self.wait_for_caller()
+        else:
+            torch.cuda.synchronize(self.device)
+        info = state.info_struct()
+        _check(self.L.mgx_load_envs(self.h, lst.ctypes.data, len(lst), C.c_void_p(data.data_ptr()), C.byref(info)))
+        self._keep_alive = data   # (read by the device after this returns)
+        if self.kind == "device":
+            self.caller_waits()
+
+    def copy_envs(self, src, dst) -> None:
+        """Copy the state of env ``src[k]`` onto env ``dst[k]``, as if every source were read before any destination
+        is written (``[0, 1] -> [1, 0]`` swaps)."""
+        s = env_list(src, self.E, "copy_envs")
+        d = env_list(dst, self.E, "copy_envs", unique=True)
+        if len(s) != len(d):
+            raise ValueError(f"copy_envs: {len(s)} sources for {len(d)} destinations")
+        self._box_check("copy_envs")
+        if self.kind == "device":
+            self.wait_for_caller()
+        _check(self.L.mgx_copy_envs(self.h, s.ctypes.data, d.ctypes.data, len(s)))
+        if self.kind == "device":
+            self.caller_waits()
 
 
 class MettaGrid:

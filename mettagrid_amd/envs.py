@@ -398,6 +398,25 @@ class MettaGridBatchedEnv:
                 self._compute_supervisor_actions()
         return eng.obs, eng.rewards, eng.terminals, eng.truncations, self._step_infos()
 
+    # ---- saving and restoring envs' state (BatchedMettaGrid.save_envs / load_envs) ----
+    def save_state(self, envs=None):
+        """The state of ``envs`` (default: all) as an ``engine.EnvState``; with ``map_fn`` it also carries the envs' host-side
+        episode counters (which pick the next episode's map and seed)."""
+        from .engine import env_list
+        lst = env_list(envs, self.E, "save_state")
+        st = self.engine.save_envs(lst)
+        if self.map_pool is None:
+            st.extra["episode"] = self.episode[lst].copy()
+        return st
+
+    def load_state(self, state, envs=None) -> None:
+        """Put ``state`` into ``envs`` (default: the slots it was saved from); they continue their saved episodes."""
+        from .engine import env_list
+        lst = env_list(state.envs if envs is None else envs, self.E, "load_state", unique=True)
+        self.engine.load_envs(state, lst)
+        if self.map_pool is None and "episode" in state.extra:
+            self.episode[lst] = np.asarray(state.extra["episode"], dtype=np.int64)
+
     def close(self) -> None:
         if self._eng is not None:
             self._eng.close()
