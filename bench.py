@@ -13,9 +13,12 @@ steps as R rounds of K/R steps; the whole region is ONE bracket (barrier + synch
 from it) and the round boundaries are HIP events on the engine's stream, so the per-round mean / sigma / CV cost no host
 synchronisation; CV > 20 % is flagged like benchmarks/perf/perf_benchmark.py:216-218.
 
-The default N=1 run also measures, after the headline and outside its bracket: BASELINE.json configs[3] (rung 4) as the
-object "rung4" (same fields, short run) and the throughput a trainer sees through the PufferEnv-shaped wrapper
-("env_wrapper").  Prints ONE JSON line on rank 0.
+A plain run does only what the headline needs: maps, warm-up, the timed steps, --dump-outputs, the line.  --full adds,
+outside the headline's bracket: per-kernel durations and the roofline of the dominant kernel ("kernels_ms", "roofline"),
+the CPU baseline ("cpu_baseline", unless --no-cpu) and, for N=1 at rung 3 unless --no-extras, a 1 000-step run
+("long_run"), the generic kernels ("generic"), a program compiled at run time ("run_time_specialisation"),
+BASELINE.json configs[3] as the object "rung4" (same fields, short run) and the throughput a trainer sees through the
+PufferEnv-shaped wrapper ("env_wrapper").  Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
 
@@ -209,10 +212,11 @@ def cpu_leg(rung: int, cpu_steps: int) -> dict:
 # ---- the GPU measurement of one rung ---------------------------------------------------------------------------------
 def measure(rung: int, cms: np.ndarray, *, envs: int, steps: int, warmup: int, rounds: int, groups: int, gather_kind: str,
             rank: int, local_rank: int, world: int, dist, spec=None, generic: bool = False, specialize="auto",
-            dump_dir: str | None = None) -> dict:
+            dump_dir: str | None = None, kernels: bool = True) -> dict:
     """spec: another game on the rung's maps (the run-time specialisation leg); generic: the kernels any program gets — no
     build-time preset instance, no generated handlers (MGX_NO_GEN / MGX_OBS_GENERIC at mgx_create), no run-time code objects;
-    dump_dir: write what the last timed step computed there (dump_outputs), on rank 0."""
+    dump_dir: write what the last timed step computed there (dump_outputs), on rank 0; kernels: afterwards, time each
+    kernel in steps of its own ("kernels_ms", "roofline")."""
     import torch
     from mettagrid_amd.compiler import compile_spec
     from mettagrid_amd.dist import GatherToRoot, shard_seeds
@@ -319,56 +323,58 @@ def measure(rung: int, cms: np.ndarray, *, envs: int, steps: int, warmup: int, r
     mean = float(np.mean(per_round))
     std = float(np.std(per_round))
     cv = std / mean if mean else 0.0
-
-    # per-kernel durations for the roofline line: HIP events between the two kernels on the engine stream
-    # (one group at a time, so that a duration is the kernel's own and not its share of an overlapped pair; a launch
-    # covers E / G envs)
-    grp.set_profiling(True)
-    nprof = min(50, max(5, steps))
-    seg = {}
-    for t in range(nprof):
-        for g, eng in enumerate(grp.engines):
-            one_step(t, only=g)
-            for k, v in eng.step_timing_segments_ms().items():   # waits for the step
-                seg[k] = seg.get(k, 0.0) + v / (nprof * G)
-    grp.set_profiling(False)
-    grp.close()
-    del grp, pre_a, pre_v
-    torch.cuda.empty_cache()
-
-    # Roofline of the dominant kernel (DESIGN.md "Roofline accounting").  Algorithmic bytes per agent-step: the
-    # observation kernel owns obs out 3T + reward 4 + terminal 1 + truncation 1 + one read of the env state
-    # S_env/A; the world-update kernel owns the two action streams (8) + one pass over S_env/A.
-    names = {"obs": "mgx_obs_kernel", "actions": "mgx_act_kernel_x" if rung == 4 else "mgx_world_kernel_fast"}
-    dom = "obs" if seg["obs"] >= seg["actions"] else "actions"
-    bytes_per_agent_step = per["obs"] if dom == "obs" else per["world"]
-    achieved = (E // G) * A * bytes_per_agent_step / (seg[dom] * 1e-3) / 1e9
-    traffic, source, valu_frac = None, None, None
-    pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(pmc):
-        try:
-            pj = json.load(open(pmc))
-            traffic = pj.get(f"rung{rung}", {}).get(names[dom] + "_bytes_per_launch")
-            valu_frac = pj.get(f"rung{rung}", {}).get(names[dom] + "_valu_frac")
-            source = f"profiles/pmc_traffic.json@{pj.get('build', '?')} (PMC FETCH_SIZE x2 + WRITE_SIZE of a profiled run, not this run)"
-        except Exception:
-            traffic = None
-    return {
+    res = {
         "value": world * E * A * steps / wall, "ms_per_step": wall * 1e3 / steps, "device_ms_per_step": dev_ms / steps,
         "steps": steps, "warmup": warmup, "variants": variants,
         "rounds": {"n": len(per_round), "steps_per_round": steps // rounds, "mean": mean * world, "std": std * world, "cv": cv,
                    "unstable": bool(cv > 0.20), "per_gpu": world > 1},
-        "kernels_ms": {"world_actions": seg["actions"], "aoe": seg["aoe"], "world_tail": seg["tail"],
-                       "mgx_obs_kernel": seg["obs"], "rewards_ext": seg["rewards"]},
-        "roofline": {"bound": "hbm", "kernel": names[dom], "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
-                     "frac": achieved / 8000.0, "traffic": traffic, "traffic_source": source,
-                     "valu_frac": valu_frac,   # share of SIMD cycles issuing VALU instructions (same profiled run as `traffic`)
-                     "bytes_per_agent_step": bytes_per_agent_step, "tick_bytes_per_agent_step": per["tick"],
-                     "kernel_ms": seg[dom]},
         "config": {"workload": desc, "baseline_config": f"configs[{rung - 1}]", "envs_per_gpu": E, "agents_per_env": A,
                    "obs_tokens": T, "gather": gather_kind, "parallelism": f"env-shard x{world}",
                    "env_groups_per_gpu": G, "envs_per_launch": E // G},
     }
+
+    if kernels:
+        # per-kernel durations for the roofline line: HIP events between the two kernels on the engine stream
+        # (one group at a time, so that a duration is the kernel's own and not its share of an overlapped pair; a launch
+        # covers E / G envs)
+        grp.set_profiling(True)
+        nprof = min(50, max(5, steps))
+        seg = {}
+        for t in range(nprof):
+            for g, eng in enumerate(grp.engines):
+                one_step(t, only=g)
+                for k, v in eng.step_timing_segments_ms().items():   # waits for the step
+                    seg[k] = seg.get(k, 0.0) + v / (nprof * G)
+        grp.set_profiling(False)
+
+        # Roofline of the dominant kernel (DESIGN.md "Roofline accounting").  Algorithmic bytes per agent-step: the
+        # observation kernel owns obs out 3T + reward 4 + terminal 1 + truncation 1 + one read of the env state
+        # S_env/A; the world-update kernel owns the two action streams (8) + one pass over S_env/A.
+        names = {"obs": "mgx_obs_kernel", "actions": "mgx_act_kernel_x" if rung == 4 else "mgx_world_kernel_fast"}
+        dom = "obs" if seg["obs"] >= seg["actions"] else "actions"
+        bytes_per_agent_step = per["obs"] if dom == "obs" else per["world"]
+        achieved = (E // G) * A * bytes_per_agent_step / (seg[dom] * 1e-3) / 1e9
+        traffic, source, valu_frac = None, None, None
+        pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+        if os.path.exists(pmc):
+            try:
+                pj = json.load(open(pmc))
+                traffic = pj.get(f"rung{rung}", {}).get(names[dom] + "_bytes_per_launch")
+                valu_frac = pj.get(f"rung{rung}", {}).get(names[dom] + "_valu_frac")
+                source = f"profiles/pmc_traffic.json@{pj.get('build', '?')} (PMC FETCH_SIZE x2 + WRITE_SIZE of a profiled run, not this run)"
+            except Exception:
+                traffic = None
+        res["kernels_ms"] = {"world_actions": seg["actions"], "aoe": seg["aoe"], "world_tail": seg["tail"],
+                             "mgx_obs_kernel": seg["obs"], "rewards_ext": seg["rewards"]}
+        res["roofline"] = {"bound": "hbm", "kernel": names[dom], "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
+                           "frac": achieved / 8000.0, "traffic": traffic, "traffic_source": source,
+                           "valu_frac": valu_frac,   # share of SIMD cycles issuing VALU instructions (same profiled run as `traffic`)
+                           "bytes_per_agent_step": bytes_per_agent_step, "tick_bytes_per_agent_step": per["tick"],
+                           "kernel_ms": seg[dom]}
+    grp.close()
+    del grp, pre_a, pre_v
+    torch.cuda.empty_cache()
+    return res
 
 
 DUMP_OBS_BYTES = 24 << 20   # float32 observation rows of the sampled envs
@@ -525,10 +531,14 @@ def main() -> None:
                     help="env groups per GPU (mettagrid_amd/groups.py): 2 = the world update of one half of the envs runs "
                          "beside the observation kernel of the other half (measured slower on MI355X: DESIGN.md); "
                          "1 = one engine, kernels back to back")
-    ap.add_argument("--cpu-steps", type=int, default=0, help="CPU baseline sample (default: about 10 s of one host core)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only: skip the rung-4 object and the env-wrapper throughput")
-    ap.add_argument("--rung4-steps", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel durations and roofline, the CPU baseline and (N=1, rung 3) the "
+                         "long run, generic kernels, run-time specialisation, rung-4 object and env-wrapper throughput")
+    ap.add_argument("--cpu-steps", type=int, default=0, help="--full: CPU baseline sample (default: about 10 s of one host core)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full without the long run, generic kernels, run-time specialisation, rung-4 object and env wrapper")
+    ap.add_argument("--rung4-steps", type=int, default=100, help="--full: timed steps of the rung-4 object")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps of the headline, write what its last step computed as DIR/<name>.npy "
                          "(float32; a fixed seeded sample of the observations; rank 0's envs): same arguments, same inputs")
@@ -550,7 +560,7 @@ def main() -> None:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks")
     if args.stub:
         raise SystemExit(stub_rank(args, rank, world))
-    extras = world == 1 and args.rung == 3 and not args.no_extras
+    extras = args.full and world == 1 and args.rung == 3 and not args.no_extras
     from mettagrid_amd.dist import env_shard
 
     # Everything that forks or spawns comes first: this process has not touched the GPU yet.
@@ -558,7 +568,7 @@ def main() -> None:
     cms = build_maps(args.rung, env_shard(rank, world, args.envs), workers)   # map seed = global env index
     cms4 = build_maps(4, env_shard(0, 1, args.envs), workers) if extras else None
     cpu = cpu4 = None
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         # about 10 s on one core, then every host core at once (one env per process, about 5 s of stepping each)
         cpu = cpu_leg(args.rung, args.cpu_steps or (300000 if args.rung == 3 else 25000))
         if extras:
@@ -586,7 +596,7 @@ def main() -> None:
 
     common = dict(envs=args.envs, groups=args.groups, gather_kind=args.gather, rank=rank, local_rank=local_rank, world=world, dist=dist)
     head = measure(args.rung, cms, steps=args.steps, warmup=args.warmup, rounds=args.rounds, dump_dir=args.dump_outputs,
-                   **common)
+                   kernels=args.full, **common)
     r4 = wrap = gen = jit_leg = long_run = None
     if extras:
         # the headline workload over the reference harness' protocol length whatever --steps says
@@ -622,12 +632,8 @@ def main() -> None:
             "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "u8", "data": "synthetic",
             "config": head["config"],
-            "device_ms_per_step": head["device_ms_per_step"],
-            "rounds": head["rounds"],
-            "kernels_ms": head["kernels_ms"],
-            "variants": head["variants"],
-            "roofline": head["roofline"],
         }
+        out.update({k: head[k] for k in ("device_ms_per_step", "rounds", "kernels_ms", "variants", "roofline") if k in head})
         if long_run is not None:
             out["long_run"] = long_run
         if gen is not None:

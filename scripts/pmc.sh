@@ -8,7 +8,7 @@ OUT="$ROOT/gpurun_out/${1:-pmc}"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 echo "[pmc] kernel trace"
-timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- python3 "$ROOT/bench.py" --steps 30 --warmup 5 --no-cpu --no-extras $BENCH_ARGS > "$OUT/trace.log" 2>&1 || { echo "[pmc] kernel trace failed"; tail -5 "$OUT/trace.log"; exit 1; }
+timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- python3 "$ROOT/bench.py" --full --steps 30 --warmup 5 --no-cpu --no-extras $BENCH_ARGS > "$OUT/trace.log" 2>&1 || { echo "[pmc] kernel trace failed"; tail -5 "$OUT/trace.log"; exit 1; }
 grep -o '"value": [0-9.]*' "$OUT/trace.log" | head -1
 i=0
 while read -r group; do
