@@ -53,7 +53,12 @@ void mgx_destroy(mgx_engine* e);
  * writes into them directly (zero-copy, like the reference's shared numpy arrays).  MGX_MEM_HOST: the engine keeps
  * device mirrors and copies actions in / results out on every step (PCIe-inclusive path).
  * n_rows must equal E*A and n_tokens the program's token budget, else MGX_ERR_BAD_ARG (validate_buffers :1104-1150).
- * Passing all-NULL pointers re-binds the engine's own internal buffers. */
+ * Passing all-NULL pointers re-binds the engine's own internal buffers.
+ * OWNERSHIP (differs from the reference, which refills the whole observation buffer every step): between two calls of this
+ * function the bound observation buffer belongs to the engine.  A step only rewrites each row as far as the longer of its
+ * new and its previous token list and relies on the 0xFF it wrote behind that earlier.  A caller that writes into the bound
+ * observation buffer must call mgx_invalidate_observations before the next step (MGX_MEM_HOST: not needed, the host buffer is
+ * copied out whole).  Reading the buffer is always fine. */
 int mgx_set_buffers(mgx_engine* e, uint8_t* observations, uint8_t* terminals, uint8_t* truncations, float* rewards,
                     int32_t* actions, int32_t* vibe_actions, int64_t n_rows, int64_t n_tokens, int32_t mem_kind);
 
@@ -166,6 +171,15 @@ int mgx_fetch_episode_stats(mgx_engine* e, int32_t wait, double* totals /* [MGX_
 /* Copy the log (all records, oldest first) to host memory and empty it; `records` must hold log_capacity records.
  * *n_dropped: episodes that finished while the log was full since the last drain (they are still in the totals). */
 int mgx_drain_episode_log(mgx_engine* e, uint32_t* records, int32_t max_records, int32_t* n_records, int32_t* n_dropped);
+
+/* Forget what the engine knows about the content of the bound observation buffer (enqueued on the engine's stream): the
+ * next observation pass rewrites every row it touches in full, 0xFF padding included, as after mgx_set_buffers.  For callers
+ * that wrote into the buffer themselves.  MGX_OBS_FULL_ROWS=1 in the environment at mgx_create makes every pass behave so. */
+int mgx_invalidate_observations(mgx_engine* e);
+/* Tokens the last observation pass wrote into each row, u16 [E*A] copied to host memory: every token of the row at or behind
+ * that index is 0xFF 0xFF 0xFF.  0xFFFF = unknown (new buffer, loaded env, invalidated, MGX_OBS_FULL_ROWS, box output since
+ * the buffer was bound). */
+int mgx_get_observation_counts(mgx_engine* e, uint16_t* out);
 
 /* Pointers to the currently bound buffers (observations(), rewards(), ... accessors, mettagrid_py.cpp:291-299);
  * device or host according to mem_kind. */

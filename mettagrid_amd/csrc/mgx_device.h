@@ -144,6 +144,9 @@ struct MgxDev {
   uint32_t* mt_idx;       // [E]
   // ---- caller-visible buffers (device pointers) ----
   uint8_t* obs;           // [E*A][T][3]
+  uint16_t* obs_used;     // [E][A] tokens the last observation pass wrote into the agent's row of `obs`: every token behind them is
+                          // 0xFF 0xFF 0xFF.  0xFFFF = unknown (new buffer, loaded env, caller wrote into it); nullptr: no such
+                          // bookkeeping, every pass rewrites whole rows (MGX_OBS_FULL_ROWS)
   float* rewards;         // [E*A]
   uint8_t* terminals;     // [E*A]
   uint8_t* truncations;   // [E*A]

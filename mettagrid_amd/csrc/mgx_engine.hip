@@ -524,11 +524,18 @@ static int launch_obs(mgx_engine* e, bool with_rewards, const uint8_t* mask = nu
   return MGX_OK;
 }
 
+// MgxDev::obs_used: nothing is known about the bound observation rows any more (stream-ordered): the next observation pass
+// rewrites every row it touches in full.
+static int invalidate_obs(mgx_engine* e) {
+  if (e->d.obs_used) HIP_TRY(hipMemsetAsync(e->d.obs_used, 0xFF, (size_t)e->d.E * e->d.A * 2, e->stream));
+  return MGX_OK;
+}
 // MettaGrid::_init_buffers (mettagrid_c.cpp:294-319): clear the bound buffers, initial observations (action 0).
 static int init_buffers(mgx_engine* e) {
   const MgxDev& d = e->d;
   size_t rows = (size_t)d.E * d.A;
   { int frc = consume_out_fence(e); if (frc) return frc; }
+  { int irc = invalidate_obs(e); if (irc) return irc; }   // the buffer may be new and hold anything
   HIP_TRY(hipMemsetAsync(d.terminals, 0, rows, e->stream));
   HIP_TRY(hipMemsetAsync(d.truncations, 0, rows, e->stream));
   HIP_TRY(hipMemsetAsync(d.rewards, 0, rows * 4, e->stream));
@@ -673,6 +680,9 @@ int mgx_create(const int32_t* program, size_t program_words, const uint16_t* cla
     }
   }
   A_(e->alloc(&e->own_obs, rows * d.T * 3, 0xFF));
+  // not an env state array: a restart keeps the rows and so their counts; whatever may break "0xFF behind the count" resets
+  // them to 0xFFFF (invalidate_obs)
+  if (sw.obs_tail) A_(e->alloc(&d.obs_used, rows, 0xFF));
   A_(e->alloc(&e->own_term, rows));
   A_(e->alloc(&e->own_trunc, rows));
   A_(e->alloc(&e->own_rew, rows));
@@ -1434,6 +1444,21 @@ int mgx_get_action_success(mgx_engine* e, uint8_t* out) {
   if (!e || !out) return fail(MGX_ERR_BAD_ARG, "mgx_get_action_success: null argument");
   return d2h(e, out, e->d.success, (size_t)e->d.E * e->d.A);
 }
+int mgx_invalidate_observations(mgx_engine* e) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_invalidate_observations: null engine");
+  HIP_TRY(hipSetDevice(e->device));
+  return invalidate_obs(e);
+}
+int mgx_get_observation_counts(mgx_engine* e, uint16_t* out) {
+  if (!e || !out) return fail(MGX_ERR_BAD_ARG, "mgx_get_observation_counts: null argument");
+  const size_t rows = (size_t)e->d.E * e->d.A;
+  if (!e->d.obs_used) {   // MGX_OBS_FULL_ROWS: nothing is kept
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (size_t i = 0; i < rows; i++) out[i] = 0xFFFF;
+    return MGX_OK;
+  }
+  return d2h(e, out, e->d.obs_used, rows * 2);
+}
 int mgx_get_current_steps(mgx_engine* e, uint32_t* out) {
   if (!e || !out) return fail(MGX_ERR_BAD_ARG, "mgx_get_current_steps: null argument");
   return d2h(e, out, e->d.step, (size_t)e->d.E * 4);
@@ -1702,7 +1727,7 @@ static int es_stage_lists(mgx_engine* e, const int32_t* a, const int32_t* b, int
 static void es_launch(mgx_engine* e, const int32_t* list, int32_t n, uint8_t* buf, int dir) {
   hipLaunchKernelGGL(mgx_env_state_kernel, dim3((unsigned)((n + MGX_ES_EPG - 1) / MGX_ES_EPG)), dim3(256), 0, e->stream,
                      (const MgxSeg*)e->d_es_segs, (int)e->es_segs_host.size(), list, (int)n, buf, (unsigned long long)e->es.record_bytes,
-                     (unsigned long long)e->es.format, dir, e->d.E, (const uint32_t*)e->d.step, e->d.err, e->d.terr_dirty);
+                     (unsigned long long)e->es.format, dir, e->d.E, (const uint32_t*)e->d.step, e->d.err, e->d.terr_dirty, e->d.obs_used, e->d.A);
 }
 // After envs were written: the auto-reset done list follows their restart-pending words; MGX_MEM_HOST: their caller rows
 // go to the bound host buffers.

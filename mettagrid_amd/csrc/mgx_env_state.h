@@ -179,11 +179,13 @@ __device__ __forceinline__ bool mgx_es_header_ok(const uint8_t* rec, unsigned lo
 // them (the lanes share each row), then all work-items the env-minor segment (consecutive envs of the list in consecutive
 // lanes: with an ascending list each access of a wavefront is 4 runs of 64 bytes).
 // Load checks each record's header first: a record of another layout leaves its env untouched and sets MGX_ENV_BAD_STATE.
-// A loaded env's territory ownership map is marked for a rebuild (terr_dirty).
+// A loaded env's territory ownership map is marked for a rebuild (terr_dirty), and the token counts of its observation rows
+// (obs_used, MgxDev::obs_used: not part of a record) become unknown: the rows now hold another env's tokens.
 __global__ void __launch_bounds__(256) mgx_env_state_kernel(const MgxSeg* __restrict__ segs, int n_segs, const int32_t* __restrict__ list,
                                                             int n, uint8_t* __restrict__ buf, unsigned long long record_bytes,
                                                             unsigned long long format, int dir, int E, const uint32_t* __restrict__ step,
-                                                            uint32_t* __restrict__ err, uint8_t* __restrict__ terr_dirty) {
+                                                            uint32_t* __restrict__ err, uint8_t* __restrict__ terr_dirty, uint16_t* __restrict__ obs_used,
+                                                            int A) {
   const int k0 = (int)blockIdx.x * MGX_ES_EPG;
   const int wave = (int)threadIdx.x / MGX_WAVE, lane = (int)threadIdx.x & (MGX_WAVE - 1), NWV = (int)blockDim.x / MGX_WAVE;
   for (int q = wave; q < MGX_ES_EPG && k0 + q < n; q += NWV) {
@@ -211,6 +213,8 @@ __global__ void __launch_bounds__(256) mgx_env_state_kernel(const MgxSeg* __rest
       else mgx_es_move(row, r, g.bytes, lane, MGX_WAVE);
     }
     if (dir == MGX_ES_LOAD && terr_dirty && lane == 0) terr_dirty[env] = 1;   // (after this lane's own copy of the byte)
+    if (dir == MGX_ES_LOAD && obs_used)
+      for (int a = lane; a < A; a += MGX_WAVE) obs_used[(size_t)env * A + a] = 0xFFFF;
   }
   // env-minor segments: work-item t moves words t / EPG, t / EPG + 256 / EPG, ... of env list[k0 + t % EPG]
   const int q = (int)threadIdx.x % MGX_ES_EPG, k = k0 + q;

@@ -8,8 +8,9 @@
 // Mapping: the env's H*W u16 occupancy grid is streamed once into LDS with coalesced 16-byte loads; each wavefront
 // then encodes agents w, w+4, ... : lanes map to window cells in the reference's Manhattan-shell order, per-cell
 // token counts are turned into output slots with a wavefront exclusive scan (ordered compaction), tokens are
-// assembled in an LDS staging row that starts out as 0xFF (the reference's separate memset of the whole buffer is
-// fused away) and the finished 3*T-byte row is written to HBM with coalesced dword stores.
+// assembled in an LDS staging row and written to HBM with coalesced dword stores.  The reference memsets the whole buffer to
+// 0xFF every step; here a row is only made right up to the longer of what this pass and the previous pass wrote into it
+// (MgxDev::obs_used): the 0xFF behind that is already in the buffer.
 // The reference's "first observer of an object this step gets the cell.visited staleness" rule (:789-796, serial
 // agent order) becomes an LDS atomicMin over observer indices followed by an in-order wavefront reduction.
 //
@@ -449,6 +450,9 @@ static __device__ __forceinline__ void mgx_obs_env(const MgxDev& d, const int en
       s_spawn[i] = spawn;
       s_vstat[i] = vs;
       s_rwinfo[i] = rwi;
+      // tokens the previous pass left in the agent's row (0xFFFF = unknown: the whole row is rewritten), parked in s_written[i]
+      // until the row's encode replaces it with this pass's count — loaded here, with everything else the env stages
+      if constexpr (!BOX) s_written[i] = d.obs_used ? (int)d.obs_used[e.ao(i)] : 0xFFFF;
       if constexpr (X) {
         if (want_mask) {   // the observer's own tag bitset (friend / foe of a cell's owner tag), once per env
           const int32_t* C = d.obj_tags ? nullptr : mgx_cls(d, d.obj_cls[e.so(slot)]);
@@ -839,7 +843,6 @@ static __device__ __forceinline__ void mgx_obs_env(const MgxDev& d, const int en
     const int ac = av ? a : A - 1;  // clamped for the unconditional reads
     const uint32_t ag = s_agents[ac];
     const int my_slot = ag & 0xFFFF;
-    for (int i = rl; i < L.row_words / 4; i += 16) ((uint4*)s_row)[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
     // global tokens were assembled once per env above; copy this agent's
     const int n_global = av ? (int)s_aginfo[ac] : 0;
     for (int k = rl; k < n_global && k < T; k += 16) s_row[k] = s_gtok[ac * GT + k];
@@ -929,6 +932,18 @@ static __device__ __forceinline__ void mgx_obs_env(const MgxDev& d, const int en
         }
       }
     }
+    // The row is made right in [0, hi): this pass's tokens, then 0xFF up to where the previous pass's tokens ended (rounded up
+    // to the four tokens one store covers).  Behind hi the bound buffer already holds 0xFF (MgxDev::obs_used).  The masked
+    // stores of the encode went to TRASH, so only [cur, hi) of the staging row needs the fill.  BOX reads the whole row back.
+    int hi = 0;
+    if (av) {
+      const int cur = min(base_pos, T);
+      const int prev = BOX ? 0xFFFF : s_written[ac];   // (read by the whole row before its lane 0 overwrites it below)
+      hi = min(L.row_words, (max(cur, prev) + 3) & ~3);
+      const int c4 = (cur + 3) & ~3;
+      if (cur + rl < c4) s_row[cur + rl] = ~0u;
+      for (int q = (c4 >> 2) + rl; q * 4 < hi; q += 16) ((uint4*)s_row)[q] = make_uint4(~0u, ~0u, ~0u, ~0u);
+    }
     if (rl == 0 && av) {
       // every addend is >= 1, so the value is non-zero and "key exists" follows from it (see astat_add): a plain
       // store, not a store plus a read-modify-write of the touched word that stalls the row for a round trip
@@ -985,7 +1000,7 @@ static __device__ __forceinline__ void mgx_obs_env(const MgxDev& d, const int en
     } else {
     // ---- pack 4 tokens (4 x u32, low 3 bytes valid) into 12 bytes and store them: the row's 16 lanes sweep it ----
     uint8_t* out = d.obs + ((size_t)env * A + ac) * (size_t)T * 3;
-    for (int q = rl; q * 4 < T && av; q += 16) {
+    for (int q = rl; q * 4 < hi; q += 16) {
       uint4 t = ((const uint4*)s_row)[q];
       uint32_t w0 = (t.x & 0xFFFFFFu) | (t.y << 24);
       uint32_t w1 = ((t.y >> 8) & 0xFFFFu) | (t.z << 16);
@@ -1017,6 +1032,10 @@ static __device__ __forceinline__ void mgx_obs_env(const MgxDev& d, const int en
     // order does not matter -> one wavefront sum.  Otherwise (or on a token overflow) replay the serial order.
     const int nw = lane < A ? s_written[lane] : 0;
     const bool over = __ballot(lane < A && nw > T) != 0;
+    if constexpr (!BOX) {   // what this pass left in the rows (a token overflow fills the row: T)
+      if (d.obs_used)
+        for (int a = lane; a < A; a += MGX_WAVE) d.obs_used[e.ao(a)] = (uint16_t)min(s_written[a], T);
+    }
     const uint32_t sum_w = mgx_wave_sum((uint32_t)nw);
     if (lane == 0) {
       // passes: an episode restart stands for the reference's new MettaGrid + set_buffers, which computes the initial

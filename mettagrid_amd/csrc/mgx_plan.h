@@ -21,7 +21,7 @@
 // the engine's lifetime: a later reset that grows the token pool sizes the observation kernel with the same ones.
 struct MgxSwitches {   // (mgx_read_switches: which switch sets or clears each)
   bool verbose, prog_lds, aoe_local, tick_in_aoe, aoe_prog_lds, flat_top, tick_split, rewards_mid, obs_512, obs_preset, act_lean,
-      act_par, act_map, act_replay, duo, shadow, gen;
+      act_par, act_map, act_replay, duo, shadow, gen, obs_tail;
 };
 inline MgxSwitches mgx_read_switches() {
   auto on = [](const char* name) { return getenv(name) != nullptr; };
@@ -44,6 +44,7 @@ inline MgxSwitches mgx_read_switches() {
   s.duo = !on("MGX_NO_DUO");
   s.shadow = !on("MGX_NO_SHADOW");                  // no integer bookkeeping
   s.gen = !on("MGX_NO_GEN");                        // handlers on the interpreter
+  s.obs_tail = !on("MGX_OBS_FULL_ROWS");            // every observation pass rewrites whole rows (no MgxDev::obs_used)
 #ifdef MGX_CPU_EMU
   // the sanitizer build runs work-items one by one: no LDS program copies (they need a workgroup barrier), no flush kernel
   // for the integer bookkeeping, no wavefront-cooperative (ballot / readlane) lane-per-agent dispatch

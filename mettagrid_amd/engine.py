@@ -148,6 +148,8 @@ def load_lib():
     L.mgx_get_episode_rewards.argtypes = [vp, vp]
     L.mgx_get_action_success.argtypes = [vp, vp]
     L.mgx_get_current_steps.argtypes = [vp, vp]
+    L.mgx_invalidate_observations.argtypes = [vp]
+    L.mgx_get_observation_counts.argtypes = [vp, vp]
     L.mgx_get_stats.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mgx_get_objects.argtypes = [vp, i32, vp, C.POINTER(i32)]
     L.mgx_get_objects_batch.argtypes = [vp, vp, i32, vp, vp]
@@ -598,6 +600,17 @@ class BatchedMettaGrid:
         out = np.empty(self.E * self.A, np.uint8)
         _check(self.L.mgx_get_action_success(self.h, out.ctypes.data))
         return out.astype(bool)
+
+    def invalidate_observations(self) -> None:
+        """For callers that wrote into the bound observation buffer: the next observation pass rewrites whole rows
+        (mgx.h mgx_invalidate_observations).  Between ``set_buffers`` calls the buffer otherwise belongs to the engine."""
+        _check(self.L.mgx_invalidate_observations(self.h))
+
+    def observation_counts(self) -> np.ndarray:
+        """Tokens the last observation pass wrote into each row, u16 [E*A]; 0xFFFF = unknown (mgx.h)."""
+        out = np.empty(self.E * self.A, np.uint16)
+        _check(self.L.mgx_get_observation_counts(self.h, out.ctypes.data))
+        return out
 
     def current_steps(self) -> np.ndarray:
         out = np.empty(self.E, np.uint32)
