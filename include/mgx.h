@@ -190,6 +190,9 @@ int mgx_get_buffers(mgx_engine* e, uint8_t** observations, uint8_t** terminals, 
 int mgx_get_episode_rewards(mgx_engine* e, float* out);
 /* action_success() — mettagrid_py.cpp:196-198.  Copies u8 [E*A]. */
 int mgx_get_action_success(mgx_engine* e, uint8_t* out);
+/* The action each agent executed in the most recent step, i32 [E*A]: the index of its last action that succeeded, 0 when none
+ * did (_last_executed_actions, mettagrid_c.cpp:962-999; grid_objects() exports it as "last_action_id"). */
+int mgx_get_executed_actions(mgx_engine* e, int32_t* out);
 /* current_step — mettagrid_py.cpp:306.  Copies u32 [E]. */
 int mgx_get_current_steps(mgx_engine* e, uint32_t* out);
 
@@ -381,6 +384,33 @@ int mgx_env_state_info(mgx_engine* e, mgx_env_state_info_t* out);
 int mgx_save_envs(mgx_engine* e, const int32_t* envs, int32_t n, void* dst);   /* dst: device memory, n * record_bytes */
 int mgx_load_envs(mgx_engine* e, const int32_t* envs, int32_t n, const void* src, const mgx_env_state_info_t* saved);
 int mgx_copy_envs(mgx_engine* e, const int32_t* src_envs, const int32_t* dst_envs, int32_t n);
+
+/* ---- Replays of watched envs (csrc/mgx_replay.h; DESIGN.md "Replays") ----
+ * Reference: ReplayLogWriter (python/src/mettagrid/simulator/replay_log_writer.py) calls grid_objects() after every step and
+ * diffs the result on the host.  Here a kernel at the end of every mgx_step compares the objects of the WATCHED envs with
+ * what it logged last and appends only the changes to a per-env log in device memory; the host drains the log whenever it
+ * likes and mettagrid_amd/replay.py turns the words into the reference's version-4 replay dicts.  An engine without a watch
+ * list enqueues nothing for this.  The log, its cursors and the shadow belong to the slot, never to a saved env state.
+ * mgx_set_replay: envs int32 [n_envs] host memory, each in [0, E) and listed once; words_per_env: uint32 words of each env's
+ *   own log region (a step that does not fit is dropped whole, the env stops logging until its next episode and raises
+ *   MGX_RPL_ENV_OVERFLOW); static_type_ids int32 [n_static] host memory: objects of these type ids are logged in keyframes
+ *   only (the reference: {"wall"}).  Every watched env starts with a keyframe.  n_envs = 0 switches the recorder off and
+ *   frees its buffers.  MGX_ERR_BAD_ARG: a list entry out of range or repeated, words_per_env <= 0, MGX_MEM_HOST buffers —
+ *   refused before anything is touched: a recorder that is running keeps running.  An accepted call replaces the recorder
+ *   and discards what the old one had logged and not drained.
+ * An END marker is written when a step leaves the env done, by mgx_record_episodes, by mgx_reset_envs* inside an episode
+ * (MGX_RPL_E_ABORTED) and by mgx_load_envs / mgx_copy_envs onto the env (MGX_RPL_E_DISCONTINUITY); a keyframe follows. */
+int mgx_set_replay(mgx_engine* e, const int32_t* envs, int32_t n_envs, int32_t words_per_env, const int32_t* static_type_ids,
+                   int32_t n_static);
+/* Layout words (int32 [MGX_RPL_L_COUNT]); the markers, flags and field groups are the MGX_RPL_* of include/mgx_program.h. */
+enum { MGX_RPL_L_NUM_ENVS = 0, MGX_RPL_L_WORDS_PER_ENV, MGX_RPL_L_STEP_WORDS, MGX_RPL_L_END_WORDS, MGX_RPL_L_SLOT_WORDS,
+       MGX_RPL_L_AMOUNT_WORDS, MGX_RPL_L_GROUPS, MGX_RPL_L_OBJECT_SLOTS,
+       MGX_RPL_L_MAX_STEP_WORDS /* the largest step: a keyframe of a full env with its END marker */, MGX_RPL_L_COUNT };
+int mgx_replay_layout(mgx_engine* e, int32_t* out /* [MGX_RPL_L_COUNT] */);
+/* Copy every watched env's used prefix to host memory — words_out uint32 [n_envs][words_per_env], n_words_out int32 [n_envs],
+ * flags_out uint32 [n_envs] (MGX_RPL_ENV_*; may be NULL), in watch-list order — and empty the logs on the engine's stream
+ * (the overflow flags with them).  The shadows stay: an episode may span drains.  Waits for the device. */
+int mgx_drain_replay(mgx_engine* e, uint32_t* words_out, int32_t* n_words_out, uint32_t* flags_out);
 
 int32_t mgx_num_envs(const mgx_engine* e);
 int32_t mgx_num_agents(const mgx_engine* e);   /* per env */

@@ -35,6 +35,23 @@
 #define MGX_ES_VERSION 1
 #define MGX_ES_HEADER_BYTES 32
 #define MGX_ES_ALIGN 16         /* every segment of a record starts on this boundary */
+/* Replay log of watched envs (include/mgx.h mgx_set_replay; mettagrid_amd/csrc/mgx_replay.h holds the word layout).  A marker
+ * word carries its flags in the low 16 bits. */
+#define MGX_RPL_STEP 0x53540000 /* step header of MGX_RPL_STEP_WORDS: marker | MGX_RPL_F_*, current step, event words that follow */
+#define MGX_RPL_END 0x454E0000  /* episode end of MGX_RPL_END_WORDS: marker | MGX_RPL_E_*, current step */
+#define MGX_RPL_STEP_WORDS 3
+#define MGX_RPL_END_WORDS 2
+#define MGX_RPL_SLOT_WORDS 28   /* logged state of one object slot = the five field groups below */
+#define MGX_RPL_AMOUNT_WORDS 7  /* u16 pairs by resource id (inventory amounts, effective limits) */
+#define MGX_RPL_GROUPS 5
+enum { MGX_RPL_F_KEYFRAME = 1 };
+enum { MGX_RPL_E_TERMINAL = 1, MGX_RPL_E_TRUNCATED = 2, MGX_RPL_E_ABORTED = 4 /* restarted by the host inside an episode */,
+       MGX_RPL_E_DISCONTINUITY = 8 /* another state was loaded or copied onto the env */ };
+/* event header = slot | field mask << 16; groups follow in bit order: CORE 2 words, INV 2 + 7, TAGS 8, LIMITS 7, AGENT 2 */
+enum { MGX_RPL_M_CORE = 1, MGX_RPL_M_INV = 2, MGX_RPL_M_TAGS = 4, MGX_RPL_M_LIMITS = 8, MGX_RPL_M_AGENT = 16 };
+/* per-env recorder state (flags_out of mgx_drain_replay) */
+enum { MGX_RPL_ENV_OVERFLOW = 1 /* a step did not fit since the last drain */, MGX_RPL_ENV_MUTED = 2 /* not logging until the next
+       episode */, MGX_RPL_ENV_KEYFRAME_NEXT = 4 /* the next logged step is a keyframe */ };
 #define MGX_MAX_QUERY_DEPTH 3          /* query nesting (the device's eval_query<3> at the top) */
 #define MGX_INVALID_WINDOW 16 /* action.invalid_index.<k> is a fixed stat column for k in [-16,-1] and [n_actions, n_actions+15] */
 #define MGX_INVALID_EXTRA 4   /* ... and one of this many (k, count) pairs per agent and episode for any other k */

@@ -20,6 +20,7 @@
 #include "mgx_episode.h"
 #include "mgx_plan.h"       // mgx_create's host-only half: validation and every create-time decision
 #include "mgx_env_state.h"  // what an env's state is (the one list of its arrays) and the save / load kernel
+#include "mgx_replay.h"     // change log of the watched envs (mgx_set_replay)
 
 
 // Territory ownership map (TerritoryTracker::compute_cell_ownership, core/territory_tracker.cpp:215-252) of every cell,
@@ -300,6 +301,9 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
   std::vector<uint8_t> es_lists;      // host side of the env lists uploaded through d_stage ...
   hipEvent_t es_ev = nullptr;         // ... recorded behind that upload: the vector is reused once it has completed
   bool es_ev_pending = false;
+  // replays of watched envs (mgx_set_replay; csrc/mgx_replay.h): slot-owned, never part of an env-state record
+  MgxRpl rpl{};                     // device pointers of the watch list, log, cursors, recorder state, shadow, static-class bits
+  int rpl_n = 0;                    // watched envs (0: the recorder is off and mgx_step enqueues nothing for it)
   int32_t* d_objs = nullptr;        // mgx_get_objects_batch: env list | counts | packed records
   size_t objs_cap = 0;              // envs the buffer holds
   float* d_scale = nullptr;         // per-feature scale of the token decode (mgx_decode_obs)
@@ -603,6 +607,36 @@ static int launch_episode_stats(mgx_engine* e) {
   return MGX_OK;
 }
 
+static void free_replay(mgx_engine* e) {
+  for (const void* p : {(const void*)e->rpl.envs, (const void*)e->rpl.log, (const void*)e->rpl.cursor, (const void*)e->rpl.state,
+                        (const void*)e->rpl.shadow, (const void*)e->rpl.static_cls})
+    if (p) (void)hipFree(const_cast<void*>(p));
+  e->rpl = MgxRpl{};
+  e->rpl_n = 0;
+}
+// The step's changes of the watched envs -> their logs (csrc/mgx_replay.h); nothing without a watch list.
+static int launch_replay(mgx_engine* e) {
+#ifndef MGX_CPU_EMU
+  if (!e->rpl_n) return MGX_OK;
+  hipLaunchKernelGGL(mgx_replay_kernel, dim3((unsigned)e->rpl_n), dim3(MGX_RPL_THREADS), 0, e->stream, dev_copy(e), e->rpl);
+  HIP_TRY(hipGetLastError());
+#else
+  (void)e;
+#endif
+  return MGX_OK;
+}
+// The episodes of the envs in a DEVICE list are cut from outside a step: END marker with `flags`, keyframe next.
+static int mark_replay(mgx_engine* e, const int32_t* dlist, int n, uint32_t flags) {
+#ifndef MGX_CPU_EMU
+  if (!e->rpl_n || n <= 0) return MGX_OK;
+  hipLaunchKernelGGL(mgx_replay_mark_kernel, dim3((unsigned)e->rpl_n), dim3(MGX_RPL_THREADS), 0, e->stream, dev_copy(e), e->rpl, dlist, n, flags);
+  HIP_TRY(hipGetLastError());
+#else
+  (void)e; (void)dlist; (void)n; (void)flags;
+#endif
+  return MGX_OK;
+}
+
 extern "C" {
 
 const char* mgx_last_error(void) { return g_err.c_str(); }
@@ -785,6 +819,7 @@ void mgx_destroy(mgx_engine* e) {
   if (e->jit_obs.mod) (void)hipModuleUnload(e->jit_obs.mod);
   if (e->jit_actx.mod) (void)hipModuleUnload(e->jit_actx.mod);
   free_episode_stats(e);
+  free_replay(e);
   for (int i = 0; i <= MGX_T_COUNT; i++) if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
   if (e->world_done) (void)hipEventDestroy(e->world_done);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -963,6 +998,8 @@ int mgx_reset_envs(mgx_engine* e, const uint8_t* env_mask, const uint16_t* class
   HIP_TRY(hipGetLastError());
   MgxList l;
   l.list = (const int32_t*)st; l.n = (const uint32_t*)(st + off_n); l.n_host = (int)n;
+  rc = mark_replay(e, l.list, (int)n, MGX_RPL_E_ABORTED);
+  if (rc) return rc;
   rc = restart_masked(e, e->dmask, false, false, l);
   if (rc) return rc;
   if (e->mem_kind == MGX_MEM_HOST) {  // host buffers: the restarted rows, one copy per contiguous run of envs
@@ -1036,6 +1073,8 @@ int mgx_reset_envs_from_pool(mgx_engine* e, const uint8_t* env_mask, const int32
   HIP_TRY(hipGetLastError());
   MgxList l;
   l.list = (const int32_t*)st; l.n = (const uint32_t*)(st + n * 12); l.n_host = (int)n;
+  rc = mark_replay(e, l.list, (int)n, MGX_RPL_E_ABORTED);
+  if (rc) return rc;
   rc = restart_masked(e, e->dmask, true, false, l);
   if (rc) return rc;
   if (e->mem_kind == MGX_MEM_HOST) {
@@ -1227,6 +1266,7 @@ int mgx_record_episodes(mgx_engine* e, const uint8_t* env_mask) {
   HIP_TRY(hipMemcpyAsync(e->d_done_list, idx.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(e->d_done_n, &n, 4, hipMemcpyHostToDevice, e->stream));
   int rc = launch_episode_stats(e);
+  if (!rc) rc = mark_replay(e, e->d_done_list, (int)n, 0);
   if (rc) return rc;
   HIP_TRY(hipMemsetAsync(e->d_done_n, 0, 4, e->stream));   // the list belongs to this call only
   HIP_TRY(hipStreamSynchronize(e->stream));  // `idx` and `n` are locals
@@ -1281,6 +1321,94 @@ int mgx_drain_episode_log(mgx_engine* e, uint32_t* records, int32_t max_records,
   HIP_TRY(hipStreamSynchronize(e->stream));
   *n_records = (int32_t)st[0];
   if (n_dropped) *n_dropped = (int32_t)st[1];
+  return MGX_OK;
+}
+
+int mgx_set_replay(mgx_engine* e, const int32_t* envs, int32_t n_envs, int32_t words_per_env, const int32_t* static_type_ids,
+                   int32_t n_static) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_replay: null engine");
+  HIP_TRY(hipSetDevice(e->device));
+  if (n_envs == 0) {
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    free_replay(e);
+    return MGX_OK;
+  }
+#ifdef MGX_CPU_EMU
+  (void)envs; (void)words_per_env; (void)static_type_ids; (void)n_static;
+  return fail(MGX_ERR_BAD_ARG, "mgx_set_replay: not part of the sanitizer build");
+#else
+  // every refusal comes before anything is touched: a recorder that is running keeps running, its log undrained
+  const MgxDev& d = e->d;
+  if (n_envs < 0 || !envs || words_per_env <= 0 || n_static < 0 || (n_static > 0 && !static_type_ids))
+    return fail(MGX_ERR_BAD_ARG, "mgx_set_replay: bad argument (env list, words_per_env > 0, static type ids)");
+  if (e->mem_kind == MGX_MEM_HOST) return fail(MGX_ERR_BAD_ARG, "mgx_set_replay: the engine is bound to host buffers (MGX_MEM_HOST); replays need device buffers");
+  std::vector<uint8_t> seen((size_t)d.E, 0);
+  for (int32_t k = 0; k < n_envs; k++) {
+    if (envs[k] < 0 || envs[k] >= d.E)
+      return fail(MGX_ERR_BAD_ARG, "mgx_set_replay: env index " + std::to_string(envs[k]) + " out of range [0, " + std::to_string(d.E) + ")");
+    if (seen[envs[k]]++) return fail(MGX_ERR_BAD_ARG, "mgx_set_replay: env " + std::to_string(envs[k]) + " listed twice");
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  free_replay(e);   // an accepted call replaces the recorder: what the old one had logged and not drained is gone
+  const int nc = e->prog[MGX_H_NUM_CLASSES];
+  std::vector<uint32_t> bits((size_t)(nc + 31) / 32 + 1, 0u);
+  const int32_t* cls0 = e->prog.data() + mgx_sec_off(e->prog.data(), MGX_SEC_CLASSES);
+  for (int c = 0; c < nc; c++)
+    for (int32_t k = 0; k < n_static; k++)
+      if (cls0[c * MGX_C_WORDS + MGX_C_TYPE_ID] == static_type_ids[k]) bits[c >> 5] |= 1u << (c & 31);
+  const std::vector<uint32_t> st0((size_t)n_envs, (uint32_t)MGX_RPL_ENV_KEYFRAME_NEXT);
+  const size_t n = (size_t)n_envs, shadow_words = n * MGX_RPL_SLOT_WORDS * (size_t)d.S;
+  MgxRpl& r = e->rpl;
+  hipError_t he = hipMalloc((void**)&r.envs, n * 4);
+  if (he == hipSuccess) he = hipMalloc((void**)&r.log, n * (size_t)words_per_env * 4);
+  if (he == hipSuccess) he = hipMalloc((void**)&r.cursor, n * 4);
+  if (he == hipSuccess) he = hipMalloc((void**)&r.state, n * 4);
+  if (he == hipSuccess) he = hipMalloc((void**)&r.shadow, shadow_words * 4);
+  if (he == hipSuccess) he = hipMalloc((void**)&r.static_cls, bits.size() * 4);
+  if (he == hipSuccess) he = hipMemcpyAsync((void*)r.envs, envs, n * 4, hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipMemcpyAsync(r.state, st0.data(), n * 4, hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipMemcpyAsync((void*)r.static_cls, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipMemsetAsync(r.cursor, 0, n * 4, e->stream);
+  if (he == hipSuccess) he = hipMemsetAsync(r.shadow, 0, shadow_words * 4, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);   // the uploads read locals
+  if (he != hipSuccess) {
+    free_replay(e);
+    return fail(MGX_ERR_HIP, std::string("mgx_set_replay: ") + hipGetErrorString(he));
+  }
+  r.words_per_env = (uint32_t)words_per_env;
+  e->rpl_n = n_envs;
+  return MGX_OK;
+#endif
+}
+
+int mgx_replay_layout(mgx_engine* e, int32_t* out) {
+  if (!e || !out) return fail(MGX_ERR_BAD_ARG, "mgx_replay_layout: null argument");
+  const long long max_step = (long long)MGX_RPL_STEP_WORDS + (long long)e->d.S * (1 + MGX_RPL_SLOT_WORDS) + MGX_RPL_END_WORDS;
+  const int32_t v[MGX_RPL_L_COUNT] = {e->rpl_n, (int32_t)e->rpl.words_per_env, MGX_RPL_STEP_WORDS, MGX_RPL_END_WORDS, MGX_RPL_SLOT_WORDS,
+                                      MGX_RPL_AMOUNT_WORDS, MGX_RPL_GROUPS, e->d.S, (int32_t)std::min<long long>(max_step, INT32_MAX)};
+  memcpy(out, v, sizeof(v));
+  return MGX_OK;
+}
+
+int mgx_drain_replay(mgx_engine* e, uint32_t* words_out, int32_t* n_words_out, uint32_t* flags_out) {
+  if (!e || !words_out || !n_words_out) return fail(MGX_ERR_BAD_ARG, "mgx_drain_replay: null argument");
+  if (!e->rpl_n) return fail(MGX_ERR_BAD_ARG, "mgx_drain_replay: no watch list (mgx_set_replay)");
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t n = (size_t)e->rpl_n, cap = e->rpl.words_per_env;
+  std::vector<uint32_t> cur(n), st(n);
+  HIP_TRY(hipMemcpyAsync(cur.data(), e->rpl.cursor, n * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(st.data(), e->rpl.state, n * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (size_t k = 0; k < n; k++) {
+    const size_t used = std::min<size_t>(cur[k], cap);
+    n_words_out[k] = (int32_t)used;
+    if (flags_out) flags_out[k] = st[k];
+    if (used) HIP_TRY(hipMemcpyAsync(words_out + k * cap, e->rpl.log + k * cap, used * 4, hipMemcpyDeviceToHost, e->stream));
+    st[k] &= ~(uint32_t)MGX_RPL_ENV_OVERFLOW;
+  }
+  HIP_TRY(hipMemsetAsync(e->rpl.cursor, 0, n * 4, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->rpl.state, st.data(), n * 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));   // `st` is a local; the caller reads words_out
   return MGX_OK;
 }
 
@@ -1376,6 +1504,7 @@ int mgx_step(mgx_engine* e) {
     HIP_TRY(hipGetLastError());
     if (e->ep_stats) { int erc = launch_episode_stats(e); if (erc) return erc; }
   }
+  if (e->rpl_n) { int prc = launch_replay(e); if (prc) return prc; }
   if (e->mem_kind == MGX_MEM_HOST) {
     HIP_TRY(hipMemcpyAsync(e->h_obs, d.obs, rows * d.T * 3, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipMemcpyAsync(e->h_term, d.terminals, rows, hipMemcpyDeviceToHost, e->stream));
@@ -1443,6 +1572,10 @@ int mgx_get_episode_rewards(mgx_engine* e, float* out) {
 int mgx_get_action_success(mgx_engine* e, uint8_t* out) {
   if (!e || !out) return fail(MGX_ERR_BAD_ARG, "mgx_get_action_success: null argument");
   return d2h(e, out, e->d.success, (size_t)e->d.E * e->d.A);
+}
+int mgx_get_executed_actions(mgx_engine* e, int32_t* out) {
+  if (!e || !out) return fail(MGX_ERR_BAD_ARG, "mgx_get_executed_actions: null argument");
+  return d2h(e, out, e->d.executed, (size_t)e->d.E * e->d.A * 4);
 }
 int mgx_invalidate_observations(mgx_engine* e) {
   if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_invalidate_observations: null engine");
@@ -1789,6 +1922,7 @@ int mgx_load_envs(mgx_engine* e, const int32_t* envs, int32_t n, const void* src
   const int32_t *dl = nullptr, *unused = nullptr;
   const uint32_t* dn = nullptr;
   if (!rc) rc = es_stage_lists(e, envs, nullptr, n, &dl, &unused, &dn);
+  if (!rc) rc = mark_replay(e, dl, n, MGX_RPL_E_DISCONTINUITY);   // (before the write: the marker carries the step of the episode that ends here)
   if (rc) return rc;
   es_launch(e, dl, n, (uint8_t*)src, MGX_ES_LOAD);
   HIP_TRY(hipGetLastError());
@@ -1817,6 +1951,8 @@ int mgx_copy_envs(mgx_engine* e, const int32_t* src_envs, const int32_t* dst_env
   if (!rc) rc = flush_shadow(e, ds, dn, (unsigned)(((long long)n * e->d.A + 255) / 256));
   if (rc) return rc;
   es_launch(e, ds, n, e->d_es_buf, MGX_ES_SAVE);
+  rc = mark_replay(e, dd, n, MGX_RPL_E_DISCONTINUITY);
+  if (rc) return rc;
   es_launch(e, dd, n, e->d_es_buf, MGX_ES_LOAD);
   HIP_TRY(hipGetLastError());
   return es_after_write(e, dst_envs, n);

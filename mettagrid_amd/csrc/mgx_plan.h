@@ -364,6 +364,10 @@ inline int mgx_plan(const int32_t* P, size_t words, const uint16_t* class_maps, 
       cap.m += per.m ? std::min<int>(d.S * per.m, 4096) : 0;
     }
     d.NF = cap.f; d.NM = cap.m; d.NTS = cap.t;
+    // A territory type without a source on any create map: the observation kernel's aoe_mask staging, the area-effect
+    // kernel and cell_owner read the ownership map and the source count of every env unconditionally, so both exist
+    // (room for one source, none registered) — with NTS = 0 they were null pointers and the first observation pass faulted.
+    if (d.NT > 0 && d.NTS == 0) d.NTS = 1;
     d.FW = std::max(1, (d.NF + 31) / 32); d.MW = std::max(1, (d.NM + 31) / 32);
     d.X = (any_aoe || d.NT > 0 || d.n_schedule > 0 || d.n_matq > 0 || d.game_on_tick >= 0 || P[MGX_H_DYNAMIC_TAGS] ||
            mgx_sec_cnt(P, MGX_SEC_QUERIES) > 0) ? 1 : 0;

@@ -148,6 +148,7 @@ def load_lib():
     L.mgx_get_episode_rewards.argtypes = [vp, vp]
     L.mgx_get_action_success.argtypes = [vp, vp]
     L.mgx_get_current_steps.argtypes = [vp, vp]
+    L.mgx_get_executed_actions.argtypes = [vp, vp]
     L.mgx_invalidate_observations.argtypes = [vp]
     L.mgx_get_observation_counts.argtypes = [vp, vp]
     L.mgx_get_stats.argtypes = [vp, i32, vp, vp, vp, vp]
@@ -192,6 +193,9 @@ def load_lib():
     L.mgx_save_envs.argtypes = [vp, vp, i32, vp]
     L.mgx_load_envs.argtypes = [vp, vp, i32, vp, C.POINTER(EnvStateInfo)]
     L.mgx_copy_envs.argtypes = [vp, vp, vp, i32]
+    L.mgx_set_replay.argtypes = [vp, vp, i32, i32, vp, i32]
+    L.mgx_replay_layout.argtypes = [vp, vp]
+    L.mgx_drain_replay.argtypes = [vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -541,6 +545,46 @@ class BatchedMettaGrid:
                 out["agent"][k] = v / A
         return out
 
+    # ---- replays of watched envs (include/mgx.h "Replays"; mettagrid_amd/replay.py) ----
+    RPL = ("NUM_ENVS", "WORDS_PER_ENV", "STEP_WORDS", "END_WORDS", "SLOT_WORDS", "AMOUNT_WORDS", "GROUPS", "OBJECT_SLOTS", "MAX_STEP_WORDS")
+
+    def set_replay(self, envs, words_per_env: int | None = None, static_types=("wall",)) -> None:
+        """Record the listed envs' episodes on the device: from the next step on, a kernel behind every step appends what
+        changed in their objects to a per-env log of ``words_per_env`` uint32 (default: room for four keyframes of a full env).
+        Objects whose type name is in ``static_types`` are logged in keyframes only (the reference's list).  An empty list
+        switches the recorder off."""
+        idx = np.ascontiguousarray(np.asarray(envs if envs is not None else [], dtype=np.int64).reshape(-1))
+        self.replay_envs = []
+        if idx.size == 0:
+            _check(self.L.mgx_set_replay(self.h, None, 0, 0, None, 0))
+            return
+        if idx.min() < -2**31 or idx.max() >= 2**31:
+            raise ValueError(f"set_replay: env index out of range [0, {self.E})")
+        idx = idx.astype(np.int32)
+        tids = np.ascontiguousarray([i for i, n in enumerate(self.prog.type_names) if n in set(static_types)], dtype=np.int32)
+        if words_per_env is None:
+            words_per_env = 4 * (K.RPL_STEP_WORDS + self.prog.max_objects * (1 + K.RPL_SLOT_WORDS) + K.RPL_END_WORDS)
+        _check(self.L.mgx_set_replay(self.h, idx.ctypes.data, int(idx.size), int(words_per_env), tids.ctypes.data if tids.size else None,
+                                     int(tids.size)))
+        self.replay_envs = [int(x) for x in idx]
+
+    def replay_layout(self) -> dict:
+        out = np.zeros(len(self.RPL), np.int32)
+        _check(self.L.mgx_replay_layout(self.h, out.ctypes.data))
+        return {k: int(v) for k, v in zip(self.RPL, out)}
+
+    def drain_replay(self):
+        """(words, flags): per watched env, in watch-list order, the uint32 words logged since the last drain and the
+        recorder's state bits (``K.RPL_ENV_OVERFLOW`` ...).  Empties the logs; waits for the device."""
+        lay = self.replay_layout()
+        n, cap = lay["NUM_ENVS"], lay["WORDS_PER_ENV"]
+        if n == 0:
+            raise ValueError("no watch list: set_replay(envs)")
+        raw = np.empty((n, cap), np.uint32)
+        used, flags = np.zeros(n, np.int32), np.zeros(n, np.uint32)
+        _check(self.L.mgx_drain_replay(self.h, raw.ctypes.data, used.ctypes.data, flags.ctypes.data))
+        return [raw[i, : used[i]].copy() for i in range(n)], [int(f) for f in flags]
+
     @property
     def stream(self) -> int:
         return int(self.L.mgx_stream(self.h) or 0)
@@ -600,6 +644,12 @@ class BatchedMettaGrid:
         out = np.empty(self.E * self.A, np.uint8)
         _check(self.L.mgx_get_action_success(self.h, out.ctypes.data))
         return out.astype(bool)
+
+    def executed_actions(self) -> np.ndarray:
+        """The action each agent executed in the last step (0: none succeeded), int32 [E*A] (mgx.h mgx_get_executed_actions)."""
+        out = np.empty(self.E * self.A, np.int32)
+        _check(self.L.mgx_get_executed_actions(self.h, out.ctypes.data))
+        return out
 
     def invalidate_observations(self) -> None:
         """For callers that wrote into the bound observation buffer: the next observation pass rewrites whole rows

@@ -154,7 +154,9 @@ class MettaGridBatchedEnv:
                  seed_fn: Optional[Callable[[int, int, int], int]] = None, device: int = 0, seed: int = 0,
                  buffers: str = "device", map_pool: Optional[np.ndarray] = None, pool_stride: int = 1,
                  desync: bool = False, validate_actions: bool = True, episode_stats: bool = True, stats_interval: int = 1,
-                 episode_log: int = 0, log_per_agent: bool = False, specialize="auto") -> None:
+                 episode_log: int = 0, log_per_agent: bool = False, specialize="auto", replay_envs=None,
+                 replay_dir: Optional[str] = None, replay_words_per_env: Optional[int] = None, replay_interval: int = 64,
+                 replay_capacity_groups: Optional[dict] = None) -> None:
         if (map_fn is None) == (map_pool is None):
             raise ValueError("give exactly one of map_fn and map_pool")
         self.prog = prog
@@ -182,6 +184,18 @@ class MettaGridBatchedEnv:
         self.log_per_agent = log_per_agent
         self.specialize = specialize      # BatchedMettaGrid(specialize=...): run-time code objects for this program (jit.py)
         self._steps = 0
+        # replays of watched envs (BatchedMettaGrid.set_replay; mettagrid_amd/replay.py)
+        self.replay_envs = [int(e) for e in (replay_envs or [])]
+        self.replay_dir = replay_dir
+        self.replay_words_per_env = replay_words_per_env
+        self.replay_interval = max(1, int(replay_interval))
+        self.replay_capacity_groups = replay_capacity_groups
+        self.replay_paths: dict = {}      # (env, episode index of that env) -> file written
+        self.replays_overflowed = 0       # drains that found a watched env's log full (that episode is not written)
+        if self.replay_envs and buffers != "device":
+            raise ValueError("replay_envs needs device buffers")
+        if self.replay_envs and not replay_dir:
+            raise ValueError("replay_envs needs replay_dir")
 
     def set_supervisor(self, supervisor) -> None:
         """Supervisor-policy path of MettaGridPufferEnv (mettagrid_puffer_env.py:399-426): after every step
@@ -257,6 +271,16 @@ class MettaGridBatchedEnv:
         if self.episode_stats:
             self._eng.set_episode_stats(True, self.episode_log, self.log_per_agent)
         self._steps = 0
+        if self.replay_envs:
+            from .replay import ReplayAssembler
+            import os
+            os.makedirs(self.replay_dir, exist_ok=True)
+            self._eng.set_replay(self.replay_envs, words_per_env=self.replay_words_per_env)
+            self._assemblers = [ReplayAssembler(self.prog, capacity_groups=self.replay_capacity_groups) for _ in self.replay_envs]
+            self._replay_count = [0] * len(self.replay_envs)          # episode index of the next replay of each watched env
+            self._replay_unnumbered = [False] * len(self.replay_envs)  # an episode was lost to overflow: indices unknown from there on
+            self._replay_steps = 0
+            self.replay_paths = {}
         ids = [self.prog.action_names.index(n) for n in self.vibe_action_names]
         self._vibe_ids_host = np.asarray(ids, dtype=np.int32)
         if self._kind == "device":
@@ -322,10 +346,45 @@ class MettaGridBatchedEnv:
             n, v = len(self.action_names), len(self.vibe_action_names)
             raise ValueError(f"Action indices out of range [0, {n + n * v if v else n}), got {value} for agent {row}")
 
+    def flush_replays(self) -> list:
+        """Drain the watched envs' logs (synchronises with the device) and write one file per episode that finished in them:
+        ``<replay_dir>/env<e>_ep<k>.json.z``, k = the env's episode index as the episode log counts it.  Returns the paths
+        written by this call.  ``step`` calls it when a watched env finishes where it has the done flags on the host anyway
+        (host map source); with a map pool the step never reads them (auto-reset is on the device), so there the logs are
+        drained every ``replay_interval`` steps — a device synchronisation each time — and by ``episode_infos()`` / ``close()``.
+        An episode lost to a full log (``replays_overflowed``) leaves no END marker, so the env's later episodes can no longer
+        be numbered: their files are named ``env<e>_unnumbered<n>.json.z`` and are not attached to ``episode_infos()``."""
+        if not self.replay_envs or self._eng is None:
+            return []
+        from .fmt import K
+        from .replay import write_replay
+        import os
+        words, flags = self.engine.drain_replay()
+        out = []
+        for k, env in enumerate(self.replay_envs):
+            for ep in self._assemblers[k].feed(words[k]):
+                n = self._replay_count[k]
+                if not self._replay_unnumbered[k]:
+                    ep["infos"]["attributes"]["seed"] = int(self.seed_fn(self._seed, env, n))
+                if self._replay_unnumbered[k]:
+                    path = os.path.join(self.replay_dir, f"env{env}_unnumbered{n}.json.z")
+                else:
+                    path = os.path.join(self.replay_dir, f"env{env}_ep{n}.json.z")
+                    self.replay_paths[(env, n)] = path
+                write_replay(ep, path)
+                self._replay_count[k] += 1
+                out.append(path)
+            if flags[k] & K.RPL_ENV_OVERFLOW:   # (a drain clears this bit: one lost episode is counted once)
+                self.replays_overflowed += 1
+            if flags[k] & (K.RPL_ENV_OVERFLOW | K.RPL_ENV_MUTED):   # (behind the episodes that were complete before it)
+                self._replay_unnumbered[k] = True
+        return out
+
     def episode_infos(self) -> list:
         """The episodes that finished since the last call, one dict each in the reference's shape (stats_tracker.py:26-76):
         ``game``, ``agent``, ``per_agent`` (with ``log_per_agent``), ``episode_rewards``, ``attributes`` (seed, map_w, map_h,
         steps, max_steps) + ``env`` / ``episode`` / ``map_index``.  Needs ``episode_log`` > 0; synchronises with the device."""
+        self.flush_replays()
         recs, dropped = self.engine.drain_episode_log()
         words = self.prog.words
         out = []
@@ -336,6 +395,8 @@ class MettaGridBatchedEnv:
                     "env": r["env"], "episode": r["episode"], "map_index": r["map_index"]}
             if "per_agent" in r:
                 info["per_agent"] = {str(i): dct for i, dct in enumerate(r["per_agent"])}
+            if (r["env"], r["episode"]) in self.replay_paths:
+                info["replay_path"] = self.replay_paths[(r["env"], r["episode"])]
             out.append(info)
         self.episodes_dropped = dropped
         return out
@@ -348,6 +409,8 @@ class MettaGridBatchedEnv:
                 idx = np.nonzero(done)[0]
                 if self.episode_stats:
                     eng.record_episodes(done)
+                if self.replay_envs and any(done[e] for e in self.replay_envs):
+                    self.flush_replays()
                 self.episode[idx] += 1
                 eng.reset_envs(done, self._maps(idx), self._seeds())
         if self._kind == "device":
@@ -396,7 +459,12 @@ class MettaGridBatchedEnv:
             eng.step()
             if self.supervisor is not None:
                 self._compute_supervisor_actions()
-        return eng.obs, eng.rewards, eng.terminals, eng.truncations, self._step_infos()
+        infos = self._step_infos()
+        if self.replay_envs and self.map_pool is not None:
+            self._replay_steps += 1
+            if self._replay_steps % self.replay_interval == 0:
+                self.flush_replays()
+        return eng.obs, eng.rewards, eng.terminals, eng.truncations, infos
 
     # ---- saving and restoring envs' state (BatchedMettaGrid.save_envs / load_envs) ----
     def save_state(self, envs=None):
@@ -419,6 +487,7 @@ class MettaGridBatchedEnv:
 
     def close(self) -> None:
         if self._eng is not None:
+            self.flush_replays()
             self._eng.close()
             self._eng = None
 
