@@ -21,6 +21,7 @@
 #include "mgx_plan.h"       // mgx_create's host-only half: validation and every create-time decision
 #include "mgx_env_state.h"  // what an env's state is (the one list of its arrays) and the save / load kernel
 #include "mgx_replay.h"     // change log of the watched envs (mgx_set_replay)
+#include "mgx_mapgen.h"     // the random map builder on the device (mgx_set_map_generator)
 
 
 // Territory ownership map (TerritoryTracker::compute_cell_ownership, core/territory_tracker.cpp:215-252) of every cell,
@@ -304,6 +305,14 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
   // replays of watched envs (mgx_set_replay; csrc/mgx_replay.h): slot-owned, never part of an env-state record
   MgxRpl rpl{};                     // device pointers of the watch list, log, cursors, recorder state, shadow, static-class bits
   int rpl_n = 0;                    // watched envs (0: the recorder is off and mgx_step enqueues nothing for it)
+  // device map generator (mgx_set_map_generator; csrc/mgx_mapgen.h): the recipe and the base seeds belong to the slot, never
+  // to a saved env state
+  MgxMapGen gen{};                  // device pointers into d_gen_recipe + the shape
+  bool gen_on = false;              // (false: mgx_step and the restarts enqueue nothing for it)
+  size_t gen_lds = 0;               // dynamic LDS of mgx_mapgen_kernel: the inner array
+  void* d_gen_recipe = nullptr;     // inner | rename | rename_off
+  uint32_t* d_gen_base = nullptr;   // [E] map seed base of each slot
+  uint32_t* d_gen_seed = nullptr;   // [E] seed of the map each env's most recent generated restart built
   int32_t* d_objs = nullptr;        // mgx_get_objects_batch: env list | counts | packed records
   size_t objs_cap = 0;              // envs the buffer holds
   float* d_scale = nullptr;         // per-feature scale of the token decode (mgx_decode_obs)
@@ -593,7 +602,7 @@ static int launch_episode_stats(mgx_engine* e) {
   }
   hipLaunchKernelGGL(mgx_episode_record_kernel, dim3((list_grid(e, dl, 128, 2048) + 3) / 4), dim3(256), 0, e->stream, dev_copy(e), e->ep,
                      (const int32_t*)e->d_done_list, (const uint32_t*)e->d_done_n, e->d_ep_rec, e->d_ep_log, (const uint32_t*)e->d_ep_log_state,
-                     e->ep_log_cap, (const uint32_t*)e->d_early, (const uint32_t*)e->d_episodes, (const int32_t*)e->d_map_index,
+                     e->ep_log_cap, (const uint32_t*)e->d_early, (const uint32_t*)e->d_episodes, (const int32_t*)(e->n_pool > 0 ? e->d_map_index : nullptr),
                      (const uint32_t*)e->dseeds);
   HIP_TRY(hipGetLastError());
   const int nchunks_max = (d.E + MGX_EP_CHUNK - 1) / MGX_EP_CHUNK;
@@ -809,6 +818,7 @@ void mgx_destroy(mgx_engine* e) {
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   for (void* p : e->allocs) (void)hipFree(p);
   if (e->d_pool) (void)hipFree(e->d_pool);
+  if (e->d_gen_recipe) (void)hipFree(e->d_gen_recipe);
   if (e->d_stage) (void)hipFree(e->d_stage);
   if (e->d_objs) (void)hipFree(e->d_objs);
   if (e->d_es_buf) (void)hipFree(e->d_es_buf);
@@ -893,8 +903,16 @@ static int stage(mgx_engine* e, size_t bytes) {
 }
 // Restart the envs of a DEVICE mask: clear their state rows, rebuild them (construction kernel), initial observations.
 // from_pool: maps come from the pool through d_map_index; bump: auto-reset bookkeeping (episode counter, next pool map).
+// generate: the listed envs' maps are generated into dmaps first (mgx_mapgen.h; gen_seeds: one seed per list entry, or the
+// slot rule base + episodes).
 // l: the same envs as an ascending device list (the kernels then walk the list with a small grid instead of testing E mask bytes).
-static int restart_masked(mgx_engine* e, const uint8_t* dmask, bool from_pool, bool bump, const MgxList& l = MgxList()) {
+#ifdef MGX_CPU_EMU
+static int launch_mapgen_envs(mgx_engine*, const MgxList&, const uint32_t*) { return MGX_OK; }   // (no generator in the sanitizer build)
+#else
+static int launch_mapgen_envs(mgx_engine* e, const MgxList& l, const uint32_t* dseeds_packed);
+#endif
+static int restart_masked(mgx_engine* e, const uint8_t* dmask, bool from_pool, bool bump, const MgxList& l = MgxList(),
+                          bool generate = false, const uint32_t* gen_seeds = nullptr) {
   const MgxDev& d = e->d;
   int rc = consume_out_fence(e);   // the cleared rows include terminals / truncations / rewards
   if (rc) return rc;
@@ -910,6 +928,10 @@ static int restart_masked(mgx_engine* e, const uint8_t* dmask, bool from_pool, b
                      e->n_rows, dmask, d.E, bump ? e->d_episodes : (uint32_t*)nullptr, bump ? e->d_map_index : (int32_t*)nullptr, e->n_pool,
                      e->pool_stride, ll.list, ll.n);
   HIP_TRY(hipGetLastError());
+  if (generate) {   // behind the bump: the map of seed base[env] + episodes[env] (or the caller's seeds) into dmaps[env]
+    rc = launch_mapgen_envs(e, ll, gen_seeds);
+    if (rc) return rc;
+  }
   MGX_LAUNCH_INIT(e->stream, dev_copy(e),
                      (const uint16_t*)(from_pool ? e->d_pool : e->dmaps), (const int32_t*)(from_pool ? e->d_map_index : nullptr),
                      (const uint32_t*)e->dseeds, dmask, ll);
@@ -1092,7 +1114,7 @@ int mgx_set_auto_reset(mgx_engine* e, int32_t enabled, int32_t pool_stride, cons
   if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_auto_reset: null engine");
   HIP_TRY(hipSetDevice(e->device));
   if (!enabled) { e->auto_reset = false; return MGX_OK; }
-  if (e->n_pool <= 0) return fail(MGX_ERR_BAD_ARG, "mgx_set_auto_reset: no map pool (mgx_set_map_pool)");
+  if (e->n_pool <= 0 && !e->gen_on) return fail(MGX_ERR_BAD_ARG, "mgx_set_auto_reset: no map pool (mgx_set_map_pool)");
   const MgxDev& d = e->d;
   int rc = MGX_OK;
   if (!e->d_next_mask) {
@@ -1129,6 +1151,221 @@ int mgx_get_episodes(mgx_engine* e, uint32_t* episodes, int32_t* map_index) {
   HIP_TRY(hipStreamSynchronize(e->stream));
   return MGX_OK;
 }
+
+#ifndef MGX_CPU_EMU
+// ---- device map generator (csrc/mgx_mapgen.h) ------------------------------------------------------------------------------
+static void free_map_generator(mgx_engine* e) {
+  if (e->d_gen_recipe) (void)hipFree(e->d_gen_recipe);
+  e->d_gen_recipe = nullptr;
+  e->gen = MgxMapGen{};
+  e->gen_on = false;
+  e->gen_lds = 0;
+}
+// mgx_mapgen_kernel's dynamic LDS limit: per kernel and process-wide, only ever raised (see raise_obs_lds).
+static int raise_mapgen_lds(mgx_engine* e, size_t bytes) {
+  static std::mutex mu;
+  static size_t cur_max_dev[64] = {};
+  if (e->device < 0 || e->device >= 64) return fail(MGX_ERR_BAD_ARG, "device ordinal out of range");
+  std::lock_guard<std::mutex> lock(mu);
+  size_t& cur_max = cur_max_dev[e->device];
+  if (bytes > 64 * 1024 && bytes > cur_max) {
+    HIP_TRY(hipFuncSetAttribute((const void*)mgx_mapgen_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    cur_max = bytes;
+  }
+  return MGX_OK;
+}
+// The listed envs' maps into dmaps (restart_masked): seeds one per list entry, or base[env] + episodes[env].
+static int launch_mapgen_envs(mgx_engine* e, const MgxList& l, const uint32_t* dseeds_packed) {
+  if (!e->gen_on || !l.list) return fail(MGX_ERR_BAD_ARG, "map generator: not set (mgx_set_map_generator)");
+  hipLaunchKernelGGL(mgx_mapgen_kernel, dim3(list_grid(e, l, 128, 2048)), dim3(MGX_WAVE), e->gen_lds, e->stream, e->gen, dseeds_packed,
+                     (const uint32_t*)e->d_gen_base, (const uint32_t*)e->d_episodes, l.list, l.n_host >= 0 ? (const uint32_t*)nullptr : l.n,
+                     l.n_host >= 0 ? l.n_host : 0, e->dmaps, e->d_gen_seed);
+  HIP_TRY(hipGetLastError());
+  return MGX_OK;
+}
+
+int mgx_set_map_generator(mgx_engine* e, const uint16_t* inner, int32_t n_inner, int32_t border_width, int32_t border_code,
+                          const uint16_t* rename, const int32_t* rename_off, int32_t n_teams, const uint32_t* map_seed_base) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_map_generator: null engine");
+  HIP_TRY(hipSetDevice(e->device));
+  const MgxDev& d = e->d;
+  if (!inner) {   // off: the recipe goes, the base seeds stay allocated with the engine
+    if (e->gen_on && e->auto_reset && e->n_pool <= 0)   // (finished envs would be rebuilt from their stale dmaps)
+      return fail(MGX_ERR_BAD_ARG, "mgx_set_map_generator: the generator is the map source of auto-reset; switch that off first (mgx_set_auto_reset)");
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    free_map_generator(e);
+    return MGX_OK;
+  }
+  const char* who = "mgx_set_map_generator";
+  const int nc = e->prog[MGX_H_NUM_CLASSES];
+  const int ih = d.H - 2 * border_width, iw = d.W - 2 * border_width;
+  if (!map_seed_base || border_width < 0 || ih <= 0 || iw <= 0 || n_inner != ih * iw)
+    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": the inner array must hold (H - 2 * border_width) * (W - 2 * border_width) = " +
+                                     std::to_string(ih > 0 && iw > 0 ? ih * iw : 0) + " cells of the program's " + std::to_string(d.H) + " x " +
+                                     std::to_string(d.W) + " map, and base seeds must be given");
+  if (n_teams < 0 || n_teams > MGX_MAPGEN_MAX_TEAMS || (n_teams > 0 && (!rename || !rename_off)) || (n_teams > 0 && rename_off[0] != 0))
+    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": bad rename tables");
+  for (int t = 0; t < n_teams; t++)
+    if (rename_off[t + 1] < rename_off[t]) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": rename offsets must ascend");
+  const int n_rename = n_teams > 0 ? rename_off[n_teams] : 0;
+  if (border_code < 0 || border_code > nc)
+    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": class map holds id " + std::to_string(border_code) + " but the program has " +
+                                     std::to_string(nc) + " classes");
+  for (int k = 0; k < n_rename; k++)
+    if (rename[k] > nc)
+      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": class map holds id " + std::to_string(rename[k]) + " but the program has " +
+                                       std::to_string(nc) + " classes");
+  // ONE generated map stands for all of them: a shuffle keeps the multiset of cells and the renaming hands out the same
+  // classes in another order, so the class ids, the AoE / territory source counts and the bound of the observation token
+  // pool are the same for every seed.  The unshuffled recipe is such a map.
+  std::vector<uint16_t> one((size_t)d.H * d.W, (uint16_t)border_code);
+  {
+    std::vector<int> seen((size_t)std::max(n_teams, 1), 0);
+    for (int i = 0; i < n_inner; i++) {
+      uint16_t v = inner[i];
+      if (v >= MGX_MAPGEN_TEAM0) {
+        const int t = v - MGX_MAPGEN_TEAM0;
+        if (t >= n_teams) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": an inner cell names team " + std::to_string(t) + " of " + std::to_string(n_teams));
+        const int k = seen[t]++;
+        if (k >= rename_off[t + 1] - rename_off[t])
+          return fail(MGX_ERR_BAD_ARG, std::string(who) + ": more cells of team " + std::to_string(t) + " than entries in its rename table");
+        v = rename[rename_off[t] + k];
+      }
+      one[(size_t)(i / iw + border_width) * d.W + (i % iw + border_width)] = v;
+    }
+  }
+  int rc = validate_maps(e, one.data(), 1, nullptr, who);
+  if (rc) return rc;
+  size_t lds_max = MGX_MAPGEN_LDS_MAX;
+  // Test hook: a map of at most 255 x 255 cells needs 127 KB, so no program reaches the real limit; the tests of this refusal
+  // lower it with MGX_MAPGEN_LDS_BYTES (a decimal byte count, only ever lowering).  Anything else in the variable is an error.
+  if (const char* s = getenv("MGX_MAPGEN_LDS_BYTES")) {
+    char* end = nullptr;
+    const unsigned long long v = strtoull(s, &end, 10);
+    if (end == s || *end || *s < '0' || *s > '9')
+      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": MGX_MAPGEN_LDS_BYTES = '" + s + "' is not a decimal byte count");
+    lds_max = std::min<size_t>(lds_max, (size_t)v);
+  }
+  const size_t lds = ((size_t)n_inner * 2 + 15) & ~(size_t)15;
+  if (lds > lds_max)
+    return fail(MGX_ERR_PROGRAM, std::string(who) + ": the inner area of " + std::to_string(n_inner) + " cells needs " + std::to_string(lds) +
+                                     " B of LDS, the generator's workgroup has " + std::to_string(lds_max));
+  rc = fit_maps(e, one.data(), 0, 1, nullptr, who);
+  if (rc) return rc;
+  rc = raise_mapgen_lds(e, lds);
+  if (rc) return rc;
+  // accepted: replace the recipe
+  const size_t off_rename = ((size_t)n_inner * 2 + 15) & ~(size_t)15, off_off = (off_rename + (size_t)n_rename * 2 + 15) & ~(size_t)15;
+  const size_t total = off_off + ((size_t)n_teams + 1) * 4;
+  std::vector<uint8_t> host(total, 0);
+  memcpy(host.data(), inner, (size_t)n_inner * 2);
+  if (n_rename) memcpy(host.data() + off_rename, rename, (size_t)n_rename * 2);
+  if (n_teams) memcpy(host.data() + off_off, rename_off, ((size_t)n_teams + 1) * 4);
+  void* blob = nullptr;
+  HIP_TRY(hipMalloc(&blob, total));
+  if (!e->d_gen_base) {
+    rc = e->alloc(&e->d_gen_base, (size_t)d.E);
+    if (!rc) rc = e->alloc(&e->d_gen_seed, (size_t)d.E);
+    if (!rc && !e->d_map_index) {   // the episode counters of auto-reset (shared with the pool)
+      rc = e->alloc(&e->d_map_index, (size_t)d.E);
+      if (!rc) rc = e->alloc(&e->d_episodes, (size_t)d.E);
+    }
+    if (rc) { (void)hipFree(blob); return rc; }
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  free_map_generator(e);
+  e->d_gen_recipe = blob;
+  HIP_TRY(hipMemcpyAsync(blob, host.data(), total, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_gen_base, map_seed_base, (size_t)d.E * 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_gen_seed, map_seed_base, (size_t)d.E * 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));   // `host` is a local
+  MgxMapGen& g = e->gen;
+  g.inner = (const uint16_t*)blob;
+  g.rename = (const uint16_t*)((const uint8_t*)blob + off_rename);
+  g.rename_off = (const int32_t*)((const uint8_t*)blob + off_off);
+  g.n_inner = n_inner; g.ih = ih; g.iw = iw; g.border = border_width; g.H = d.H; g.W = d.W; g.n_teams = n_teams;
+  g.border_code = (uint32_t)border_code;
+  e->gen_lds = lds;
+  e->gen_on = true;
+  return MGX_OK;
+}
+
+int mgx_generate_maps(mgx_engine* e, const uint32_t* map_seeds, int32_t n, uint16_t* out, int32_t out_is_device) {
+  if (!e || !map_seeds || !out || n <= 0) return fail(MGX_ERR_BAD_ARG, "mgx_generate_maps: null/empty argument");
+  if (!e->gen_on) return fail(MGX_ERR_BAD_ARG, "mgx_generate_maps: no map generator (mgx_set_map_generator)");
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t HW = (size_t)e->d.H * e->d.W, seed_bytes = ((size_t)n * 4 + 15) & ~(size_t)15;
+  int rc = stage(e, seed_bytes + (out_is_device ? 0 : (size_t)n * HW * 2));
+  if (rc) return rc;
+  uint8_t* st = (uint8_t*)e->d_stage;
+  uint16_t* dout = out_is_device ? out : (uint16_t*)(st + seed_bytes);
+  HIP_TRY(hipMemcpyAsync(st, map_seeds, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(mgx_mapgen_kernel, dim3((unsigned)n), dim3(MGX_WAVE), e->gen_lds, e->stream, e->gen, (const uint32_t*)st,
+                     (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const int32_t*)nullptr, (const uint32_t*)nullptr, (int)n, dout,
+                     (uint32_t*)nullptr);
+  HIP_TRY(hipGetLastError());
+  if (!out_is_device) HIP_TRY(hipMemcpyAsync(out, dout, (size_t)n * HW * 2, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));   // the caller's seeds were read; host output has landed
+  return MGX_OK;
+}
+
+int mgx_reset_envs_generated(mgx_engine* e, const uint8_t* env_mask, const uint32_t* map_seeds, const uint32_t* seeds) {
+  if (!e || !env_mask) return fail(MGX_ERR_BAD_ARG, "mgx_reset_envs_generated: null argument");
+  if (!e->gen_on) return fail(MGX_ERR_BAD_ARG, "mgx_reset_envs_generated: no map generator (mgx_set_map_generator)");
+  HIP_TRY(hipSetDevice(e->device));
+  const MgxDev& d = e->d;
+  const size_t E = d.E, A = d.A;
+  std::vector<int32_t> idx;
+  for (size_t i = 0; i < E; i++) if (env_mask[i]) idx.push_back((int32_t)i);
+  if (idx.empty()) return MGX_OK;
+  const size_t n = idx.size();
+  // ONE contiguous upload: [indices | packed map seeds | packed seeds | n]
+  std::vector<uint8_t> host(n * 12 + 16);
+  memcpy(host.data(), idx.data(), n * 4);
+  { const uint32_t n32 = (uint32_t)n; memcpy(host.data() + n * 12, &n32, 4); }
+  for (size_t k = 0; k < n; k++) {
+    if (map_seeds) memcpy(host.data() + n * 4 + k * 4, map_seeds + idx[k], 4);
+    if (seeds) memcpy(host.data() + n * 8 + k * 4, seeds + idx[k], 4);
+  }
+  int rc = stage(e, host.size());
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(e->dmask, env_mask, E, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_stage, host.data(), host.size(), hipMemcpyHostToDevice, e->stream));
+  const uint8_t* st = (const uint8_t*)e->d_stage;
+  if (seeds) hipLaunchKernelGGL(mgx_scatter_words_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, e->dseeds,
+                                (const uint32_t*)(st + n * 8), (const int32_t*)st, (int)n);
+  HIP_TRY(hipGetLastError());
+  MgxList l;
+  l.list = (const int32_t*)st; l.n = (const uint32_t*)(st + n * 12); l.n_host = (int)n;
+  rc = mark_replay(e, l.list, (int)n, MGX_RPL_E_ABORTED);
+  if (rc) return rc;
+  rc = restart_masked(e, e->dmask, false, false, l, true, map_seeds ? (const uint32_t*)(st + n * 4) : nullptr);
+  if (rc) return rc;
+  if (e->mem_kind == MGX_MEM_HOST) {  // host buffers: the restarted rows, one copy per contiguous run of envs
+    for (size_t k = 0; k < n;) {
+      size_t j = k;
+      while (j + 1 < n && idx[j + 1] == idx[j] + 1) j++;
+      const size_t r0 = (size_t)idx[k] * A, rows = (size_t)(idx[j] - idx[k] + 1) * A;
+      HIP_TRY(hipMemcpyAsync(e->h_obs + r0 * d.T * 3, d.obs + r0 * d.T * 3, rows * d.T * 3, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipMemcpyAsync(e->h_term + r0, d.terminals + r0, rows, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipMemcpyAsync(e->h_trunc + r0, d.truncations + r0, rows, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipMemcpyAsync(e->h_rew + r0, d.rewards + r0, rows * 4, hipMemcpyDeviceToHost, e->stream));
+      k = j + 1;
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));  // `host` is a local
+  return MGX_OK;
+}
+
+int mgx_get_map_seeds(mgx_engine* e, uint32_t* out) {
+  if (!e || !out) return fail(MGX_ERR_BAD_ARG, "mgx_get_map_seeds: null argument");
+  if (!e->d_gen_seed) return fail(MGX_ERR_BAD_ARG, "mgx_get_map_seeds: no map generator (mgx_set_map_generator)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipMemcpyAsync(out, e->d_gen_seed, (size_t)e->d.E * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return MGX_OK;
+}
+#endif  // MGX_CPU_EMU
 
 int mgx_attach_code(mgx_engine* e, int32_t kind, const char* path) {
   if (!e || !path) return fail(MGX_ERR_BAD_ARG, "mgx_attach_code: null argument");
@@ -1430,7 +1667,9 @@ int mgx_step(mgx_engine* e) {
     if (!known_none) {
       MgxList l;
       l.list = e->d_done_list; l.n = e->d_done_n;
-      int rrc = restart_masked(e, e->d_next_mask, true, true, l);
+      // map source: the pool when there is one, else the generator (mgx_set_auto_reset refuses an engine with neither)
+      const bool pool = e->n_pool > 0;
+      int rrc = restart_masked(e, e->d_next_mask, pool, true, l, !pool && e->gen_on);
       if (rrc) return rrc;
     }
   }

@@ -196,6 +196,11 @@ def load_lib():
     L.mgx_set_replay.argtypes = [vp, vp, i32, i32, vp, i32]
     L.mgx_replay_layout.argtypes = [vp, vp]
     L.mgx_drain_replay.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "mgx_set_map_generator"):   # (absent from the CPU sanitizer build, like the packed rows)
+        L.mgx_set_map_generator.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, vp]
+        L.mgx_generate_maps.argtypes = [vp, vp, i32, vp, i32]
+        L.mgx_reset_envs_generated.argtypes = [vp, vp, vp, vp]
+        L.mgx_get_map_seeds.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -429,6 +434,59 @@ class BatchedMettaGrid:
         ep, mi = np.empty(self.E, np.uint32), np.empty(self.E, np.int32)
         _check(self.L.mgx_get_episodes(self.h, ep.ctypes.data, mi.ctypes.data))
         return ep, mi
+
+    # ---- device map generator (include/mgx.h "Device map generator"; csrc/mgx_mapgen.h) ----
+    def set_map_generator(self, spec, map_seed_base=0) -> None:
+        """New episodes' maps from the reference's RandomMapBuilder on the device.  ``spec``: a ``mapgen.RandomMapSpec`` (or what
+        its ``lower(prog)`` returns), ``None`` switches the generator off; ``map_seed_base``: uint32 [E] (or one value for all)."""
+        if spec is None:
+            _check(self.L.mgx_set_map_generator(self.h, None, 0, 0, 0, None, None, 0, None))
+            return
+        low = spec.lower(self.prog) if hasattr(spec, "lower") else spec
+        inner = np.ascontiguousarray(low.inner, dtype=np.uint16)
+        rename = np.ascontiguousarray(low.rename, dtype=np.uint16)
+        off = np.ascontiguousarray(low.rename_off, dtype=np.int32)
+        base = np.ascontiguousarray(np.broadcast_to(np.asarray(map_seed_base, dtype=np.uint32), (self.E,)))
+        n_teams = int(off.size) - 1
+        _check(self.L.mgx_set_map_generator(self.h, inner.ctypes.data, int(inner.size), int(low.border_width), int(low.border_code),
+                                            rename.ctypes.data if rename.size else None, off.ctypes.data if n_teams > 0 else None,
+                                            n_teams, base.ctypes.data))
+
+    def generate_maps(self, map_seeds, out=None):
+        """The generator's maps for ``map_seeds`` (uint32 [n]) -> uint16 [n, H, W]; no env is touched.  ``out``: a contiguous
+        torch int16 / uint16 device tensor of that shape to fill instead of returning a numpy array; the engine's stream
+        waits for what the caller's current torch stream has enqueued (whatever produced ``out``) before it writes, and the
+        call returns once the maps have landed."""
+        sd = np.ascontiguousarray(np.asarray(map_seeds, dtype=np.uint32).reshape(-1))
+        H, W = int(self.prog.words[K.H_HEIGHT]), int(self.prog.words[K.H_WIDTH])
+        if out is not None:
+            if tuple(out.shape) != (sd.size, H, W) or out.element_size() != 2 or not out.is_contiguous() or not out.is_cuda:
+                raise ValueError(f"out must be a contiguous 16-bit device tensor of shape {(sd.size, H, W)}")
+            self.wait_for_caller()
+            _check(self.L.mgx_generate_maps(self.h, sd.ctypes.data, int(sd.size), C.c_void_p(out.data_ptr()), 1))
+            return out
+        maps = np.empty((sd.size, H, W), np.uint16)
+        _check(self.L.mgx_generate_maps(self.h, sd.ctypes.data, int(sd.size), maps.ctypes.data, 0))
+        return maps
+
+    def reset_envs_generated(self, env_mask, map_seeds=None, seeds=None) -> None:
+        """``reset_envs`` with the masked envs' maps generated on the device: ``map_seeds`` uint32 [E] (only masked envs are
+        read) or None = each slot's base seed + its episode count."""
+        mask = np.ascontiguousarray(np.asarray(env_mask, dtype=np.uint8).reshape(self.E))
+        ms_ptr = sd_ptr = None
+        if map_seeds is not None:
+            ms = np.ascontiguousarray(np.broadcast_to(np.asarray(map_seeds, dtype=np.uint32), (self.E,)))
+            ms_ptr = ms.ctypes.data
+        if seeds is not None:
+            sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint32), (self.E,)))
+            sd_ptr = sd.ctypes.data
+        _check(self.L.mgx_reset_envs_generated(self.h, mask.ctypes.data, ms_ptr, sd_ptr))
+
+    def map_seeds(self) -> np.ndarray:
+        """uint32 [E]: the seed of the map each env's most recent generated restart built."""
+        out = np.empty(self.E, np.uint32)
+        _check(self.L.mgx_get_map_seeds(self.h, out.ctypes.data))
+        return out
 
     # ---- episode-end statistics (include/mgx.h "Episode-end statistics"; the reference's StatsTracker.on_episode_end) ----
     EPL = ("NG", "NS", "A", "TOTALS_WORDS", "REC_WORDS", "LOG_WORDS", "OFF_GAME", "OFF_GAME_BITS", "OFF_AGENT", "OFF_AGENT_BITS",

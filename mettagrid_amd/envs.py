@@ -117,7 +117,7 @@ def decode_actions_unchecked(a, num_primary: int, vibe_action_ids):
 class MettaGridBatchedEnv:
     """E envs x A agents behind the PufferEnv call pattern.
 
-    Two sources of maps for new episodes:
+    Three sources of maps for new episodes (exactly one is given):
 
     * ``map_pool`` (uint16 [M, H, W], class index + 1): the maps are uploaded to the GPU once and finished envs restart
       ON THE DEVICE (``mgx_set_map_pool`` / ``mgx_set_auto_reset``): no host round trip per step, episode ``k`` of env
@@ -127,6 +127,12 @@ class MettaGridBatchedEnv:
       same step.
     * ``map_fn(env_index, episode_index) -> uint16 class map [H, W]``: maps built on the host once per episode, as in the
       reference (simulator.py:83); the done test then costs a device->host read per step.
+    * ``map_gen`` (a ``mapgen.RandomMapSpec``): a fresh map per episode like ``map_fn``, generated ON THE DEVICE at restart
+      like ``map_pool`` (``mgx_set_map_generator``): the reference's RandomMapBuilder seeded ``base[e] + k`` for episode ``k``
+      of env ``e`` (simulator.py:403-409), ``base[e] = (map_seed + e * map_seed_stride) mod 2**32``.  ``map_seed_stride``
+      defaults to 2**16, so the seed ranges of two envs do not overlap before an env has played 2**16 episodes (for up to
+      2**16 envs; beyond that the bases wrap).  ``desync`` as for ``map_pool``.  ``engine.map_seeds()`` / episode-log records
+      (``base[env] + episode``) name the seed of a played map and ``engine.generate_maps`` rebuilds it.
 
     Engine seeds: ``seed_fn(base, env, episode)`` (default: the seed given to ``reset`` plus the env index, constant
     across auto-resets like the reference's ``_current_seed``).
@@ -156,9 +162,13 @@ class MettaGridBatchedEnv:
                  desync: bool = False, validate_actions: bool = True, episode_stats: bool = True, stats_interval: int = 1,
                  episode_log: int = 0, log_per_agent: bool = False, specialize="auto", replay_envs=None,
                  replay_dir: Optional[str] = None, replay_words_per_env: Optional[int] = None, replay_interval: int = 64,
-                 replay_capacity_groups: Optional[dict] = None) -> None:
-        if (map_fn is None) == (map_pool is None):
-            raise ValueError("give exactly one of map_fn and map_pool")
+                 replay_capacity_groups: Optional[dict] = None, map_gen=None, map_seed: int = 0,
+                 map_seed_stride: int = 1 << 16) -> None:
+        if (map_fn is not None) + (map_pool is not None) + (map_gen is not None) != 1:
+            raise ValueError("give exactly one of map_fn, map_pool and map_gen")
+        self.map_gen = map_gen
+        self.map_seed, self.map_seed_stride = int(map_seed), int(map_seed_stride)
+        self._device_restarts = map_fn is None    # finished envs restart on the device (pool or generator): no done read per step
         self.prog = prog
         self.E = num_envs
         self.map_fn = map_fn
@@ -244,6 +254,10 @@ class MettaGridBatchedEnv:
             return ((np.int64(self._seed) + np.arange(self.E, dtype=np.int64)) & 0xFFFFFFFF).astype(np.uint32)
         return np.array([self.seed_fn(self._seed, e, int(self.episode[e])) for e in range(self.E)], dtype=np.uint32)
 
+    def map_seed_bases(self) -> np.ndarray:
+        """``map_gen``: the map seed base of every env, uint32 [E]."""
+        return ((self.map_seed + np.arange(self.E, dtype=np.int64) * self.map_seed_stride) & 0xFFFFFFFF).astype(np.uint32)
+
     def early_end_steps(self) -> np.ndarray:
         """EarlyResetHandler.on_episode_start for every env: one draw from a generator seeded with the env's seed."""
         ms = int(self.prog.words[11])   # MGX_H_MAX_STEPS
@@ -265,6 +279,15 @@ class MettaGridBatchedEnv:
                                          specialize=self.specialize)
             self._eng.set_map_pool(self.map_pool)
             self._eng.set_auto_reset(True, self.pool_stride, self.early_end_steps() if self.desync else None)
+        elif self.map_gen is not None:
+            from .mapgen import generated_class_maps
+            # capacities are sized from the create maps, and every map of a recipe holds the same cells: one host-built map
+            one = generated_class_maps(self.map_gen, self.prog, [int(self.map_seed_bases()[0])])
+            self._eng = BatchedMettaGrid(self.prog, np.broadcast_to(one, (self.E,) + one.shape[1:]), self._seeds(), device=self._device,
+                                         buffers=self._kind, specialize=self.specialize)
+            self._eng.set_map_generator(self.map_gen, self.map_seed_bases())
+            self._eng.reset_envs_generated(np.ones(self.E, np.uint8))
+            self._eng.set_auto_reset(True, 1, self.early_end_steps() if self.desync else None)
         else:
             self._eng = BatchedMettaGrid(self.prog, self._maps(range(self.E)), self._seeds(), device=self._device,
                                          buffers=self._kind, specialize=self.specialize)
@@ -327,7 +350,7 @@ class MettaGridBatchedEnv:
             return {}
         eng = self.engine
         self._steps += 1
-        if self.map_pool is None or self._kind != "device":   # these paths synchronise with the device every step anyway
+        if not self._device_restarts or self._kind != "device":   # these paths synchronise with the device every step anyway
             return self._infos_from_totals(eng.drain_episode_stats()) if self._steps % self.stats_interval == 0 else {}
         out = {}
         if self._steps % self.stats_interval == 0:
@@ -403,7 +426,7 @@ class MettaGridBatchedEnv:
 
     def step(self, actions):
         eng = self.engine
-        if self.map_pool is None:  # host map source: the done test needs the flags on the host
+        if not self._device_restarts:  # host map source: the done test needs the flags on the host
             done = self._done_envs()
             if done.any():  # lazy auto-reset at the start of the next step (mettagrid_puffer_env.py:299-302)
                 idx = np.nonzero(done)[0]
@@ -460,7 +483,7 @@ class MettaGridBatchedEnv:
             if self.supervisor is not None:
                 self._compute_supervisor_actions()
         infos = self._step_infos()
-        if self.replay_envs and self.map_pool is not None:
+        if self.replay_envs and self._device_restarts:
             self._replay_steps += 1
             if self._replay_steps % self.replay_interval == 0:
                 self.flush_replays()
@@ -473,7 +496,7 @@ class MettaGridBatchedEnv:
         from .engine import env_list
         lst = env_list(envs, self.E, "save_state")
         st = self.engine.save_envs(lst)
-        if self.map_pool is None:
+        if not self._device_restarts:
             st.extra["episode"] = self.episode[lst].copy()
         return st
 
@@ -482,7 +505,7 @@ class MettaGridBatchedEnv:
         from .engine import env_list
         lst = env_list(state.envs if envs is None else envs, self.E, "load_state", unique=True)
         self.engine.load_envs(state, lst)
-        if self.map_pool is None and "episode" in state.extra:
+        if not self._device_restarts and "episode" in state.extra:
             self.episode[lst] = np.asarray(state.extra["episode"], dtype=np.int64)
 
     def close(self) -> None:

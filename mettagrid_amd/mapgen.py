@@ -101,3 +101,152 @@ def random_class_maps(prog, height: int, width: int, objects: dict, agents: dict
             inner = np.where(mask, np.uint16(prog.cell_to_class[name] + 1), inner)
     out[:, border_width:border_width + ih, border_width:border_width + iw] = inner.reshape(len(seeds), ih, iw)
     return out
+
+
+# ---- the random builder as a recipe + numpy's stream restated on arrays of seeds (csrc/mgx_mapgen.h is the device form) ----
+TEAM0 = 0xF000          # inner cell codes TEAM0 + t: a cell of agent team t (MGX_MAPGEN_TEAM0)
+MAX_TEAMS = 256         # MGX_MAPGEN_MAX_TEAMS
+
+
+class LoweredMap:
+    """What ``RandomMapSpec.lower`` makes: the arguments of ``mgx_set_map_generator``."""
+
+    def __init__(self, height, width, border_width, border_code, inner, rename, rename_off):
+        self.height, self.width, self.border_width, self.border_code = height, width, border_width, border_code
+        self.inner = inner              # uint16 [ih * iw]: class index + 1 in the reference's order, TEAM0 + t, then zeros
+        self.rename = rename            # uint16: class index + 1 of the k-th agent of team t at rename[rename_off[t] + k]
+        self.rename_off = rename_off    # int32 [n_teams + 1]
+        self.ih, self.iw = height - 2 * border_width, width - 2 * border_width
+
+    @property
+    def n_teams(self) -> int:
+        return len(self.rename_off) - 1
+
+
+class RandomMapSpec:
+    """The configuration of the reference's RandomMapBuilder (map_builder/random_map.py:13-27) without its seed."""
+
+    def __init__(self, height: int, width: int, objects: dict, agents: dict | int, border_width: int = 1,
+                 border_object: str = "wall") -> None:
+        self.height, self.width, self.objects, self.agents = height, width, dict(objects), agents
+        self.border_width, self.border_object = border_width, border_object
+
+    def random_map(self, seed: int) -> np.ndarray:
+        return random_map(self.height, self.width, self.objects, self.agents, seed, self.border_width, self.border_object)
+
+    def lower(self, prog) -> LoweredMap:
+        """The seed-independent half of ``RandomMapBuilder.build``: the halving rule (random_map.py:62-71), the unshuffled
+        inner array, the border code and the per-team rename tables (the k-th cell of a team in row-major order becomes the
+        team's k-th agent class, ``prog.agent_rename``)."""
+        H, W, b = self.height, self.width, self.border_width
+        if (H, W) != (int(prog.words[3]), int(prog.words[4])):
+            raise ValueError(f"RandomMapSpec is {H} x {W} but the program's map is {int(prog.words[3])} x {int(prog.words[4])}")
+        ih, iw = H - 2 * b, W - 2 * b
+        if b < 0 or ih <= 0 or iw <= 0:
+            raise ValueError("RandomMapSpec: no inner area")
+        area = ih * iw
+        if isinstance(self.agents, int):
+            agent_cells = [("agent.agent", self.agents)]
+        else:
+            agent_cells = [("agent." + n, c) for n, c in self.agents.items()]
+        n_agents = sum(c for _, c in agent_cells)
+        objects = dict(self.objects)
+        total = sum(objects.values()) + n_agents
+        while total > area:
+            # The reference stops when every object count is <= 1 AND there is at most one agent (random_map.py:66-68); with
+            # more agents and nothing left to halve its loop halves ones for ever.  Here that case ends the loop too, and
+            # the recipe is refused below.
+            if all(c <= 1 for c in objects.values()):
+                break
+            for k in objects:
+                objects[k] = max(1, objects[k] // 2)
+            total = sum(objects.values()) + n_agents
+        if total > area:
+            raise ValueError(f"RandomMapSpec: {total} symbols do not fit {area} inner cells (the reference cannot build this map either)")
+        codes: list = []
+        for name, count in objects.items():
+            codes += [prog.cell_to_class[name] + 1] * count
+        rename: list = []
+        rename_off = [0]
+        for name, count in agent_cells:
+            if name in prog.agent_rename:
+                group = prog.agent_rename[name]
+                if count > len(group):
+                    raise ValueError(f"Map has more '{name}' cells than agents in the group ({len(group)})")
+                if len(rename_off) > MAX_TEAMS:
+                    raise ValueError(f"RandomMapSpec: more than {MAX_TEAMS} agent teams")
+                codes += [TEAM0 + len(rename_off) - 1] * count
+                rename += [c + 1 for c in group]
+                rename_off.append(len(rename))
+            else:
+                codes += [prog.cell_to_class[name] + 1] * count
+        border = prog.cell_to_class[self.border_object] + 1 if b > 0 else 0
+        if max([border] + rename + [prog.cell_to_class[n] + 1 for n in objects]) >= TEAM0:
+            raise ValueError("RandomMapSpec: class ids reach the team codes")
+        inner = np.array(codes + [0] * (area - len(codes)), dtype=np.uint16)
+        return LoweredMap(H, W, b, border, inner, np.array(rename, dtype=np.uint16), np.array(rename_off, dtype=np.int32))
+
+
+def shuffled_rows(base: np.ndarray, seeds) -> np.ndarray:
+    """``[default_rng(int(s)).shuffle(copy of base) for s in seeds]`` for a 1-d array, vectorised over the seeds:
+    ``SeedSequence`` and PCG64 from early_reset, then ``Generator.shuffle`` — for i = n-1 .. 1: j = random_interval(i), swap
+    a[i], a[j] — with random_interval's masked rejection on buffered 32-bit halves (low half of each 64-bit output first)."""
+    from . import early_reset as er
+    seeds = np.asarray(seeds, dtype=np.uint64).reshape(-1)
+    S, n = len(seeds), len(base)
+    out = np.tile(np.asarray(base), (S, 1))
+    if n < 2 or S == 0:
+        return out
+    u64 = np.uint64
+    with np.errstate(over="ignore"):
+        w = er.generate_state8(er.seedseq_pool(seeds))
+        v = [w[2 * i] | (w[2 * i + 1] << u64(32)) for i in range(4)]
+        ih = (v[2] << u64(1)) | (v[3] >> u64(63)); il = (v[3] << u64(1)) | u64(1)
+        sh, sl = er.step(np.zeros(S, u64), np.zeros(S, u64), ih, il)
+        sh, sl = er.add128(sh, sl, v[0], v[1])
+        sh, sl = er.step(sh, sl, ih, il)
+        have_hi = np.zeros(S, bool)          # the high half of the last output is still buffered
+        hi_half = np.zeros(S, u64)
+        rows = np.arange(S)
+        for i in range(n - 1, 0, -1):
+            mask = u64((1 << int(i).bit_length()) - 1)
+            j = np.zeros(S, np.int64)
+            todo = rows
+            while len(todo):
+                use_hi = have_hi[todo]
+                fresh = todo[~use_hi]
+                nh, nl = er.step(sh[fresh], sl[fresh], ih[fresh], il[fresh])
+                sh[fresh], sl[fresh] = nh, nl
+                x = nh ^ nl
+                rot = nh >> u64(58)
+                o = (x >> rot) | (x << ((u64(64) - rot) & u64(63)))
+                half = hi_half[todo].copy()
+                half[~use_hi] = o & er.M32
+                hi_half[fresh] = o >> u64(32)
+                have_hi[todo] = ~use_hi
+                val = half & mask
+                ok = val <= u64(i)
+                j[todo[ok]] = val[ok].astype(np.int64)
+                todo = todo[~ok]
+            ai = out[:, i].copy()
+            out[:, i] = out[rows, j]
+            out[rows, j] = ai
+    return out
+
+
+def generated_class_maps(spec: RandomMapSpec, prog, seeds) -> np.ndarray:
+    """``random_class_maps(prog, ...)`` / ``prog.class_map(spec.random_map(seed))`` for many seeds (< 2**32) -> uint16
+    [n][H][W], without a numpy generator per map and with the halving rule: the host restatement of mgx_mapgen_kernel."""
+    low = spec.lower(prog)
+    seeds = np.asarray(seeds, dtype=np.uint64).reshape(-1)
+    inner = shuffled_rows(low.inner, seeds)
+    for t in range(low.n_teams):
+        group = low.rename[low.rename_off[t]:low.rename_off[t + 1]]
+        m = inner == TEAM0 + t
+        if len(group):
+            k = np.cumsum(m, axis=1) - 1
+            inner = np.where(m, group[np.clip(k, 0, len(group) - 1)], inner)
+    out = np.full((len(seeds), low.height, low.width), low.border_code, dtype=np.uint16)
+    b = low.border_width
+    out[:, b:b + low.ih, b:b + low.iw] = inner.reshape(len(seeds), low.ih, low.iw)
+    return out
