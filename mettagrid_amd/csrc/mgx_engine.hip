@@ -543,6 +543,35 @@ static int invalidate_obs(mgx_engine* e) {
   if (e->d.obs_used) HIP_TRY(hipMemsetAsync(e->d.obs_used, 0xFF, (size_t)e->d.E * e->d.A * 2, e->stream));
   return MGX_OK;
 }
+// MGX_MEM_HOST: the caller-visible rows of envs [env0, env0 + n_envs) -> the bound host buffers (stream-ordered).
+static int copy_out(mgx_engine* e, size_t env0, size_t n_envs) {
+  if (e->mem_kind != MGX_MEM_HOST) return MGX_OK;
+  const MgxDev& d = e->d;
+  const size_t r0 = env0 * d.A, rows = n_envs * d.A;
+  HIP_TRY(hipMemcpyAsync(e->h_obs + r0 * d.T * 3, d.obs + r0 * d.T * 3, rows * d.T * 3, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->h_term + r0, d.terminals + r0, rows, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->h_trunc + r0, d.truncations + r0, rows, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->h_rew + r0, d.rewards + r0, rows * 4, hipMemcpyDeviceToHost, e->stream));
+  return MGX_OK;
+}
+// The same for a list of envs (any order): one copy_out per run of consecutive envs.
+static int copy_out_envs(mgx_engine* e, const int32_t* envs, size_t n) {
+  if (e->mem_kind != MGX_MEM_HOST) return MGX_OK;
+  std::vector<int32_t> sorted;
+  if (!std::is_sorted(envs, envs + n)) {
+    sorted.assign(envs, envs + n);
+    std::sort(sorted.begin(), sorted.end());
+    envs = sorted.data();
+  }
+  for (size_t k = 0; k < n;) {
+    size_t j = k;
+    while (j + 1 < n && envs[j + 1] == envs[j] + 1) j++;
+    int rc = copy_out(e, (size_t)envs[k], (size_t)(envs[j] - envs[k] + 1));
+    if (rc) return rc;
+    k = j + 1;
+  }
+  return MGX_OK;
+}
 // MettaGrid::_init_buffers (mettagrid_c.cpp:294-319): clear the bound buffers, initial observations (action 0).
 static int init_buffers(mgx_engine* e) {
   const MgxDev& d = e->d;
@@ -555,13 +584,8 @@ static int init_buffers(mgx_engine* e) {
   HIP_TRY(hipMemsetAsync(d.episode_rewards, 0, rows * 4, e->stream));
   HIP_TRY(hipMemsetAsync(d.executed, 0, rows * 4, e->stream));
   int rc = launch_obs(e, false);
+  if (!rc) rc = copy_out(e, 0, (size_t)d.E);
   if (rc) return rc;
-  if (e->mem_kind == MGX_MEM_HOST) {
-    HIP_TRY(hipMemcpyAsync(e->h_obs, d.obs, rows * d.T * 3, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->h_term, d.terminals, rows, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->h_trunc, d.truncations, rows, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->h_rew, d.rewards, rows * 4, hipMemcpyDeviceToHost, e->stream));
-  }
   HIP_TRY(hipStreamSynchronize(e->stream));
   return MGX_OK;
 }
@@ -576,23 +600,31 @@ static void free_episode_stats(mgx_engine* e) {
   e->d_ep_log = nullptr; e->d_ep_log_state = nullptr; e->h_ep_snap = nullptr; e->ep_ev = nullptr;
   e->ep_stats = false; e->ep_pending = false; e->ep_log_cap = 0;
 }
+static void free_replay(mgx_engine* e) {
+  for (const void* p : {(const void*)e->rpl.envs, (const void*)e->rpl.log, (const void*)e->rpl.cursor, (const void*)e->rpl.state,
+                        (const void*)e->rpl.shadow, (const void*)e->rpl.static_cls})
+    if (p) (void)hipFree(const_cast<void*>(p));
+  e->rpl = MgxRpl{};
+  e->rpl_n = 0;
+}
+
+#ifdef MGX_CPU_EMU   // the sanitizer build has no episode statistics, no replay recorder and no map generator
+static int flush_shadow(mgx_engine*, const int32_t*, const uint32_t*, unsigned) { return MGX_OK; }
+static int launch_episode_stats(mgx_engine*) { return MGX_OK; }
+static int launch_replay(mgx_engine*) { return MGX_OK; }
+static int mark_replay(mgx_engine*, const int32_t*, int, uint32_t) { return MGX_OK; }
+static int launch_mapgen_envs(mgx_engine*, const MgxList&, const uint32_t*) { return MGX_OK; }
+#else
+static int launch_mapgen_envs(mgx_engine* e, const MgxList& l, const uint32_t* dseeds_packed);   // (beside mgx_set_map_generator)
 // d.shadow: bring the float stat cells of the listed envs (or all) up to date with the integer counters (mgx_episode.h)
 static int flush_shadow(mgx_engine* e, const int32_t* list, const uint32_t* list_n, unsigned grid) {
-#ifndef MGX_CPU_EMU
   if (!e->d.shadow) return MGX_OK;
   hipLaunchKernelGGL(mgx_shadow_flush_kernel, dim3(grid), dim3(256), 0, e->stream, dev_copy(e), list, list_n);
   HIP_TRY(hipGetLastError());
-#else
-  (void)e; (void)list; (void)list_n; (void)grid;
-#endif
   return MGX_OK;
-}
-static int flush_shadow_all(mgx_engine* e) {
-  return flush_shadow(e, nullptr, nullptr, (unsigned)std::min<long long>(((long long)e->d.E * e->d.A + 255) / 256, 4096));
 }
 // Episode-end statistics of the envs in the done list (csrc/mgx_episode.h): records, then batch totals (+ log).
 static int launch_episode_stats(mgx_engine* e) {
-#ifndef MGX_CPU_EMU
   const MgxDev& d = e->d;
   MgxList dl;
   dl.n_host = -1;
@@ -610,40 +642,25 @@ static int launch_episode_stats(mgx_engine* e) {
                      (const uint32_t*)e->d_done_n, (const uint32_t*)e->d_ep_rec, e->d_ep_partial, e->d_ep_totals, e->d_ep_ticket,
                      e->d_ep_log_state, e->ep_log_cap, e->d_ep_log ? 1 : 0);
   HIP_TRY(hipGetLastError());
-#else
-  (void)e;
-#endif
   return MGX_OK;
-}
-
-static void free_replay(mgx_engine* e) {
-  for (const void* p : {(const void*)e->rpl.envs, (const void*)e->rpl.log, (const void*)e->rpl.cursor, (const void*)e->rpl.state,
-                        (const void*)e->rpl.shadow, (const void*)e->rpl.static_cls})
-    if (p) (void)hipFree(const_cast<void*>(p));
-  e->rpl = MgxRpl{};
-  e->rpl_n = 0;
 }
 // The step's changes of the watched envs -> their logs (csrc/mgx_replay.h); nothing without a watch list.
 static int launch_replay(mgx_engine* e) {
-#ifndef MGX_CPU_EMU
   if (!e->rpl_n) return MGX_OK;
   hipLaunchKernelGGL(mgx_replay_kernel, dim3((unsigned)e->rpl_n), dim3(MGX_RPL_THREADS), 0, e->stream, dev_copy(e), e->rpl);
   HIP_TRY(hipGetLastError());
-#else
-  (void)e;
-#endif
   return MGX_OK;
 }
 // The episodes of the envs in a DEVICE list are cut from outside a step: END marker with `flags`, keyframe next.
 static int mark_replay(mgx_engine* e, const int32_t* dlist, int n, uint32_t flags) {
-#ifndef MGX_CPU_EMU
   if (!e->rpl_n || n <= 0) return MGX_OK;
   hipLaunchKernelGGL(mgx_replay_mark_kernel, dim3((unsigned)e->rpl_n), dim3(MGX_RPL_THREADS), 0, e->stream, dev_copy(e), e->rpl, dlist, n, flags);
   HIP_TRY(hipGetLastError());
-#else
-  (void)e; (void)dlist; (void)n; (void)flags;
-#endif
   return MGX_OK;
+}
+#endif  // MGX_CPU_EMU
+static int flush_shadow_all(mgx_engine* e) {
+  return flush_shadow(e, nullptr, nullptr, (unsigned)std::min<long long>(((long long)e->d.E * e->d.A + 255) / 256, 4096));
 }
 
 extern "C" {
@@ -906,11 +923,6 @@ static int stage(mgx_engine* e, size_t bytes) {
 // generate: the listed envs' maps are generated into dmaps first (mgx_mapgen.h; gen_seeds: one seed per list entry, or the
 // slot rule base + episodes).
 // l: the same envs as an ascending device list (the kernels then walk the list with a small grid instead of testing E mask bytes).
-#ifdef MGX_CPU_EMU
-static int launch_mapgen_envs(mgx_engine*, const MgxList&, const uint32_t*) { return MGX_OK; }   // (no generator in the sanitizer build)
-#else
-static int launch_mapgen_envs(mgx_engine* e, const MgxList& l, const uint32_t* dseeds_packed);
-#endif
 static int restart_masked(mgx_engine* e, const uint8_t* dmask, bool from_pool, bool bump, const MgxList& l = MgxList(),
                           bool generate = false, const uint32_t* gen_seeds = nullptr) {
   const MgxDev& d = e->d;
@@ -983,61 +995,68 @@ static int fit_maps(mgx_engine* e, const uint16_t* maps, size_t first, size_t co
   return MGX_OK;
 }
 
-int mgx_reset_envs(mgx_engine* e, const uint8_t* env_mask, const uint16_t* class_maps, const uint32_t* seeds) {
-  if (!e || !env_mask) return fail(MGX_ERR_BAD_ARG, "mgx_reset_envs: null argument");
-  HIP_TRY(hipSetDevice(e->device));
+// One per-env uint32 column of a host-driven restart: the masked envs' values of `src` (host [E], or none) travel in the
+// staging block and are scattered into the device array `dst` [E] (none: only read from the block, as generator seeds are).
+struct MgxResetCol { const uint32_t* src; uint32_t* dst; };
+// The host-driven restart behind mgx_reset_envs*: the masked envs as ONE upload [indices | column 0 | column 1 | maps | n]
+// (absent sections take no room, every section starts on a 16-byte boundary), scattered on the device; then the replay
+// marker (it carries the step of the episode that ends, so it stays in front of the clear), restart_masked, and the
+// restarted rows to host buffers.  gen_col: the column restart_masked's generator reads its seeds from (generate only).
+static int reset_from_host(mgx_engine* e, const uint8_t* env_mask, MgxResetCol col0, MgxResetCol col1, const uint16_t* class_maps,
+                           bool from_pool, bool generate = false, int gen_col = -1) {
   const MgxDev& d = e->d;
-  const size_t E = d.E, HW = (size_t)d.H * d.W, A = d.A;
+  const size_t E = d.E, HW = (size_t)d.H * d.W;
   std::vector<int32_t> idx;
   for (size_t i = 0; i < E; i++) if (env_mask[i]) idx.push_back((int32_t)i);
   if (idx.empty()) return MGX_OK;
   const size_t n = idx.size();
-  if (class_maps) {
-    int rc = validate_maps(e, class_maps, E, env_mask, "mgx_reset_envs");
-    if (!rc) rc = fit_maps(e, class_maps, 0, E, env_mask, "mgx_reset_envs");
-    if (rc) return rc;
-  }
-  // ONE contiguous upload: [indices | packed seeds | packed maps] of the masked envs, scattered on the device
-  const size_t off_seeds = n * 4, off_maps = (off_seeds + (seeds ? n * 4 : 0) + 15) & ~(size_t)15;
-  const size_t off_n = (off_maps + (class_maps ? n * HW * 2 : 0) + 15) & ~(size_t)15;   // the list length, for the list-walking kernels
-  const size_t total = off_n + 16;
-  std::vector<uint8_t> host(total);
+  const MgxResetCol cols[2] = {col0, col1};
+  size_t off_col[2], end = n * 4;
+  auto section = [&end](size_t bytes) { const size_t off = (end + 15) & ~(size_t)15; end = off + bytes; return off; };
+  for (int c = 0; c < 2; c++) off_col[c] = section(cols[c].src ? n * 4 : 0);
+  const size_t off_maps = section(class_maps ? n * HW * 2 : 0);
+  const size_t off_n = section(16);   // the list length, for the list-walking kernels
+  std::vector<uint8_t> host(end);
   memcpy(host.data(), idx.data(), n * 4);
   { const uint32_t n32 = (uint32_t)n; memcpy(host.data() + off_n, &n32, 4); }
   for (size_t k = 0; k < n; k++) {
-    if (seeds) memcpy(host.data() + off_seeds + k * 4, seeds + idx[k], 4);
+    for (int c = 0; c < 2; c++) if (cols[c].src) memcpy(host.data() + off_col[c] + k * 4, cols[c].src + idx[k], 4);
     if (class_maps) memcpy(host.data() + off_maps + k * HW * 2, class_maps + (size_t)idx[k] * HW, HW * 2);
   }
-  int rc = stage(e, total);
+  int rc = stage(e, host.size());
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(e->dmask, env_mask, E, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->d_stage, host.data(), total, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_stage, host.data(), host.size(), hipMemcpyHostToDevice, e->stream));
   const uint8_t* st = (const uint8_t*)e->d_stage;
-  if (seeds) hipLaunchKernelGGL(mgx_scatter_words_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, e->dseeds,
-                                (const uint32_t*)(st + off_seeds), (const int32_t*)st, (int)n);
-  if (class_maps) hipLaunchKernelGGL(mgx_scatter_maps_kernel, dim3(4, (unsigned)n), dim3(256), 0, e->stream, e->dmaps,
-                                     (const uint16_t*)(st + off_maps), (const int32_t*)st, (int)n, (int)HW);
-  HIP_TRY(hipGetLastError());
   MgxList l;
   l.list = (const int32_t*)st; l.n = (const uint32_t*)(st + off_n); l.n_host = (int)n;
+  for (int c = 0; c < 2; c++)
+    if (cols[c].src && cols[c].dst)
+      hipLaunchKernelGGL(mgx_scatter_words_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, cols[c].dst,
+                         (const uint32_t*)(st + off_col[c]), l.list, (int)n);
+  if (class_maps) hipLaunchKernelGGL(mgx_scatter_maps_kernel, dim3(4, (unsigned)n), dim3(256), 0, e->stream, e->dmaps,
+                                     (const uint16_t*)(st + off_maps), l.list, (int)n, (int)HW);
+  HIP_TRY(hipGetLastError());
   rc = mark_replay(e, l.list, (int)n, MGX_RPL_E_ABORTED);
   if (rc) return rc;
-  rc = restart_masked(e, e->dmask, false, false, l);
+  rc = restart_masked(e, e->dmask, from_pool, false, l, generate,
+                      gen_col >= 0 && cols[gen_col].src ? (const uint32_t*)(st + off_col[gen_col]) : nullptr);
   if (rc) return rc;
-  if (e->mem_kind == MGX_MEM_HOST) {  // host buffers: the restarted rows, one copy per contiguous run of envs
-    for (size_t k = 0; k < n;) {
-      size_t j = k;
-      while (j + 1 < n && idx[j + 1] == idx[j] + 1) j++;
-      const size_t r0 = (size_t)idx[k] * A, rows = (size_t)(idx[j] - idx[k] + 1) * A;
-      HIP_TRY(hipMemcpyAsync(e->h_obs + r0 * d.T * 3, d.obs + r0 * d.T * 3, rows * d.T * 3, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipMemcpyAsync(e->h_term + r0, d.terminals + r0, rows, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipMemcpyAsync(e->h_trunc + r0, d.truncations + r0, rows, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipMemcpyAsync(e->h_rew + r0, d.rewards + r0, rows * 4, hipMemcpyDeviceToHost, e->stream));
-      k = j + 1;
-    }
-  }
+  rc = copy_out_envs(e, idx.data(), n);
+  if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));  // `host` is a local
   return MGX_OK;
+}
+
+int mgx_reset_envs(mgx_engine* e, const uint8_t* env_mask, const uint16_t* class_maps, const uint32_t* seeds) {
+  if (!e || !env_mask) return fail(MGX_ERR_BAD_ARG, "mgx_reset_envs: null argument");
+  HIP_TRY(hipSetDevice(e->device));
+  if (class_maps) {
+    int rc = validate_maps(e, class_maps, (size_t)e->d.E, env_mask, "mgx_reset_envs");
+    if (!rc) rc = fit_maps(e, class_maps, 0, (size_t)e->d.E, env_mask, "mgx_reset_envs");
+    if (rc) return rc;
+  }
+  return reset_from_host(e, env_mask, {seeds, e->dseeds}, {nullptr, nullptr}, class_maps, false);
 }
 
 int mgx_set_map_pool(mgx_engine* e, const uint16_t* class_maps, int32_t n_maps) {
@@ -1067,47 +1086,10 @@ int mgx_reset_envs_from_pool(mgx_engine* e, const uint8_t* env_mask, const int32
   if (!e || !env_mask || !pool_index) return fail(MGX_ERR_BAD_ARG, "mgx_reset_envs_from_pool: null argument");
   if (e->n_pool <= 0) return fail(MGX_ERR_BAD_ARG, "mgx_reset_envs_from_pool: no map pool (mgx_set_map_pool)");
   HIP_TRY(hipSetDevice(e->device));
-  const MgxDev& d = e->d;
-  const size_t E = d.E;
-  std::vector<int32_t> idx;
-  std::vector<uint32_t> vals;
-  for (size_t i = 0; i < E; i++) if (env_mask[i]) {
-    if (pool_index[i] < 0 || pool_index[i] >= e->n_pool) return fail(MGX_ERR_BAD_ARG, "mgx_reset_envs_from_pool: pool index out of range");
-    idx.push_back((int32_t)i);
-  }
-  if (idx.empty()) return MGX_OK;
-  const size_t n = idx.size();
-  std::vector<uint8_t> host(n * 12 + 16);
-  memcpy(host.data(), idx.data(), n * 4);
-  { const uint32_t n32 = (uint32_t)n; memcpy(host.data() + n * 12, &n32, 4); }
-  for (size_t k = 0; k < n; k++) {
-    memcpy(host.data() + n * 4 + k * 4, pool_index + idx[k], 4);
-    if (seeds) memcpy(host.data() + n * 8 + k * 4, seeds + idx[k], 4);
-  }
-  int rc = stage(e, host.size());
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(e->dmask, env_mask, E, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->d_stage, host.data(), host.size(), hipMemcpyHostToDevice, e->stream));
-  const uint8_t* st = (const uint8_t*)e->d_stage;
-  const dim3 g((unsigned)((n + 255) / 256)), b(256);
-  hipLaunchKernelGGL(mgx_scatter_words_kernel, g, b, 0, e->stream, (uint32_t*)e->d_map_index, (const uint32_t*)(st + n * 4), (const int32_t*)st, (int)n);
-  if (seeds) hipLaunchKernelGGL(mgx_scatter_words_kernel, g, b, 0, e->stream, e->dseeds, (const uint32_t*)(st + n * 8), (const int32_t*)st, (int)n);
-  HIP_TRY(hipGetLastError());
-  MgxList l;
-  l.list = (const int32_t*)st; l.n = (const uint32_t*)(st + n * 12); l.n_host = (int)n;
-  rc = mark_replay(e, l.list, (int)n, MGX_RPL_E_ABORTED);
-  if (rc) return rc;
-  rc = restart_masked(e, e->dmask, true, false, l);
-  if (rc) return rc;
-  if (e->mem_kind == MGX_MEM_HOST) {
-    const size_t rows = E * d.A;
-    HIP_TRY(hipMemcpyAsync(e->h_obs, d.obs, rows * d.T * 3, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->h_term, d.terminals, rows, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->h_trunc, d.truncations, rows, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->h_rew, d.rewards, rows * 4, hipMemcpyDeviceToHost, e->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return MGX_OK;
+  for (int i = 0; i < e->d.E; i++)
+    if (env_mask[i] && (pool_index[i] < 0 || pool_index[i] >= e->n_pool))
+      return fail(MGX_ERR_BAD_ARG, "mgx_reset_envs_from_pool: pool index out of range");
+  return reset_from_host(e, env_mask, {(const uint32_t*)pool_index, (uint32_t*)e->d_map_index}, {seeds, e->dseeds}, nullptr, true);
 }
 
 int mgx_set_auto_reset(mgx_engine* e, int32_t enabled, int32_t pool_stride, const uint32_t* early_end_steps) {
@@ -1313,48 +1295,7 @@ int mgx_reset_envs_generated(mgx_engine* e, const uint8_t* env_mask, const uint3
   if (!e || !env_mask) return fail(MGX_ERR_BAD_ARG, "mgx_reset_envs_generated: null argument");
   if (!e->gen_on) return fail(MGX_ERR_BAD_ARG, "mgx_reset_envs_generated: no map generator (mgx_set_map_generator)");
   HIP_TRY(hipSetDevice(e->device));
-  const MgxDev& d = e->d;
-  const size_t E = d.E, A = d.A;
-  std::vector<int32_t> idx;
-  for (size_t i = 0; i < E; i++) if (env_mask[i]) idx.push_back((int32_t)i);
-  if (idx.empty()) return MGX_OK;
-  const size_t n = idx.size();
-  // ONE contiguous upload: [indices | packed map seeds | packed seeds | n]
-  std::vector<uint8_t> host(n * 12 + 16);
-  memcpy(host.data(), idx.data(), n * 4);
-  { const uint32_t n32 = (uint32_t)n; memcpy(host.data() + n * 12, &n32, 4); }
-  for (size_t k = 0; k < n; k++) {
-    if (map_seeds) memcpy(host.data() + n * 4 + k * 4, map_seeds + idx[k], 4);
-    if (seeds) memcpy(host.data() + n * 8 + k * 4, seeds + idx[k], 4);
-  }
-  int rc = stage(e, host.size());
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(e->dmask, env_mask, E, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->d_stage, host.data(), host.size(), hipMemcpyHostToDevice, e->stream));
-  const uint8_t* st = (const uint8_t*)e->d_stage;
-  if (seeds) hipLaunchKernelGGL(mgx_scatter_words_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, e->dseeds,
-                                (const uint32_t*)(st + n * 8), (const int32_t*)st, (int)n);
-  HIP_TRY(hipGetLastError());
-  MgxList l;
-  l.list = (const int32_t*)st; l.n = (const uint32_t*)(st + n * 12); l.n_host = (int)n;
-  rc = mark_replay(e, l.list, (int)n, MGX_RPL_E_ABORTED);
-  if (rc) return rc;
-  rc = restart_masked(e, e->dmask, false, false, l, true, map_seeds ? (const uint32_t*)(st + n * 4) : nullptr);
-  if (rc) return rc;
-  if (e->mem_kind == MGX_MEM_HOST) {  // host buffers: the restarted rows, one copy per contiguous run of envs
-    for (size_t k = 0; k < n;) {
-      size_t j = k;
-      while (j + 1 < n && idx[j + 1] == idx[j] + 1) j++;
-      const size_t r0 = (size_t)idx[k] * A, rows = (size_t)(idx[j] - idx[k] + 1) * A;
-      HIP_TRY(hipMemcpyAsync(e->h_obs + r0 * d.T * 3, d.obs + r0 * d.T * 3, rows * d.T * 3, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipMemcpyAsync(e->h_term + r0, d.terminals + r0, rows, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipMemcpyAsync(e->h_trunc + r0, d.truncations + r0, rows, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipMemcpyAsync(e->h_rew + r0, d.rewards + r0, rows * 4, hipMemcpyDeviceToHost, e->stream));
-      k = j + 1;
-    }
-  }
-  HIP_TRY(hipStreamSynchronize(e->stream));  // `host` is a local
-  return MGX_OK;
+  return reset_from_host(e, env_mask, {map_seeds, nullptr}, {seeds, e->dseeds}, nullptr, false, true, 0);
 }
 
 int mgx_get_map_seeds(mgx_engine* e, uint32_t* out) {
@@ -1745,10 +1686,8 @@ int mgx_step(mgx_engine* e) {
   }
   if (e->rpl_n) { int prc = launch_replay(e); if (prc) return prc; }
   if (e->mem_kind == MGX_MEM_HOST) {
-    HIP_TRY(hipMemcpyAsync(e->h_obs, d.obs, rows * d.T * 3, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->h_term, d.terminals, rows, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->h_trunc, d.truncations, rows, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->h_rew, d.rewards, rows * 4, hipMemcpyDeviceToHost, e->stream));
+    rc = copy_out(e, 0, (size_t)d.E);
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
   }
   return MGX_OK;
@@ -2111,20 +2050,9 @@ static int es_after_write(mgx_engine* e, const int32_t* envs, int32_t n) {
                        e->d_done_n, (volatile uint32_t*)e->h_flags_dev, e->step_seq);
     HIP_TRY(hipGetLastError());
   }
-  if (e->mem_kind == MGX_MEM_HOST) {   // one copy per run of consecutive envs
-    std::vector<int32_t> idx(envs, envs + n);
-    std::sort(idx.begin(), idx.end());
-    const size_t A = d.A;
-    for (size_t k = 0; k < idx.size();) {
-      size_t j = k;
-      while (j + 1 < idx.size() && idx[j + 1] == idx[j] + 1) j++;
-      const size_t r0 = (size_t)idx[k] * A, rows = (size_t)(idx[j] - idx[k] + 1) * A;
-      HIP_TRY(hipMemcpyAsync(e->h_obs + r0 * d.T * 3, d.obs + r0 * d.T * 3, rows * d.T * 3, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipMemcpyAsync(e->h_term + r0, d.terminals + r0, rows, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipMemcpyAsync(e->h_trunc + r0, d.truncations + r0, rows, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipMemcpyAsync(e->h_rew + r0, d.rewards + r0, rows * 4, hipMemcpyDeviceToHost, e->stream));
-      k = j + 1;
-    }
+  if (e->mem_kind == MGX_MEM_HOST) {
+    int rc = copy_out_envs(e, envs, (size_t)n);
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
   }
   return MGX_OK;

@@ -385,22 +385,27 @@ class BatchedMettaGrid:
         self._out_fences = (getattr(self, "_out_fences", []) + [event])[-4:]   # (several consumers: none is freed while pending)
         _check(self.L.mgx_wait_before_outputs(self.h, C.c_void_p(event.cuda_event)))
 
+    def _per_env(self, a, dtype=np.uint8) -> np.ndarray:
+        """An env mask (or another array with one entry per env) -> contiguous ``dtype`` [E]."""
+        return np.ascontiguousarray(np.asarray(a, dtype=dtype).reshape(self.E))
+
+    def _per_env_or_all(self, v, dtype):
+        """One value for all envs, or one per env -> contiguous ``dtype`` [E]; None stays None."""
+        return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (self.E,)))
+
     def reset_envs(self, env_mask, class_maps=None, seeds=None) -> None:
         """Restart the selected envs in place on the device (new episode): optional new maps / seeds for them.
         Their buffer rows are cleared and receive the initial observations, exactly like a fresh reference
         ``MettaGrid`` + ``set_buffers``."""
-        mask = np.ascontiguousarray(np.asarray(env_mask, dtype=np.uint8).reshape(self.E))
-        cm_ptr = sd_ptr = None
+        mask, sd = self._per_env(env_mask), self._per_env_or_all(seeds, np.uint32)
+        cm_ptr = None
         if class_maps is not None:
             cm = np.ascontiguousarray(class_maps, dtype=np.uint16)
             H, W = int(self.prog.words[K.H_HEIGHT]), int(self.prog.words[K.H_WIDTH])
             if cm.shape != (self.E, H, W):
                 raise ValueError(f"class_maps must have shape {(self.E, H, W)} (only masked envs are read)")
             cm_ptr = cm.ctypes.data
-        if seeds is not None:
-            sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint32), (self.E,)))
-            sd_ptr = sd.ctypes.data
-        _check(self.L.mgx_reset_envs(self.h, mask.ctypes.data, cm_ptr, sd_ptr))
+        _check(self.L.mgx_reset_envs(self.h, mask.ctypes.data, cm_ptr, None if sd is None else sd.ctypes.data))
 
     # ---- device-resident map pool + auto-reset (SURVEY.md §8f-1) ----
     def set_map_pool(self, class_maps) -> None:
@@ -413,22 +418,15 @@ class BatchedMettaGrid:
         self.pool_size = cm.shape[0]
 
     def reset_envs_from_pool(self, env_mask, pool_index, seeds=None) -> None:
-        mask = np.ascontiguousarray(np.asarray(env_mask, dtype=np.uint8).reshape(self.E))
-        idx = np.ascontiguousarray(np.broadcast_to(np.asarray(pool_index, dtype=np.int32), (self.E,)))
-        sd_ptr = None
-        if seeds is not None:
-            sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint32), (self.E,)))
-            sd_ptr = sd.ctypes.data
-        _check(self.L.mgx_reset_envs_from_pool(self.h, mask.ctypes.data, idx.ctypes.data, sd_ptr))
+        mask, sd = self._per_env(env_mask), self._per_env_or_all(seeds, np.uint32)
+        idx = self._per_env_or_all(np.asarray(pool_index), np.int32)
+        _check(self.L.mgx_reset_envs_from_pool(self.h, mask.ctypes.data, idx.ctypes.data, None if sd is None else sd.ctypes.data))
 
     def set_auto_reset(self, enabled: bool = True, pool_stride: int = 1, early_end_steps=None) -> None:
         """Lazy auto-reset on the device (MettaGridPufferEnv.step, mettagrid_puffer_env.py:299-302); ``early_end_steps``
         [E]: step at which each env's first episode is truncated early (EarlyResetHandler), 0 = never."""
-        ptr = None
-        if early_end_steps is not None:
-            ee = np.ascontiguousarray(np.asarray(early_end_steps, dtype=np.uint32).reshape(self.E))
-            ptr = ee.ctypes.data
-        _check(self.L.mgx_set_auto_reset(self.h, 1 if enabled else 0, int(pool_stride), ptr))
+        ee = None if early_end_steps is None else self._per_env(early_end_steps, np.uint32)
+        _check(self.L.mgx_set_auto_reset(self.h, 1 if enabled else 0, int(pool_stride), None if ee is None else ee.ctypes.data))
 
     def episodes(self):
         ep, mi = np.empty(self.E, np.uint32), np.empty(self.E, np.int32)
@@ -472,15 +470,10 @@ class BatchedMettaGrid:
     def reset_envs_generated(self, env_mask, map_seeds=None, seeds=None) -> None:
         """``reset_envs`` with the masked envs' maps generated on the device: ``map_seeds`` uint32 [E] (only masked envs are
         read) or None = each slot's base seed + its episode count."""
-        mask = np.ascontiguousarray(np.asarray(env_mask, dtype=np.uint8).reshape(self.E))
-        ms_ptr = sd_ptr = None
-        if map_seeds is not None:
-            ms = np.ascontiguousarray(np.broadcast_to(np.asarray(map_seeds, dtype=np.uint32), (self.E,)))
-            ms_ptr = ms.ctypes.data
-        if seeds is not None:
-            sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint32), (self.E,)))
-            sd_ptr = sd.ctypes.data
-        _check(self.L.mgx_reset_envs_generated(self.h, mask.ctypes.data, ms_ptr, sd_ptr))
+        mask = self._per_env(env_mask)
+        ms, sd = self._per_env_or_all(map_seeds, np.uint32), self._per_env_or_all(seeds, np.uint32)
+        _check(self.L.mgx_reset_envs_generated(self.h, mask.ctypes.data, None if ms is None else ms.ctypes.data,
+                                               None if sd is None else sd.ctypes.data))
 
     def map_seeds(self) -> np.ndarray:
         """uint32 [E]: the seed of the map each env's most recent generated restart built."""
@@ -505,8 +498,7 @@ class BatchedMettaGrid:
 
     def record_episodes(self, env_mask) -> None:
         """Host-driven restarts: record the masked envs' episodes as finished now (call before ``reset_envs``)."""
-        mask = np.ascontiguousarray(np.asarray(env_mask, dtype=np.uint8).reshape(self.E))
-        _check(self.L.mgx_record_episodes(self.h, mask.ctypes.data))
+        _check(self.L.mgx_record_episodes(self.h, self._per_env(env_mask).ctypes.data))
 
     def request_episode_stats(self) -> None:
         _check(self.L.mgx_request_episode_stats(self.h))
