@@ -13,6 +13,7 @@
 #include "mgx.h"
 #include "mgx_device.h"
 #include "mgx_obs.h"
+#include "mgx_obs_instances.h"
 #include "mgx_presets_gen.h"   // MgxObsShapeR3 / R4: the benchmark presets' shapes (mettagrid_amd/gen_presets.py, written at build())
 #include "mgx_handlers_fp.h"   // fingerprints of the presets' handler tables (mettagrid_amd/gen_handlers.py, written at build())
 #include "mgx_world.h"
@@ -192,11 +193,6 @@ __global__ void __launch_bounds__(256) mgx_objects_kernel(const MgxDev* __restri
   }
 }
 
-// dense-output instances of the observation kernel (mgx_obs_box.hip)
-bool mgx_launch_obs_box(hipStream_t stream, const MgxDev& dd, size_t lds, int pool_tokens, int pool_prefix, const uint8_t* mask, int blk_start,
-                        int blk_words, int rewards_early, bool with_rewards, bool X, bool PL, int threads, int ew, void* box, const float* scale,
-                        int C, int dtype, const int32_t* env_list, const uint32_t* env_list_n, int list_grid, int stat_passes);
-bool mgx_obs_box_set_lds(size_t lds);
 // token decode kernel (mgx_decode.hip)
 int mgx_launch_decode(hipStream_t stream, const uint8_t* tokens, float* box, const float* scale_dev, long long rows, int T, int C, int H, int W);
 
@@ -355,6 +351,34 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
   }
 };
 
+// The token-row instances of the observation kernel (the dense-output ones: mgx_obs_box.hip): the preset shapes, lean
+// without / with the program block in LDS, extended with 256 threads or 512 threads and 4 / 3 / 2 encode wavefronts.
+static const MgxObsInstance g_obs_instances[] = {
+    MGX_OBS_INSTANCE(false, true, MGX_OBS_THREADS, MGX_OBS_THREADS / MGX_WAVE, MgxObsShapeR3, false),
+    MGX_OBS_INSTANCE(false, true, MGX_OBS_THREADS, MGX_OBS_THREADS / MGX_WAVE, MgxObsShapeR3AnyLength, false),
+    MGX_OBS_INSTANCE(false, false, MGX_OBS_THREADS, MGX_OBS_THREADS / MGX_WAVE, MgxObsShapeDyn, false),
+    MGX_OBS_INSTANCE(false, true, MGX_OBS_THREADS, MGX_OBS_THREADS / MGX_WAVE, MgxObsShapeDyn, false),
+    MGX_OBS_INSTANCE(true, false, MGX_OBS_THREADS, MGX_OBS_THREADS / MGX_WAVE, MgxObsShapeDyn, false),
+    MGX_OBS_INSTANCE(true, false, 512, 4, MgxObsShapeDyn, false),
+    MGX_OBS_INSTANCE(true, false, 512, 3, MgxObsShapeDyn, false),
+    MGX_OBS_INSTANCE(true, false, 512, 2, MgxObsShapeDyn, false),
+};
+// The instance an engine runs, or nullptr.  A program whose shape equals a preset's runs that preset's instance (shape =
+// compile-time constants); dense output (mgx_set_box_output) has generic instances only.  Not asked for obs_variant 9.
+static const MgxObsInstance* find_obs_instance(const mgx_engine* e) {
+  const bool box = e->box_dtype != MGX_BOX_OFF, x = e->d.X != 0, pl = !x && e->obs_blk_lds;
+  const int variant = !box && (e->obs_variant == 3 || e->obs_variant == 5) ? e->obs_variant : 0;
+  int n = (int)(sizeof g_obs_instances / sizeof *g_obs_instances);
+  const MgxObsInstance* t = box ? mgx_obs_box_instances(&n) : g_obs_instances;
+  for (const MgxObsInstance* r = t; r < t + n; r++)
+    if (r->box == box && r->x == x && r->pl == pl && r->threads == e->obs_threads && r->ew == e->obs_ew && r->variant == variant) return r;
+  return nullptr;
+}
+static int set_obs_lds(const MgxObsInstance* t, int n, size_t lds) {
+  for (const MgxObsInstance* r = t; r < t + n; r++)
+    for (const void* f : r->fn) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return MGX_OK;
+}
 // Raise the observation kernels' dynamic LDS limit to the engine's lds_obs (mgx_create; fit_maps when new maps need a
 // larger pool).
 static int raise_obs_lds(mgx_engine* e) {
@@ -369,18 +393,11 @@ static int raise_obs_lds(mgx_engine* e) {
   size_t& cur_max = cur_max_dev[e->device];
   std::lock_guard<std::mutex> lock(mu);
   if (e->lds_obs > cur_max) {
-    const void* fns[] = {(const void*)mgx_obs_kernel<true, false, true, MGX_OBS_THREADS, MGX_OBS_THREADS / MGX_WAVE, MgxObsShapeR3>,
-                         (const void*)mgx_obs_kernel<false, false, true, MGX_OBS_THREADS, MGX_OBS_THREADS / MGX_WAVE, MgxObsShapeR3>,
-                         (const void*)mgx_obs_kernel<true, false, true, MGX_OBS_THREADS, MGX_OBS_THREADS / MGX_WAVE, MgxObsShapeR3AnyLength>,
-                         (const void*)mgx_obs_kernel<false, false, true, MGX_OBS_THREADS, MGX_OBS_THREADS / MGX_WAVE, MgxObsShapeR3AnyLength>,
-                         (const void*)mgx_obs_kernel<true, false, false>, (const void*)mgx_obs_kernel<false, false, false>,
-                         (const void*)mgx_obs_kernel<true, false, true>,  (const void*)mgx_obs_kernel<false, false, true>,
-                         (const void*)mgx_obs_kernel<true, true, false>,  (const void*)mgx_obs_kernel<false, true, false>,
-                         (const void*)mgx_obs_kernel<true, true, false, 512, 4>, (const void*)mgx_obs_kernel<false, true, false, 512, 4>,
-                         (const void*)mgx_obs_kernel<true, true, false, 512, 3>, (const void*)mgx_obs_kernel<false, true, false, 512, 3>,
-                         (const void*)mgx_obs_kernel<true, true, false, 512, 2>, (const void*)mgx_obs_kernel<false, true, false, 512, 2>};
-    for (const void* f : fns) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_obs));
-    if (!mgx_obs_box_set_lds(e->lds_obs)) return fail(MGX_ERR_HIP, "cannot raise the dense-output observation kernels' dynamic LDS limit");
+    int nb = 0;
+    const MgxObsInstance* box = mgx_obs_box_instances(&nb);
+    int rc = set_obs_lds(g_obs_instances, (int)(sizeof g_obs_instances / sizeof *g_obs_instances), e->lds_obs);
+    if (!rc) rc = set_obs_lds(box, nb, e->lds_obs);
+    if (rc) return rc;
     cur_max = e->lds_obs;
   }
   return MGX_OK;
@@ -397,39 +414,35 @@ static unsigned list_grid(const mgx_engine* e, const MgxList& l, int lo, int hi)
   const int hint = e->h_flags ? (int)std::min<uint32_t>(e->h_flags[1], 1u << 20) : 0;
   return (unsigned)std::max(1, std::min(e->d.E, std::min(hi, std::max(lo, 2 * hint))));
 }
-template <bool X, bool PL, int NTH = MGX_OBS_THREADS, int EW = NTH / MGX_WAVE, class K = MgxObsShapeDyn>
-static void launch_obs_t(mgx_engine* e, bool with_rewards, const uint8_t* mask, const MgxList& l) {
-  const bool listed = !with_rewards && l.list;
-  dim3 grid(listed ? list_grid(e, l, 128, 2048) : (unsigned)e->d.E), block(NTH);
-  const int32_t* ll = listed ? l.list : nullptr;
-  const uint32_t* ln = listed ? l.n : nullptr;
-  if (listed) mask = nullptr;
-  MgxDev dd = e->d;
-  if (PL)  // the interpreted sections are addressed relative to their LDS copy
-    for (int k = MGX_SEC_INV_FEATURES; k < MGX_SEC_WORDLIST; k++) dd.sec[k] -= e->obs_blk_start;
-  if (with_rewards)
-    hipLaunchKernelGGL((mgx_obs_kernel<true, X, PL, NTH, EW, K>), grid, block, e->lds_obs, e->stream, dd, e->pool_tokens, e->pool_prefix, mask, e->obs_blk_start, e->obs_blk_words, e->rmode, (void*)nullptr, (const float*)nullptr, 0, 0, ll, ln, l.passes);
-  else
-    hipLaunchKernelGGL((mgx_obs_kernel<false, X, PL, NTH, EW, K>), grid, block, e->lds_obs, e->stream, dd, e->pool_tokens, e->pool_prefix, mask, e->obs_blk_start, e->obs_blk_words, e->rmode, (void*)nullptr, (const float*)nullptr, 0, 0, ll, ln, l.passes);
-}
-// The observation kernel of a run-time code object: same arguments as mgx_obs_kernel, through hipModuleLaunchKernel.
-static int launch_obs_jit(mgx_engine* e, bool with_rewards, const uint8_t* mask, const MgxList& l) {
-  const bool listed = !with_rewards && l.list;
-  MgxDev dd = e->d;
-  for (int k = MGX_SEC_INV_FEATURES; k < MGX_SEC_WORDLIST; k++) dd.sec[k] -= e->obs_blk_start;   // (PL: relative to the LDS copy)
-  int pool_tokens = e->pool_tokens, pool_prefix = e->pool_prefix, blk_start = e->obs_blk_start, blk_words = e->obs_blk_words;
-  int rmode = e->rmode, zero = 0, passes = l.passes;
-  void* box = nullptr;
-  const float* scale = nullptr;
-  const uint8_t* m = listed ? nullptr : mask;
-  const int32_t* ll = listed ? l.list : nullptr;
-  const uint32_t* ln = listed ? l.n : nullptr;
-  void* params[] = {&dd, &pool_tokens, &pool_prefix, &m, &blk_start, &blk_words, &rmode, &box, &scale, &zero, &zero, &ll, &ln, &passes};
-  const unsigned grid = listed ? list_grid(e, l, 128, 2048) : (unsigned)e->d.E;
-  HIP_TRY(hipModuleLaunchKernel(with_rewards ? e->jit_obs.f0 : e->jit_obs.f1, grid, 1, 1, (unsigned)e->jit_obs.threads, 1, 1, (unsigned)e->lds_obs,
-                                e->stream, params, nullptr));
-  return MGX_OK;
-}
+// The observation kernel's arguments (mgx_obs_kernel, and the same list for a run-time code object's kernels) and grid for one
+// launch.  params[] points into the block itself: filled in place, never copied.
+struct MgxObsArgs {
+  MgxDev dd;
+  int pool_tokens, pool_prefix, blk_start, blk_words, rmode, box_C, box_dtype, passes;
+  const uint8_t* mask;
+  void* box;
+  const float* scale;
+  const int32_t* list;
+  const uint32_t* list_n;
+  unsigned grid;
+  void* params[14] = {&dd, &pool_tokens, &pool_prefix, &mask, &blk_start, &blk_words, &rmode, &box, &scale, &box_C, &box_dtype, &list, &list_n, &passes};
+  // pl: the instance keeps the interpreted program block in LDS.  A device env list replaces the mask, without rewards only.
+  MgxObsArgs(const mgx_engine* e, bool pl, bool with_rewards, const uint8_t* m, const MgxList& l) {
+    const bool listed = !with_rewards && l.list, boxed = e->box_dtype != MGX_BOX_OFF;
+    dd = e->d;
+    if (pl)  // the interpreted sections are addressed relative to their LDS copy
+      for (int k = MGX_SEC_INV_FEATURES; k < MGX_SEC_WORDLIST; k++) dd.sec[k] -= e->obs_blk_start;
+    pool_tokens = e->pool_tokens; pool_prefix = e->pool_prefix;
+    mask = listed ? nullptr : m;
+    blk_start = e->obs_blk_start; blk_words = e->obs_blk_words; rmode = e->rmode;
+    box = boxed ? e->box_out : nullptr; scale = boxed ? e->d_scale : nullptr;
+    box_C = boxed ? e->box_C : 0; box_dtype = boxed ? e->box_dtype : 0;
+    list = listed ? l.list : nullptr; list_n = listed ? l.n : nullptr;
+    passes = l.passes;
+    grid = listed ? list_grid(e, l, 128, 2048) : (unsigned)e->d.E;
+  }
+  MgxObsArgs(const MgxObsArgs&) = delete;
+};
 // The lean world kernel of a run-time code object: its MgxDev lives in the module's constant memory.
 static int launch_world_jit(mgx_engine* e, int prog_words) {
   mgx_engine::Jit& j = e->jit_world;
@@ -476,6 +489,16 @@ static const MgxDev* dev_copy_hot(mgx_engine* e) {
   }
   return e->d_hot;
 }
+// The extended games' world launches of mgx_step: the lane-per-agent dispatch (an attached code object's, else the built-in
+// one) and the world kernel's `phases`.
+static int launch_act_x(mgx_engine* e, int pw) {
+  if (e->jit_actx.mod) return launch_act_x_jit(e, dev_copy_world_x(e), pw);
+  mgx_launch_act_x(e->prog_in_lds, e->lds_act, e->stream, e->d, dev_copy_world_x(e), pw);
+  return MGX_OK;
+}
+static void launch_world_x(mgx_engine* e, int pw, int phases) {
+  mgx_launch_world_x(e->prog_in_lds, e->lds_world, e->stream, e->d, dev_copy_world_x(e), pw, phases);
+}
 // mgx_wait_before_outputs: whatever writes the bound output buffers next goes behind the caller's event.
 static int consume_out_fence(mgx_engine* e) {
   if (e->out_fence) {
@@ -507,32 +530,18 @@ static int launch_obs(mgx_engine* e, bool with_rewards, const uint8_t* mask = nu
   if (e->d.obsval) mgx_launch_values(e->stream, e->d, dev_copy(e), 0, mask);
   MGX_TRACE_POINT(e, "values kernel");
   if (e->rewards_ext) with_rewards = false;
-  if (e->box_dtype != MGX_BOX_OFF) {   // fused dense output (mgx_set_box_output): the BOX instances live in mgx_obs_box.hip
-    MgxDev dd = e->d;
-    const bool pl = !e->d.X && e->obs_blk_lds;
-    if (pl)
-      for (int k = MGX_SEC_INV_FEATURES; k < MGX_SEC_WORDLIST; k++) dd.sec[k] -= e->obs_blk_start;
-    if (!mgx_launch_obs_box(e->stream, dd, e->lds_obs, e->pool_tokens, e->pool_prefix, mask, e->obs_blk_start, e->obs_blk_words,
-                            e->rmode, with_rewards, e->d.X != 0, pl, e->obs_threads, e->obs_ew, e->box_out, e->d_scale,
-                            e->box_C, e->box_dtype, with_rewards ? nullptr : l.list, l.n, (int)list_grid(e, l, 128, 2048), l.passes))
-      return fail(MGX_ERR_PROGRAM, "mgx_step: no dense-output instance of the observation kernel for this configuration");
-    HIP_TRY(hipGetLastError());
-    return MGX_OK;
-  }
-  if (e->obs_variant == 9) {   // the instance compiled for this program at run time (mgx_attach_code)
-    int jrc = launch_obs_jit(e, with_rewards, mask, l);
-    if (jrc) return jrc;
-    return MGX_OK;
-  }
-  // a program whose shape equals a preset's runs that preset's instance of the kernel (shape = compile-time constants)
-  if (e->obs_variant == 3) launch_obs_t<false, true, MGX_OBS_THREADS, MGX_OBS_THREADS / MGX_WAVE, MgxObsShapeR3>(e, with_rewards, mask, l);
-  else if (e->obs_variant == 5) launch_obs_t<false, true, MGX_OBS_THREADS, MGX_OBS_THREADS / MGX_WAVE, MgxObsShapeR3AnyLength>(e, with_rewards, mask, l);
-  else if (e->d.X && e->obs_threads == 512 && e->obs_ew == 4) launch_obs_t<true, false, 512, 4>(e, with_rewards, mask, l);
-  else if (e->d.X && e->obs_threads == 512 && e->obs_ew == 3) launch_obs_t<true, false, 512, 3>(e, with_rewards, mask, l);
-  else if (e->d.X && e->obs_threads == 512) launch_obs_t<true, false, 512, 2>(e, with_rewards, mask, l);
-  else if (e->d.X) launch_obs_t<true, false>(e, with_rewards, mask, l);
-  else if (e->obs_blk_lds) launch_obs_t<false, true>(e, with_rewards, mask, l);
-  else launch_obs_t<false, false>(e, with_rewards, mask, l);
+  // the instance compiled for this program at run time (mgx_attach_code: lean, token rows, program block in LDS), or a row
+  // of the instance tables
+  const bool box = e->box_dtype != MGX_BOX_OFF, jit = !box && e->obs_variant == 9;
+  const MgxObsInstance* row = jit ? nullptr : find_obs_instance(e);
+  if (!jit && !row)
+    return fail(MGX_ERR_PROGRAM, std::string("mgx_step: no ") + (box ? "dense-output" : "token-row") + " instance of the observation kernel for this configuration");
+  MgxObsArgs a(e, jit || row->pl, with_rewards, mask, l);
+  if (jit)
+    HIP_TRY(hipModuleLaunchKernel(with_rewards ? e->jit_obs.f0 : e->jit_obs.f1, a.grid, 1, 1, (unsigned)e->jit_obs.threads, 1, 1, (unsigned)e->lds_obs,
+                                  e->stream, a.params, nullptr));
+  else
+    (void)hipLaunchKernel(row->fn[with_rewards], dim3(a.grid), dim3((unsigned)row->threads), a.params, e->lds_obs, e->stream);   // (a failure is the last error)
   HIP_TRY(hipGetLastError());
   return MGX_OK;
 }
@@ -1633,11 +1642,11 @@ int mgx_step(mgx_engine* e) {
       MGX_MARK(1); MGX_MARK(2); MGX_MARK(3);
     } else if (e->aoe_kernel) {
       if (d.act_par) {
-        if (e->jit_actx.mod) { int jrc = launch_act_x_jit(e, dev_copy_world_x(e), pw); if (jrc) return jrc; }
-        else mgx_launch_act_x(e->prog_in_lds, e->lds_act, e->stream, e->d, dev_copy_world_x(e), pw);
-        if (x_events) mgx_launch_world_x(e->prog_in_lds, e->lds_world, e->stream, e->d, dev_copy_world_x(e), pw, MGX_PH_EVENTS);
+        int jrc = launch_act_x(e, pw);
+        if (jrc) return jrc;
+        if (x_events) launch_world_x(e, pw, MGX_PH_EVENTS);
       } else {
-        mgx_launch_world_x(e->prog_in_lds, e->lds_world, e->stream, e->d, dev_copy_world_x(e), pw, MGX_PH_ACTIONS | MGX_PH_EVENTS);
+        launch_world_x(e, pw, MGX_PH_ACTIONS | MGX_PH_EVENTS);
       }
       MGX_TRACE_POINT(e, "world kernel (actions)");
       MGX_MARK(1);
@@ -1646,16 +1655,16 @@ int mgx_step(mgx_engine* e) {
       mgx_launch_aoe(e->stream, e->d, dev_copy(e), e->aoe_prog_lds ? dev_copy_hot(e) : nullptr, e->aoe_prog_lds ? e->prog_lds_words : 0);
       MGX_TRACE_POINT(e, "aoe kernel");
       MGX_MARK(2);
-      if (!d.cov_in_aoe) mgx_launch_world_x(e->prog_in_lds, e->lds_world, e->stream, e->d, dev_copy_world_x(e), pw, MGX_PH_TAIL);
+      if (!d.cov_in_aoe) launch_world_x(e, pw, MGX_PH_TAIL);
       else e->terr_fresh = true;   // target-local area effects move no source and change no tag: the ownership maps stay current
       MGX_MARK(3);
     } else {
       if (d.act_par) {
-        if (e->jit_actx.mod) { int jrc = launch_act_x_jit(e, dev_copy_world_x(e), pw); if (jrc) return jrc; }
-        else mgx_launch_act_x(e->prog_in_lds, e->lds_act, e->stream, e->d, dev_copy_world_x(e), pw);
-        mgx_launch_world_x(e->prog_in_lds, e->lds_world, e->stream, e->d, dev_copy_world_x(e), pw, MGX_PH_ALL & ~MGX_PH_ACTIONS);
+        int jrc = launch_act_x(e, pw);
+        if (jrc) return jrc;
+        launch_world_x(e, pw, MGX_PH_ALL & ~MGX_PH_ACTIONS);
       } else {
-        mgx_launch_world_x(e->prog_in_lds, e->lds_world, e->stream, e->d, dev_copy_world_x(e), pw, MGX_PH_ALL);
+        launch_world_x(e, pw, MGX_PH_ALL);
       }
       MGX_MARK(1); MGX_MARK(2); MGX_MARK(3);
     }
