@@ -26,10 +26,9 @@
 #endif
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-
 #include "mgx_device.h"
 #include "mgx_act.h"
+#include "mgx_host.h"
 
 #ifdef MGX_CPU_EMU
 #define MGX_WPE_ATTR
@@ -41,25 +40,13 @@ __global__ void __launch_bounds__(256) MGX_WPE_ATTR mgx_act_kernel_x(const MgxDe
   mgx_act_entry<PROG_LDS, true>(*dp, prog_words);
 }
 
-static std::mutex g_lds_mutex;
-static size_t g_lds_max_dev[64] = {0};   // the attribute is per kernel AND per device: one maximum for each
-bool mgx_act_x_set_lds(size_t lds) {
-  std::lock_guard<std::mutex> lock(g_lds_mutex);
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  size_t& g_lds_max = g_lds_max_dev[dev];
-  if (lds <= g_lds_max) return true;
-  if (hipFuncSetAttribute((const void*)mgx_act_kernel_x<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return false;
-  g_lds_max = lds;
-  return true;
-}
+static MgxLdsLimit g_lds_limit;
+bool mgx_act_x_set_lds(size_t lds) { return g_lds_limit.raise_current({(const void*)mgx_act_kernel_x<true>}, lds); }
 size_t mgx_act_x_lds_bytes(int A, bool aoe_lds, int extra) { return (size_t)mgx_world_lds_fixed(A, true, aoe_lds, extra); }
 int mgx_act_x_epg() { return MGX_WORLD_EPG; }
 
 void mgx_launch_act_x(bool prog_lds, size_t lds, hipStream_t stream, const MgxDev& d, const MgxDev* dp, int prog_words) {
-  int ap = 1;
-  while (ap < d.A) ap <<= 1;
+  const int ap = mgx_pow2_at_least(d.A);
   dim3 grid((d.E + MGX_WORLD_EPG - 1) / MGX_WORLD_EPG), block(MGX_WORLD_EPG * ap);
   // (only the variant with the hot program range in LDS is built — the fully inlined kernel takes minutes to compile;
   // programs whose hot range does not fit keep the lane-per-env kernel: mgx_create)
@@ -76,10 +63,5 @@ extern "C" int mgx_debug_act_read(uint32_t* out) {
 #endif
 
 #ifdef MGX_WORLD_TIMING  // instrumented developer build only (scripts/act_timing.py); not part of the ABI
-extern "C" int mgx_debug_act_x_cycles(unsigned long long* out, int reset) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(mgx_tu_actx::mgx_dbg_cycles), sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(mgx_tu_actx::mgx_dbg_cycles), z, sizeof z); }
-  return 0;
-}
+extern "C" int mgx_debug_act_x_cycles(unsigned long long* out, int reset) { return mgx_read_cycles(&mgx_tu_actx::mgx_dbg_cycles, out, reset); }
 #endif

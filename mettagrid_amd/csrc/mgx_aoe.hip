@@ -17,6 +17,7 @@
 #include "mgx_device.h"
 #include "mgx_world.h"
 #include "mgx_aoe_local.h"
+#include "mgx_host.h"
 
 #ifdef MGX_CPU_EMU
 #define MGX_AOE_OCCUPANCY
@@ -145,15 +146,10 @@ void mgx_launch_aoe(hipStream_t stream, const MgxDev& d, const MgxDev* dp, const
   if (hot) hipLaunchKernelGGL((mgx_aoe_kernel<true>), grid, block, lds, stream, hot, prog_words);
   else hipLaunchKernelGGL((mgx_aoe_kernel<false>), grid, block, lds, stream, dp, 0);
 }
-bool mgx_aoe_set_lds(int nstat, int prog_words) {   // dynamic LDS past 64 KB needs the opt-in attribute
-#ifdef MGX_CPU_EMU
-  (void)nstat; (void)prog_words;
-  return true;
-#else
-  const int lds = mgx_aoe_lds_bytes(nstat) + prog_words * 4;
-  return hipFuncSetAttribute((const void*)mgx_aoe_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess &&
-         hipFuncSetAttribute((const void*)mgx_aoe_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
-#endif
+static MgxLdsLimit g_lds_limit;
+bool mgx_aoe_set_lds(int nstat, int prog_words) {
+  return g_lds_limit.raise_current({(const void*)mgx_aoe_kernel<true>, (const void*)mgx_aoe_kernel<false>},
+                                   (size_t)mgx_aoe_lds_bytes(nstat) + (size_t)prog_words * 4);
 }
 
 // Host analysis: true when every AoE record and every territory handler of the program is "target-local" — its filters
@@ -376,10 +372,5 @@ void mgx_aoe_collect_stats(const int32_t* P, bool with_on_tick, bool with_covera
 }
 
 #ifdef MGX_WORLD_TIMING  // instrumented developer build only (scripts/aoe_timing.py); not part of the ABI
-extern "C" int mgx_debug_aoe_cycles(unsigned long long* out, int reset) {
-  hipDeviceSynchronize();
-  hipMemcpyFromSymbol(out, HIP_SYMBOL(mgx_tu_aoe::mgx_dbg_cycles), sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(mgx_tu_aoe::mgx_dbg_cycles), z, sizeof z); }
-  return 0;
-}
+extern "C" int mgx_debug_aoe_cycles(unsigned long long* out, int reset) { return mgx_read_cycles(&mgx_tu_aoe::mgx_dbg_cycles, out, reset); }
 #endif

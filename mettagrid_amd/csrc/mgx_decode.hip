@@ -13,9 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <string>
-
 #include "mgx.h"
+#include "mgx_host.h"
 
 #define MGX_DEC_WAVES 4
 #define MGX_DEC_WAVE 64
@@ -101,17 +100,12 @@ size_t mgx_decode_lds_bytes(int T, int C, int H, int W) {
   return (size_t)MGX_DEC_WAVES * ((size_t)tok_pad * 4 + (size_t)bmw * 8);
 }
 
+static MgxLdsLimit g_lds_limit;
 int mgx_launch_decode(hipStream_t stream, const uint8_t* tokens, float* box, const float* scale_dev, long long rows, int T, int C, int H,
                       int W) {
   const size_t lds = mgx_decode_lds_bytes(T, C, H, W);
   if (lds > 160 * 1024) return -1;
-  static size_t cur_max[64] = {};   // the attribute is per device
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -2;
-  if (lds > cur_max[dev]) {
-    if (hipFuncSetAttribute((const void*)mgx_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -2;
-    cur_max[dev] = lds;
-  }
+  if (!g_lds_limit.raise_current({(const void*)mgx_decode_kernel}, lds)) return -2;
   const long long blocks = (rows + MGX_DEC_WAVES - 1) / MGX_DEC_WAVES;
   hipLaunchKernelGGL(mgx_decode_kernel, dim3((unsigned)blocks), dim3(MGX_DEC_WAVES * MGX_DEC_WAVE), lds, stream, tokens, box, scale_dev, rows, T, C,
                      H, W);

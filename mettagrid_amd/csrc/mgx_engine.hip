@@ -17,6 +17,7 @@
 #include "mgx_presets_gen.h"   // MgxObsShapeR3 / R4: the benchmark presets' shapes (mettagrid_amd/gen_presets.py, written at build())
 #include "mgx_handlers_fp.h"   // fingerprints of the presets' handler tables (mettagrid_amd/gen_handlers.py, written at build())
 #include "mgx_world.h"
+#include "mgx_host.h"      // what the kernel units' host code shares, and their launchers
 #include "mgx_aoe_local.h"
 #include "mgx_episode.h"
 #include "mgx_plan.h"       // mgx_create's host-only half: validation and every create-time decision
@@ -193,9 +194,6 @@ __global__ void __launch_bounds__(256) mgx_objects_kernel(const MgxDev* __restri
   }
 }
 
-// token decode kernel (mgx_decode.hip)
-int mgx_launch_decode(hipStream_t stream, const uint8_t* tokens, float* box, const float* scale_dev, long long rows, int T, int C, int H, int W);
-
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) {
   g_err = msg;
@@ -211,11 +209,9 @@ static int fail(int code, const std::string& msg) {
 struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layout) + the resources behind it
   MgxSwitches sw{};            // the create-time switches, for the rest of the engine's life
   MgxDev* d_dev = nullptr;     // copy of `d` in device memory for the kernels that take it by pointer (extended path)
-  MgxDev d_dev_host{};         // what d_dev holds
-  bool d_dev_valid = false;
+  MgxDevImage d_dev_image;     // what d_dev holds
   MgxDev* d_hot = nullptr;     // the extended world kernel's copy: sec[] of the hot program range relative to its LDS copy
-  MgxDev d_hot_host{};
-  bool d_hot_valid = false;
+  MgxDevImage d_hot_image;
   int device = 0;
   hipStream_t stream = nullptr;
   std::vector<void*> allocs;
@@ -267,8 +263,7 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
     hipModule_t mod = nullptr;
     hipFunction_t f0 = nullptr, f1 = nullptr;   // world: the kernel for this engine's prog_in_lds; obs: with / without rewards
     void* dev_sym = nullptr;                     // world: address of the module's g_mgx_dev
-    MgxDev dev_host{};                           // ... and what it holds
-    bool dev_valid = false;
+    MgxDevImage dev_image;                       // ... and what it holds
     int epg = 0, threads = 0;
   } jit_world, jit_obs, jit_actx;
   int32_t* d_done_list = nullptr;   // [E] the envs of d_next_mask in ascending order (mgx_episode_end_kernel) ...
@@ -374,9 +369,9 @@ static const MgxObsInstance* find_obs_instance(const mgx_engine* e) {
     if (r->box == box && r->x == x && r->pl == pl && r->threads == e->obs_threads && r->ew == e->obs_ew && r->variant == variant) return r;
   return nullptr;
 }
-static int set_obs_lds(const MgxObsInstance* t, int n, size_t lds) {
-  for (const MgxObsInstance* r = t; r < t + n; r++)
-    for (const void* f : r->fn) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+// A kernel set's dynamic LDS limit on the engine's device (MgxLdsLimit: shared by every engine, only ever raised).
+static int raise_lds(MgxLdsLimit& limit, const std::vector<const void*>& kernels, const mgx_engine* e, size_t bytes) {
+  HIP_TRY(limit.raise(kernels.data(), kernels.size(), e->device, bytes));
   return MGX_OK;
 }
 // Raise the observation kernels' dynamic LDS limit to the engine's lds_obs (mgx_create; fit_maps when new maps need a
@@ -385,22 +380,13 @@ static int raise_obs_lds(mgx_engine* e) {
   if (e->sw.verbose)
     fprintf(stderr, "[mgx] obs: lds=%zu B pool=%d tokens (prefix %d) blk_lds=%d rewards_early=%d threads=%d encode wavefronts=%d (4 would need %zu B)\n",
             e->lds_obs, e->pool_tokens, e->pool_prefix, (int)e->obs_blk_lds, e->rmode, e->obs_threads, e->obs_ew, e->obs_lds_bytes(4));
-  // The attribute is per kernel and process-wide: keep one maximum and only ever raise it, so that a second engine
-  // with a smaller requirement cannot lower the limit under a live one.
-  static std::mutex mu;
-  static size_t cur_max_dev[64] = {};   // (function attributes are per device)
-  if (e->device < 0 || e->device >= 64) return fail(MGX_ERR_BAD_ARG, "device ordinal out of range");
-  size_t& cur_max = cur_max_dev[e->device];
-  std::lock_guard<std::mutex> lock(mu);
-  if (e->lds_obs > cur_max) {
-    int nb = 0;
-    const MgxObsInstance* box = mgx_obs_box_instances(&nb);
-    int rc = set_obs_lds(g_obs_instances, (int)(sizeof g_obs_instances / sizeof *g_obs_instances), e->lds_obs);
-    if (!rc) rc = set_obs_lds(box, nb, e->lds_obs);
-    if (rc) return rc;
-    cur_max = e->lds_obs;
-  }
-  return MGX_OK;
+  static MgxLdsLimit limit;
+  int nb = 0;
+  const MgxObsInstance* box = mgx_obs_box_instances(&nb);
+  std::vector<const void*> kernels;   // every instance of both tables
+  for (const MgxObsInstance& r : g_obs_instances) kernels.insert(kernels.end(), std::begin(r.fn), std::end(r.fn));
+  for (const MgxObsInstance* r = box; r < box + nb; r++) kernels.insert(kernels.end(), std::begin(r->fn), std::end(r->fn));
+  return raise_lds(limit, kernels, e, e->lds_obs);
 }
 
 // Grid of a restart kernel that walks a device list whose length only the device knows: enough workgroups to fill the chip,
@@ -443,14 +429,16 @@ struct MgxObsArgs {
   }
   MgxObsArgs(const MgxObsArgs&) = delete;
 };
+// The lean world unit's launcher and limit function by constant-memory slot (mgx_engine::slot).
+static const struct {
+  void (*launch)(bool prog_lds, size_t lds, hipStream_t stream, const MgxDev& d, int prog_words);
+  bool (*set_lds)(size_t lds);
+} g_world_fast[MGX_FAST_SLOTS] = {{mgx_launch_world_fast_s0, mgx_world_fast_set_lds_s0}, {mgx_launch_world_fast_s1, mgx_world_fast_set_lds_s1}};
 // The lean world kernel of a run-time code object: its MgxDev lives in the module's constant memory.
 static int launch_world_jit(mgx_engine* e, int prog_words) {
   mgx_engine::Jit& j = e->jit_world;
-  if (!j.dev_valid || memcmp(&j.dev_host, &e->d, sizeof(MgxDev)) != 0) {
-    memcpy(&j.dev_host, &e->d, sizeof(MgxDev));   // (stream-ordered: the kernels still reading the old content are ahead of the copy)
-    HIP_TRY(hipMemcpyAsync(j.dev_sym, &j.dev_host, sizeof(MgxDev), hipMemcpyHostToDevice, e->stream));
-    j.dev_valid = true;
-  }
+  if (j.dev_image.differs(e->d))   // (stream-ordered: the kernels still reading the old content are ahead of the copy)
+    HIP_TRY(hipMemcpyAsync(j.dev_sym, &j.dev_image.host, sizeof(MgxDev), hipMemcpyHostToDevice, e->stream));
   void* params[] = {&prog_words};
   const unsigned grid = (unsigned)((e->d.E + j.epg - 1) / j.epg);
   HIP_TRY(hipModuleLaunchKernel(j.f0, grid, 1, 1, (unsigned)j.threads, 1, 1, (unsigned)e->lds_world, e->stream, params, nullptr));
@@ -467,11 +455,7 @@ static int launch_act_x_jit(mgx_engine* e, const MgxDev* dp, int prog_words) {
 }
 // Device-memory copy of e->d, brought up to date (stream-ordered) whenever the host table changed.
 static const MgxDev* dev_copy(mgx_engine* e) {
-  if (!e->d_dev_valid || memcmp(&e->d_dev_host, &e->d, sizeof(MgxDev)) != 0) {
-    (void)hipMemcpyAsync(e->d_dev, &e->d, sizeof(MgxDev), hipMemcpyHostToDevice, e->stream);
-    memcpy(&e->d_dev_host, &e->d, sizeof(MgxDev));
-    e->d_dev_valid = true;
-  }
+  if (e->d_dev_image.differs(e->d)) (void)hipMemcpyAsync(e->d_dev, &e->d, sizeof(MgxDev), hipMemcpyHostToDevice, e->stream);
   return e->d_dev;
 }
 // ... and the extended world kernel's variant of it when that kernel keeps the hot program range in LDS.
@@ -482,11 +466,7 @@ static const MgxDev* dev_copy_hot(mgx_engine* e) {
   h.hot_lo = e->hot_lo;
   for (int k = 0; k < MGX_SEC_COUNT; k++)
     if (h.sec[k] >= e->hot_lo && h.sec[k] <= e->hot_hi && k != MGX_SEC_TAG_LISTS && k != MGX_SEC_SCHEDULE && k != MGX_SEC_CLASSES) h.sec[k] -= e->hot_lo;
-  if (!e->d_hot_valid || memcmp(&e->d_hot_host, &h, sizeof(MgxDev)) != 0) {
-    (void)hipMemcpyAsync(e->d_hot, &h, sizeof(MgxDev), hipMemcpyHostToDevice, e->stream);
-    memcpy(&e->d_hot_host, &h, sizeof(MgxDev));
-    e->d_hot_valid = true;
-  }
+  if (e->d_hot_image.differs(h)) (void)hipMemcpyAsync(e->d_hot, &h, sizeof(MgxDev), hipMemcpyHostToDevice, e->stream);
   return e->d_hot;
 }
 // The extended games' world launches of mgx_step: the lane-per-agent dispatch (an attached code object's, else the built-in
@@ -793,8 +773,7 @@ int mgx_create(const int32_t* program, size_t program_words, const uint16_t* cla
   }
   if (rc == MGX_OK && e->aoe_kernel && !mgx_aoe_set_lds(d.aoe_nstat, e->aoe_prog_lds ? e->prog_lds_words : 0))
     rc = fail(MGX_ERR_HIP, "mgx_create: cannot raise the area-effect kernel's dynamic LDS limit");
-  if (rc == MGX_OK && !(d.X ? mgx_world_x_set_lds(e->lds_world)
-                            : (e->slot == 0 ? mgx_world_fast_set_lds_s0(e->lds_world) : mgx_world_fast_set_lds_s1(e->lds_world))))
+  if (rc == MGX_OK && !(d.X ? mgx_world_x_set_lds(e->lds_world) : g_world_fast[e->slot].set_lds(e->lds_world)))
     rc = fail(MGX_ERR_HIP, "mgx_create: cannot raise the world kernel's dynamic LDS limit");
   if (rc == MGX_OK && d.act_par && !(d.X ? mgx_act_x_set_lds(e->lds_act) : mgx_act_fast_set_lds_s0(e->lds_act)))
     rc = fail(MGX_ERR_HIP, "mgx_create: cannot raise the action kernel's dynamic LDS limit");
@@ -1152,18 +1131,9 @@ static void free_map_generator(mgx_engine* e) {
   e->gen_on = false;
   e->gen_lds = 0;
 }
-// mgx_mapgen_kernel's dynamic LDS limit: per kernel and process-wide, only ever raised (see raise_obs_lds).
 static int raise_mapgen_lds(mgx_engine* e, size_t bytes) {
-  static std::mutex mu;
-  static size_t cur_max_dev[64] = {};
-  if (e->device < 0 || e->device >= 64) return fail(MGX_ERR_BAD_ARG, "device ordinal out of range");
-  std::lock_guard<std::mutex> lock(mu);
-  size_t& cur_max = cur_max_dev[e->device];
-  if (bytes > 64 * 1024 && bytes > cur_max) {
-    HIP_TRY(hipFuncSetAttribute((const void*)mgx_mapgen_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    cur_max = bytes;
-  }
-  return MGX_OK;
+  static MgxLdsLimit limit;
+  return raise_lds(limit, {(const void*)mgx_mapgen_kernel}, e, bytes);
 }
 // The listed envs' maps into dmaps (restart_masked): seeds one per list entry, or base[env] + episodes[env].
 static int launch_mapgen_envs(mgx_engine* e, const MgxList& l, const uint32_t* dseeds_packed) {
@@ -1339,35 +1309,39 @@ int mgx_attach_code(mgx_engine* e, int32_t kind, const char* path) {
     if (hipModuleGetGlobal(&p, &n, mod, name) != hipSuccess || n < bytes) return false;
     return hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost) == hipSuccess;
   };
+  // The 8-word mgx_jit_info block of a world / dispatch code object: empty when it fits this library, this engine's
+  // program and 64 KiB of LDS, else why not.
+  unsigned long long info[8] = {};
+  auto info_refusal = [&](unsigned long long magic, const char* what, size_t lds, bool name_fps) -> std::string {
+    if (!read_sym("mgx_jit_info", info, sizeof info) || info[0] != magic) return std::string("not a ") + what + " code object";
+    if (info[1] != sizeof(MgxDev) || info[6] != (unsigned long long)MGX_VERSION) return "built against other headers than this libmgx";
+    if (info[4] != e->handler_fp) {
+      char buf[96] = "";
+      if (name_fps) snprintf(buf, sizeof buf, " (code object %016llx, engine %016llx)", info[4], e->handler_fp);
+      return std::string("generated for another program (handler tables differ)") + buf;
+    }
+    if (lds > 64 * 1024) return "the kernel needs more than 64 KiB of LDS";
+    return "";
+  };
   if (kind == MGX_CODE_ACT_X) {
     if (!d.act_par) return refuse("the engine does not run the lane-per-agent dispatch for this program");
-    unsigned long long info[8] = {};
-    if (!read_sym("mgx_jit_info", info, sizeof info) || info[0] != 0x4D47584A49544131ull) return refuse("not a dispatch code object");
-    if (info[1] != sizeof(MgxDev) || info[6] != (unsigned long long)MGX_VERSION) return refuse("built against other headers than this libmgx");
-    if (info[4] != e->handler_fp) return refuse("generated for another program (handler tables differ)");
+    const std::string why = info_refusal(0x4D47584A49544131ull, "dispatch", e->lds_act, false);
+    if (!why.empty()) return refuse(why);
     if ((int)info[2] != mgx_act_x_epg()) return refuse("built for another workgroup shape");
-    if (e->lds_act > 64 * 1024) return refuse("the kernel needs more than 64 KiB of LDS");
     if (hipModuleGetFunction(&j.f0, mod, "mgx_jit_act_x") != hipSuccess) return refuse("no mgx_jit_act_x kernel");
     j.epg = (int)info[2];
     j.mod = mod;
     e->d.gen_prog = (int)info[5];
   } else if (kind == MGX_CODE_WORLD) {
     if (d.act_par) return refuse("the engine runs the lane-per-agent dispatch (MGX_ACT_LEAN), not the kernel this code object replaces");
-    unsigned long long info[8] = {};
-    if (!read_sym("mgx_jit_info", info, sizeof info) || info[0] != 0x4D47584A49545731ull) return refuse("not a world code object");
-    if (info[1] != sizeof(MgxDev) || info[6] != (unsigned long long)MGX_VERSION) return refuse("built against other headers than this libmgx");
-    if (info[4] != e->handler_fp) {
-      char buf[96];
-      snprintf(buf, sizeof buf, " (code object %016llx, engine %016llx)", info[4], e->handler_fp);
-      return refuse(std::string("generated for another program (handler tables differ)") + buf);
-    }
-    if (e->lds_world > 64 * 1024) return refuse("the kernel needs more than 64 KiB of LDS");
+    const std::string why = info_refusal(0x4D47584A49545731ull, "world", e->lds_world, true);
+    if (!why.empty()) return refuse(why);
     hipDeviceptr_t sym = nullptr;
     size_t n = 0;
     if (hipModuleGetGlobal(&sym, &n, mod, "g_mgx_dev") != hipSuccess || n != sizeof(MgxDev)) return refuse("no g_mgx_dev symbol of the right size");
     if (hipModuleGetFunction(&j.f0, mod, e->prog_in_lds ? "mgx_jit_world_pl" : "mgx_jit_world_pg") != hipSuccess)
       return refuse(std::string("no ") + (e->prog_in_lds ? "mgx_jit_world_pl" : "mgx_jit_world_pg") + " kernel");
-    j.dev_sym = sym; j.epg = (int)info[2]; j.threads = (int)info[3]; j.dev_valid = false;
+    j.dev_sym = sym; j.epg = (int)info[2]; j.threads = (int)info[3];
     j.mod = mod;
     e->d.gen_prog = (int)info[5];
   } else {
@@ -1636,8 +1610,7 @@ int mgx_step(mgx_engine* e) {
         mgx_launch_act_fast_s0(e->prog_in_lds, e->lds_act, e->stream, e->d, pw);   // (one constant-memory copy: an opt-in path)
       } else {
         if (e->jit_world.mod) { int jrc = launch_world_jit(e, pw); if (jrc) return jrc; }
-        else if (e->slot == 0) mgx_launch_world_fast_s0(e->prog_in_lds, e->lds_world, e->stream, e->d, pw);
-        else mgx_launch_world_fast_s1(e->prog_in_lds, e->lds_world, e->stream, e->d, pw);
+        else g_world_fast[e->slot].launch(e->prog_in_lds, e->lds_world, e->stream, e->d, pw);
       }
       MGX_MARK(1); MGX_MARK(2); MGX_MARK(3);
     } else if (e->aoe_kernel) {
@@ -2322,9 +2295,5 @@ int64_t mgx_state_bytes(const mgx_engine* e) { return e ? e->state_bytes : 0; }
 }  // extern "C"
 
 #ifdef MGX_WORLD_TIMING  // instrumented developer build only (scripts/world_timing.py); not part of the ABI
-extern "C" void mgx_debug_obs_cycles(unsigned long long* out, int reset) {
-  hipDeviceSynchronize();
-  hipMemcpyFromSymbol(out, HIP_SYMBOL(mgx_dbg_cycles), sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(mgx_dbg_cycles), z, sizeof z); }
-}
+extern "C" void mgx_debug_obs_cycles(unsigned long long* out, int reset) { (void)mgx_read_cycles(&mgx_dbg_cycles, out, reset); }
 #endif

@@ -13,6 +13,7 @@
 #include "mgx_device.h"
 #include "mgx_obs.h"
 #include "mgx_world.h"
+#include "mgx_host.h"   // the kernel units' sizes and host analyses, mgx_pow2_at_least
 #include "mgx_aoe_local.h"
 #include "mgx_presets_gen.h"
 #include "mgx_handlers_fp.h"
@@ -159,11 +160,6 @@ inline std::vector<MgxSources> mgx_class_sources(const int32_t* P) {
 
 // Entries of the observation kernel's LDS token pool: the class-tag prefix + the per-step lists, capped and rounded to 8.
 inline int mgx_pool_tokens(int prefix, long long list_tokens) { return (prefix + (int)std::min<long long>(list_tokens, 16384) + 7) & ~7; }
-inline int mgx_pow2_at_least(int n) {
-  int p = 1;
-  while (p < n) p <<= 1;
-  return p;
-}
 
 struct MgxPlan {
   MgxDev d{};                  // every scalar field and path decision; the pointers are the engine's

@@ -2520,40 +2520,7 @@ __device__ __forceinline__ void mgx_world_entry(const MgxDev& d, int prog_words,
 }  // namespace MGX_TU_NS
 using namespace MGX_TU_NS;
 
-// Host launcher of the non-extended world kernels (defined in mgx_world_fast.hip).
-// (one copy per constant-memory slot: mgx_world_fast.hip is compiled with MGX_SLOT = 0 and 1)
-#define MGX_FAST_SLOTS 2
-size_t mgx_world_fast_lds_bytes(int A);   // dynamic LDS of the unit's kernels without the program copy
-void mgx_launch_world_fast_s0(bool prog_lds, size_t lds, hipStream_t stream, const MgxDev& d, int prog_words);
-void mgx_launch_world_fast_s1(bool prog_lds, size_t lds, hipStream_t stream, const MgxDev& d, int prog_words);
-bool mgx_world_fast_set_lds_s0(size_t lds);  // raises the kernels' dynamic LDS limit (needed past 64 KB)
-bool mgx_world_fast_set_lds_s1(size_t lds);
-// the lane-per-agent action kernels (mgx_act_fast.hip, mgx_act_x.hip; mgx_act.h)
-size_t mgx_act_fast_lds_bytes(int A, int extra);
-int mgx_act_fast_epg();   // envs per workgroup of the unit
-void mgx_launch_act_fast_s0(bool prog_lds, size_t lds, hipStream_t stream, const MgxDev& d, int prog_words);
-bool mgx_act_fast_set_lds_s0(size_t lds);
-void mgx_launch_act_x(bool prog_lds, size_t lds, hipStream_t stream, const MgxDev& d, const MgxDev* dev_copy, int prog_words);
-bool mgx_act_x_set_lds(size_t lds);
-size_t mgx_act_x_lds_bytes(int A, bool aoe_lds, int extra);
-int mgx_act_x_epg();
-// ... and of the extended one (mgx_world_x.hip)
-void mgx_launch_world_x(bool prog_lds, size_t lds, hipStream_t stream, const MgxDev& d, const MgxDev* dev_copy, int prog_words, int phases);
-bool mgx_world_x_set_lds(size_t lds);
-size_t mgx_world_x_lds_bytes(int A, bool aoe_lds);
-size_t mgx_world_x_private_bytes();
-void mgx_launch_values(hipStream_t stream, const MgxDev& d, const MgxDev* dev_copy, int phase, const uint8_t* env_mask);
-// lane-per-agent area effects (mgx_aoe.hip) and the host analysis that allows them
-// (dev_copy: absolute section offsets, for the source-record kernel; hot_copy + prog_words: the copy whose hot sections are
-// relative to the kernel's LDS program copy, or nullptr / 0 when the program stays in HBM / L2)
-void mgx_launch_aoe(hipStream_t stream, const MgxDev& d, const MgxDev* dev_copy, const MgxDev* hot_copy, int prog_words);
-bool mgx_aoe_is_target_local(const int32_t* program);
-bool mgx_aoe_on_tick_local(const int32_t* program);  // + every per-agent on_tick handler is a leaf that only touches its own agent
-bool mgx_aoe_set_lds(int nstat, int prog_words);
-#ifdef __cplusplus
-#include <vector>
-void mgx_aoe_collect_stats(const int32_t* program, bool with_on_tick, bool with_coverage, std::vector<int16_t>& out);
-#endif
+// (the prototypes of the units' host launchers: mgx_host.h)
 
 #ifndef MGX_WORLD_FAST_TU
 // Construction: MettaGrid ctor + _init_grid (mettagrid_c.cpp:42-191, 200-269).  One lane per env scans the class

@@ -29,13 +29,9 @@
 #endif
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <mutex>
-
 #include "mgx_device.h"
 #include "mgx_world.h"
+#include "mgx_host.h"
 
 #ifdef MGX_WORLD_WPE
 #define MGX_WPE_ATTR __attribute__((amdgpu_waves_per_eu(MGX_WORLD_WPE, MGX_WORLD_WPE)))
@@ -53,62 +49,23 @@ __global__ void __launch_bounds__(MGX_WORLD_THREADS) MGX_WPE_ATTR mgx_world_kern
 }
 }  // namespace
 
-// One process-wide maximum per kernel: the attribute is per kernel, not per engine, and must never be lowered under a
-// live engine that needs more.
-static std::mutex g_lds_mutex;
-static size_t g_lds_max_dev[64] = {0};   // the attribute is per kernel AND per device: one maximum for each
+static MgxLdsLimit g_lds_limit;
 bool MGX_CAT(mgx_world_fast_set_lds_s, MGX_SLOT)(size_t lds) {
-  std::lock_guard<std::mutex> lock(g_lds_mutex);
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  size_t& g_lds_max = g_lds_max_dev[dev];
-  if (lds <= g_lds_max) return true;
-  if (hipFuncSetAttribute((const void*)mgx_world_kernel_fast<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-      hipFuncSetAttribute((const void*)mgx_world_kernel_fast<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return false;
-  g_lds_max = lds;
-  return true;
+  return g_lds_limit.raise_current({(const void*)mgx_world_kernel_fast<true>, (const void*)mgx_world_kernel_fast<false>}, lds);
 }
 
 #if MGX_SLOT == 0
 size_t mgx_world_fast_lds_bytes(int A) { return (size_t)mgx_world_lds_fixed(A, false); }
 #endif
 
-// Keeps this slot's g_mgx_dev equal to the launching engine's MgxDev.  A change of content first waits for the kernels
-// that still read the old content (another engine on the same slot, or re-bound buffers).
-static std::mutex g_dev_mutex;
-static MgxDev g_dev_host_dev[16];     // the __constant__ symbol exists once per DEVICE: one host image for each
-static bool g_dev_valid_dev[16] = {false};
-static bool g_thrash_warned = false;
+static MgxConstDev g_const_dev;   // keeps this slot's g_mgx_dev equal to the launching engine's MgxDev
 void MGX_CAT(mgx_launch_world_fast_s, MGX_SLOT)(bool prog_lds, size_t lds, hipStream_t stream, const MgxDev& d, int prog_words) {
-  std::lock_guard<std::mutex> lock(g_dev_mutex);
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-  MgxDev& g_dev_host = g_dev_host_dev[dev];
-  bool& g_dev_valid = g_dev_valid_dev[dev];
-  if (!g_dev_valid || memcmp(&g_dev_host, &d, sizeof(MgxDev)) != 0) {
-    if (g_dev_valid) {
-      (void)hipDeviceSynchronize();
-      if (!g_thrash_warned && getenv("MGX_VERBOSE")) {   // two engines alternating on one slot pay a device-wide wait per step
-        fprintf(stderr, "[mgx] %s: the constant-memory engine table of device %d changed (another engine on the same slot, or re-bound "
-                        "buffers): device synchronised before the upload\n", __func__, dev);
-        g_thrash_warned = true;
-      }
-    }
-    (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_mgx_dev), &d, sizeof(MgxDev), 0, hipMemcpyHostToDevice, stream);
-    memcpy(&g_dev_host, &d, sizeof(MgxDev));
-    g_dev_valid = true;
-  }
+  const auto lock = g_const_dev.upload(&g_mgx_dev, d, stream, __func__);
   dim3 grid((d.E + MGX_WORLD_EPG - 1) / MGX_WORLD_EPG), block(MGX_WORLD_THREADS);
   if (prog_lds) hipLaunchKernelGGL((mgx_world_kernel_fast<true>), grid, block, lds, stream, prog_words);
   else hipLaunchKernelGGL((mgx_world_kernel_fast<false>), grid, block, lds, stream, prog_words);
 }
 
 #if defined(MGX_WORLD_TIMING) && MGX_SLOT == 0  // instrumented developer build only (scripts/world_timing.py); not part of the ABI
-extern "C" int mgx_debug_world_cycles(unsigned long long* out, int reset) {
-  hipDeviceSynchronize();
-  hipMemcpyFromSymbol(out, HIP_SYMBOL(mgx_dbg_cycles), sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(mgx_dbg_cycles), z, sizeof z); }
-  return 0;
-}
+extern "C" int mgx_debug_world_cycles(unsigned long long* out, int reset) { return mgx_read_cycles(&mgx_dbg_cycles, out, reset); }
 #endif

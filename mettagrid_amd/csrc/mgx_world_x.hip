@@ -23,10 +23,9 @@
 #endif
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-
 #include "mgx_device.h"
 #include "mgx_world.h"
+#include "mgx_host.h"
 
 template <bool PROG_LDS>
 __global__ void __launch_bounds__(MGX_WORLD_THREADS) mgx_world_kernel_x(const MgxDev* __restrict__ dp, int prog_words, int phases) {
@@ -84,19 +83,9 @@ void mgx_launch_values(hipStream_t stream, const MgxDev& d, const MgxDev* dp, in
   hipLaunchKernelGGL(mgx_values_kernel, grid, block, 0, stream, dp, phase, env_mask);
 }
 
-static std::mutex g_lds_mutex;
-static size_t g_lds_max_dev[64] = {0};   // the attribute is per kernel AND per device: one maximum for each
-bool mgx_world_x_set_lds(size_t lds) {  // process-wide maximum, only ever raised (the attribute is per kernel)
-  std::lock_guard<std::mutex> lock(g_lds_mutex);
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  size_t& g_lds_max = g_lds_max_dev[dev];
-  if (lds <= g_lds_max) return true;
-  if (hipFuncSetAttribute((const void*)mgx_world_kernel_x<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-      hipFuncSetAttribute((const void*)mgx_world_kernel_x<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return false;
-  g_lds_max = lds;
-  return true;
+static MgxLdsLimit g_lds_limit;
+bool mgx_world_x_set_lds(size_t lds) {
+  return g_lds_limit.raise_current({(const void*)mgx_world_kernel_x<true>, (const void*)mgx_world_kernel_x<false>}, lds);
 }
 
 size_t mgx_world_x_lds_bytes(int A, bool aoe_lds) { return (size_t)mgx_world_lds_fixed(A, true, aoe_lds); }
@@ -116,10 +105,5 @@ void mgx_launch_world_x(bool prog_lds, size_t lds, hipStream_t stream, const Mgx
 }
 
 #ifdef MGX_WORLD_TIMING  // instrumented developer build only (scripts/world_timing_x.py); not part of the ABI
-extern "C" int mgx_debug_world_x_cycles(unsigned long long* out, int reset) {
-  hipDeviceSynchronize();
-  hipMemcpyFromSymbol(out, HIP_SYMBOL(mgx_tu_x::mgx_dbg_cycles), sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(mgx_tu_x::mgx_dbg_cycles), z, sizeof z); }
-  return 0;
-}
+extern "C" int mgx_debug_world_x_cycles(unsigned long long* out, int reset) { return mgx_read_cycles(&mgx_tu_x::mgx_dbg_cycles, out, reset); }
 #endif

@@ -14,6 +14,8 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <mutex>
 
 #define __device__
 #define __host__
@@ -37,7 +39,7 @@ static inline char2 make_char2(signed char a, signed char b) { return char2{a, b
 extern thread_local dim3 threadIdx, blockIdx, blockDim, gridDim;
 
 typedef int hipError_t;
-enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorNotReady = 600 };
+enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorInvalidDevice = 101, hipErrorNotReady = 600 };
 typedef void* hipModule_t;      // run-time code objects are not part of the sanitizer build (mgx_attach_code refuses)
 typedef void* hipFunction_t;
 typedef struct emu_stream* hipStream_t;
@@ -47,7 +49,8 @@ enum { hipFuncAttributeMaxDynamicSharedMemorySize = 8 };
 struct hipFuncAttributes { size_t localSizeBytes = 0; };
 static inline const char* hipGetErrorString(hipError_t) { return "emu"; }
 static inline hipError_t hipSetDevice(int) { return hipSuccess; }
-static inline hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
+inline int emu_current_device = 0;   // what hipGetDevice answers (a test may steer it; the emulated engine never does)
+static inline hipError_t hipGetDevice(int* d) { *d = emu_current_device; return hipSuccess; }
 static inline hipError_t hipGetLastError() { return hipSuccess; }
 static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 static inline hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n ? n : 1); return *p ? hipSuccess : 1; }
@@ -60,6 +63,7 @@ static inline hipError_t hipModuleUnload(hipModule_t) { return hipSuccess; }
 static inline hipError_t hipModuleLaunchKernel(hipFunction_t, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t, void**, void**) { return hipErrorInvalidValue; }
 static inline hipError_t hipLaunchKernel(const void*, dim3, dim3, void**, size_t, hipStream_t) { return hipErrorInvalidValue; }   // (launches go through hipLaunchKernelGGL below)
 template <class T> static inline hipError_t hipMemcpyToSymbolAsync(T& sym, const void* s, size_t n, size_t, int, hipStream_t) { memcpy(&sym, s, n); return hipSuccess; }
+static inline hipError_t hipMemcpyToSymbolAsync(const void* sym, const void* s, size_t n, size_t, int, hipStream_t) { memcpy((void*)sym, s, n); return hipSuccess; }   // (by address: mgx_host.h)
 template <class T> static inline hipError_t hipMemcpyToSymbol(T& sym, const void* s, size_t n) { memcpy(&sym, s, n); return hipSuccess; }
 template <class T> static inline hipError_t hipMemcpyFromSymbol(void* d, T& sym, size_t n) { memcpy(d, &sym, n); return hipSuccess; }
 static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, int) { *s = nullptr; return hipSuccess; }
@@ -74,7 +78,16 @@ static inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuc
 static inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 static inline hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
 static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return hipSuccess; }
-static inline hipError_t hipFuncSetAttribute(const void*, int, int) { return hipSuccess; }
+// the last value set per kernel address, and how many calls there were (tests/cpu_emu/host_header_check.cpp)
+inline std::mutex emu_func_attr_mu;
+inline std::map<const void*, int> emu_func_attr;
+inline long emu_func_attr_calls = 0;
+static inline hipError_t hipFuncSetAttribute(const void* f, int, int v) {
+  std::lock_guard<std::mutex> lock(emu_func_attr_mu);
+  emu_func_attr[f] = v;
+  emu_func_attr_calls++;
+  return hipSuccess;
+}
 static inline hipError_t hipFuncGetAttributes(hipFuncAttributes* a, const void*) { a->localSizeBytes = 0; return hipSuccess; }
 enum { hipEventDisableTiming = 2 };
 

@@ -788,51 +788,76 @@ def scenario(name: str) -> tuple:
     return SCENARIOS[name] if name in SCENARIOS else LIMIT_SCENARIOS[name]
 
 
-def run_parity(name: str, E: int, check_envs, steps: int | None = None) -> dict:
-    """Step ``E`` envs of scenario ``name`` (SCENARIOS or LIMIT_SCENARIOS) on the engine and the oracle with the same
-    seeded actions; after every step the caller-visible buffers of ``check_envs`` must be equal (compare_snapshots), at
-    the end their signature payloads, and no env may report an error bit.  Returns the final stats of check_envs[0]."""
-    from mettagrid_amd.engine import BatchedMettaGrid
-    import oracle_py as op
-    spec_f, map_f, nsteps, invalid = scenario(name)
-    steps = nsteps if steps is None else steps
-    spec = spec_f()
-    maps = [map_f(s) for s in range(E)]
-    prog = compile_scenario(name, spec, *maps[0].shape)
-    cms = np.stack([prog.class_map(m) for m in maps])
-    seeds = np.arange(E, dtype=np.uint32) * 7 + 3
-    eng = BatchedMettaGrid(prog, cms, seeds, buffers="host")
-    try:
-        oracles = {i: op.OracleSim(prog, cms[i], int(seeds[i])) for i in check_envs}
-        for o in oracles.values():
-            o.reinit_buffers()
-        acts = [make_actions(prog, i, steps, invalid) for i in range(E)]
-        A = prog.num_agents
+class ParityRun:
+    """``E`` envs of scenario ``name`` (SCENARIOS or LIMIT_SCENARIOS) on the engine and on the oracle with the same seeded
+    actions, stepped from outside: step() advances both by one step and compares the caller-visible buffers of
+    ``check_envs`` (compare_snapshots; the constructor compares the initial ones), finish() compares their signature
+    payloads, requires that no env reports an error bit and returns the final stats of check_envs[0]."""
 
-        def check(t):
-            snap = eng.snapshot()
-            for i, o in oracles.items():
-                compare_snapshots(o.snapshot(), {k: v[i * A:(i + 1) * A] for k, v in snap.items()}, f"{name} env {i} step {t}")
+    def __init__(self, name: str, E: int, check_envs, steps: int | None = None):
+        from mettagrid_amd.engine import BatchedMettaGrid
+        import oracle_py as op
+        spec_f, map_f, nsteps, invalid = scenario(name)
+        self.name, self.E, self.check_envs, self.t = name, E, check_envs, 0
+        self.steps = nsteps if steps is None else steps
+        maps = [map_f(s) for s in range(E)]
+        self.prog = compile_scenario(name, spec_f(), *maps[0].shape)
+        cms = np.stack([self.prog.class_map(m) for m in maps])
+        self.seeds = np.arange(E, dtype=np.uint32) * 7 + 3
+        self.eng = BatchedMettaGrid(self.prog, cms, self.seeds, buffers="host")
+        try:
+            self.oracles = {i: op.OracleSim(self.prog, cms[i], int(self.seeds[i])) for i in check_envs}
+            for o in self.oracles.values():
+                o.reinit_buffers()
+            self.acts = [make_actions(self.prog, i, self.steps, invalid) for i in range(E)]
+            self.check()
+        except BaseException:
+            self.close()
+            raise
 
-        check(0)
-        for t in range(steps):
-            eng.actions[:] = np.concatenate([acts[i][0][t] for i in range(E)])
-            eng.vibe_actions[:] = np.concatenate([acts[i][1][t] for i in range(E)])
-            eng.step()
-            for i, o in oracles.items():
-                o.step(acts[i][0][t], acts[i][1][t])
-            check(t + 1)
+    def check(self) -> None:
+        A = self.prog.num_agents
+        snap = self.eng.snapshot()
+        for i, o in self.oracles.items():
+            compare_snapshots(o.snapshot(), {k: v[i * A:(i + 1) * A] for k, v in snap.items()}, f"{self.name} env {i} step {self.t}")
+
+    def step(self) -> None:
+        t, acts = self.t, self.acts
+        self.eng.actions[:] = np.concatenate([acts[i][0][t] for i in range(self.E)])
+        self.eng.vibe_actions[:] = np.concatenate([acts[i][1][t] for i in range(self.E)])
+        self.eng.step()
+        for i, o in self.oracles.items():
+            o.step(acts[i][0][t], acts[i][1][t])
+        self.t = t + 1
+        self.check()
+
+    def finish(self) -> dict:
+        eng, prog, name, A = self.eng, self.prog, self.name, self.prog.num_agents
         bits, first = eng.poll_errors()
         assert bits == 0, f"{name}: env error bits {bits} (first env {first})"
         snap = eng.snapshot()
-        for i, o in oracles.items():
+        for i, o in self.oracles.items():
             mine = {k: v[i * A:(i + 1) * A] for k, v in snap.items()}
-            pa = payload_from_raw(prog, o.raw_objects(), o.current_stat_reward(), o.raw_stats(), o.snapshot(), steps, int(seeds[i]))
-            pb = payload_from_raw(prog, eng.raw_objects(i), eng.current_stat_reward(i), eng.raw_stats(i), mine, steps, int(seeds[i]))
+            seed = int(self.seeds[i])
+            pa = payload_from_raw(prog, o.raw_objects(), o.current_stat_reward(), o.raw_stats(), o.snapshot(), self.t, seed)
+            pb = payload_from_raw(prog, eng.raw_objects(i), eng.current_stat_reward(i), eng.raw_stats(i), mine, self.t, seed)
             assert pa == pb, f"{name} env {i}: signature payload differs: {diff_payload(pa, pb)}"
-        return eng.get_episode_stats(check_envs[0])
+        return eng.get_episode_stats(self.check_envs[0])
+
+    def close(self) -> None:
+        self.eng.close()
+
+
+def run_parity(name: str, E: int, check_envs, steps: int | None = None) -> dict:
+    """A whole ParityRun: every step compared, then the signature payloads and the error bits.  Returns the final stats of
+    check_envs[0]."""
+    run = ParityRun(name, E, check_envs, steps)
+    try:
+        for _ in range(run.steps):
+            run.step()
+        return run.finish()
     finally:
-        eng.close()
+        run.close()
 
 
 def create_one(name: str, **compile_kw):
