@@ -97,7 +97,8 @@ int mgx_chain_world(mgx_engine* e, mgx_engine* after);
  * mettagrid_amd/dist.py): the NEXT engine work that writes observations / rewards / terminals / truncations — the
  * observation kernel of the next mgx_step, or an episode restart — first waits for `hip_event` (a hipEvent_t recorded by
  * the caller on any stream of the engine's device).  The world-update kernels of that step are not held back: they do not
- * touch those buffers.  The event must stay alive until that work has been enqueued.  NULL clears a pending wait; a second
+ * touch those buffers.  The tensors of mgx_set_step_stats count as outputs: their kernel runs behind the observation kernel
+ * of its step.  The event must stay alive until that work has been enqueued.  NULL clears a pending wait; a second
  * event given while one is pending does not replace it: the engine's stream waits for the pending one at once.  No
  * reference counterpart: the reference's caller and engine share one thread. */
 int mgx_wait_before_outputs(mgx_engine* e, void* hip_event);
@@ -213,6 +214,32 @@ int mgx_fetch_episode_stats(mgx_engine* e, int32_t wait, double* totals /* [MGX_
 /* Copy the log (all records, oldest first) to host memory and empty it; `records` must hold log_capacity records.
  * *n_dropped: episodes that finished while the log was full since the last drain (they are still in the totals). */
 int mgx_drain_episode_log(mgx_engine* e, uint32_t* records, int32_t max_records, int32_t* n_records, int32_t* n_dropped);
+
+/* ---- Chosen stats of every env and agent after every step (the per-step `infos` of MettaGridPufferEnv.step) ----------------
+ * Reference: MettaGridPufferEnv(step_info_keys=...) (python/src/mettagrid/envs/mettagrid_puffer_env.py:81, 132-183) reads the
+ * chosen game stats, attributes, per-agent stats and the step / episode rewards after every sim.step() and returns them as the
+ * step's info payload (_build_step_info_payload :230-282, step :402-408).  Here the host resolves the keys once into COLUMNS and
+ * a kernel at the end of every mgx_step (csrc/mgx_step_stats.h: one lane per (row, column) pair) writes the columns of all
+ * envs / agents into caller-owned DEVICE memory: game_out f32 [E][n_game] with game_exists u8 [E][n_game] ("the reference's dict
+ * holds the key": touched or != 0, as mgx_get_stats), agent_out f32 [E*A][n_agent] with agent_exists u8 [E*A][n_agent].
+ * game_cols / agent_cols (host memory): stat ids of the program's game / agent tables, or the MGX_SS_* codes of
+ * include/mgx_program.h (ABSENT; agent: REWARD_STEP, REWARD_EPISODE; game: STEPS = current_step, simulator.py's
+ * Simulation.current_step).  n_game == n_agent == 0 switches the readout off: mgx_step then enqueues nothing for it.
+ * The kernel reads engine state only: a stat kept as an integer beside the stat rows (mgx_integer_bookkeeping) is read from
+ * there and converted as the flush converts it, and no flush runs.  It runs behind the episode statistics, so the step that
+ * ends an episode reports that episode's final values and the next step those of the restarted episode, as the reference's
+ * payload does.  The tensors describe the LAST STEP only: after mgx_reset_envs*, mgx_load_envs or mgx_copy_envs they are stale
+ * until the next step.  They are outputs like the bound buffers: mgx_wait_before_outputs covers them.
+ * MGX_ERR_BAD_ARG, before anything is enqueued or changed: an id outside its table (or a code of the other table), more than
+ * MGX_SS_MAX_COLUMNS columns in a table, a null column list or output of a non-empty table, MGX_MEM_HOST buffers.  The
+ * "action.invalid_index.<k>" keys without a stat column (mgx_get_invalid_index_extra) have no column.
+ * Not part of the CPU sanitizer build. */
+int mgx_set_step_stats(mgx_engine* e, const int32_t* game_cols, int32_t n_game, const int32_t* agent_cols, int32_t n_agent,
+                       float* game_out, uint8_t* game_exists, float* agent_out, uint8_t* agent_exists);
+/* What each column was resolved to — MGX_SSK_* of include/mgx_program.h, int32 [n_game + n_agent], game columns first: which
+ * columns read the integer bookkeeping.  The reference's per-key reads are get_game_stat / get_agent_stat
+ * (cpp/bindings/mettagrid_py.cpp:181-197: StatsTracker::get_if_present); it has no such split.  Diagnostic. */
+int mgx_step_stats_columns(mgx_engine* e, int32_t* kinds_out);
 
 /* Forget what the engine knows about the content of the bound observation buffer (enqueued on the engine's stream): the
  * next observation pass rewrites every row it touches in full, 0xFF padding included, as after mgx_set_buffers.  For callers

@@ -52,6 +52,16 @@ enum { MGX_RPL_M_CORE = 1, MGX_RPL_M_INV = 2, MGX_RPL_M_TAGS = 4, MGX_RPL_M_LIMI
 /* per-env recorder state (flags_out of mgx_drain_replay) */
 enum { MGX_RPL_ENV_OVERFLOW = 1 /* a step did not fit since the last drain */, MGX_RPL_ENV_MUTED = 2 /* not logging until the next
        episode */, MGX_RPL_ENV_KEYFRAME_NEXT = 4 /* the next logged step is a keyframe */ };
+/* Per-step stat readout (include/mgx.h mgx_set_step_stats; mettagrid_amd/csrc/mgx_step_stats.h).  A column is a stat id of the
+ * program's game / agent table (>= 0) or one of these codes: ABSENT = a key the program does not hold (value 0, never exists),
+ * REWARD_STEP / REWARD_EPISODE (agent columns) = the bound rewards buffer / the episode rewards, STEPS (game columns) = the
+ * env's current step. */
+enum { MGX_SS_ABSENT = -1, MGX_SS_REWARD_STEP = -2, MGX_SS_REWARD_EPISODE = -3, MGX_SS_STEPS = -4 };
+/* ... and what mgx_set_step_stats resolved it to (mgx_step_stats_columns): COUNTER / COV_* only in an engine that keeps that
+ * stat as an integer (mgx_integer_bookkeeping) */
+enum { MGX_SSK_ABSENT = 0, MGX_SSK_STAT, MGX_SSK_COUNTER, MGX_SSK_COV_UNIQUE, MGX_SSK_COV_MAXDIST, MGX_SSK_REWARD_STEP,
+       MGX_SSK_REWARD_EPISODE, MGX_SSK_STEPS };
+#define MGX_SS_MAX_COLUMNS 64          /* game columns, and agent columns, of one readout */
 #define MGX_MAX_QUERY_DEPTH 3          /* query nesting (the device's eval_query<3> at the top) */
 #define MGX_INVALID_WINDOW 16 /* action.invalid_index.<k> is a fixed stat column for k in [-16,-1] and [n_actions, n_actions+15] */
 #define MGX_INVALID_EXTRA 4   /* ... and one of this many (k, count) pairs per agent and episode for any other k */

@@ -24,6 +24,7 @@
 #include "mgx_env_state.h"  // what an env's state is (the one list of its arrays) and the save / load kernel
 #include "mgx_replay.h"     // change log of the watched envs (mgx_set_replay)
 #include "mgx_mapgen.h"     // the random map builder on the device (mgx_set_map_generator)
+#include "mgx_step_stats.h" // chosen stats of every env / agent read out behind every step (mgx_set_step_stats)
 
 
 // Territory ownership map (TerritoryTracker::compute_cell_ownership, core/territory_tracker.cpp:215-252) of every cell,
@@ -296,6 +297,10 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
   // replays of watched envs (mgx_set_replay; csrc/mgx_replay.h): slot-owned, never part of an env-state record
   MgxRpl rpl{};                     // device pointers of the watch list, log, cursors, recorder state, shadow, static-class bits
   int rpl_n = 0;                    // watched envs (0: the recorder is off and mgx_step enqueues nothing for it)
+  // per-step stat readout (mgx_set_step_stats; csrc/mgx_step_stats.h): the outputs are the caller's, the column table the slot's
+  MgxStepStats ss{};                // the kernel's argument: column table (device), the four output tensors
+  bool ss_on = false;               // (false: mgx_step enqueues nothing for it)
+  int32_t ss_kinds[2 * MGX_SS_MAX_COLUMNS] = {};   // resolved kind of each column, game columns first (mgx_step_stats_columns)
   // device map generator (mgx_set_map_generator; csrc/mgx_mapgen.h): the recipe and the base seeds belong to the slot, never
   // to a saved env state
   MgxMapGen gen{};                  // device pointers into d_gen_recipe + the shape
@@ -597,7 +602,14 @@ static void free_replay(mgx_engine* e) {
   e->rpl_n = 0;
 }
 
-#ifdef MGX_CPU_EMU   // the sanitizer build has no episode statistics, no replay recorder and no map generator
+static void free_step_stats(mgx_engine* e) {
+  if (e->ss.cols) (void)hipFree(const_cast<uint32_t*>(e->ss.cols));
+  e->ss = MgxStepStats{};
+  e->ss_on = false;
+}
+
+#ifdef MGX_CPU_EMU   // the sanitizer build has no episode statistics, no replay recorder, no map generator and no step stats
+static int launch_step_stats(mgx_engine*) { return MGX_OK; }
 static int flush_shadow(mgx_engine*, const int32_t*, const uint32_t*, unsigned) { return MGX_OK; }
 static int launch_episode_stats(mgx_engine*) { return MGX_OK; }
 static int launch_replay(mgx_engine*) { return MGX_OK; }
@@ -644,6 +656,17 @@ static int launch_replay(mgx_engine* e) {
 static int mark_replay(mgx_engine* e, const int32_t* dlist, int n, uint32_t flags) {
   if (!e->rpl_n || n <= 0) return MGX_OK;
   hipLaunchKernelGGL(mgx_replay_mark_kernel, dim3((unsigned)e->rpl_n), dim3(MGX_RPL_THREADS), 0, e->stream, dev_copy(e), e->rpl, dlist, n, flags);
+  HIP_TRY(hipGetLastError());
+  return MGX_OK;
+}
+// The chosen stat columns of every env and agent -> the caller's tensors (csrc/mgx_step_stats.h); nothing without columns.
+// One lane per (row, column) pair, at most 2 048 workgroups walking the pairs grid-stride.
+static int launch_step_stats(mgx_engine* e) {
+  if (!e->ss_on) return MGX_OK;
+  { int frc = consume_out_fence(e); if (frc) return frc; }   // (the step's observation pass has consumed it: a writer of outputs all the same)
+  const long long pairs = (long long)e->d.E * e->d.A * e->ss.KA + (long long)e->d.E * e->ss.KG;
+  const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>((pairs + 255) / 256, 2048));
+  hipLaunchKernelGGL(mgx_step_stats_kernel, dim3(grid), dim3(256), 0, e->stream, dev_copy(e), e->ss);
   HIP_TRY(hipGetLastError());
   return MGX_OK;
 }
@@ -835,6 +858,7 @@ void mgx_destroy(mgx_engine* e) {
   if (e->jit_actx.mod) (void)hipModuleUnload(e->jit_actx.mod);
   free_episode_stats(e);
   free_replay(e);
+  free_step_stats(e);
   for (int i = 0; i <= MGX_T_COUNT; i++) if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
   if (e->world_done) (void)hipEventDestroy(e->world_done);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -1573,6 +1597,90 @@ int mgx_drain_replay(mgx_engine* e, uint32_t* words_out, int32_t* n_words_out, u
   return MGX_OK;
 }
 
+#ifndef MGX_CPU_EMU
+// ---- per-step stat readout (csrc/mgx_step_stats.h) --------------------------------------------------------------------------
+int mgx_set_step_stats(mgx_engine* e, const int32_t* game_cols, int32_t n_game, const int32_t* agent_cols, int32_t n_agent,
+                       float* game_out, uint8_t* game_exists, float* agent_out, uint8_t* agent_exists) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_step_stats: null engine");
+  HIP_TRY(hipSetDevice(e->device));
+  const MgxDev& d = e->d;
+  if (n_game < 0 || n_agent < 0 || n_game > MGX_SS_MAX_COLUMNS || n_agent > MGX_SS_MAX_COLUMNS)
+    return fail(MGX_ERR_BAD_ARG, "mgx_set_step_stats: at most " + std::to_string(MGX_SS_MAX_COLUMNS) + " game and " +
+                                     std::to_string(MGX_SS_MAX_COLUMNS) + " agent columns (got " + std::to_string(n_game) + ", " +
+                                     std::to_string(n_agent) + ")");
+  if (n_game == 0 && n_agent == 0) {   // off: the step enqueues nothing for it any more
+    HIP_TRY(hipStreamSynchronize(e->stream));   // (a kernel in flight still reads the column table)
+    free_step_stats(e);
+    return MGX_OK;
+  }
+  if (e->mem_kind == MGX_MEM_HOST)
+    return fail(MGX_ERR_BAD_ARG, "mgx_set_step_stats: the engine is bound to host buffers (MGX_MEM_HOST); the readout needs device buffers");
+  if ((n_game > 0 && (!game_cols || !game_out || !game_exists)) || (n_agent > 0 && (!agent_cols || !agent_out || !agent_exists)))
+    return fail(MGX_ERR_BAD_ARG, "mgx_set_step_stats: null column list or output of a non-empty table");
+  // resolve every column before anything is touched: a readout that is running keeps running when the call is refused
+  uint32_t cols[2 * MGX_SS_MAX_COLUMNS];
+  int32_t kinds[2 * MGX_SS_MAX_COLUMNS];
+  for (int c = 0; c < n_game; c++) {
+    const int id = game_cols[c];
+    int kind;
+    if (id == MGX_SS_ABSENT) kind = MGX_SSK_ABSENT;
+    else if (id == MGX_SS_STEPS) kind = MGX_SSK_STEPS;
+    else if (id >= 0 && id < d.NG) kind = MGX_SSK_STAT;
+    else return fail(MGX_ERR_BAD_ARG, "mgx_set_step_stats: game column " + std::to_string(c) + ": id " + std::to_string(id) +
+                                          " is neither a game stat id in [0, " + std::to_string(d.NG) + ") nor MGX_SS_ABSENT / MGX_SS_STEPS");
+    kinds[c] = kind;
+    cols[c] = MGX_SS_COL(kind, 0, kind == MGX_SSK_STAT ? id : 0);
+  }
+  // the stats this engine keeps as integers (d.shadow): ids in the order of mgx_shadow_flush_kernel's loop
+  const int cnt_ids[8] = {d.wk[MGX_S_NOOP_SUCCESS], d.wk[MGX_S_NOOP_SUCCESS + 1], d.wk[MGX_S_MOVE_SUCCESS], d.wk[MGX_S_MOVE_SUCCESS + 1],
+                          d.wk[MGX_S_VIBE_SUCCESS], d.wk[MGX_S_VIBE_SUCCESS + 1], d.wk[MGX_S_ACTION_FAILED], d.wk[MGX_S_MAX_STEPS_WITHOUT_MOTION]};
+  for (int c = 0; c < n_agent; c++) {
+    const int id = agent_cols[c];
+    int kind, q = 0;
+    if (id == MGX_SS_ABSENT) kind = MGX_SSK_ABSENT;
+    else if (id == MGX_SS_REWARD_STEP) kind = MGX_SSK_REWARD_STEP;
+    else if (id == MGX_SS_REWARD_EPISODE) kind = MGX_SSK_REWARD_EPISODE;
+    else if (id >= 0 && id < d.NS) {
+      kind = MGX_SSK_STAT;
+      if (d.shadow & 1)
+        for (int k = 0; k < 8; k++)
+          if (cnt_ids[k] == id) { kind = MGX_SSK_COUNTER; q = k; }
+      if (d.shadow & 2) {
+        if (d.wk[MGX_S_CELL_UNIQUE] == id) kind = MGX_SSK_COV_UNIQUE;
+        if (d.wk[MGX_S_CELL_MAXDIST] == id) kind = MGX_SSK_COV_MAXDIST;
+      }
+    } else
+      return fail(MGX_ERR_BAD_ARG, "mgx_set_step_stats: agent column " + std::to_string(c) + ": id " + std::to_string(id) +
+                                       " is neither an agent stat id in [0, " + std::to_string(d.NS) +
+                                       ") nor MGX_SS_ABSENT / MGX_SS_REWARD_STEP / MGX_SS_REWARD_EPISODE");
+    kinds[n_game + c] = kind;
+    cols[n_game + c] = MGX_SS_COL(kind, q, id >= 0 ? id : 0);
+  }
+  if (d.NS > 0xFFFF || d.NG > 0xFFFF) return fail(MGX_ERR_BAD_ARG, "mgx_set_step_stats: stat ids do not fit a column word");
+  uint32_t* dcols = nullptr;
+  HIP_TRY(hipMalloc((void**)&dcols, sizeof(cols)));
+  hipError_t he = hipMemcpyAsync(dcols, cols, (size_t)(n_game + n_agent) * 4, hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);   // `cols` is a local; a kernel in flight still reads the old table
+  if (he != hipSuccess) {
+    (void)hipFree(dcols);
+    return fail(MGX_ERR_HIP, std::string("mgx_set_step_stats: ") + hipGetErrorString(he));
+  }
+  free_step_stats(e);
+  e->ss.KG = n_game; e->ss.KA = n_agent; e->ss.cols = dcols;
+  e->ss.game_out = game_out; e->ss.game_exists = game_exists; e->ss.agent_out = agent_out; e->ss.agent_exists = agent_exists;
+  memcpy(e->ss_kinds, kinds, (size_t)(n_game + n_agent) * sizeof(int32_t));
+  e->ss_on = true;
+  return MGX_OK;
+}
+
+int mgx_step_stats_columns(mgx_engine* e, int32_t* kinds_out) {
+  if (!e || !kinds_out) return fail(MGX_ERR_BAD_ARG, "mgx_step_stats_columns: null argument");
+  if (!e->ss_on) return fail(MGX_ERR_BAD_ARG, "mgx_step_stats_columns: no columns set (mgx_set_step_stats)");
+  memcpy(kinds_out, e->ss_kinds, (size_t)(e->ss.KG + e->ss.KA) * sizeof(int32_t));
+  return MGX_OK;
+}
+#endif  // MGX_CPU_EMU
+
 int mgx_step(mgx_engine* e) {
   if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_step: null engine");
   HIP_TRY(hipSetDevice(e->device));
@@ -1667,6 +1775,7 @@ int mgx_step(mgx_engine* e) {
     if (e->ep_stats) { int erc = launch_episode_stats(e); if (erc) return erc; }
   }
   if (e->rpl_n) { int prc = launch_replay(e); if (prc) return prc; }
+  if (e->ss_on) { int src = launch_step_stats(e); if (src) return src; }   // (behind the episode statistics: a step that ends an episode reports its final values)
   if (e->mem_kind == MGX_MEM_HOST) {
     rc = copy_out(e, 0, (size_t)d.E);
     if (rc) return rc;

@@ -196,6 +196,9 @@ def load_lib():
     L.mgx_set_replay.argtypes = [vp, vp, i32, i32, vp, i32]
     L.mgx_replay_layout.argtypes = [vp, vp]
     L.mgx_drain_replay.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "mgx_set_step_stats"):      # (absent from the CPU sanitizer build)
+        L.mgx_set_step_stats.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp]
+        L.mgx_step_stats_columns.argtypes = [vp, vp]
     if hasattr(L, "mgx_set_map_generator"):   # (absent from the CPU sanitizer build, like the packed rows)
         L.mgx_set_map_generator.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, vp]
         L.mgx_generate_maps.argtypes = [vp, vp, i32, vp, i32]
@@ -634,6 +637,62 @@ class BatchedMettaGrid:
         used, flags = np.zeros(n, np.int32), np.zeros(n, np.uint32)
         _check(self.L.mgx_drain_replay(self.h, raw.ctypes.data, used.ctypes.data, flags.ctypes.data))
         return [raw[i, : used[i]].copy() for i in range(n)], [int(f) for f in flags]
+
+    # ---- chosen stats after every step (include/mgx.h mgx_set_step_stats; csrc/mgx_step_stats.h) ----
+    SSK = ("absent", "stat", "counter", "cov_unique", "cov_maxdist", "reward_step", "reward_episode", "steps")   # MGX_SSK_*
+
+    def step_stat_columns(self, game_keys, agent_keys) -> tuple:
+        """The column codes ``set_step_stats`` hands to the engine: per key the id of the program's game / agent stat table,
+        ``K.SS_ABSENT`` for a name the table does not hold, or the code of a special key (host-only)."""
+        gid = {n: i for i, n in enumerate(self.prog.game_stat_names)}
+        aid = {n: i for i, n in enumerate(self.prog.agent_stat_names)}
+        special_g = {"attributes/steps": K.SS_STEPS}
+        special_a = {"reward_step": K.SS_REWARD_STEP, "reward_episode": K.SS_REWARD_EPISODE}
+        g = [special_g[k] if k in special_g else gid.get(k, K.SS_ABSENT) for k in game_keys]
+        a = [special_a[k] if k in special_a else aid.get(k, K.SS_ABSENT) for k in agent_keys]
+        return np.asarray(g, dtype=np.int32), np.asarray(a, dtype=np.int32)
+
+    def set_step_stats(self, game_keys, agent_keys) -> None:
+        """From the next step on, a kernel behind every step writes the chosen stats of ALL envs and agents into four device
+        tensors (``step_stats``) — what ``MettaGridPufferEnv(step_info_keys=...)`` reads after every ``sim.step()``
+        (mettagrid_puffer_env.py:230-282).  ``game_keys``: names of game stats (``team/<t>/<s>`` keys are the game stats
+        ``<t>/<s>``) or ``"attributes/steps"`` (the env's current step); ``agent_keys``: names of agent stats, ``"reward_step"``
+        or ``"reward_episode"``.  At most 64 of each; two empty lists switch the readout off.  A name the compiled program's
+        stat tables do not hold becomes an absent column (value 0, exists 0): the reference returns None for such a key and
+        omits it.  The one known difference: ``action.invalid_index.<k>`` for k outside the fixed stat columns lives in the
+        extras table (``invalid_index_extra``) and is reported as absent.  The tensors hold the LAST STEP's values: after
+        ``reset_envs*`` / ``load_envs`` / ``copy_envs`` they are stale until the next step.  Device buffers only."""
+        import torch
+        game_keys, agent_keys = [str(k) for k in game_keys], [str(k) for k in agent_keys]
+        if not game_keys and not agent_keys:
+            _check(self.L.mgx_set_step_stats(self.h, None, 0, None, 0, None, None, None, None))
+            self._step_stats, self.step_stat_keys = None, ([], [])
+            return
+        g, a = self.step_stat_columns(game_keys, agent_keys)
+        dev = torch.device("cuda", self.device)
+        rows = self.E * self.A
+        t = (torch.zeros((self.E, g.size), dtype=torch.float32, device=dev), torch.zeros((self.E, g.size), dtype=torch.uint8, device=dev),
+             torch.zeros((rows, a.size), dtype=torch.float32, device=dev), torch.zeros((rows, a.size), dtype=torch.uint8, device=dev))
+        torch.cuda.synchronize(dev)   # (the engine's stream writes them from the next step on)
+        ptr = [x.data_ptr() if x.numel() else None for x in t]
+        _check(self.L.mgx_set_step_stats(self.h, g.ctypes.data if g.size else None, int(g.size), a.ctypes.data if a.size else None,
+                                         int(a.size), *ptr))
+        self._step_stats, self.step_stat_keys = t, (game_keys, agent_keys)   # (the old tensors are released only now)
+
+    @property
+    def step_stats(self):
+        """(game f32 [E, KG], game_exists u8 [E, KG], agent f32 [E*A, KA], agent_exists u8 [E*A, KA]) of the last step, on the
+        device and ordered on the engine's stream (``caller_waits``); None while no keys are set."""
+        return getattr(self, "_step_stats", None)
+
+    def step_stats_columns(self) -> tuple:
+        """What the engine resolved each column to (``SSK`` names; include/mgx.h mgx_step_stats_columns): ``"counter"`` /
+        ``"cov_unique"`` / ``"cov_maxdist"`` columns read the integer bookkeeping.  (game kinds, agent kinds)."""
+        gk, ak = self.step_stat_keys if self.step_stats is not None else ([], [])
+        out = np.zeros(len(gk) + len(ak), np.int32)
+        _check(self.L.mgx_step_stats_columns(self.h, out.ctypes.data))
+        names = [self.SSK[int(v)] for v in out]
+        return names[:len(gk)], names[len(gk):]
 
     @property
     def stream(self) -> int:

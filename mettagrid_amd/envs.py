@@ -114,6 +114,101 @@ def decode_actions_unchecked(a, num_primary: int, vibe_action_ids):
     return core, vibe
 
 
+STEP_INFO_ATTRIBUTES = ("seed", "map_w", "map_h", "steps", "max_steps")
+
+
+def parse_step_info_keys(step_info_keys) -> tuple:
+    """``MettaGridPufferEnv._configure_step_info_keys`` (mettagrid_puffer_env.py:132-183), host-only: the keys sorted into
+    (game keys [(raw key, game stat name)], attribute keys [(raw key, attribute)], agent keys [name]), duplicates dropped in
+    first-seen order, with the reference's ValueErrors.  ``env_`` in front of a game / attributes / team key is dropped;
+    ``team/<t>/<s>`` is the game stat ``<t>/<s>``.  An attribute the reference does not know raises its ValueError
+    (:257-260) here, where the reference raises it from the first payload it builds."""
+    game, attrs, agent = [], [], []
+    for key in step_info_keys or ():
+        key_str = str(key)
+        if key_str.startswith("agent/"):
+            agent_key = key_str[len("agent/"):]
+            if not agent_key:
+                raise ValueError("step_info_keys contains invalid entry 'agent/' (missing key suffix)")
+            agent.append(agent_key)
+            continue
+        raw = key_str[len("env_"):] if key_str.startswith("env_") else key_str
+        if raw.startswith("game/"):
+            stat_key = raw[len("game/"):]
+            if not stat_key:
+                raise ValueError("step_info_keys contains invalid entry 'game/' (missing key suffix)")
+            game.append((raw, stat_key))
+            continue
+        if raw.startswith("attributes/"):
+            attr_key = raw[len("attributes/"):]
+            if not attr_key:
+                raise ValueError("step_info_keys contains invalid entry 'attributes/' (missing key suffix)")
+            if attr_key not in STEP_INFO_ATTRIBUTES:
+                raise ValueError(f"Unsupported step_info_keys attribute {raw!r}. Supported: seed, map_w, map_h, steps, max_steps.")
+            attrs.append((raw, attr_key))
+            continue
+        if raw.startswith("team/"):
+            remainder = raw[len("team/"):]
+            slash = remainder.find("/")
+            if slash <= 0:
+                raise ValueError(f"step_info_keys entry {key_str!r}: expected 'team/{{team}}/{{stat}}'")
+            stat_key = remainder[slash + 1:]
+            if not stat_key:
+                raise ValueError(f"step_info_keys entry {key_str!r}: missing stat key after team name")
+            game.append((raw, f"{remainder[:slash]}/{stat_key}"))
+            continue
+        raise ValueError(f"Unsupported step_info_keys entry {key_str!r}; "
+                         "expected 'game/...', 'attributes/...', 'team/...', or 'agent/...'.")
+    return tuple(dict.fromkeys(game)), tuple(dict.fromkeys(attrs)), tuple(dict.fromkeys(agent))
+
+
+class StepInfo:
+    """What ``MettaGridBatchedEnv.step`` puts under ``infos["step_info"]`` when ``step_info_keys`` are set: the last step's
+    values of the chosen keys for ALL envs, on the device and ordered on the caller's stream like the observations.
+
+    ``game`` f32 [E, KG] / ``game_exists`` u8 [E, KG]: column k is ``game_columns[k]`` (a game stat name, or
+    ``"attributes/steps"``); ``agent`` f32 [E*A, KA] / ``agent_exists`` u8 [E*A, KA]: column k is ``agent_keys[k]``.  A key
+    whose exists flag is 0 is one the reference's payload omits.  ``game_keys`` / ``attribute_keys`` / ``agent_keys`` are the
+    parsed key lists (``parse_step_info_keys``); ``constants`` holds the attributes that never change (map_w, map_h,
+    max_steps; seed: ``seeds`` [E])."""
+
+    def __init__(self, env: "MettaGridBatchedEnv") -> None:
+        self._env = env
+        self.game_keys, self.attribute_keys, self.agent_keys = env._si_keys
+        self.game_columns = env._si_game_columns
+        # (keys that are all host constants need no readout: no tensors)
+        self.game, self.game_exists, self.agent, self.agent_exists = env.engine.step_stats or (None,) * 4
+        words = env.prog.words
+        self.constants = {"map_w": float(words[4]), "map_h": float(words[3]), "max_steps": float(words[11])}
+        self.seeds = env._seeds()
+
+    def payload(self, env: int) -> dict:
+        """The dict ``MettaGridPufferEnv._build_step_info_payload`` (mettagrid_puffer_env.py:230-282) would have returned for
+        env ``env`` after this step, without the episode-end infos it starts from: ``{raw key: float}`` for the game and
+        attribute keys that exist and ``_per_agent_infos`` ``{agent index: {key: float}}`` when agent keys are set.
+        Synchronises with the device: for tests and debugging."""
+        A = self._env.prog.num_agents
+        if self.game is not None:
+            g, ge = self.game[env].cpu().numpy(), self.game_exists[env].cpu().numpy()
+        col = {name: k for k, name in enumerate(self.game_columns)}
+        out = {}
+        for raw, stat in self.game_keys:
+            if ge[col[stat]]:
+                out[raw] = float(g[col[stat]])
+        for raw, attr in self.attribute_keys:
+            if attr == "seed":
+                out[raw] = float(self.seeds[env])
+            elif attr == "steps":
+                out[raw] = float(g[col["attributes/steps"]])
+            else:
+                out[raw] = self.constants[attr]
+        if self.agent_keys:
+            a = self.agent[env * A:(env + 1) * A].cpu().numpy()
+            ae = self.agent_exists[env * A:(env + 1) * A].cpu().numpy()
+            out["_per_agent_infos"] = {i: {k: float(a[i, c]) for c, k in enumerate(self.agent_keys) if ae[i, c]} for i in range(A)}
+        return out
+
+
 class MettaGridBatchedEnv:
     """E envs x A agents behind the PufferEnv call pattern.
 
@@ -154,6 +249,14 @@ class MettaGridBatchedEnv:
     host synchronisation: the aggregate trails the step that produced it by ``stats_interval`` steps), ``{}`` otherwise.
     ``episode_infos()`` returns the finished episodes one by one in the reference's shape from a bounded device log
     (``episode_log`` records; ``log_per_agent`` adds ``per_agent``).
+
+    ``step_info_keys``: the reference's per-step payload (mettagrid_puffer_env.py:81, 132-183, 230-282) — ``game/<stat>``,
+    ``team/<team>/<stat>``, ``attributes/seed|map_w|map_h|steps|max_steps`` (each with an optional ``env_`` prefix),
+    ``agent/<stat>``, ``agent/reward_step``, ``agent/reward_episode``.  A kernel behind every step gathers the chosen values of
+    all envs and agents on the device (``BatchedMettaGrid.set_step_stats``; device buffers only) and ``step`` returns them as
+    ``infos["step_info"]``, a ``StepInfo``: the tensors, the key lists and ``payload(env)``, the reference's dict for one env.
+    A step that ends an episode reports that episode's final values, the next step those of the restarted episode.  ``reset``
+    returns no payload (the tensors are written by steps).  Without keys ``infos`` is what it is without this argument.
     """
 
     def __init__(self, prog: Program, num_envs: int, map_fn: Optional[Callable[[int, int], np.ndarray]] = None,
@@ -163,7 +266,15 @@ class MettaGridBatchedEnv:
                  episode_log: int = 0, log_per_agent: bool = False, specialize="auto", replay_envs=None,
                  replay_dir: Optional[str] = None, replay_words_per_env: Optional[int] = None, replay_interval: int = 64,
                  replay_capacity_groups: Optional[dict] = None, map_gen=None, map_seed: int = 0,
-                 map_seed_stride: int = 1 << 16) -> None:
+                 map_seed_stride: int = 1 << 16, step_info_keys=None) -> None:
+        self._si_keys = parse_step_info_keys(step_info_keys)
+        # the game columns of the readout: the distinct stat names, then the step counter when an attribute key asks for it
+        self._si_game_columns = list(dict.fromkeys(stat for _, stat in self._si_keys[0]))
+        if any(attr == "steps" for _, attr in self._si_keys[1]):
+            self._si_game_columns.append("attributes/steps")
+        self._si_on = any(self._si_keys)
+        if self._si_on and buffers != "device":
+            raise ValueError("step_info_keys needs device buffers")
         if (map_fn is not None) + (map_pool is not None) + (map_gen is not None) != 1:
             raise ValueError("give exactly one of map_fn, map_pool and map_gen")
         self.map_gen = map_gen
@@ -294,6 +405,9 @@ class MettaGridBatchedEnv:
         if self.episode_stats:
             self._eng.set_episode_stats(True, self.episode_log, self.log_per_agent)
         self._steps = 0
+        if self._si_on and (self._si_game_columns or self._si_keys[2]):
+            self._eng.set_step_stats(self._si_game_columns, self._si_keys[2])
+        self._step_info = StepInfo(self) if self._si_on else None   # (one object: the engine rewrites its tensors every step)
         if self.replay_envs:
             from .replay import ReplayAssembler
             import os
@@ -483,6 +597,8 @@ class MettaGridBatchedEnv:
             if self.supervisor is not None:
                 self._compute_supervisor_actions()
         infos = self._step_infos()
+        if self._si_on:
+            infos = dict(infos, step_info=self._step_info)
         if self.replay_envs and self._device_restarts:
             self._replay_steps += 1
             if self._replay_steps % self.replay_interval == 0:
