@@ -167,6 +167,33 @@ int mgx_get_episodes(mgx_engine* e, uint32_t* episodes, int32_t* map_index);
  *   first one).  Slot-owned: after mgx_load_envs / mgx_copy_envs it still names the slot's last map until the next restart. */
 int mgx_set_map_generator(mgx_engine* e, const uint16_t* inner, int32_t n_inner, int32_t border_width, int32_t border_code,
                           const uint16_t* rename, const int32_t* rename_off, int32_t n_teams, const uint32_t* map_seed_base);
+/* mgx_set_map_scene_generator — the second recipe kind: the reference's MapGen with a Random instance scene, the map builder of
+ *   its arena (python/src/mettagrid/builder/envs.py:54-67).  MapGen.build (python/src/mettagrid/mapgen/mapgen.py:167-473) lays
+ *   n_inst rooms of room_height x room_width out in a grid of rows = ceil(sqrt(n_inst)) x cols = ceil(n_inst / rows),
+ *   instance_border_width apart, inside an outer wall of border_width: the program's map must be
+ *   (rows * room_height + (rows - 1) * instance_border_width + 2 * border_width) high and as wide by the same rule.  For
+ *   n_inst > 1 the area between the rooms holds instance_border_code (RoomGrid, mapgen/scenes/room_grid.py:63-76); instance k
+ *   fills room k in row-major order and rooms past n_inst stay empty.  An instance is Random.render
+ *   (mapgen/scenes/random.py:19-69): its n_sym symbols (symbols [n_inst][n_sym] host memory, objects in dict order, then the
+ *   agents: class index + 1, 0xF000 + t = a cell of agent team t; rows differ only under set_team_by_instance) are shuffled,
+ *   then the room's cell indices are shuffled on the same generator, and symbol k lands on index k; n_sym <= room area
+ *   (the reference would cap the objects with another draw, or fail: refused), n_sym = 0 draws nothing.  Generators:
+ *   first_on_root != 0 — instance 0 draws from default_rng(seed) itself (num_agents set: it is pre-rendered, mapgen.py:199-241;
+ *   or a lone instance that is the root scene, mapgen.py:340-368); every other instance k is the k-th child of Generator.spawn
+ *   (mapgen/scene.py:199), PCG64(SeedSequence(seed, spawn_key=(k,))).  border_code / instance_border_code: class index + 1,
+ *   0 = empty.  rename / rename_off as above, the cells of a team counted in row-major order over the WHOLE map
+ *   (rename_map_agents, python/src/mettagrid/config/mettagrid_c_config.py:549-568).  The seed of an episode's map is
+ *   map_seed_base[env] + episodes so far (simulator.py:342-352, 403-409), as above.
+ *   An engine holds ONE recipe: setting either kind replaces the other, mgx_set_map_generator(inner = NULL) switches either
+ *   off, and mgx_generate_maps, mgx_reset_envs_generated, mgx_get_map_seeds, auto-reset, save / load / copy and the
+ *   episode-log convention work with whichever is set.  Validation as above, before anything is touched: class ids, the
+ *   capacity checks on one generated map (every map of a recipe holds the same cells, all symbols are always placed), and the
+ *   LDS need — the map, the index array and the symbols, 2 * (H * W + room area + n_sym) B — against 160 KB (MGX_MAPGEN_LDS_BYTES
+ *   as above). */
+int mgx_set_map_scene_generator(mgx_engine* e, int32_t room_height, int32_t room_width, int32_t n_inst, int32_t rows, int32_t cols,
+                                int32_t border_width, int32_t instance_border_width, int32_t border_code, int32_t instance_border_code,
+                                int32_t first_on_root, const uint16_t* symbols, int32_t n_sym, const uint16_t* rename,
+                                const int32_t* rename_off, int32_t n_teams, const uint32_t* map_seed_base);
 int mgx_generate_maps(mgx_engine* e, const uint32_t* map_seeds, int32_t n, uint16_t* out, int32_t out_is_device);
 int mgx_reset_envs_generated(mgx_engine* e, const uint8_t* env_mask, const uint32_t* map_seeds, const uint32_t* seeds);
 int mgx_get_map_seeds(mgx_engine* e, uint32_t* out);

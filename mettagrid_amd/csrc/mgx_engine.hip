@@ -304,9 +304,11 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
   // device map generator (mgx_set_map_generator; csrc/mgx_mapgen.h): the recipe and the base seeds belong to the slot, never
   // to a saved env state
   MgxMapGen gen{};                  // device pointers into d_gen_recipe + the shape
+  MgxMapScene gen_scene{};          // ... of the scene recipe (gen_is_scene; an engine holds one recipe of either kind)
+  bool gen_is_scene = false;
   bool gen_on = false;              // (false: mgx_step and the restarts enqueue nothing for it)
-  size_t gen_lds = 0;               // dynamic LDS of mgx_mapgen_kernel: the inner array
-  void* d_gen_recipe = nullptr;     // inner | rename | rename_off
+  size_t gen_lds = 0;               // dynamic LDS of mgx_mapgen_kernel: the inner array (scene: map, indices, symbols)
+  void* d_gen_recipe = nullptr;     // inner (scene: symbols) | rename | rename_off
   uint32_t* d_gen_base = nullptr;   // [E] map seed base of each slot
   uint32_t* d_gen_seed = nullptr;   // [E] seed of the map each env's most recent generated restart built
   int32_t* d_objs = nullptr;        // mgx_get_objects_batch: env list | counts | packed records
@@ -1152,21 +1154,107 @@ static void free_map_generator(mgx_engine* e) {
   if (e->d_gen_recipe) (void)hipFree(e->d_gen_recipe);
   e->d_gen_recipe = nullptr;
   e->gen = MgxMapGen{};
+  e->gen_scene = MgxMapScene{};
+  e->gen_is_scene = false;
   e->gen_on = false;
   e->gen_lds = 0;
 }
 static int raise_mapgen_lds(mgx_engine* e, size_t bytes) {
   static MgxLdsLimit limit;
-  return raise_lds(limit, {(const void*)mgx_mapgen_kernel}, e, bytes);
+  return raise_lds(limit, {(const void*)mgx_mapgen_kernel, (const void*)mgx_mapscene_kernel}, e, bytes);
+}
+// The kernel of the recipe that is set: map k of `grid`-strided n (or *n_dev) maps (mgx_mapgen_kernel's arguments).
+static int launch_mapgen(mgx_engine* e, unsigned grid, const uint32_t* seeds, const uint32_t* base, const uint32_t* episodes,
+                         const int32_t* env_list, const uint32_t* n_dev, int n, uint16_t* out, uint32_t* cur_seed) {
+  if (e->gen_is_scene)
+    hipLaunchKernelGGL(mgx_mapscene_kernel, dim3(grid), dim3(MGX_WAVE), e->gen_lds, e->stream, e->gen_scene, seeds, base, episodes, env_list,
+                       n_dev, n, out, cur_seed);
+  else
+    hipLaunchKernelGGL(mgx_mapgen_kernel, dim3(grid), dim3(MGX_WAVE), e->gen_lds, e->stream, e->gen, seeds, base, episodes, env_list, n_dev,
+                       n, out, cur_seed);
+  HIP_TRY(hipGetLastError());
+  return MGX_OK;
 }
 // The listed envs' maps into dmaps (restart_masked): seeds one per list entry, or base[env] + episodes[env].
 static int launch_mapgen_envs(mgx_engine* e, const MgxList& l, const uint32_t* dseeds_packed) {
   if (!e->gen_on || !l.list) return fail(MGX_ERR_BAD_ARG, "map generator: not set (mgx_set_map_generator)");
-  hipLaunchKernelGGL(mgx_mapgen_kernel, dim3(list_grid(e, l, 128, 2048)), dim3(MGX_WAVE), e->gen_lds, e->stream, e->gen, dseeds_packed,
-                     (const uint32_t*)e->d_gen_base, (const uint32_t*)e->d_episodes, l.list, l.n_host >= 0 ? (const uint32_t*)nullptr : l.n,
-                     l.n_host >= 0 ? l.n_host : 0, e->dmaps, e->d_gen_seed);
-  HIP_TRY(hipGetLastError());
+  return launch_mapgen(e, list_grid(e, l, 128, 2048), dseeds_packed, (const uint32_t*)e->d_gen_base, (const uint32_t*)e->d_episodes, l.list,
+                       l.n_host >= 0 ? (const uint32_t*)nullptr : l.n, l.n_host >= 0 ? l.n_host : 0, e->dmaps, e->d_gen_seed);
+}
+
+// What both recipe kinds share once a recipe is accepted: the LDS limit (MGX_MAPGEN_LDS_BYTES test hook), the capacity checks
+// on ONE generated map, the per-slot seed arrays and the upload of `host` (the recipe blob) with the base seeds.  The old
+// recipe is freed only when nothing can fail any more; on return e->d_gen_recipe is the new blob and gen_on is still false.
+static int accept_map_recipe(mgx_engine* e, const char* who, const std::vector<uint16_t>& one, size_t lds, const std::string& lds_what,
+                             const std::vector<uint8_t>& host, const uint32_t* map_seed_base) {
+  const MgxDev& d = e->d;
+  int rc = validate_maps(e, one.data(), 1, nullptr, who);
+  if (rc) return rc;
+  size_t lds_max = MGX_MAPGEN_LDS_MAX;
+  // Test hook: a map of at most 255 x 255 cells needs 127 KB, so no program reaches the real limit; the tests of this refusal
+  // lower it with MGX_MAPGEN_LDS_BYTES (a decimal byte count, only ever lowering).  Anything else in the variable is an error.
+  if (const char* s = getenv("MGX_MAPGEN_LDS_BYTES")) {
+    char* end = nullptr;
+    const unsigned long long v = strtoull(s, &end, 10);
+    if (end == s || *end || *s < '0' || *s > '9')
+      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": MGX_MAPGEN_LDS_BYTES = '" + s + "' is not a decimal byte count");
+    lds_max = std::min<size_t>(lds_max, (size_t)v);
+  }
+  if (lds > lds_max)
+    return fail(MGX_ERR_PROGRAM, std::string(who) + ": " + lds_what + " needs " + std::to_string(lds) +
+                                     " B of LDS, the generator's workgroup has " + std::to_string(lds_max));
+  rc = fit_maps(e, one.data(), 0, 1, nullptr, who);
+  if (rc) return rc;
+  rc = raise_mapgen_lds(e, lds);
+  if (rc) return rc;
+  // accepted: replace the recipe
+  void* blob = nullptr;
+  HIP_TRY(hipMalloc(&blob, host.size()));
+  if (!e->d_gen_base) {
+    rc = e->alloc(&e->d_gen_base, (size_t)d.E);
+    if (!rc) rc = e->alloc(&e->d_gen_seed, (size_t)d.E);
+    if (!rc && !e->d_map_index) {   // the episode counters of auto-reset (shared with the pool)
+      rc = e->alloc(&e->d_map_index, (size_t)d.E);
+      if (!rc) rc = e->alloc(&e->d_episodes, (size_t)d.E);
+    }
+    if (rc) { (void)hipFree(blob); return rc; }
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  free_map_generator(e);
+  e->d_gen_recipe = blob;
+  HIP_TRY(hipMemcpyAsync(blob, host.data(), host.size(), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_gen_base, map_seed_base, (size_t)d.E * 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_gen_seed, map_seed_base, (size_t)d.E * 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));   // `host` is the caller's local
+  e->gen_lds = lds;
   return MGX_OK;
+}
+// rename / rename_off of either recipe kind: shape, ascending offsets, class ids.
+static int check_rename_tables(const mgx_engine* e, const char* who, const uint16_t* rename, const int32_t* rename_off, int32_t n_teams) {
+  const int nc = e->prog[MGX_H_NUM_CLASSES];
+  if (n_teams < 0 || n_teams > MGX_MAPGEN_MAX_TEAMS || (n_teams > 0 && (!rename || !rename_off)) || (n_teams > 0 && rename_off[0] != 0))
+    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": bad rename tables");
+  for (int t = 0; t < n_teams; t++)
+    if (rename_off[t + 1] < rename_off[t]) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": rename offsets must ascend");
+  const int n_rename = n_teams > 0 ? rename_off[n_teams] : 0;
+  for (int k = 0; k < n_rename; k++)
+    if (rename[k] > nc)
+      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": class map holds id " + std::to_string(rename[k]) + " but the program has " +
+                                       std::to_string(nc) + " classes");
+  return MGX_OK;
+}
+// The recipe blob: cells | rename | rename_off, 16-byte aligned parts.
+struct MgxRecipeBlob { std::vector<uint8_t> host; size_t off_rename, off_off; };
+static MgxRecipeBlob pack_map_recipe(const uint16_t* cells, size_t n_cells, const uint16_t* rename, const int32_t* rename_off, int32_t n_teams) {
+  const int n_rename = n_teams > 0 ? rename_off[n_teams] : 0;
+  MgxRecipeBlob b;
+  b.off_rename = (n_cells * 2 + 15) & ~(size_t)15;
+  b.off_off = (b.off_rename + (size_t)n_rename * 2 + 15) & ~(size_t)15;
+  b.host.assign(b.off_off + ((size_t)n_teams + 1) * 4, 0);
+  if (n_cells) memcpy(b.host.data(), cells, n_cells * 2);
+  if (n_rename) memcpy(b.host.data() + b.off_rename, rename, (size_t)n_rename * 2);
+  if (n_teams) memcpy(b.host.data() + b.off_off, rename_off, ((size_t)n_teams + 1) * 4);
+  return b;
 }
 
 int mgx_set_map_generator(mgx_engine* e, const uint16_t* inner, int32_t n_inner, int32_t border_width, int32_t border_code,
@@ -1188,18 +1276,11 @@ int mgx_set_map_generator(mgx_engine* e, const uint16_t* inner, int32_t n_inner,
     return fail(MGX_ERR_BAD_ARG, std::string(who) + ": the inner array must hold (H - 2 * border_width) * (W - 2 * border_width) = " +
                                      std::to_string(ih > 0 && iw > 0 ? ih * iw : 0) + " cells of the program's " + std::to_string(d.H) + " x " +
                                      std::to_string(d.W) + " map, and base seeds must be given");
-  if (n_teams < 0 || n_teams > MGX_MAPGEN_MAX_TEAMS || (n_teams > 0 && (!rename || !rename_off)) || (n_teams > 0 && rename_off[0] != 0))
-    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": bad rename tables");
-  for (int t = 0; t < n_teams; t++)
-    if (rename_off[t + 1] < rename_off[t]) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": rename offsets must ascend");
-  const int n_rename = n_teams > 0 ? rename_off[n_teams] : 0;
+  int rc = check_rename_tables(e, who, rename, rename_off, n_teams);
+  if (rc) return rc;
   if (border_code < 0 || border_code > nc)
     return fail(MGX_ERR_BAD_ARG, std::string(who) + ": class map holds id " + std::to_string(border_code) + " but the program has " +
                                      std::to_string(nc) + " classes");
-  for (int k = 0; k < n_rename; k++)
-    if (rename[k] > nc)
-      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": class map holds id " + std::to_string(rename[k]) + " but the program has " +
-                                       std::to_string(nc) + " classes");
   // ONE generated map stands for all of them: a shuffle keeps the multiset of cells and the renaming hands out the same
   // classes in another order, so the class ids, the AoE / territory source counts and the bound of the observation token
   // pool are the same for every seed.  The unshuffled recipe is such a map.
@@ -1219,58 +1300,92 @@ int mgx_set_map_generator(mgx_engine* e, const uint16_t* inner, int32_t n_inner,
       one[(size_t)(i / iw + border_width) * d.W + (i % iw + border_width)] = v;
     }
   }
-  int rc = validate_maps(e, one.data(), 1, nullptr, who);
-  if (rc) return rc;
-  size_t lds_max = MGX_MAPGEN_LDS_MAX;
-  // Test hook: a map of at most 255 x 255 cells needs 127 KB, so no program reaches the real limit; the tests of this refusal
-  // lower it with MGX_MAPGEN_LDS_BYTES (a decimal byte count, only ever lowering).  Anything else in the variable is an error.
-  if (const char* s = getenv("MGX_MAPGEN_LDS_BYTES")) {
-    char* end = nullptr;
-    const unsigned long long v = strtoull(s, &end, 10);
-    if (end == s || *end || *s < '0' || *s > '9')
-      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": MGX_MAPGEN_LDS_BYTES = '" + s + "' is not a decimal byte count");
-    lds_max = std::min<size_t>(lds_max, (size_t)v);
-  }
   const size_t lds = ((size_t)n_inner * 2 + 15) & ~(size_t)15;
-  if (lds > lds_max)
-    return fail(MGX_ERR_PROGRAM, std::string(who) + ": the inner area of " + std::to_string(n_inner) + " cells needs " + std::to_string(lds) +
-                                     " B of LDS, the generator's workgroup has " + std::to_string(lds_max));
-  rc = fit_maps(e, one.data(), 0, 1, nullptr, who);
+  const MgxRecipeBlob blob_host = pack_map_recipe(inner, (size_t)n_inner, rename, rename_off, n_teams);
+  rc = accept_map_recipe(e, who, one, lds, "the inner area of " + std::to_string(n_inner) + " cells", blob_host.host, map_seed_base);
   if (rc) return rc;
-  rc = raise_mapgen_lds(e, lds);
-  if (rc) return rc;
-  // accepted: replace the recipe
-  const size_t off_rename = ((size_t)n_inner * 2 + 15) & ~(size_t)15, off_off = (off_rename + (size_t)n_rename * 2 + 15) & ~(size_t)15;
-  const size_t total = off_off + ((size_t)n_teams + 1) * 4;
-  std::vector<uint8_t> host(total, 0);
-  memcpy(host.data(), inner, (size_t)n_inner * 2);
-  if (n_rename) memcpy(host.data() + off_rename, rename, (size_t)n_rename * 2);
-  if (n_teams) memcpy(host.data() + off_off, rename_off, ((size_t)n_teams + 1) * 4);
-  void* blob = nullptr;
-  HIP_TRY(hipMalloc(&blob, total));
-  if (!e->d_gen_base) {
-    rc = e->alloc(&e->d_gen_base, (size_t)d.E);
-    if (!rc) rc = e->alloc(&e->d_gen_seed, (size_t)d.E);
-    if (!rc && !e->d_map_index) {   // the episode counters of auto-reset (shared with the pool)
-      rc = e->alloc(&e->d_map_index, (size_t)d.E);
-      if (!rc) rc = e->alloc(&e->d_episodes, (size_t)d.E);
-    }
-    if (rc) { (void)hipFree(blob); return rc; }
-  }
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  free_map_generator(e);
-  e->d_gen_recipe = blob;
-  HIP_TRY(hipMemcpyAsync(blob, host.data(), total, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->d_gen_base, map_seed_base, (size_t)d.E * 4, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->d_gen_seed, map_seed_base, (size_t)d.E * 4, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));   // `host` is a local
+  const uint8_t* blob = (const uint8_t*)e->d_gen_recipe;
+  const size_t off_rename = blob_host.off_rename, off_off = blob_host.off_off;
   MgxMapGen& g = e->gen;
   g.inner = (const uint16_t*)blob;
   g.rename = (const uint16_t*)((const uint8_t*)blob + off_rename);
   g.rename_off = (const int32_t*)((const uint8_t*)blob + off_off);
   g.n_inner = n_inner; g.ih = ih; g.iw = iw; g.border = border_width; g.H = d.H; g.W = d.W; g.n_teams = n_teams;
   g.border_code = (uint32_t)border_code;
-  e->gen_lds = lds;
+  e->gen_on = true;
+  return MGX_OK;
+}
+
+int mgx_set_map_scene_generator(mgx_engine* e, int32_t room_height, int32_t room_width, int32_t n_inst, int32_t rows, int32_t cols,
+                                int32_t border_width, int32_t instance_border_width, int32_t border_code, int32_t instance_border_code,
+                                int32_t first_on_root, const uint16_t* symbols, int32_t n_sym, const uint16_t* rename,
+                                const int32_t* rename_off, int32_t n_teams, const uint32_t* map_seed_base) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_map_scene_generator: null engine");
+  HIP_TRY(hipSetDevice(e->device));
+  const MgxDev& d = e->d;
+  const char* who = "mgx_set_map_scene_generator";
+  const int nc = e->prog[MGX_H_NUM_CLASSES];
+  const int rh = room_height, rw = room_width, b = border_width, ibw = instance_border_width;
+  if (!map_seed_base || rh <= 0 || rw <= 0 || rh > d.H || rw > d.W || b < 0 || ibw < 0 || ibw > 0xFFFF || n_inst < 1 || rows < 1 || cols < 1 || n_sym < 0 ||
+      (n_sym > 0 && !symbols))
+    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": null / negative argument, or base seeds not given");
+  {   // MapGen.prepare_grid (mapgen.py:305-315), in 64 bits
+    int want_rows = 1;
+    while ((long long)want_rows * want_rows < n_inst) want_rows++;
+    const int want_cols = (n_inst + want_rows - 1) / want_rows;
+    const long long wantH = (long long)rows * rh + (long long)(rows - 1) * ibw + 2LL * b, wantW = (long long)cols * rw + (long long)(cols - 1) * ibw + 2LL * b;
+    if (rows != want_rows || cols != want_cols || wantH != d.H || wantW != d.W)
+      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": " + std::to_string(n_inst) + " instances are a grid of " + std::to_string(want_rows) + " x " +
+                                       std::to_string(want_cols) + " rooms, and rooms, instance borders and the outer border must add up to the program's " +
+                                       std::to_string(d.H) + " x " + std::to_string(d.W) + " map (they give " + std::to_string(wantH) + " x " +
+                                       std::to_string(wantW) + ")");
+  }
+  const int area = rh * rw;
+  if (n_sym > area)
+    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": " + std::to_string(n_sym) + " symbols do not fit the " + std::to_string(area) + " cells of a room");
+  int rc = check_rename_tables(e, who, rename, rename_off, n_teams);
+  if (rc) return rc;
+  for (int code : {border_code, instance_border_code})
+    if (code < 0 || code > nc)
+      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": class map holds id " + std::to_string(code) + " but the program has " + std::to_string(nc) +
+                                       " classes");
+  // ONE generated map stands for all of them: every symbol is always placed, so all maps of a recipe hold the same multiset
+  // of cells and the renaming hands out the same classes in another order.  The unshuffled recipe (symbol k of an instance on
+  // cell k of its room) is such a map.
+  std::vector<uint16_t> one((size_t)d.H * d.W, (uint16_t)border_code);
+  const int ph = rh + ibw, pw = rw + ibw;
+  for (int r = 0; r < d.H - 2 * b; r++)
+    for (int c = 0; c < d.W - 2 * b; c++)
+      one[(size_t)(r + b) * d.W + c + b] = (n_inst > 1 && (r % ph >= rh || c % pw >= rw)) ? (uint16_t)instance_border_code : (uint16_t)0;
+  for (int k = 0; k < n_inst; k++)
+    for (int i = 0; i < n_sym; i++)
+      one[(size_t)(b + (k / cols) * ph + i / rw) * d.W + b + (k % cols) * pw + i % rw] = symbols[(size_t)k * n_sym + i];
+  {
+    std::vector<int> seen((size_t)std::max(n_teams, 1), 0);
+    for (uint16_t& v : one) {   // row-major over the whole map
+      if (v < MGX_MAPGEN_TEAM0) continue;
+      const int t = v - MGX_MAPGEN_TEAM0;
+      if (t >= n_teams) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": a symbol names team " + std::to_string(t) + " of " + std::to_string(n_teams));
+      const int k = seen[t]++;
+      if (k >= rename_off[t + 1] - rename_off[t])
+        return fail(MGX_ERR_BAD_ARG, std::string(who) + ": more cells of team " + std::to_string(t) + " than entries in its rename table");
+      v = rename[rename_off[t] + k];
+    }
+  }
+  const size_t lds = MGX_MAPSCENE_LDS_BYTES((size_t)d.H * d.W, area, n_sym);
+  const MgxRecipeBlob blob_host = pack_map_recipe(symbols, (size_t)n_inst * n_sym, rename, rename_off, n_teams);
+  rc = accept_map_recipe(e, who, one, lds, "the map of " + std::to_string(d.H * d.W) + " cells with a room of " + std::to_string(area) + " and " +
+                                               std::to_string(n_sym) + " symbols", blob_host.host, map_seed_base);
+  if (rc) return rc;
+  const uint8_t* blob = (const uint8_t*)e->d_gen_recipe;
+  MgxMapScene& g = e->gen_scene;
+  g.symbols = (const uint16_t*)blob;
+  g.rename = (const uint16_t*)(blob + blob_host.off_rename);
+  g.rename_off = (const int32_t*)(blob + blob_host.off_off);
+  g.n_sym = n_sym; g.rh = rh; g.rw = rw; g.n_inst = n_inst; g.rows = rows; g.cols = cols; g.border = b; g.ibw = ibw; g.H = d.H; g.W = d.W;
+  g.n_teams = n_teams; g.first_on_root = first_on_root ? 1 : 0;
+  g.border_code = (uint32_t)border_code; g.iborder_code = (uint32_t)instance_border_code;
+  e->gen_is_scene = true;
   e->gen_on = true;
   return MGX_OK;
 }
@@ -1285,10 +1400,8 @@ int mgx_generate_maps(mgx_engine* e, const uint32_t* map_seeds, int32_t n, uint1
   uint8_t* st = (uint8_t*)e->d_stage;
   uint16_t* dout = out_is_device ? out : (uint16_t*)(st + seed_bytes);
   HIP_TRY(hipMemcpyAsync(st, map_seeds, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-  hipLaunchKernelGGL(mgx_mapgen_kernel, dim3((unsigned)n), dim3(MGX_WAVE), e->gen_lds, e->stream, e->gen, (const uint32_t*)st,
-                     (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const int32_t*)nullptr, (const uint32_t*)nullptr, (int)n, dout,
-                     (uint32_t*)nullptr);
-  HIP_TRY(hipGetLastError());
+  rc = launch_mapgen(e, (unsigned)n, (const uint32_t*)st, nullptr, nullptr, nullptr, nullptr, (int)n, dout, nullptr);
+  if (rc) return rc;
   if (!out_is_device) HIP_TRY(hipMemcpyAsync(out, dout, (size_t)n * HW * 2, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));   // the caller's seeds were read; host output has landed
   return MGX_OK;

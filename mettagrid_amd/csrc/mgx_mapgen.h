@@ -20,6 +20,24 @@
 // pair of halves straddles one).  Then the agent cells are renamed in row-major order (ballot + popcount carry the running
 // count of a team over 64-cell chunks: the order in which the construction kernel walks cells), and border and inner cells
 // go to the destination map with coalesced stores.  No atomics: one wavefront owns one map.
+//
+// The second recipe kind (mgx_set_map_scene_generator) is the reference's MapGen with a Random instance scene, the map builder
+// of its arena (python/src/mettagrid/builder/envs.py:54-67):
+//   MapGen.build (mapgen/mapgen.py:167-473): n instances in a grid of rows = ceil(sqrt(n)) x cols = ceil(n / rows) rooms of
+//   height x width, instance_border_width apart, inside an outer wall of border_width; for n > 1 a RoomGrid
+//   (mapgen/scenes/room_grid.py:63-76) fills the inner area with instance_border_object and clears the rooms in row-major
+//   order; instance k is rendered into room k, rooms past n stay empty.
+//   Random.render (mapgen/scenes/random.py:19-69): shuffle the symbols (objects in dict order, then the agents), shuffle
+//   arange(height * width) ON THE SAME GENERATOR, place symbol k at index k.  No symbols: no draw.
+//   Generators: the one of default_rng(seed) for an instance rendered by the root (instance 0 when num_agents is set, or a
+//   lone instance), else the k-th child of Generator.spawn = PCG64(SeedSequence(seed, spawn_key=(k,))) (mapgen/scene.py:199):
+//   the one-word entropy padded with zeros to the pool, the key as a fifth word hash-mixed into every pool word after the
+//   4 x 4 mixing (bit_generator.pyx mix_entropy).
+//   rename_map_agents (python/src/mettagrid/config/mettagrid_c_config.py:549-568) counts agent cells over the whole map.
+// One wavefront per map here too, the instances one after another (an instance's chain of area + n_sym draws is serial, and
+// four arena rooms are fewer draws than one rung-4 map): the whole map, the index array and the symbols live in LDS; MgxDraws
+// is the consumer both kernels share, and a second shuffle continues where the first stopped, buffered half included
+// (mettagrid_amd/mapgen.py generated_class_maps restates this kernel for a MapGenSpec).
 #ifndef MGX_MAPGEN_H_
 #define MGX_MAPGEN_H_
 
@@ -37,6 +55,14 @@ struct MgxMapGen {
   uint32_t border_code;
 };
 
+struct MgxMapScene {
+  const uint16_t* symbols;     // [n_inst][n_sym] the unshuffled symbols of each instance: class index + 1, TEAM0 + t
+  const uint16_t* rename;      // as MgxMapGen's; the cells of a team are counted over the whole map
+  const int32_t* rename_off;   // [n_teams + 1]
+  int n_sym, rh, rw, n_inst, rows, cols, border, ibw, H, W, n_teams, first_on_root;
+  uint32_t border_code, iborder_code;   // outer wall; fill between the rooms (n_inst > 1)
+};
+
 #ifndef MGX_CPU_EMU
 struct MgxU128 { unsigned long long hi, lo; };
 __device__ __forceinline__ MgxU128 mgx_mul128(MgxU128 a, MgxU128 b) {   // low 128 bits of the product
@@ -48,8 +74,10 @@ __device__ __forceinline__ MgxU128 mgx_add128(MgxU128 a, MgxU128 b) {
 }
 #define MGX_PCG_MULT (MgxU128{0x2360ED051FC65DA4ull, 0x4385DF649FCCF645ull})
 
-// SeedSequence(seed).generate_state(4, uint64) -> PCG64 state and increment after pcg64_set_seed.
-__device__ __forceinline__ void mgx_pcg64_seed(uint32_t seed, MgxU128& state, MgxU128& inc) {
+// SeedSequence(seed).generate_state(4, uint64) -> PCG64 state and increment after pcg64_set_seed.  KEYED: of
+// SeedSequence(seed, spawn_key=(key,)).
+template <bool KEYED = false>
+__device__ __forceinline__ void mgx_pcg64_seed(uint32_t seed, MgxU128& state, MgxU128& inc, uint32_t key = 0) {
   uint32_t hc = 0x43b0d7e5u;
   auto hashmix = [&](uint32_t v) {
     v ^= hc; hc *= 0x931e8875u; v *= hc;
@@ -68,6 +96,9 @@ __device__ __forceinline__ void mgx_pcg64_seed(uint32_t seed, MgxU128& state, Mg
 #pragma unroll
     for (int d = 0; d < 4; d++)
       if (s != d) pool[d] = mix(pool[d], hashmix(pool[s]));
+  if (KEYED)
+#pragma unroll
+    for (int d = 0; d < 4; d++) pool[d] = mix(pool[d], hashmix(key));
   uint32_t hb = 0x8b51f9ddu, w[8];
 #pragma unroll
   for (int i = 0; i < 8; i++) {
@@ -84,44 +115,48 @@ __device__ __forceinline__ void mgx_pcg64_seed(uint32_t seed, MgxU128& state, Mg
   state = mgx_add128(mgx_mul128(s, MGX_PCG_MULT), inc);
 }
 
-// One map: seed -> shuffled, renamed inner cells in `a` (LDS, n_inner u16) -> dst [H][W].  Called by all 64 lanes.
-__device__ __forceinline__ void mgx_mapgen_one(const MgxMapGen& g, uint32_t seed, MgxU128 mulA, MgxU128 mulG, uint16_t* a,
-                                               uint16_t* __restrict__ dst) {
-  const int lane = threadIdx.x;
-  const int n = g.n_inner;
-  for (int i = lane; i < n; i += MGX_WAVE) a[i] = g.inner[i];
+// The draw consumer: a PCG64 stream handed out in rounds of 64 outputs = 128 halves (lane l computes output l of the round
+// from M^(l+1) and G_(l+1)), walked in order with wavefront-uniform control flow.  p: the next half of the round, 128 = used
+// up (a fresh stream starts there: nothing is buffered).
+struct MgxDraws {
   MgxU128 base, inc;
-  mgx_pcg64_seed(seed, base, inc);
-  __syncthreads();
   uint32_t out_lo = 0, out_hi = 0;
-  int p = 2 * MGX_WAVE;   // next half of the round; 128 = used up
-  for (int i = n - 1; i >= 1; i--) {
-    const uint32_t mask = 0xFFFFFFFFu >> __builtin_clz((unsigned)i);
-    uint32_t j;
-    do {
-      if (p == 2 * MGX_WAVE) {   // a round: lane l -> output l of the next 64
-        const MgxU128 s = mgx_add128(mgx_mul128(mulA, base), mgx_mul128(mulG, inc));
-        const unsigned long long x = s.hi ^ s.lo;
-        const unsigned rot = (unsigned)(s.hi >> 58);
-        const unsigned long long o = (x >> rot) | (x << ((64u - rot) & 63u));
-        out_lo = (uint32_t)o; out_hi = (uint32_t)(o >> 32);
-        base.lo = ((unsigned long long)__builtin_amdgcn_readlane((int)(uint32_t)(s.lo >> 32), MGX_WAVE - 1) << 32) |
-                  (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)s.lo, MGX_WAVE - 1);
-        base.hi = ((unsigned long long)__builtin_amdgcn_readlane((int)(uint32_t)(s.hi >> 32), MGX_WAVE - 1) << 32) |
-                  (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)s.hi, MGX_WAVE - 1);
-        p = 0;
-      }
-      const uint32_t h = (uint32_t)((p & 1) ? __builtin_amdgcn_readlane((int)out_hi, p >> 1) : __builtin_amdgcn_readlane((int)out_lo, p >> 1));
-      p++;
-      j = h & mask;
-    } while (j > (uint32_t)i);
-    const uint16_t ai = a[i], aj = a[j];   // (every lane the same addresses: broadcast reads, same-value writes)
-    a[i] = aj; a[j] = ai;
+  int p = 2 * MGX_WAVE;
+  // next_uint32: the low half of a 64-bit output, then its high half
+  __device__ __forceinline__ uint32_t half(const MgxU128& mulA, const MgxU128& mulG) {
+    if (p == 2 * MGX_WAVE) {   // a round: lane l -> output l of the next 64
+      const MgxU128 s = mgx_add128(mgx_mul128(mulA, base), mgx_mul128(mulG, inc));
+      const unsigned long long x = s.hi ^ s.lo;
+      const unsigned rot = (unsigned)(s.hi >> 58);
+      const unsigned long long o = (x >> rot) | (x << ((64u - rot) & 63u));
+      out_lo = (uint32_t)o; out_hi = (uint32_t)(o >> 32);
+      base.lo = ((unsigned long long)__builtin_amdgcn_readlane((int)(uint32_t)(s.lo >> 32), MGX_WAVE - 1) << 32) |
+                (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)s.lo, MGX_WAVE - 1);
+      base.hi = ((unsigned long long)__builtin_amdgcn_readlane((int)(uint32_t)(s.hi >> 32), MGX_WAVE - 1) << 32) |
+                (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)s.hi, MGX_WAVE - 1);
+      p = 0;
+    }
+    const uint32_t h = (uint32_t)((p & 1) ? __builtin_amdgcn_readlane((int)out_hi, p >> 1) : __builtin_amdgcn_readlane((int)out_lo, p >> 1));
+    p++;
+    return h;
   }
-  __syncthreads();
-  // rename: the k-th cell of team t in row-major order becomes rename[rename_off[t] + k]
-  for (int t = 0; t < g.n_teams; t++) {
-    const int off = g.rename_off[t], len = g.rename_off[t + 1] - off;
+  // Generator.shuffle of a [n] in LDS: i = n-1 .. 1, j = random_interval(i) by masked rejection, swap a[i], a[j]
+  __device__ __forceinline__ void shuffle(uint16_t* a, int n, const MgxU128& mulA, const MgxU128& mulG) {
+    for (int i = n - 1; i >= 1; i--) {
+      const uint32_t mask = 0xFFFFFFFFu >> __builtin_clz((unsigned)i);
+      uint32_t j;
+      do j = half(mulA, mulG) & mask; while (j > (uint32_t)i);
+      const uint16_t ai = a[i], aj = a[j];   // (every lane the same addresses: broadcast reads, same-value writes)
+      a[i] = aj; a[j] = ai;
+    }
+  }
+};
+
+// The k-th cell of team t in row-major order over a [n] becomes rename[rename_off[t] + k] (ballot + popcount carry the count).
+__device__ __forceinline__ void mgx_mapgen_rename(uint16_t* a, int n, const uint16_t* rename, const int32_t* rename_off, int n_teams) {
+  const int lane = threadIdx.x;
+  for (int t = 0; t < n_teams; t++) {
+    const int off = rename_off[t], len = rename_off[t + 1] - off;
     const uint32_t code = MGX_MAPGEN_TEAM0 + (uint32_t)t;
     int seen = 0;
     for (int c0 = 0; c0 < n; c0 += MGX_WAVE) {
@@ -129,10 +164,24 @@ __device__ __forceinline__ void mgx_mapgen_one(const MgxMapGen& g, uint32_t seed
       const bool is = i < n && a[i] == code;
       const unsigned long long b = __ballot(is);
       const int k = seen + __popcll(b & ((1ull << lane) - 1ull));
-      if (is && k < len) a[i] = g.rename[off + k];
+      if (is && k < len) a[i] = rename[off + k];
       seen += __popcll(b);
     }
   }
+}
+
+// One map: seed -> shuffled, renamed inner cells in `a` (LDS, n_inner u16) -> dst [H][W].  Called by all 64 lanes.
+__device__ __forceinline__ void mgx_mapgen_one(const MgxMapGen& g, uint32_t seed, MgxU128 mulA, MgxU128 mulG, uint16_t* a,
+                                               uint16_t* __restrict__ dst) {
+  const int lane = threadIdx.x;
+  const int n = g.n_inner;
+  for (int i = lane; i < n; i += MGX_WAVE) a[i] = g.inner[i];
+  MgxDraws d;
+  mgx_pcg64_seed(seed, d.base, d.inc);
+  __syncthreads();
+  d.shuffle(a, n, mulA, mulG);
+  __syncthreads();
+  mgx_mapgen_rename(a, n, g.rename, g.rename_off, g.n_teams);
   __syncthreads();
   const int HW = g.H * g.W;
   for (int i = lane; i < HW; i += MGX_WAVE) {
@@ -141,6 +190,17 @@ __device__ __forceinline__ void mgx_mapgen_one(const MgxMapGen& g, uint32_t seed
     dst[i] = in ? a[r * g.iw + c] : (uint16_t)g.border_code;
   }
   __syncthreads();   // (the next map of this wavefront refills `a`)
+}
+
+// lane l: M^(l+1) and G_(l+1) = 1 + M + ... + M^l
+__device__ __forceinline__ void mgx_mapgen_multipliers(MgxU128& mulA, MgxU128& mulG) {
+  const int lane = threadIdx.x;
+  mulA = {0, 1}; mulG = {0, 0};
+  for (int k = 0; k < MGX_WAVE; k++)
+    if (k <= lane) {
+      mulG = mgx_add128(mgx_mul128(mulG, MGX_PCG_MULT), MgxU128{0, 1});
+      mulA = mgx_mul128(mulA, MGX_PCG_MULT);
+    }
 }
 
 // Map k of the launch: seed = seeds[k] when given, else base[env] + episodes[env] (mod 2^32); destination out + k * H * W
@@ -152,13 +212,8 @@ __global__ void __launch_bounds__(MGX_WAVE) mgx_mapgen_kernel(MgxMapGen g, const
                                                               uint32_t* __restrict__ cur_seed) {
   extern __shared__ uint16_t mgx_mapgen_lds[];
   const int lane = threadIdx.x;
-  // lane l: M^(l+1) and G_(l+1) = 1 + M + ... + M^l
-  MgxU128 mulA{0, 1}, mulG{0, 0};
-  for (int k = 0; k < MGX_WAVE; k++)
-    if (k <= lane) {
-      mulG = mgx_add128(mgx_mul128(mulG, MGX_PCG_MULT), MgxU128{0, 1});
-      mulA = mgx_mul128(mulA, MGX_PCG_MULT);
-    }
+  MgxU128 mulA, mulG;
+  mgx_mapgen_multipliers(mulA, mulG);
   const int count = n_dev ? (int)*n_dev : n;
   const size_t HW = (size_t)g.H * g.W;
   for (int k = blockIdx.x; k < count; k += gridDim.x) {
@@ -166,6 +221,68 @@ __global__ void __launch_bounds__(MGX_WAVE) mgx_mapgen_kernel(MgxMapGen g, const
     const uint32_t seed = seeds ? seeds[k] : base[env] + episodes[env];
     if (cur_seed && lane == 0) cur_seed[env] = seed;
     mgx_mapgen_one(g, seed, mulA, mulG, mgx_mapgen_lds, out + (size_t)env * HW);
+  }
+}
+
+// LDS of the scene kernel: the map [H * W], the index array [rh * rw], the symbols [n_sym], u16 each.
+#define MGX_MAPSCENE_LDS_BYTES(HW, area, n_sym) ((((size_t)(HW) + (size_t)(area) + (size_t)(n_sym)) * 2 + 15) & ~(size_t)15)
+
+// One map of the scene recipe: border, fill and empty rooms in `map` (LDS, H * W u16), then per instance the two shuffles on
+// one stream and the scatter into its room, then the rename over the whole map -> dst [H][W].  Called by all 64 lanes.
+__device__ __forceinline__ void mgx_mapscene_one(const MgxMapScene& g, uint32_t seed, MgxU128 mulA, MgxU128 mulG, uint16_t* map,
+                                                 uint16_t* __restrict__ dst) {
+  const int lane = threadIdx.x;
+  const int HW = g.H * g.W, area = g.rh * g.rw, n_sym = g.n_sym;
+  uint16_t* idx = map + HW;
+  uint16_t* sym = idx + area;
+  const int ph = g.rh + g.ibw, pw = g.rw + g.ibw;   // room pitch
+  const int inh = g.H - 2 * g.border, inw = g.W - 2 * g.border;
+  for (int i = lane; i < HW; i += MGX_WAVE) {
+    const int r = i / g.W - g.border, c = i % g.W - g.border;
+    uint32_t v = g.border_code;
+    if (r >= 0 && r < inh && c >= 0 && c < inw) v = (g.n_inst > 1 && (r % ph >= g.rh || c % pw >= g.rw)) ? g.iborder_code : 0u;
+    map[i] = (uint16_t)v;
+  }
+  for (int k = 0; k < g.n_inst && n_sym > 0; k++) {
+    __syncthreads();   // (the map is filled / the scatter of the instance before has read idx and sym)
+    for (int i = lane; i < n_sym; i += MGX_WAVE) sym[i] = g.symbols[(size_t)k * n_sym + i];
+    for (int i = lane; i < area; i += MGX_WAVE) idx[i] = (uint16_t)i;
+    MgxDraws d;
+    if (k == 0 && g.first_on_root) mgx_pcg64_seed<false>(seed, d.base, d.inc);
+    else mgx_pcg64_seed<true>(seed, d.base, d.inc, (uint32_t)k);
+    __syncthreads();
+    d.shuffle(sym, n_sym, mulA, mulG);
+    d.shuffle(idx, area, mulA, mulG);
+    __syncthreads();
+    const int y0 = g.border + (k / g.cols) * ph, x0 = g.border + (k % g.cols) * pw;
+    for (int t = lane; t < n_sym; t += MGX_WAVE) {   // (distinct targets: idx is a permutation, n_sym <= area)
+      const int v = idx[t];
+      map[(y0 + v / g.rw) * g.W + x0 + v % g.rw] = sym[t];
+    }
+  }
+  __syncthreads();
+  mgx_mapgen_rename(map, HW, g.rename, g.rename_off, g.n_teams);
+  __syncthreads();
+  for (int i = lane; i < HW; i += MGX_WAVE) dst[i] = map[i];
+  __syncthreads();   // (the next map of this wavefront refills `map`)
+}
+
+// mgx_mapgen_kernel for the scene recipe: the same launch arguments.
+__global__ void __launch_bounds__(MGX_WAVE) mgx_mapscene_kernel(MgxMapScene g, const uint32_t* __restrict__ seeds, const uint32_t* __restrict__ base,
+                                                                const uint32_t* __restrict__ episodes, const int32_t* __restrict__ env_list,
+                                                                const uint32_t* __restrict__ n_dev, int n, uint16_t* __restrict__ out,
+                                                                uint32_t* __restrict__ cur_seed) {
+  extern __shared__ uint16_t mgx_mapgen_lds[];
+  const int lane = threadIdx.x;
+  MgxU128 mulA, mulG;
+  mgx_mapgen_multipliers(mulA, mulG);
+  const int count = n_dev ? (int)*n_dev : n;
+  const size_t HW = (size_t)g.H * g.W;
+  for (int k = blockIdx.x; k < count; k += gridDim.x) {
+    const int env = env_list ? env_list[k] : k;
+    const uint32_t seed = seeds ? seeds[k] : base[env] + episodes[env];
+    if (cur_seed && lane == 0) cur_seed[env] = seed;
+    mgx_mapscene_one(g, seed, mulA, mulG, mgx_mapgen_lds, out + (size_t)env * HW);
   }
 }
 #endif  // MGX_CPU_EMU

@@ -10,8 +10,11 @@ against numpy itself.
 import numpy as np
 M32 = np.uint64(0xFFFFFFFF)
 def _u32(x): return x & M32
-def seedseq_pool(seeds):
-    """SeedSequence(int seed < 2**32).pool for many seeds at once (numpy/random/bit_generator.pyx)."""
+def seedseq_pool(seeds, key=None):
+    """SeedSequence(int seed < 2**32).pool for many seeds at once (numpy/random/bit_generator.pyx).  ``key`` (an int <
+    2**32): the pool of ``SeedSequence(seed, spawn_key=(key,))``, the key-th child of ``spawn`` — the one-word entropy is
+    padded with zeros to the pool size, the key is the fifth word, and mix_entropy hash-mixes every word past the pool into
+    each pool word after the 4 x 4 mixing."""
     n = len(seeds)
     INIT_A, MULT_A = 0x43b0d7e5, 0x931e8875
     MIX_L, MIX_R = np.uint64(0xca01f9dd), np.uint64(0x4973f715)
@@ -30,6 +33,10 @@ def seedseq_pool(seeds):
         for d in range(4):
             if s != d:
                 pool[d] = mix(pool[d], hashmix(pool[s]))
+    if key is not None:
+        word = np.full(n, int(key), np.uint64)
+        for d in range(4):
+            pool[d] = mix(pool[d], hashmix(word))
     return pool
 def generate_state8(pool):
     INIT_B, MULT_B = 0x8b51f9dd, 0x58f38ded

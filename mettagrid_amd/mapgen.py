@@ -187,66 +187,314 @@ class RandomMapSpec:
         return LoweredMap(H, W, b, border, inner, np.array(rename, dtype=np.uint16), np.array(rename_off, dtype=np.int32))
 
 
-def shuffled_rows(base: np.ndarray, seeds) -> np.ndarray:
-    """``[default_rng(int(s)).shuffle(copy of base) for s in seeds]`` for a 1-d array, vectorised over the seeds:
-    ``SeedSequence`` and PCG64 from early_reset, then ``Generator.shuffle`` — for i = n-1 .. 1: j = random_interval(i), swap
-    a[i], a[j] — with random_interval's masked rejection on buffered 32-bit halves (low half of each 64-bit output first)."""
-    from . import early_reset as er
-    seeds = np.asarray(seeds, dtype=np.uint64).reshape(-1)
-    S, n = len(seeds), len(base)
-    out = np.tile(np.asarray(base), (S, 1))
-    if n < 2 or S == 0:
-        return out
-    u64 = np.uint64
-    with np.errstate(over="ignore"):
-        w = er.generate_state8(er.seedseq_pool(seeds))
-        v = [w[2 * i] | (w[2 * i + 1] << u64(32)) for i in range(4)]
-        ih = (v[2] << u64(1)) | (v[3] >> u64(63)); il = (v[3] << u64(1)) | u64(1)
-        sh, sl = er.step(np.zeros(S, u64), np.zeros(S, u64), ih, il)
-        sh, sl = er.add128(sh, sl, v[0], v[1])
-        sh, sl = er.step(sh, sl, ih, il)
-        have_hi = np.zeros(S, bool)          # the high half of the last output is still buffered
-        hi_half = np.zeros(S, u64)
+class LoweredScene:
+    """What ``MapGenSpec.lower`` makes: the arguments of ``mgx_set_map_scene_generator``."""
+
+    def __init__(self, height, width, room_height, room_width, n_inst, rows, cols, border_width, instance_border_width, border_code,
+                 instance_border_code, first_on_root, symbols, rename, rename_off):
+        self.height, self.width, self.room_height, self.room_width = height, width, room_height, room_width
+        self.n_inst, self.rows, self.cols = n_inst, rows, cols
+        self.border_width, self.instance_border_width = border_width, instance_border_width
+        self.border_code, self.instance_border_code = border_code, instance_border_code   # class index + 1, 0 = empty
+        self.first_on_root = first_on_root   # instance 0 draws from default_rng(seed) itself, not from spawn key (0,)
+        self.symbols = symbols               # uint16 [n_inst][n_sym]: class index + 1 in the reference's order, TEAM0 + t
+        self.rename, self.rename_off = rename, rename_off   # as LoweredMap's; cells are counted over the whole map
+
+    @property
+    def n_sym(self) -> int:
+        return self.symbols.shape[1]
+
+    @property
+    def n_teams(self) -> int:
+        return len(self.rename_off) - 1
+
+
+class MapGenSpec:
+    """The reference's ``MapGen.Config`` (mapgen/mapgen.py:22-153) with a ``Random.Config`` instance scene
+    (mapgen/scenes/random.py:6-9) without its seed: ``instances`` rooms of ``height`` x ``width`` in a room grid, each filled by
+    the Random scene from a generator of its own, inside an outer wall.  ``make_arena`` (builder/envs.py:54-67) builds its
+    maps with this."""
+
+    def __init__(self, width: int, height: int, objects: dict, agents: dict | int, num_agents: int | None = None,
+                 instances: int | None = None, border_width: int = 5, instance_border_width: int = 5,
+                 instance_border_object: str = "wall", set_team_by_instance: bool = False) -> None:
+        self.width, self.height, self.objects, self.agents = int(width), int(height), dict(objects), agents
+        self.num_agents, self.instances = num_agents, instances
+        self.border_width, self.instance_border_width = int(border_width), int(instance_border_width)
+        self.instance_border_object, self.set_team_by_instance = instance_border_object, bool(set_team_by_instance)
+        per = agents if isinstance(agents, int) else sum(agents.values())
+        if self.width <= 0 or self.height <= 0 or self.border_width < 0 or self.instance_border_width < 0:
+            raise ValueError("MapGenSpec: rooms need a positive width and height, borders a width >= 0")
+        if instances is not None and instances < 1:
+            raise ValueError("MapGenSpec: instances must be >= 1")
+        # what the reference cannot build either is kept as a refusal: the spec has a shape, lower() and random_map() raise
+        self.refusal = None
+        n = instances
+        if num_agents:   # mapgen.py:280-296
+            if per <= 0 or num_agents % per:
+                self.refusal = f"MapGenSpec: num_agents {num_agents} is not divisible by the {per} agents of one instance"
+            n = max(1, num_agents // per) if per > 0 else (instances or 1)
+            if instances and instances != n and not self.refusal:
+                self.refusal = f"MapGenSpec: num_agents gives {n} instances, instances asks for {instances}"
+        self.instances_count = n = 1 if n is None else int(n)
+        # instance 0 is pre-rendered on the builder's own generator when num_agents is set (mapgen.py:199-241); otherwise a
+        # lone instance is the root scene on that generator (mapgen.py:340-368) unless set_team_by_instance wraps it in a Nop
+        # scene, whose child it then is (mapgen.py:434-449), and every room of a room grid is a child scene.
+        self.first_on_root = bool(num_agents) or (n == 1 and not self.set_team_by_instance)
+        if self.border_width == 0 and n == 1 and not num_agents and not self.refusal:
+            # mapgen.py:323-326 with a border of 0 turns the whole grid to wall ([-0:] is everything); a pre-rendered instance
+            # or a room grid overwrites that, a lone scene finds no empty cell and fails on its assignment (random.py:67)
+            self.refusal = "MapGenSpec: border_width 0 with one instance and no num_agents (the reference cannot build this map)"
+        self.rows = int(np.ceil(np.sqrt(n)))             # mapgen.py:305-315
+        self.cols = int(np.ceil(n / self.rows))
+        self.map_width = self.width * self.cols + (self.cols - 1) * self.instance_border_width + 2 * self.border_width
+        self.map_height = self.height * self.rows + (self.rows - 1) * self.instance_border_width + 2 * self.border_width
+
+    def room_origin(self, k: int) -> tuple:
+        """(y, x) of room k in the map (scenes/room_grid.py:71-76, row-major)."""
+        return (self.border_width + (k // self.cols) * (self.height + self.instance_border_width),
+                self.border_width + (k % self.cols) * (self.width + self.instance_border_width))
+
+    def instance_symbols(self, k: int) -> list:
+        """The Random scene's symbols for instance k before its shuffle (random.py:22-49)."""
+        if isinstance(self.agents, int):
+            agent_syms = [f"agent.team_{k}" if self.set_team_by_instance else "agent.agent"] * self.agents
+        else:
+            agent_syms = ["agent." + str(name) for name, c in self.agents.items() for _ in range(c)]
+        return [name for name, c in self.objects.items() for _ in range(c)] + agent_syms
+
+    def _generator(self, seed: int, k: int) -> np.random.Generator:
+        if k == 0 and self.first_on_root:
+            return np.random.default_rng(int(seed))
+        return np.random.Generator(np.random.PCG64(np.random.SeedSequence(int(seed), spawn_key=(k,))))
+
+    def random_map(self, seed: int) -> np.ndarray:
+        """``MapGen(config with this seed).build().grid`` with numpy's own generators."""
+        if self.refusal:
+            raise ValueError(self.refusal)
+        H, W, b = self.map_height, self.map_width, self.border_width
+        grid = np.full((H, W), "wall", dtype="<U50")
+        grid[b:H - b, b:W - b] = self.instance_border_object if self.instances_count > 1 else "empty"
+        area = self.height * self.width
+        for k in range(self.rows * self.cols):
+            y, x = self.room_origin(k)
+            room = np.full(area, "empty", dtype="<U50")
+            sym = self.instance_symbols(k) if k < self.instances_count else []
+            if len(sym) > area:
+                raise ValueError(f"MapGenSpec: {len(sym)} symbols do not fit the {area} cells of a room")
+            if sym:
+                rng = self._generator(seed, k)
+                sym = np.array(sym).astype(str)
+                rng.shuffle(sym)
+                idx = np.arange(area)
+                rng.shuffle(idx)
+                room[idx[:len(sym)]] = sym
+            grid[y:y + self.height, x:x + self.width] = room.reshape(self.height, self.width)
+        return grid
+
+    def lower(self, prog) -> LoweredScene:
+        """The seed-independent half of ``MapGen.build``: per instance the unshuffled symbols as codes, the rename tables
+        (``prog.agent_rename``; names of one agent group share a table, as they share a counter in ``prog.class_map``), the
+        room grid and the two border codes."""
+        if self.refusal:
+            raise ValueError(self.refusal)
+        H, W = self.map_height, self.map_width
+        if (H, W) != (int(prog.words[3]), int(prog.words[4])):
+            raise ValueError(f"MapGenSpec is {H} x {W} but the program's map is {int(prog.words[3])} x {int(prog.words[4])}")
+        area, n = self.height * self.width, self.instances_count
+        rename: list = []
+        rename_off = [0]
+        team_of: dict = {}     # id(agent group) -> team index
+        placed: dict = {}      # team index -> cells of that team in the whole map
+        rows, plain = [], []
+        for k in range(n):
+            codes = []
+            for name in self.instance_symbols(k):
+                if name in prog.agent_rename:
+                    group = prog.agent_rename[name]
+                    if id(group) not in team_of:
+                        if len(rename_off) > MAX_TEAMS:
+                            raise ValueError(f"MapGenSpec: more than {MAX_TEAMS} agent teams")
+                        team_of[id(group)] = len(rename_off) - 1
+                        rename += [c + 1 for c in group]
+                        rename_off.append(len(rename))
+                    t = team_of[id(group)]
+                    placed[t] = placed.get(t, 0) + 1
+                    if placed[t] > len(group):
+                        raise ValueError(f"Map has more '{name}' cells than agents in the group ({len(group)})")
+                    codes.append(TEAM0 + t)
+                elif name in prog.cell_to_class:
+                    codes.append(prog.cell_to_class[name] + 1)
+                    plain.append(codes[-1])
+                else:
+                    raise RuntimeError(f"Unknown object type: {name}")
+            if len(codes) > area:
+                raise ValueError(f"MapGenSpec: {len(codes)} symbols do not fit the {area} cells of a room (the reference would "
+                                 "cap the objects with a draw of its own, or fail)")
+            rows.append(codes)
+        border = prog.cell_to_class["wall"] + 1 if self.border_width > 0 else 0
+        iborder = 0
+        if n > 1 and self.instance_border_width > 0 and self.instance_border_object != "empty":
+            iborder = prog.cell_to_class[self.instance_border_object] + 1
+        if max([border, iborder] + rename + plain) >= TEAM0:
+            raise ValueError("MapGenSpec: class ids reach the team codes")
+        return LoweredScene(H, W, self.height, self.width, n, self.rows, self.cols, self.border_width, self.instance_border_width,
+                            border, iborder, self.first_on_root, np.array(rows, dtype=np.uint16).reshape(n, -1),
+                            np.array(rename, dtype=np.uint16), np.array(rename_off, dtype=np.int32))
+
+
+class UnsupportedMapBuilder(ValueError):
+    """``spec_from_config``: the map builder config asks for something the device generators do not restate."""
+
+
+_RANDOM_BUILDER = "mettagrid.map_builder.random_map.RandomMapBuilder.Config"
+_MAPGEN = "mettagrid.mapgen.mapgen.MapGen.Config"
+_RANDOM_SCENE = "mettagrid.mapgen.scenes.random.Random.Config"
+
+
+def spec_from_config(d: dict):
+    """The spec of a reference map builder config, given as the plain dict its ``model_dump(mode="json")`` yields: a
+    ``RandomMapSpec`` for ``RandomMapBuilder.Config``, a ``MapGenSpec`` for ``MapGen.Config`` with a ``Random.Config`` instance.
+    The config's own ``seed`` is not part of a spec (the seed rule of an episode's map is ``base + episodes so far``).
+    Anything else raises ``UnsupportedMapBuilder`` naming the field."""
+    def refuse(field, why):
+        raise UnsupportedMapBuilder(f"map builder config: '{field}' {why}")
+    t = d.get("type")
+    if t == _RANDOM_BUILDER:
+        return RandomMapSpec(d["height"], d["width"], d.get("objects", {}), d.get("agents", 0), d.get("border_width", 0),
+                             d.get("border_object", "wall"))
+    if t != _MAPGEN:
+        refuse("type", f"is {t!r}: only RandomMapBuilder.Config and MapGen.Config are generated on the device")
+    inst = d.get("instance")
+    if not isinstance(inst, dict):
+        refuse("instance", "is required")
+    it = inst.get("type")
+    if it != _RANDOM_SCENE:
+        if isinstance(it, str) and (it == _MAPGEN or ".map_builder." in it or it.endswith("MapBuilder.Config")):
+            refuse("instance", f"is a map builder ({it}); only a Random.Config scene is supported")
+        refuse("instance.type", f"is {it!r}: only the scene Random.Config is supported")
+    if inst.get("children"):
+        refuse("instance.children", "must be empty")
+    if inst.get("transform", "identity") != "identity":
+        refuse("instance.transform", f"is {inst['transform']!r}: only 'identity' is supported")
+    if inst.get("seed") is not None:
+        refuse("instance.seed", "is set: a scene-level seed replaces the per-episode generator")
+    if d.get("instance_border_clear_radius", 0) > 0:
+        refuse("instance_border_clear_radius", "must be 0")
+    if d.get("instance_object_remap"):
+        refuse("instance_object_remap", "must be empty")
+    if d.get("instance_names") is not None:
+        refuse("instance_names", "must not be set")
+    if d.get("width") is None or d.get("height") is None:
+        refuse("width", "and 'height' must be set (a Random scene has no size of its own)")
+    return MapGenSpec(d["width"], d["height"], inst.get("objects", {}), inst.get("agents", 0), d.get("num_agents"), d.get("instances"),
+                      d.get("border_width", 5), d.get("instance_border_width", 5), d.get("instance_border_object", "wall"),
+                      d.get("set_team_by_instance", False))
+
+
+class _Streams:
+    """One PCG64 per row, as ``default_rng(seed)`` (key None) or ``Generator(PCG64(SeedSequence(seed, spawn_key=(key,))))``
+    seeds it, with ``next_uint32``'s buffered high half.  ``shuffle`` is ``Generator.shuffle`` of a 1-d array — for i = n-1 .. 1:
+    j = random_interval(i), swap a[i], a[j] — with random_interval's masked rejection on the buffered 32-bit halves (low half
+    of each 64-bit output first).  Shuffles on one object continue one stream, as two calls on one numpy generator do."""
+
+    def __init__(self, seeds, key=None) -> None:
+        from . import early_reset as er
+        self.er = er
+        u64 = np.uint64
+        S = self.S = len(seeds)
+        with np.errstate(over="ignore"):
+            w = er.generate_state8(er.seedseq_pool(seeds, key))
+            v = [w[2 * i] | (w[2 * i + 1] << u64(32)) for i in range(4)]
+            self.ih = (v[2] << u64(1)) | (v[3] >> u64(63)); self.il = (v[3] << u64(1)) | u64(1)
+            sh, sl = er.step(np.zeros(S, u64), np.zeros(S, u64), self.ih, self.il)
+            sh, sl = er.add128(sh, sl, v[0], v[1])
+            self.sh, self.sl = er.step(sh, sl, self.ih, self.il)
+        self.have_hi = np.zeros(S, bool)          # the high half of the last output is still buffered
+        self.hi_half = np.zeros(S, u64)
+
+    def shuffle(self, out: np.ndarray) -> None:
+        er, u64 = self.er, np.uint64
+        S, n = out.shape
+        sh, sl, ih, il, have_hi, hi_half = self.sh, self.sl, self.ih, self.il, self.have_hi, self.hi_half
         rows = np.arange(S)
-        for i in range(n - 1, 0, -1):
-            mask = u64((1 << int(i).bit_length()) - 1)
-            j = np.zeros(S, np.int64)
-            todo = rows
-            while len(todo):
-                use_hi = have_hi[todo]
-                fresh = todo[~use_hi]
-                nh, nl = er.step(sh[fresh], sl[fresh], ih[fresh], il[fresh])
-                sh[fresh], sl[fresh] = nh, nl
-                x = nh ^ nl
-                rot = nh >> u64(58)
-                o = (x >> rot) | (x << ((u64(64) - rot) & u64(63)))
-                half = hi_half[todo].copy()
-                half[~use_hi] = o & er.M32
-                hi_half[fresh] = o >> u64(32)
-                have_hi[todo] = ~use_hi
-                val = half & mask
-                ok = val <= u64(i)
-                j[todo[ok]] = val[ok].astype(np.int64)
-                todo = todo[~ok]
-            ai = out[:, i].copy()
-            out[:, i] = out[rows, j]
-            out[rows, j] = ai
-    return out
+        with np.errstate(over="ignore"):
+            for i in range(n - 1, 0, -1):
+                mask = u64((1 << int(i).bit_length()) - 1)
+                j = np.zeros(S, np.int64)
+                todo = rows
+                while len(todo):
+                    use_hi = have_hi[todo]
+                    fresh = todo[~use_hi]
+                    nh, nl = er.step(sh[fresh], sl[fresh], ih[fresh], il[fresh])
+                    sh[fresh], sl[fresh] = nh, nl
+                    x = nh ^ nl
+                    rot = nh >> u64(58)
+                    o = (x >> rot) | (x << ((u64(64) - rot) & u64(63)))
+                    half = hi_half[todo].copy()
+                    half[~use_hi] = o & er.M32
+                    hi_half[fresh] = o >> u64(32)
+                    have_hi[todo] = ~use_hi
+                    val = half & mask
+                    ok = val <= u64(i)
+                    j[todo[ok]] = val[ok].astype(np.int64)
+                    todo = todo[~ok]
+                ai = out[:, i].copy()
+                out[:, i] = out[rows, j]
+                out[rows, j] = ai
 
 
-def generated_class_maps(spec: RandomMapSpec, prog, seeds) -> np.ndarray:
-    """``random_class_maps(prog, ...)`` / ``prog.class_map(spec.random_map(seed))`` for many seeds (< 2**32) -> uint16
-    [n][H][W], without a numpy generator per map and with the halving rule: the host restatement of mgx_mapgen_kernel."""
-    low = spec.lower(prog)
+def shuffled_rows(base: np.ndarray, seeds, then=None, key=None):
+    """``[default_rng(int(s)).shuffle(copy of base) for s in seeds]`` for a 1-d array, vectorised over the seeds (``_Streams``).
+    ``then``: a second 1-d array that every row's generator shuffles after ``base``, on the same stream (the buffered half the
+    first shuffle leaves is the first the second consumes) -> (rows of base, rows of then).  ``key``: the generators are those
+    of ``SeedSequence(seed, spawn_key=(key,))`` instead."""
     seeds = np.asarray(seeds, dtype=np.uint64).reshape(-1)
-    inner = shuffled_rows(low.inner, seeds)
-    for t in range(low.n_teams):
-        group = low.rename[low.rename_off[t]:low.rename_off[t + 1]]
-        m = inner == TEAM0 + t
+    out = np.tile(np.asarray(base), (len(seeds), 1))
+    out2 = None if then is None else np.tile(np.asarray(then), (len(seeds), 1))
+    if len(seeds) and (out.shape[1] >= 2 or (out2 is not None and out2.shape[1] >= 2)):
+        st = _Streams(seeds, key)
+        st.shuffle(out)
+        if out2 is not None:
+            st.shuffle(out2)
+    return out if then is None else (out, out2)
+
+
+def _rename_rows(cells: np.ndarray, rename, rename_off) -> np.ndarray:
+    """cells [S][n] in row-major order: the k-th TEAM0 + t cell of a row becomes rename[rename_off[t] + k]."""
+    for t in range(len(rename_off) - 1):
+        group = rename[rename_off[t]:rename_off[t + 1]]
+        m = cells == TEAM0 + t
         if len(group):
             k = np.cumsum(m, axis=1) - 1
-            inner = np.where(m, group[np.clip(k, 0, len(group) - 1)], inner)
-    out = np.full((len(seeds), low.height, low.width), low.border_code, dtype=np.uint16)
+            cells = np.where(m, group[np.clip(k, 0, len(group) - 1)], cells)
+    return cells
+
+
+def generated_class_maps(spec, prog, seeds) -> np.ndarray:
+    """``prog.class_map(spec.random_map(seed))`` for many seeds (< 2**32) -> uint16 [n][H][W], without a numpy generator per
+    map: the host restatement of mgx_mapgen_kernel (a ``RandomMapSpec``, with the halving rule) or of mgx_mapscene_kernel (a
+    ``MapGenSpec``: per instance one stream, the shuffle of the symbols, then the shuffle of the room's cell indices)."""
+    low = spec.lower(prog)
+    seeds = np.asarray(seeds, dtype=np.uint64).reshape(-1)
+    S = len(seeds)
+    if isinstance(low, LoweredScene):
+        H, W, b, h, w = low.height, low.width, low.border_width, low.room_height, low.room_width
+        out = np.full((S, H, W), low.border_code, dtype=np.uint16)
+        out[:, b:H - b, b:W - b] = low.instance_border_code if low.n_inst > 1 else 0
+        flat = out.reshape(S, H * W)
+        for k in range(low.rows * low.cols):
+            y0, x0 = b + (k // low.cols) * (h + low.instance_border_width), b + (k % low.cols) * (w + low.instance_border_width)
+            out[:, y0:y0 + h, x0:x0 + w] = 0
+            if k >= low.n_inst or low.n_sym == 0:
+                continue
+            sym, idx = shuffled_rows(low.symbols[k], seeds, then=np.arange(h * w, dtype=np.int64),
+                                     key=None if (k == 0 and low.first_on_root) else k)
+            idx = idx[:, :low.n_sym]
+            flat[np.arange(S)[:, None], (y0 + idx // w) * W + x0 + idx % w] = sym
+        return _rename_rows(flat, low.rename, low.rename_off).reshape(S, H, W)
+    inner = _rename_rows(shuffled_rows(low.inner, seeds), low.rename, low.rename_off)
+    out = np.full((S, low.height, low.width), low.border_code, dtype=np.uint16)
     b = low.border_width
-    out[:, b:b + low.ih, b:b + low.iw] = inner.reshape(len(seeds), low.ih, low.iw)
+    out[:, b:b + low.ih, b:b + low.iw] = inner.reshape(S, low.ih, low.iw)
     return out

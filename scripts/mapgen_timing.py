@@ -10,7 +10,12 @@ variant the median over the rounds with min / max and the coefficient of variati
            envs and rounds), the first round is the warm-up.
   wrapper  MettaGridBatchedEnv's ms per step at `envs` envs, rung 3, max_steps = 128, desync=True: map_pool (16 maps) against
            map_gen, `steps` event-timed steps per round.
-  all      gen, then wrapper (the default).
+  scene    the scene recipe (MapGen + Random scene, mgx_mapscene_kernel): the reference arena as 1 instance (25 x 25 room, border
+           6: a 37 x 37 map) and as 4 instances (a 62 x 62 map), each beside its yardstick, the random-builder kernel on a map of
+           the same size with the same number of inner cells (625 / 2 500); generate_maps of `envs` and of 64 maps as in `gen`.
+           Then the wrapper's ms per step with the 4-instance recipe on rung-3 rules at min(envs, 16 384) envs, map_pool (16 maps)
+           against map_gen.
+  all      gen, then wrapper, then scene (the default).
 A plain `python bench.py` of this tree against its parent is run by hand, the two alternating.
 Prints one JSON line.  Usage (GPU box): python scripts/mapgen_timing.py [envs] [steps] [rounds] [mode] [trace csv]"""
 import csv
@@ -60,7 +65,7 @@ from mettagrid_amd import presets  # noqa: E402
 from mettagrid_amd.compiler import compile_spec  # noqa: E402
 from mettagrid_amd.engine import BatchedMettaGrid  # noqa: E402
 from mettagrid_amd.envs import MettaGridBatchedEnv  # noqa: E402
-from mettagrid_amd.mapgen import RandomMapSpec, generated_class_maps, random_class_maps  # noqa: E402
+from mettagrid_amd.mapgen import MapGenSpec, RandomMapSpec, generated_class_maps, random_class_maps  # noqa: E402
 
 spec3 = presets.rung3_spec()
 spec3.max_steps = 128
@@ -121,5 +126,69 @@ if mode in ("wrapper", "all"):
     for k, v in wms.items():
         out[f"wrapper_{k}_ms_per_step"] = stats(v)
         out[f"wrapper_{k}_ms_rounds"] = [round(float(x), 4) for x in v]
+        envs[k].close()
+
+if mode in ("scene", "all"):
+    # the arena's 24 agents scaled to the 16 (8 red + 8 blue) of the rung-3 rules
+    arena1 = MapGenSpec(25, 25, {"wall": 10}, {"red": 8, "blue": 8}, num_agents=16, border_width=6, instance_border_width=0)
+    arena4 = MapGenSpec(25, 25, {"wall": 10}, {"red": 2, "blue": 2}, num_agents=16, border_width=6, instance_border_width=0)
+    recipes, shapes = {}, {}
+    for name, scene in (("arena1", arena1), ("arena4", arena4)):
+        H, W = shapes[name + "_scene"] = shapes[name + "_random"] = scene.map_height, scene.map_width
+        n_walls = 10 * scene.instances_count
+        recipes[name + "_scene"] = scene
+        recipes[name + "_random"] = RandomMapSpec(H, W, {"wall": n_walls}, {"red": 8, "blue": 8}, border_width=6)   # the yardstick
+    progs = {name: compile_spec(spec3, *shapes[name], max_objects=2048) for name in recipes}   # (1 344 border walls at 62 x 62)
+    order = [(name, n) for name in recipes for n in (E, 64)]
+    engs = {}
+    for name, rec in recipes.items():
+        engs[name] = BatchedMettaGrid(progs[name], generated_class_maps(rec, progs[name], [0]), [0], buffers="device", specialize=False)
+        engs[name].set_map_generator(rec, [0])
+    bufs = {(name, n): torch.zeros((n,) + shapes[name], dtype=torch.int16, device="cuda") for name, n in order}
+    seeds = {E: (np.arange(E, dtype=np.uint64) * 2654435761 % (1 << 32)).astype(np.uint32), 64: np.arange(64, dtype=np.uint32) + 12345}
+    ms = {k: [] for k in order}
+    for r in range(rounds + 1):   # (round 0 warms up)
+        for name, n in order:
+            eng = engs[name]
+            st = eng._ext_stream()
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record(st)
+            eng.generate_maps(seeds[n], out=bufs[(name, n)])
+            t1.record(st)
+            t1.synchronize()
+            if r:
+                ms[(name, n)].append(t0.elapsed_time(t1))
+    for (name, n), v in ms.items():
+        out[f"generate_{name}_{n}_ms"] = stats(v, n)
+    for name in ("arena1", "arena4"):
+        for n in (E, 64):
+            out[f"ratio_{name}_{n}"] = round(out[f"generate_{name}_scene_{n}_ms"]["median"] / out[f"generate_{name}_random_{n}_ms"]["median"], 3)
+    for eng in engs.values():
+        eng.close()
+    del bufs
+    prog = progs["arena4_scene"]
+    pool = generated_class_maps(arena4, prog, range(16))
+    EW = min(E, 16384)   # (2 048 object slots per env: a quarter of the batch keeps two engines of this size side by side small)
+    out["wrapper_arena4_envs"] = EW
+    envs = {"map_pool": MettaGridBatchedEnv(prog, EW, map_pool=pool, desync=True, episode_stats=False, specialize=False),
+            "map_gen": MettaGridBatchedEnv(prog, EW, map_gen=arena4, desync=True, episode_stats=False, specialize=False)}
+    g = torch.Generator(device="cuda").manual_seed(1)
+    for env in envs.values():
+        env.reset()
+    acts = [torch.randint(0, envs["map_gen"].transport_action_n, (EW * prog.num_agents,), generator=g, device="cuda", dtype=torch.int32) for _ in range(8)]
+    wms = {k: [] for k in envs}
+    for r in range(rounds + 1):
+        for k, env in envs.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for t in range(steps):
+                env.step(acts[t % 8])
+            t1.record()
+            t1.synchronize()
+            if r:
+                wms[k].append(t0.elapsed_time(t1) / steps)
+    for k, v in wms.items():
+        out[f"wrapper_arena4_{k}_ms_per_step"] = stats(v)
+        out[f"wrapper_arena4_{k}_ms_rounds"] = [round(float(x), 4) for x in v]
         envs[k].close()
 print(json.dumps(out), flush=True)
