@@ -49,6 +49,10 @@ struct MgxDev {
                           //    disjoint (host analysis like act_par: handlers stay with actor and target, move range 1)
   int tick_split;         // 1: every per-agent on_tick handler touches its own agent only: in the lean lane-per-env kernel the
                           //    env's helper lane (MGX_WORLD_HELPERS) runs them for the second half of the agents
+  int coop_passes;        // 1: in the lean lane-per-env kernel a full wavefront walks its 32 envs' agents as ONE flat run in the
+                          //    batched per-agent passes (clears, staging, vibe pass, tail_shadow): lane l of trip t takes element
+                          //    64 t + l, so every access is coalesced (mgx_world.h; 0 under env MGX_WORLD_PASSES_PER_ENV).  Engine
+                          //    configuration, not env state: it changes speed only and is in no record
   int act_ngset;          // game-scope stats the action-phase handlers SET (StatsMutation): applied in agent order at the end
   int act_gset_ids[4];
   int act_lds_extra;      // bytes per workgroup behind the game-stat cells: footprints u32[A'][EPG] | cell map u8[EPG][H*W] (0: no cell map)

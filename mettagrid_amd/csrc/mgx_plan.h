@@ -22,7 +22,7 @@
 // the engine's lifetime: a later reset that grows the token pool sizes the observation kernel with the same ones.
 struct MgxSwitches {   // (mgx_read_switches: which switch sets or clears each)
   bool verbose, prog_lds, aoe_local, tick_in_aoe, aoe_prog_lds, flat_top, tick_split, rewards_mid, obs_512, obs_preset, act_lean,
-      act_par, act_map, act_replay, duo, shadow, gen, obs_tail;
+      act_par, act_map, act_replay, duo, coop_passes, shadow, gen, obs_tail;
 };
 inline MgxSwitches mgx_read_switches() {
   auto on = [](const char* name) { return getenv(name) != nullptr; };
@@ -43,6 +43,7 @@ inline MgxSwitches mgx_read_switches() {
   s.act_map = !on("MGX_ACT_NO_MAP");                // conflicts by an all-pairs walk
   s.act_replay = on("MGX_ACT_SHUFFLE_REPLAY");      // the shuffle always takes its serial replay path (tests)
   s.duo = !on("MGX_NO_DUO");
+  s.coop_passes = !on("MGX_WORLD_PASSES_PER_ENV");  // the lean kernel's batched per-agent passes one lane per env
   s.shadow = !on("MGX_NO_SHADOW");                  // no integer bookkeeping
   s.gen = !on("MGX_NO_GEN");                        // handlers on the interpreter
   s.obs_tail = !on("MGX_OBS_FULL_ROWS");            // every observation pass rewrites whole rows (no MgxDev::obs_used)
@@ -601,6 +602,7 @@ inline int mgx_plan(const int32_t* P, size_t words, const uint16_t* class_maps, 
     d.act_par = par ? 1 : 0;
     d.act_tick = (par && !d.X) ? 1 : 0;
     d.duo = duo ? 1 : 0;
+    d.coop_passes = (!d.X && sw.coop_passes) ? 1 : 0;
     d.act_replay = sw.act_replay ? 1 : 0;
     // game-stat SETs are applied in agent order through per-env cells (the paired dispatch too)
     const std::vector<int>& sets = par ? gset : duo ? act_sets : std::vector<int>();

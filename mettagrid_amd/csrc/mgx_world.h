@@ -106,6 +106,13 @@ MGX_DBG_LINKAGE __device__ unsigned long long mgx_dbg_cycles[16];
 // takes the second half of the agents in the three batched per-agent passes (staging, deferred bookkeeping, coverage), whose
 // time is the number of chunks of eight agents a lane walks; during the serial action dispatch it is masked off and costs
 // nothing.  Same instruction stream, half the trips of those passes.
+// Since MgxDev::coop_passes a FULL wavefront no longer splits those passes by env at all: its 64 lanes walk the 32 envs' agents
+// as one flat run of 32 A elements ([E][A] arrays: contiguous), lane l of trip t on element 64 t + l — the clears of executed /
+// success, the staging, the straight vibe pass and tail_shadow (tail_shadow_flat).  The trip count is the same (32 A / 64 =
+// A / 2 per lane); what changes is that one vector memory instruction touches consecutive bytes (a u16 array: one 128-byte
+// line instead of 16, an ag_cnt half-record: 1 KB instead of 64 lines) and that 16-byte stores fill whole lines.  The helper
+// lanes still take their half of the per-env forms where those remain: partial wavefronts, invalid vibe indices, on_tick
+// (tick_split), the paired dispatch (duo), the non-integer bookkeeping, and everything under MGX_WORLD_PASSES_PER_ENV.
 #if defined(MGX_WORLD_HELPERS) && !defined(MGX_CPU_EMU) && !defined(MGX_ACT_TU) && MGX_WORLD_LPW * 2 == MGX_WAVE
 #define MGX_HELPERS_ON 1
 #else
@@ -1949,6 +1956,120 @@ struct MgxEnvT {  // per-lane view of one env
     }
   }
 
+#if MGX_HELPERS_ON
+  // tail_shadow by a whole wavefront over the flat run of its 32 envs' agents (MgxDev::coop_passes, mgx_world_body): lane wl
+  // of trip t takes element 64 t + wl.  Two loops.  The ag_cnt records go by HALVES (16 bytes: noop / move counters | vibe
+  // counters, action.failed, max steps without motion), each updated from the result bytes alone, so a load or store of the
+  // wavefront is 1 KB of consecutive bytes; then coverage and the swm / prev_location write-back, one agent per lane.
+  __device__ MGX_BIG void tail_shadow_flat(int wl, int wenv0) const {
+    const int A = d.A, n_flat = MGX_WORLD_LPW * A;
+    const size_t g0 = ((size_t)(blockIdx.x * MGX_WORLD_EPG) + wenv0) * A;
+    const MgxALds al = AL();
+    auto flat_li = [&](int p) {
+      const int w = (int)((uint32_t)p / (uint32_t)A);
+      return (p - w * A) * MGX_WORLD_EPG + wenv0 + w;
+    };
+    const uint4* __restrict__ cnt = (const uint4*)d.ag_cnt + g0 * 2;
+    uint4* __restrict__ cnt_w = (uint4*)d.ag_cnt + g0 * 2;
+    for (int t0 = 0; t0 * MGX_WAVE < 2 * n_flat; t0 += 8) {
+      uint32_t res0[8], res1[8], swm0[8];
+      uint4 c[8];
+#pragma unroll
+      for (int q = 0; q < 8; q++) {
+        const int u = (t0 + q) * MGX_WAVE + wl, uc = min(u, 2 * n_flat - 1);
+        const int li = flat_li(uc >> 1);
+        res0[q] = (uint32_t)(uint16_t)al.act[li];
+        res1[q] = (uint32_t)(uint16_t)al.act[A * MGX_WORLD_EPG + li];
+        if (u >= 2 * n_flat) res0[q] = res1[q] = 0;
+        swm0[q] = d.ag_swm[g0 + (uc >> 1)];
+        c[q] = cnt[uc];
+      }
+#pragma unroll
+      for (int q = 0; q < 8; q++) {
+        if (!((res0[q] | res1[q]) & 1)) continue;
+        const int u = (t0 + q) * MGX_WAVE + wl;
+        const bool second = (u & 1) != 0;
+        // replay the calls (actions/action_handler.hpp:78-105): result bytes have bit 0 set, bit 3 = success, bit 4 = moved
+        uint32_t swm = swm0[q];
+        uint4 h = c[q];
+#pragma unroll
+        for (int call = 0; call < 2; call++) {
+          const uint32_t r = call ? res1[q] : res0[q];
+          if (!(r & 1)) continue;
+          const int kind = (r >> 1) & 3;
+          const uint32_t ok = (r >> 3) & 1u, no = ok ^ 1u;
+          if (second) {
+            if (r & 16) swm = 0;
+            else { swm += 1; h.w = max(h.w, swm); }
+            if (kind != MGX_AK_NOOP && kind != MGX_AK_MOVE) { h.x += ok; h.y += no; }
+            h.z += no;
+          } else {
+            if (kind == MGX_AK_NOOP) { h.x += ok; h.y += no; }
+            else if (kind == MGX_AK_MOVE) { h.z += ok; h.w += no; }
+          }
+        }
+        cnt_w[u] = h;
+      }
+    }
+    for (int t0 = 0; t0 * MGX_WAVE < n_flat; t0 += 8) {
+      uint32_t res0[8], res1[8], swm0[8];
+      uint16_t rc8[8], cov8[8], sp8[8];
+      uint32_t w8[8], un8[8], md8[8];
+#pragma unroll
+      for (int q = 0; q < 8; q++) {
+        const int p = (t0 + q) * MGX_WAVE + wl, pc = min(p, n_flat - 1);
+        const int li = flat_li(pc);
+        res0[q] = (uint32_t)(uint16_t)al.act[li];
+        res1[q] = (uint32_t)(uint16_t)al.act[A * MGX_WORLD_EPG + li];
+        if (p >= n_flat) res0[q] = res1[q] = 0;
+        swm0[q] = d.ag_swm[g0 + pc];
+        rc8[q] = al.rc[li];
+        cov8[q] = d.ag_covrc[g0 + pc];
+      }
+#pragma unroll
+      for (int q = 0; q < 8; q++) {   // second level, only for agents that moved
+        const int p = (t0 + q) * MGX_WAVE + wl;
+        if (p < n_flat && rc8[q] != cov8[q]) {
+          const size_t g = g0 + p;
+          const int bit = (rc8[q] >> 8) * d.W + (rc8[q] & 0xFF);
+          sp8[q] = d.ag_spawn[g];
+          w8[q] = d.ag_seen[g * d.SEENW + (bit >> 5)];
+          un8[q] = d.ag_unique[g];
+          md8[q] = d.ag_maxdist[g];
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 8; q++) {
+        const int p = (t0 + q) * MGX_WAVE + wl;
+        if (p >= n_flat) continue;
+        const size_t g = g0 + p;
+        if (rc8[q] != cov8[q]) {   // track_coverage (objects/agent.cpp:49-57): the position changed since the last call
+          const int r = rc8[q] >> 8, c = rc8[q] & 0xFF;
+          const int bit = r * d.W + c;
+          d.ag_covrc[g] = rc8[q];
+          if (!(w8[q] & (1u << (bit & 31)))) {
+            d.ag_seen[g * d.SEENW + (bit >> 5)] = w8[q] | (1u << (bit & 31));
+            d.ag_unique[g] = un8[q] + 1;
+          }
+          const int dist = abs((int)(sp8[q] >> 8) - r) + abs(c - (int)(sp8[q] & 0xFF));
+          if ((uint32_t)dist > md8[q]) d.ag_maxdist[g] = (uint32_t)dist;
+        }
+        if (!((res0[q] | res1[q]) & 1)) continue;
+        uint32_t swm = swm0[q];
+#pragma unroll
+        for (int call = 0; call < 2; call++) {
+          const uint32_t r = call ? res1[q] : res0[q];
+          if (!(r & 1)) continue;
+          if (r & 16) swm = 0;
+          else swm += 1;
+        }
+        d.ag_swm[g] = swm;
+        d.ag_prev[g] = al.prev[flat_li(p)];
+      }
+    }
+  }
+#endif
+
   // bookkeeping_flush for ONE agent (the lane-per-agent kernel, mgx_act.h: every lane flushes its own agent)
   __device__ MGX_BIG void bookkeeping_flush_one(int i) const {
     const int A = d.A, lane = AL().lane;
@@ -2230,6 +2351,29 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
   constexpr bool HELP = !X && MGX_HELPERS_ON;
   const int a_split = HELP ? min(A, ((A + 1) / 2 + 7) & ~7) : A;
   const int a_lo = helper ? a_split : 0, a_hi = helper ? A : a_split;
+  // MgxDev::coop_passes: the wavefront-cooperative form of those passes.  Every per-agent array is [E][A], so the 32 envs of
+  // a wavefront own ONE contiguous run of 32 A elements: lane l of trip t takes element p = 64 t + l of it (env p / A of
+  // the wavefront, agent p % A), whoever's env that is — what the passes hand to the dispatch is in LDS, which any lane can
+  // read and write.  A wavefront that is not full (the last envs of the batch) keeps the per-env form: chosen per wavefront.
+  bool coop = false;
+  int wl = 0, wenv0 = 0, genv0 = 0, n_flat = 0;   // lane in the wavefront; the wavefront's first env in the workgroup / the batch
+  size_t g0 = 0;                                  // the run's first element
+#if MGX_HELPERS_ON
+  if constexpr (HELP) {
+    wl = (int)(threadIdx.x & (MGX_WAVE - 1));
+    wenv0 = (int)(threadIdx.x >> 6) * MGX_WORLD_LPW;
+    genv0 = (int)(blockIdx.x * MGX_WORLD_EPG) + wenv0;
+    coop = d.coop_passes != 0 && (phases & MGX_PH_ACTIONS) != 0 && genv0 + MGX_WORLD_LPW <= d.E;
+    n_flat = MGX_WORLD_LPW * A;
+    g0 = (size_t)genv0 * A;
+  }
+#endif
+  // LDS cell [agent][env] of element p of the run; *ew: its env inside the wavefront
+  auto flat_li = [&](int p, int* ew = nullptr) {
+    const int w = (int)((uint32_t)p / (uint32_t)A);
+    if (ew) *ew = w;
+    return (p - w * A) * MGX_WORLD_EPG + wenv0 + w;
+  };
   {   // ++current_step (:933): both lanes of a pair read the old value in the same instruction, the env's own lane stores
     const uint32_t s0 = d.step[env];
     e.step = act ? s0 + 1 : s0;
@@ -2241,6 +2385,12 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
       if (k >= (uint32_t)d.n_schedule || (uint32_t)d.P[d.sec[MGX_SEC_SCHEDULE] + k * MGX_SC_WORDS + MGX_SC_TIMESTEP] > e.step) return;
     }
   }
+  if (coop) {   // ... as 16-byte stores over the wavefront's run: 128 A bytes of executed, 32 A bytes of success, both 32-byte aligned
+    uint4* ex = (uint4*)(d.executed + g0);
+    for (int k = wl; k < n_flat / 4; k += MGX_WAVE) ex[k] = make_uint4(0u, 0u, 0u, 0u);
+    uint4* su = (uint4*)(d.success + g0);
+    for (int k = wl; k < n_flat / 16; k += MGX_WAVE) su[k] = make_uint4(0u, 0u, 0u, 0u);
+  } else
   if (act && !helper) {  // executed_actions / _action_success cleared (mettagrid_c.cpp:944,962-964): done here (a few 16-byte
               // stores per env) instead of two memset launches per step
     if ((A & 3) == 0) {
@@ -2256,6 +2406,36 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
   // ---- stage every agent's own state + both action streams in LDS.  The loads of one chunk are independent, so
   // they are all in flight together instead of one HBM round trip per agent inside the serial loop below. ----
   const bool want_stepprev = (d.flags & MGX_G_LAST_ACTION_MOVE) != 0;
+  if (coop) {   // eight trips of the flat run at a time: every load is one to four whole lines
+    for (int t0 = 0; t0 * MGX_WAVE < n_flat; t0 += 8) {
+      uint16_t slot8[8], prev8[8], rc8[8], cls8[8];
+      uint32_t swm8[8];
+      int32_t a8[8], v8[8];
+#pragma unroll
+      for (int q = 0; q < 8; q++) {
+        const size_t g = g0 + min((t0 + q) * MGX_WAVE + wl, n_flat - 1);
+        slot8[q] = d.ag_obj[g];
+        prev8[q] = d.ag_prev[g];
+        swm8[q] = d.ag_swm[g];
+        a8[q] = d.actions[g];
+        v8[q] = d.vibe_actions[g];
+        rc8[q] = d.ag_rc[g];
+        cls8[q] = d.ag_cls[g];
+      }
+#pragma unroll
+      for (int q = 0; q < 8; q++) {
+        const int p = (t0 + q) * MGX_WAVE + wl;
+        if (p < n_flat) {
+          const int li = flat_li(p);
+          al.slot[li] = slot8[q]; al.rc[li] = rc8[q]; al.prev[li] = prev8[q]; al.swm[li] = swm8[q];
+          if (al.cls) al.cls[li] = cls8[q];
+          al.act[li] = mgx_sat16(a8[q]); al.act[A * MGX_WORLD_EPG + li] = mgx_sat16(v8[q]);
+          if (want_stepprev) d.ag_stepprev[g0 + p] = rc8[q];  // mettagrid_c.cpp:929-931
+          order[li] = (uint8_t)(li / MGX_WORLD_EPG);
+        }
+      }
+    }
+  } else
   for (int i0 = a_lo; i0 < a_hi; i0 += 8) {
     uint16_t slot8[8], prev8[8], rc8[8], cls8[8];
     uint32_t swm8[8];
@@ -2327,6 +2507,39 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
       // its own bookkeeping and nothing reads either before the stream ends, so the order of the agents cannot be observed
       // — one straight pass per lane over its half of the agents (this lane's and its helper's), without the trip loop's
       // pairing, fences and the call into handle_action (measured: 6 000 cycles per trip for one store).
+      if (stream == 1 && d.defer_book && coop) {
+        // ... and over the flat run when the wavefront walks it together.  An invalid index needs the stat rows of its env's
+        // own lanes (MgxEnvT works on the lane's env): the flat pass marks it (-1: the raw index is read again from HBM), and
+        // only when the wavefront has one the envs' lanes walk their agents for the marked entries.  Their bookkeeping touches
+        // the acting agent only, so it may come after the others'.
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the primary stream's positions and counters, written by the envs' lanes
+        __builtin_amdgcn_wave_barrier();
+        bool invalid = false;
+        for (int p = wl; p < n_flat; p += MGX_WAVE) {
+          int ew;
+          const int li = flat_li(p, &ew), ri = A * MGX_WORLD_EPG + li;
+          const int a = al.act[ri];
+          if (a < 0 || a >= d.nact) { al.act[ri] = -1; invalid = true; continue; }
+          if (acts[a * MGX_AC_WORDS + MGX_AC_KIND] != MGX_AK_VIBE) { al.act[ri] = 0; continue; }
+          d.obj_vibe[(size_t)(genv0 + ew) * d.S + al.slot[li]] = (uint8_t)acts[a * MGX_AC_WORDS + MGX_AC_ARG];
+          const uint16_t rc = al.rc[li], prev = al.prev[li];
+          const bool moved = rc != prev;
+          if (moved) { al.swm[li] = 0; al.prev[li] = rc; }
+          else al.swm[li] += 1;
+          al.act[ri] = (int16_t)(1 | (MGX_AK_VIBE << 1) | 8 | (moved ? 16 : 0));
+          d.executed[g0 + p] = a;
+          d.success[g0 + p] = 1;
+        }
+        const bool any_invalid = __ballot(invalid) != 0ull;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        if (any_invalid) {
+          for (int i = a_lo; i < a_hi; i++)
+            if (al.act[(A + i) * MGX_WORLD_EPG + lane] < 0) mgx_dispatch_one(e, d, acts, al, i, 1, lane, repeats);
+        }
+        MGX_TICK(3);
+        continue;
+      }
       if (stream == 1 && d.defer_book) {
         for (int i = a_lo; i < a_hi; i++) {
           const int li = i * MGX_WORLD_EPG + lane, ri = (A + i) * MGX_WORLD_EPG + lane;
@@ -2462,6 +2675,10 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
     }
   }
   MGX_TICK(4);
+#if MGX_HELPERS_ON
+  if (!X && d.shadow == 3 && coop) e.tail_shadow_flat(wl, wenv0);
+  else
+#endif
   if (!X && d.shadow == 3 && act) e.tail_shadow(a_lo, a_hi);   // (d.shadow implies d.defer_book)
   else {
     if (d.defer_book && act) e.bookkeeping_flush(a_lo, a_hi);
