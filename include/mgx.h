@@ -242,6 +242,44 @@ int mgx_fetch_episode_stats(mgx_engine* e, int32_t wait, double* totals /* [MGX_
  * *n_dropped: episodes that finished while the log was full since the last drain (they are still in the totals). */
 int mgx_drain_episode_log(mgx_engine* e, uint32_t* records, int32_t max_records, int32_t* n_records, int32_t* n_dropped);
 
+/* ---- Time-averaged game stats of every episode (time_averaged_game_stats of the reference's evaluation result) -------------
+ * Reference: the episode runner attaches a TimeAveragedStatsHandler to every evaluation episode
+ * (python/src/mettagrid/simulator/time_averaged_stats.py:17-41, used at runner/rollout.py:107-135): after every sim.step() it
+ * adds each value of episode_stats["game"] into a Python-float sum (on_step :30-36) and reports sum / steps per key at the end
+ * (:38-41); simulator/multi_episode/summary.py:50-77 averages those over the episodes (sum over episodes / number of episodes).
+ * Here a pass at the end of every mgx_step — behind the observation pass and the values kernel, which write the token
+ * statistics, and in front of the step's episode end (on_step, then is_done, then on_episode_end: simulator.py:180-190) — adds
+ * (double)game_stats[env][c] into f64 sums, ORs "key exists" (touched bit OR value != 0, the rule of mgx_get_stats) into
+ * seen bits and counts the step (csrc/mgx_time_avg.h).  On the done list (auto-reset, or mgx_record_episodes) each finished
+ * env's sum[c] / (double)ta_steps — f64, correctly rounded: the reference's bits — goes into a record, a bounded log and
+ * batch totals accumulated in the order of the episode totals (list order, chunks of 256, chunk sums in chunk order).
+ * An episode's accumulators are zero when it starts (every restart; switching the feature on).  An episode whose own step
+ * count differs from the env's current step at its end (switched on mid-episode; a state loaded without its accumulators) is
+ * PARTIAL: flagged, logged divided by its own count, left out of the totals and counted in MGX_TAT_PARTIAL.
+ * The accumulators are not part of an env's saved state: mgx_copy_envs copies them, mgx_load_envs zeroes the destinations'
+ * (put them back with mgx_put_time_average_state).  Needs episode statistics (MGX_ERR_BAD_ARG otherwise); switching those off
+ * or setting them again switches this off. */
+enum { MGX_TAT_EPISODES = 0, MGX_TAT_PARTIAL, MGX_TAT_HEADER };   /* totals: header, NG sums of the averages, NG counts of episodes holding the key */
+int mgx_set_time_averages(mgx_engine* e, int32_t enabled, int32_t log_capacity);
+/* Layout words (int32 [MGX_TAL_COUNT]).  A record is REC_WORDS uint32: [0] env [1] episodes the env had finished before
+ * [2] the env's step at the end [3] steps accumulated (time_averaged_stats.py:36) [4] flags (bit 1: partial) [5..7] 0;
+ * OFF_AVG: f64 [NG]; OFF_SEEN: key-exists bits.  Totals are TOTALS_WORDS doubles.  mgx_time_average_layout_of is a TEST AID:
+ * the same words from NG alone, so that the layout can be checked on a host without a GPU; integrations call the first form. */
+enum { MGX_TAL_NG = 0, MGX_TAL_SEEN_WORDS, MGX_TAL_REC_WORDS, MGX_TAL_LOG_WORDS, MGX_TAL_HEADER_WORDS, MGX_TAL_OFF_AVG, MGX_TAL_OFF_SEEN,
+       MGX_TAL_TOTALS_WORDS, MGX_TAL_TOTALS_HEADER, MGX_TAL_LOG_CAPACITY, MGX_TAL_COUNT };
+int mgx_time_average_layout(mgx_engine* e, int32_t* out /* [MGX_TAL_COUNT] */);
+int mgx_time_average_layout_of(int32_t num_game_stats, int32_t log_capacity, int32_t* out /* [MGX_TAL_COUNT] */);
+/* Snapshot-and-clear of the totals, as mgx_request_episode_stats / mgx_fetch_episode_stats (summary.py:50-77 sums these). */
+int mgx_request_time_averages(mgx_engine* e);
+int mgx_fetch_time_averages(mgx_engine* e, int32_t wait, double* totals /* [MGX_TAL_TOTALS_WORDS] */, int32_t* ready);
+/* The log (oldest first) to host memory, emptied; `records` must hold log_capacity records (time_averaged_stats.py:38-41). */
+int mgx_drain_time_average_log(mgx_engine* e, uint32_t* records, int32_t max_records, int32_t* n_records, int32_t* n_dropped);
+/* Raw accumulators of n envs (host memory: sums f64 [n][NG], steps u32 [n], seen u32 [n][SEEN_WORDS]): the handler's state
+ * mid-episode (time_averaged_stats.py:38-41 read as a property) and what carries it across mgx_save_envs / mgx_load_envs.
+ * Both wait for the device. */
+int mgx_get_time_average_state(mgx_engine* e, const int32_t* envs, int32_t n, double* sums, uint32_t* steps, uint32_t* seen);
+int mgx_put_time_average_state(mgx_engine* e, const int32_t* envs, int32_t n, const double* sums, const uint32_t* steps, const uint32_t* seen);
+
 /* ---- Chosen stats of every env and agent after every step (the per-step `infos` of MettaGridPufferEnv.step) ----------------
  * Reference: MettaGridPufferEnv(step_info_keys=...) (python/src/mettagrid/envs/mettagrid_puffer_env.py:81, 132-183) reads the
  * chosen game stats, attributes, per-agent stats and the step / episode rewards after every sim.step() and returns them as the

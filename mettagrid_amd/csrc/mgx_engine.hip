@@ -25,6 +25,7 @@
 #include "mgx_replay.h"     // change log of the watched envs (mgx_set_replay)
 #include "mgx_mapgen.h"     // the random map builder on the device (mgx_set_map_generator)
 #include "mgx_step_stats.h" // chosen stats of every env / agent read out behind every step (mgx_set_step_stats)
+#include "mgx_time_avg.h"   // time-averaged game stats of every episode (mgx_set_time_averages)
 
 
 // Territory ownership map (TerritoryTracker::compute_cell_ownership, core/territory_tracker.cpp:215-252) of every cell,
@@ -284,6 +285,22 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
   hipEvent_t ep_ev = nullptr;       // recorded behind the snapshot copy
   bool ep_pending = false;          // a snapshot has been requested and not fetched yet
   int ep_tw() const { return MGX_EP_TOT_HDR + 2 * (ep.NG + ep.NS); }
+  // time-averaged game stats (mgx_set_time_averages; csrc/mgx_time_avg.h): slot-side arrays outside the saved env record
+  bool ta_on = false;
+  MgxTimeAvg ta{};                  // layout + ta_sum [E][NG], ta_seen [E][NGW], ta_steps [E]
+  uint32_t* d_ta_rec = nullptr;     // [E][ta.L.rec_words] records of the envs that finished in the last step
+  double* d_ta_partial = nullptr;   // [ceil(E / 256)][tot_words] chunk sums
+  double* d_ta_totals = nullptr;    // [tot_words] batch totals since the last snapshot
+  double* d_ta_snap = nullptr;      // [tot_words] snapshot taken by mgx_request_time_averages
+  double* h_ta_snap = nullptr;      // pinned host copy of the snapshot
+  uint32_t* d_ta_ticket = nullptr;  // [1]
+  uint32_t* d_ta_log = nullptr;     // [ta_log_cap][ta.L.rec_words] records kept for mgx_drain_time_average_log
+  uint32_t* d_ta_log_state = nullptr;  // [2] records in the log, records dropped
+  int ta_log_cap = 0;
+  uint8_t* d_ta_block = nullptr;    // staging of mgx_copy_envs / get / put: packed accumulators of a list of envs
+  size_t ta_block_bytes = 0;
+  hipEvent_t ta_ev = nullptr;       // recorded behind the snapshot copy
+  bool ta_pending = false;
   unsigned long long* d_digest = nullptr;   // [E] mgx_state_digests
   // saved env state (mgx_env_state.h): the record layout, the device segment table, the staging of mgx_copy_envs
   MgxEnvStateLayout es;
@@ -586,7 +603,19 @@ static int init_buffers(mgx_engine* e) {
   return MGX_OK;
 }
 
+static void free_time_averages(mgx_engine* e) {
+  for (void* p : {(void*)e->ta.sum, (void*)e->ta.seen, (void*)e->ta.steps, (void*)e->d_ta_rec, (void*)e->d_ta_partial, (void*)e->d_ta_totals,
+                  (void*)e->d_ta_snap, (void*)e->d_ta_ticket, (void*)e->d_ta_log, (void*)e->d_ta_log_state, (void*)e->d_ta_block})
+    if (p) (void)hipFree(p);
+  if (e->h_ta_snap) (void)hipHostFree(e->h_ta_snap);
+  if (e->ta_ev) (void)hipEventDestroy(e->ta_ev);
+  e->ta = MgxTimeAvg{};
+  e->d_ta_rec = nullptr; e->d_ta_partial = nullptr; e->d_ta_totals = nullptr; e->d_ta_snap = nullptr; e->d_ta_ticket = nullptr;
+  e->d_ta_log = nullptr; e->d_ta_log_state = nullptr; e->d_ta_block = nullptr; e->h_ta_snap = nullptr; e->ta_ev = nullptr;
+  e->ta_on = false; e->ta_pending = false; e->ta_log_cap = 0; e->ta_block_bytes = 0;
+}
 static void free_episode_stats(mgx_engine* e) {
+  free_time_averages(e);   // (the time averages are finished on the episode statistics' done list)
   for (void* p : {(void*)e->d_ep_rec, (void*)e->d_ep_partial, (void*)e->d_ep_totals, (void*)e->d_ep_snap, (void*)e->d_ep_ticket,
                   (void*)e->d_ep_log, (void*)e->d_ep_log_state})
     if (p) (void)hipFree(p);
@@ -614,6 +643,10 @@ static void free_step_stats(mgx_engine* e) {
 static int launch_step_stats(mgx_engine*) { return MGX_OK; }
 static int flush_shadow(mgx_engine*, const int32_t*, const uint32_t*, unsigned) { return MGX_OK; }
 static int launch_episode_stats(mgx_engine*) { return MGX_OK; }
+static int launch_time_avg_accum(mgx_engine*) { return MGX_OK; }
+static int launch_time_avg_finish(mgx_engine*) { return MGX_OK; }
+static int clear_time_avg(mgx_engine*, const int32_t*, const uint32_t*, int, const uint8_t*) { return MGX_OK; }
+static int move_time_avg(mgx_engine*, const int32_t*, int, int) { return MGX_OK; }
 static int launch_replay(mgx_engine*) { return MGX_OK; }
 static int mark_replay(mgx_engine*, const int32_t*, int, uint32_t) { return MGX_OK; }
 static int launch_mapgen_envs(mgx_engine*, const MgxList&, const uint32_t*) { return MGX_OK; }
@@ -644,6 +677,62 @@ static int launch_episode_stats(mgx_engine* e) {
   hipLaunchKernelGGL(mgx_episode_accum_kernel, dim3((unsigned)std::min(nchunks_max, 16)), dim3(256), 0, e->stream, e->ep,
                      (const uint32_t*)e->d_done_n, (const uint32_t*)e->d_ep_rec, e->d_ep_partial, e->d_ep_totals, e->d_ep_ticket,
                      e->d_ep_log_state, e->ep_log_cap, e->d_ep_log ? 1 : 0);
+  HIP_TRY(hipGetLastError());
+  return MGX_OK;
+}
+// Time-averaged game stats (csrc/mgx_time_avg.h).  Every step: sums += the step's game stats, one lane per (env, column) slot,
+// at most 2 048 workgroups walking the slots grid-stride.
+static int launch_time_avg_accum(mgx_engine* e) {
+  const long long slots = (long long)e->d.E * e->ta.L.NGP;
+  const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>((slots + 255) / 256, 2048));
+  hipLaunchKernelGGL(mgx_time_avg_accum_kernel, dim3(grid), dim3(256), 0, e->stream, dev_copy(e), e->ta);
+  HIP_TRY(hipGetLastError());
+  return MGX_OK;
+}
+// The envs of the done list: averages -> records (+ log), then batch totals in the fixed chunk order.
+static int launch_time_avg_finish(mgx_engine* e) {
+  MgxList dl;
+  dl.n_host = -1;
+  hipLaunchKernelGGL(mgx_time_avg_finish_kernel, dim3((list_grid(e, dl, 128, 2048) + 3) / 4), dim3(256), 0, e->stream, dev_copy(e), e->ta,
+                     (const int32_t*)e->d_done_list, (const uint32_t*)e->d_done_n, e->d_ta_rec, e->d_ta_log, (const uint32_t*)e->d_ta_log_state,
+                     e->ta_log_cap, (const uint32_t*)e->d_episodes);
+  HIP_TRY(hipGetLastError());
+  const int nchunks_max = (e->d.E + MGX_EP_CHUNK - 1) / MGX_EP_CHUNK;
+  hipLaunchKernelGGL(mgx_time_avg_total_kernel, dim3((unsigned)std::min(nchunks_max, 16)), dim3(256), 0, e->stream, e->ta.L,
+                     (const uint32_t*)e->d_done_n, (const uint32_t*)e->d_ta_rec, e->d_ta_partial, e->d_ta_totals, e->d_ta_ticket,
+                     e->d_ta_log_state, e->ta_log_cap, e->d_ta_log ? 1 : 0);
+  HIP_TRY(hipGetLastError());
+  return MGX_OK;
+}
+// on_episode_start: the accumulators of a device list of envs (n on the device, or n_host >= 0), or of a device mask, -> 0.
+static int clear_time_avg(mgx_engine* e, const int32_t* list, const uint32_t* list_n, int n_host, const uint8_t* dmask) {
+  if (!e->ta_on) return MGX_OK;
+  MgxList l;
+  l.list = list; l.n = list_n; l.n_host = n_host;
+  hipLaunchKernelGGL(mgx_time_avg_clear_kernel, dim3(list ? list_grid(e, l, 128, 1024) : (unsigned)std::min(e->d.E, 4096)), dim3(64), 0, e->stream,
+                     e->ta, list, list_n, n_host, dmask, e->d.E);
+  HIP_TRY(hipGetLastError());
+  return MGX_OK;
+}
+// d_ta_block for the packed accumulators of n envs.
+static int reserve_time_avg_block(mgx_engine* e, int n) {
+  const size_t bytes = mgx_ta_block_bytes(e->ta.L, (size_t)n);
+  if (bytes > e->ta_block_bytes) {
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->d_ta_block) (void)hipFree(e->d_ta_block);
+    e->d_ta_block = nullptr;
+    e->ta_block_bytes = 0;
+    HIP_TRY(hipMalloc((void**)&e->d_ta_block, bytes));
+    e->ta_block_bytes = bytes;
+  }
+  return MGX_OK;
+}
+// The packed accumulators of n listed envs (device list) <-> d_ta_block (dir 0: get).
+static int move_time_avg(mgx_engine* e, const int32_t* dlist, int n, int dir) {
+  { int rc = reserve_time_avg_block(e, n); if (rc) return rc; }
+  const long long lanes = (long long)n * std::max(1, e->ta.L.NG);
+  hipLaunchKernelGGL(mgx_time_avg_move_kernel, dim3((unsigned)std::min<long long>((lanes + 255) / 256, 1024)), dim3(256), 0, e->stream, e->ta,
+                     dlist, n, e->d_ta_block, dir);
   HIP_TRY(hipGetLastError());
   return MGX_OK;
 }
@@ -954,6 +1043,7 @@ static int restart_masked(mgx_engine* e, const uint8_t* dmask, bool from_pool, b
                      e->n_rows, dmask, d.E, bump ? e->d_episodes : (uint32_t*)nullptr, bump ? e->d_map_index : (int32_t*)nullptr, e->n_pool,
                      e->pool_stride, ll.list, ll.n);
   HIP_TRY(hipGetLastError());
+  if (e->ta_on) { rc = clear_time_avg(e, ll.list, ll.n, ll.n_host, dmask); if (rc) return rc; }   // on_episode_start (time_averaged_stats.py:26-28)
   if (generate) {   // behind the bump: the map of seed base[env] + episodes[env] (or the caller's seeds) into dmaps[env]
     rc = launch_mapgen_envs(e, ll, gen_seeds);
     if (rc) return rc;
@@ -1564,6 +1654,7 @@ int mgx_record_episodes(mgx_engine* e, const uint8_t* env_mask) {
   HIP_TRY(hipMemcpyAsync(e->d_done_list, idx.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(e->d_done_n, &n, 4, hipMemcpyHostToDevice, e->stream));
   int rc = launch_episode_stats(e);
+  if (!rc && e->ta_on) rc = launch_time_avg_finish(e);
   if (!rc) rc = mark_replay(e, e->d_done_list, (int)n, 0);
   if (rc) return rc;
   HIP_TRY(hipMemsetAsync(e->d_done_n, 0, 4, e->stream));   // the list belongs to this call only
@@ -1616,6 +1707,120 @@ int mgx_drain_episode_log(mgx_engine* e, uint32_t* records, int32_t max_records,
   HIP_TRY(hipStreamSynchronize(e->stream));
   if (st[0]) HIP_TRY(hipMemcpyAsync(records, e->d_ep_log, (size_t)st[0] * e->ep.log_words * 4, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemsetAsync(e->d_ep_log_state, 0, 8, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  *n_records = (int32_t)st[0];
+  if (n_dropped) *n_dropped = (int32_t)st[1];
+  return MGX_OK;
+}
+
+// ---- time-averaged game stats (csrc/mgx_time_avg.h) -----------------------------------------------------------------------
+static void ta_layout_words(const MgxTaLayout& L, int log_cap, int32_t* out) {
+  const int32_t v[MGX_TAL_COUNT] = {L.NG, L.NGW, L.rec_words, L.rec_words, MGX_TA_HDR, L.off_avg, L.off_seen, L.tot_words, MGX_TA_TOT_HDR, log_cap};
+  memcpy(out, v, sizeof(v));
+}
+int mgx_time_average_layout_of(int32_t num_game_stats, int32_t log_capacity, int32_t* out) {
+  if (!out || num_game_stats < 0 || log_capacity < 0) return fail(MGX_ERR_BAD_ARG, "mgx_time_average_layout_of: null / negative argument");
+  ta_layout_words(mgx_ta_layout(num_game_stats), log_capacity, out);
+  return MGX_OK;
+}
+int mgx_time_average_layout(mgx_engine* e, int32_t* out) {
+  if (!e || !out) return fail(MGX_ERR_BAD_ARG, "mgx_time_average_layout: null argument");
+  if (!e->ta_on) return fail(MGX_ERR_BAD_ARG, "mgx_time_average_layout: time averages are off (mgx_set_time_averages)");
+  ta_layout_words(e->ta.L, e->ta_log_cap, out);
+  return MGX_OK;
+}
+
+int mgx_set_time_averages(mgx_engine* e, int32_t enabled, int32_t log_capacity) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_time_averages: null engine");
+  if (enabled && !e->ep_stats)
+    return fail(MGX_ERR_BAD_ARG, "mgx_set_time_averages: episode statistics are off (mgx_set_episode_stats): the averages are finished on their done list");
+  if (enabled && log_capacity < 0) return fail(MGX_ERR_BAD_ARG, "mgx_set_time_averages: negative log capacity");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  free_time_averages(e);
+  if (!enabled) return MGX_OK;
+#ifdef MGX_CPU_EMU
+  return fail(MGX_ERR_BAD_ARG, "mgx_set_time_averages: not part of the sanitizer build");
+#else
+  static_assert(MGX_TAT_HEADER == MGX_TA_TOT_HDR, "totals header");
+  const MgxDev& d = e->d;
+  e->ta.L = mgx_ta_layout(d.NG);
+  const MgxTaLayout& L = e->ta.L;
+  const size_t E = (size_t)d.E, TW = (size_t)L.tot_words, nch = (E + MGX_EP_CHUNK - 1) / MGX_EP_CHUNK;
+  const size_t sum_bytes = std::max<size_t>(8, E * L.NG * 8), seen_bytes = std::max<size_t>(4, E * L.NGW * 4);
+  HIP_TRY(hipMalloc((void**)&e->ta.sum, sum_bytes));
+  HIP_TRY(hipMalloc((void**)&e->ta.seen, seen_bytes));
+  HIP_TRY(hipMalloc((void**)&e->ta.steps, E * 4));
+  HIP_TRY(hipMalloc((void**)&e->d_ta_rec, E * L.rec_words * 4));
+  HIP_TRY(hipMalloc((void**)&e->d_ta_partial, nch * TW * 8));
+  HIP_TRY(hipMalloc((void**)&e->d_ta_totals, TW * 8));
+  HIP_TRY(hipMalloc((void**)&e->d_ta_snap, TW * 8));
+  HIP_TRY(hipMalloc((void**)&e->d_ta_ticket, 4));
+  HIP_TRY(hipMalloc((void**)&e->d_ta_log_state, 8));
+  HIP_TRY(hipHostMalloc((void**)&e->h_ta_snap, TW * 8, hipHostMallocDefault));
+  HIP_TRY(hipEventCreateWithFlags(&e->ta_ev, hipEventDisableTiming));
+  // an episode's accumulators are zero when it starts; an env inside an episode now finishes it as a partial one
+  HIP_TRY(hipMemsetAsync(e->ta.sum, 0, sum_bytes, e->stream));
+  HIP_TRY(hipMemsetAsync(e->ta.seen, 0, seen_bytes, e->stream));
+  HIP_TRY(hipMemsetAsync(e->ta.steps, 0, E * 4, e->stream));
+  HIP_TRY(hipMemsetAsync(e->d_ta_totals, 0, TW * 8, e->stream));
+  HIP_TRY(hipMemsetAsync(e->d_ta_ticket, 0, 4, e->stream));
+  HIP_TRY(hipMemsetAsync(e->d_ta_log_state, 0, 8, e->stream));
+  if (log_capacity > 0) {
+    HIP_TRY(hipMalloc((void**)&e->d_ta_log, (size_t)log_capacity * L.rec_words * 4));
+    e->ta_log_cap = log_capacity;
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->ta_on = true;
+  return MGX_OK;
+#endif
+}
+
+int mgx_request_time_averages(mgx_engine* e) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_request_time_averages: null engine");
+  if (!e->ta_on) return fail(MGX_ERR_BAD_ARG, "mgx_request_time_averages: time averages are off (mgx_set_time_averages)");
+  if (e->ta_pending) return MGX_OK;   // the snapshot already under way is fetched first; the totals keep accumulating
+#ifndef MGX_CPU_EMU
+  HIP_TRY(hipSetDevice(e->device));
+  const int TW = e->ta.L.tot_words;
+  hipLaunchKernelGGL(mgx_time_avg_snapshot_kernel, dim3(1), dim3(256), 0, e->stream, e->d_ta_totals, e->d_ta_snap, TW);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(e->h_ta_snap, e->d_ta_snap, (size_t)TW * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipEventRecord(e->ta_ev, e->stream));
+  e->ta_pending = true;
+#endif
+  return MGX_OK;
+}
+
+int mgx_fetch_time_averages(mgx_engine* e, int32_t wait, double* totals, int32_t* ready) {
+  if (!e || !totals || !ready) return fail(MGX_ERR_BAD_ARG, "mgx_fetch_time_averages: null argument");
+  *ready = 0;
+  if (!e->ta_on) return fail(MGX_ERR_BAD_ARG, "mgx_fetch_time_averages: time averages are off (mgx_set_time_averages)");
+  if (!e->ta_pending) return MGX_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  if (wait) {
+    HIP_TRY(hipEventSynchronize(e->ta_ev));
+  } else {
+    const hipError_t q = hipEventQuery(e->ta_ev);
+    if (q == hipErrorNotReady) return MGX_OK;
+    if (q != hipSuccess) return fail(MGX_ERR_HIP, std::string("hipEventQuery: ") + hipGetErrorString(q));
+  }
+  memcpy(totals, e->h_ta_snap, (size_t)e->ta.L.tot_words * 8);
+  e->ta_pending = false;
+  *ready = 1;
+  return MGX_OK;
+}
+
+int mgx_drain_time_average_log(mgx_engine* e, uint32_t* records, int32_t max_records, int32_t* n_records, int32_t* n_dropped) {
+  if (!e || !records || !n_records) return fail(MGX_ERR_BAD_ARG, "mgx_drain_time_average_log: null argument");
+  if (!e->ta_on || !e->d_ta_log) return fail(MGX_ERR_BAD_ARG, "mgx_drain_time_average_log: no log (mgx_set_time_averages)");
+  if (max_records < e->ta_log_cap) return fail(MGX_ERR_BAD_ARG, "mgx_drain_time_average_log: the buffer must hold the whole log (log_capacity records)");
+  HIP_TRY(hipSetDevice(e->device));
+  uint32_t st[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(st, e->d_ta_log_state, 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (st[0]) HIP_TRY(hipMemcpyAsync(records, e->d_ta_log, (size_t)st[0] * e->ta.L.rec_words * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemsetAsync(e->d_ta_log_state, 0, 8, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   *n_records = (int32_t)st[0];
   if (n_dropped) *n_dropped = (int32_t)st[1];
@@ -1874,6 +2079,7 @@ int mgx_step(mgx_engine* e) {
   MGX_MARK(5);
 #undef MGX_MARK
   if (e->profiling) e->timing_valid = true;
+  if (e->ta_on) { int trc = launch_time_avg_accum(e); if (trc) return trc; }   // on_step, before the done envs are finished (simulator.py:180-190)
   if (e->auto_reset) {
     e->step_seq++;
 #ifdef MGX_CPU_EMU
@@ -1886,6 +2092,7 @@ int mgx_step(mgx_engine* e) {
                        e->d_counters + 1, e->d_done_list, e->d_done_n);
     HIP_TRY(hipGetLastError());
     if (e->ep_stats) { int erc = launch_episode_stats(e); if (erc) return erc; }
+    if (e->ta_on) { int trc = launch_time_avg_finish(e); if (trc) return trc; }
   }
   if (e->rpl_n) { int prc = launch_replay(e); if (prc) return prc; }
   if (e->ss_on) { int src = launch_step_stats(e); if (src) return src; }   // (behind the episode statistics: a step that ends an episode reports its final values)
@@ -2261,6 +2468,51 @@ static int es_after_write(mgx_engine* e, const int32_t* envs, int32_t n) {
   }
   return MGX_OK;
 }
+// The raw time-average accumulators of a host list of envs (csrc/mgx_time_avg.h), read (put = false) or written through the
+// staged list and d_ta_block; both wait for the device.
+static int ta_state(mgx_engine* e, const int32_t* envs, int32_t n, double* sums, uint32_t* steps, uint32_t* seen, bool put, const char* who) {
+  if (!e || !sums || !steps || !seen) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (!e->ta_on) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": time averages are off (mgx_set_time_averages)");
+  if (!envs || n <= 0) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": empty env list");
+  std::vector<uint8_t> dup(put ? (size_t)e->d.E : 0, 0);
+  for (int32_t k = 0; k < n; k++) {
+    if (envs[k] < 0 || envs[k] >= e->d.E)
+      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": env index " + std::to_string(envs[k]) + " out of range [0, " + std::to_string(e->d.E) + ")");
+    if (put && dup[envs[k]]++) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": env " + std::to_string(envs[k]) + " listed twice");
+  }
+#ifndef MGX_CPU_EMU
+  HIP_TRY(hipSetDevice(e->device));
+  const MgxTaLayout& L = e->ta.L;
+  const size_t sb = (size_t)n * L.NG * 8, wb = (size_t)n * L.NGW * 4, tb = (size_t)n * 4;
+  const int32_t *dl = nullptr, *unused = nullptr;
+  const uint32_t* dn = nullptr;
+  int rc = es_stage_lists(e, envs, nullptr, n, &dl, &unused, &dn);
+  if (rc) return rc;
+  if (put) {
+    rc = reserve_time_avg_block(e, n);
+    if (rc) return rc;
+    if (sb) HIP_TRY(hipMemcpyAsync(e->d_ta_block, sums, sb, hipMemcpyHostToDevice, e->stream));
+    if (wb) HIP_TRY(hipMemcpyAsync(e->d_ta_block + sb, seen, wb, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_ta_block + sb + wb, steps, tb, hipMemcpyHostToDevice, e->stream));
+    rc = move_time_avg(e, dl, n, 1);
+    if (rc) return rc;
+  } else {
+    rc = move_time_avg(e, dl, n, 0);
+    if (rc) return rc;
+    if (sb) HIP_TRY(hipMemcpyAsync(sums, e->d_ta_block, sb, hipMemcpyDeviceToHost, e->stream));
+    if (wb) HIP_TRY(hipMemcpyAsync(seen, e->d_ta_block + sb, wb, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(steps, e->d_ta_block + sb + wb, tb, hipMemcpyDeviceToHost, e->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
+#endif
+  return MGX_OK;
+}
+int mgx_get_time_average_state(mgx_engine* e, const int32_t* envs, int32_t n, double* sums, uint32_t* steps, uint32_t* seen) {
+  return ta_state(e, envs, n, sums, steps, seen, false, "mgx_get_time_average_state");
+}
+int mgx_put_time_average_state(mgx_engine* e, const int32_t* envs, int32_t n, const double* sums, const uint32_t* steps, const uint32_t* seen) {
+  return ta_state(e, envs, n, const_cast<double*>(sums), const_cast<uint32_t*>(steps), const_cast<uint32_t*>(seen), true, "mgx_put_time_average_state");
+}
 int mgx_save_envs(mgx_engine* e, const int32_t* envs, int32_t n, void* dst) {
   if (!e || !dst) return fail(MGX_ERR_BAD_ARG, "mgx_save_envs: null argument");
   int rc = es_check_list(e, envs, n, false, "mgx_save_envs");
@@ -2297,6 +2549,7 @@ int mgx_load_envs(mgx_engine* e, const int32_t* envs, int32_t n, const void* src
   if (rc) return rc;
   es_launch(e, dl, n, (uint8_t*)src, MGX_ES_LOAD);
   HIP_TRY(hipGetLastError());
+  if (e->ta_on) { rc = clear_time_avg(e, dl, dn, n, nullptr); if (rc) return rc; }   // the record holds no accumulators: the episode is partial unless they are put back
   return es_after_write(e, envs, n);
 }
 int mgx_copy_envs(mgx_engine* e, const int32_t* src_envs, const int32_t* dst_envs, int32_t n) {
@@ -2326,6 +2579,11 @@ int mgx_copy_envs(mgx_engine* e, const int32_t* src_envs, const int32_t* dst_env
   if (rc) return rc;
   es_launch(e, dd, n, e->d_es_buf, MGX_ES_LOAD);
   HIP_TRY(hipGetLastError());
+  if (e->ta_on) {   // a fork continues the source's average: every source is read before any destination is written
+    rc = move_time_avg(e, ds, n, 0);
+    if (!rc) rc = move_time_avg(e, dd, n, 1);
+    if (rc) return rc;
+  }
   return es_after_write(e, dst_envs, n);
 }
 

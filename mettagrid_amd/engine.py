@@ -171,6 +171,14 @@ def load_lib():
     L.mgx_request_episode_stats.argtypes = [vp]
     L.mgx_fetch_episode_stats.argtypes = [vp, i32, vp, C.POINTER(i32)]
     L.mgx_drain_episode_log.argtypes = [vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]
+    L.mgx_set_time_averages.argtypes = [vp, i32, i32]
+    L.mgx_time_average_layout.argtypes = [vp, vp]
+    L.mgx_time_average_layout_of.argtypes = [i32, i32, vp]
+    L.mgx_request_time_averages.argtypes = [vp]
+    L.mgx_fetch_time_averages.argtypes = [vp, i32, vp, C.POINTER(i32)]
+    L.mgx_drain_time_average_log.argtypes = [vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]
+    L.mgx_get_time_average_state.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.mgx_put_time_average_state.argtypes = [vp, vp, i32, vp, vp, vp]
     L.mgx_count_objects_with_tag.argtypes = [vp, i32, i32, C.POINTER(i32)]
     L.mgx_set_profiling.argtypes = [vp, i32]
     L.mgx_get_step_timing.argtypes = [vp, vp]
@@ -505,6 +513,7 @@ class BatchedMettaGrid:
         records, with the per-agent rows if asked) before the auto-reset wipes them."""
         _check(self.L.mgx_set_episode_stats(self.h, 1 if enabled else 0, int(log_capacity), 1 if log_per_agent else 0))
         self._epl = None
+        self._tal = None   # (the engine switches the time averages off with the statistics they ride on)
         if enabled:
             out = np.zeros(len(self.EPL), np.int32)
             _check(self.L.mgx_episode_stats_layout(self.h, out.ctypes.data))
@@ -608,6 +617,108 @@ class BatchedMettaGrid:
             for k, v in extra.items():
                 out["agent"][k] = v / A
         return out
+
+    # ---- time-averaged game stats (include/mgx.h "Time-averaged game stats"; the reference's TimeAveragedStatsHandler) ----
+    TAL = ("NG", "SEEN_WORDS", "REC_WORDS", "LOG_WORDS", "HEADER_WORDS", "OFF_AVG", "OFF_SEEN", "TOTALS_WORDS", "TOTALS_HEADER",
+           "LOG_CAPACITY")
+    TA_PARTIAL = 2   # record flags, bit 1
+
+    def set_time_averages(self, enabled: bool = True, log_capacity: int = 0) -> None:
+        """Accumulate every env's game stats after every step on the device and finish ``sum / steps`` per key when its
+        episode ends (time_averaged_stats.py:17-41).  Needs ``set_episode_stats``."""
+        _check(self.L.mgx_set_time_averages(self.h, 1 if enabled else 0, int(log_capacity)))
+        self._tal = None
+        if enabled:
+            out = np.zeros(len(self.TAL), np.int32)
+            _check(self.L.mgx_time_average_layout(self.h, out.ctypes.data))
+            self._tal = {k: int(v) for k, v in zip(self.TAL, out)}
+
+    def _ta_layout(self) -> dict:
+        if getattr(self, "_tal", None) is None:
+            raise ValueError("time averages are off: set_time_averages()")
+        return self._tal
+
+    def time_average_state(self, envs) -> dict:
+        """Raw accumulators of ``envs``: {"sum": f64 [n][NG], "steps": u32 [n], "seen": u32 [n][SEEN_WORDS]}.  Synchronises."""
+        Lw = self._ta_layout()
+        lst = env_list(envs, self.E, "time_average_state")
+        out = {"sum": np.zeros((len(lst), Lw["NG"]), np.float64), "steps": np.zeros(len(lst), np.uint32),
+               "seen": np.zeros((len(lst), Lw["SEEN_WORDS"]), np.uint32)}
+        _check(self.L.mgx_get_time_average_state(self.h, lst.ctypes.data, len(lst), out["sum"].ctypes.data, out["steps"].ctypes.data,
+                                                 out["seen"].ctypes.data))
+        return out
+
+    def put_time_average_state(self, envs, state: dict) -> None:
+        """Write accumulators read by ``time_average_state`` into ``envs`` (e.g. behind ``load_envs``)."""
+        Lw = self._ta_layout()
+        lst = env_list(envs, self.E, "put_time_average_state", unique=True)
+        sums = np.ascontiguousarray(state["sum"], dtype=np.float64)
+        steps = np.ascontiguousarray(state["steps"], dtype=np.uint32)
+        seen = np.ascontiguousarray(state["seen"], dtype=np.uint32)
+        if sums.shape != (len(lst), Lw["NG"]) or steps.shape != (len(lst),) or seen.shape != (len(lst), Lw["SEEN_WORDS"]):
+            raise ValueError(f"put_time_average_state: accumulators of shape {sums.shape}, {steps.shape}, {seen.shape} for "
+                             f"{len(lst)} envs, {Lw['NG']} game stats")
+        _check(self.L.mgx_put_time_average_state(self.h, lst.ctypes.data, len(lst), sums.ctypes.data, steps.ctypes.data, seen.ctypes.data))
+
+    def _ta_keys(self, values, seen_words) -> dict:
+        names = self.prog.game_stat_names
+        return {names[i]: float(values[i]) for i in range(len(values)) if (int(seen_words[i >> 5]) >> (i & 31)) & 1}
+
+    def time_averages(self, envs) -> list:
+        """``TimeAveragedStatsHandler.time_averaged_game_stats`` of ``envs`` read mid-episode: one {key: sum / steps} dict per
+        env, {} at zero steps.  Synchronises with the device."""
+        st = self.time_average_state(envs)
+        return [self._ta_keys(st["sum"][k] / float(st["steps"][k]), st["seen"][k]) if st["steps"][k] else {} for k in range(len(st["steps"]))]
+
+    def request_time_averages(self) -> None:
+        _check(self.L.mgx_request_time_averages(self.h))
+
+    def _fetch_ta_raw(self, wait: bool):
+        out = np.zeros(self._ta_layout()["TOTALS_WORDS"], np.float64)
+        ready = C.c_int32(0)
+        _check(self.L.mgx_fetch_time_averages(self.h, 1 if wait else 0, out.ctypes.data, C.byref(ready)))
+        return out if ready.value else None
+
+    def fetch_time_averages(self, wait: bool = False):
+        """The snapshot requested last as a dict (see ``time_average_totals_dict``), or None while its copy is in flight."""
+        raw = self._fetch_ta_raw(wait)
+        return None if raw is None else self.time_average_totals_dict(raw)
+
+    def drain_time_averages(self) -> dict:
+        """Everything finished up to now, synchronously; a snapshot still in flight is added to a fresh one."""
+        first = self._fetch_ta_raw(True)
+        self.request_time_averages()
+        tot = self._fetch_ta_raw(True)
+        return self.time_average_totals_dict(tot if first is None else first + tot)
+
+    def time_average_totals_dict(self, totals: np.ndarray) -> dict:
+        """Raw totals -> {"episodes", "partial", "sum": {key: f64 sum of the per-episode averages}, "count": {key: episodes
+        holding the key}} (only keys some finished episode held; partial episodes are in neither)."""
+        Lw = self._ta_layout()
+        NG, H = Lw["NG"], Lw["TOTALS_HEADER"]
+        names = self.prog.game_stat_names
+        s, c = totals[H:H + NG], totals[H + NG:H + 2 * NG]
+        return {"episodes": int(totals[0]), "partial": int(totals[1]),
+                "sum": {names[i]: float(s[i]) for i in range(NG) if c[i]},
+                "count": {names[i]: int(c[i]) for i in range(NG) if c[i]}}
+
+    def drain_time_average_log(self):
+        """(list of per-episode dicts, dropped count).  Each dict: env, episode, steps (the env's step at the end), ta_steps
+        (steps accumulated), partial, time_averaged_game_stats {key: f64}."""
+        Lw = self._ta_layout()
+        cap, W, NG = Lw["LOG_CAPACITY"], Lw["LOG_WORDS"], Lw["NG"]
+        if cap <= 0:
+            raise ValueError("no time-average log: set_time_averages(log_capacity=...)")
+        raw = np.zeros((cap, W), np.uint32)
+        n, dropped = C.c_int32(0), C.c_int32(0)
+        _check(self.L.mgx_drain_time_average_log(self.h, raw.ctypes.data, cap, C.byref(n), C.byref(dropped)))
+        out = []
+        for r in raw[:n.value]:
+            avg = np.ascontiguousarray(r[Lw["OFF_AVG"]:Lw["OFF_AVG"] + 2 * NG]).view(np.float64)
+            out.append({"env": int(r[0]), "episode": int(r[1]), "steps": int(r[2]), "ta_steps": int(r[3]),
+                        "partial": bool(int(r[4]) & self.TA_PARTIAL),
+                        "time_averaged_game_stats": self._ta_keys(avg, r[Lw["OFF_SEEN"]:Lw["OFF_SEEN"] + Lw["SEEN_WORDS"]])})
+        return out, dropped.value
 
     # ---- replays of watched envs (include/mgx.h "Replays"; mettagrid_amd/replay.py) ----
     RPL = ("NUM_ENVS", "WORDS_PER_ENV", "STEP_WORDS", "END_WORDS", "SLOT_WORDS", "AMOUNT_WORDS", "GROUPS", "OBJECT_SLOTS", "MAX_STEP_WORDS")

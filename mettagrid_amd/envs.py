@@ -259,6 +259,14 @@ class MettaGridBatchedEnv:
     ``infos["step_info"]``, a ``StepInfo``: the tensors, the key lists and ``payload(env)``, the reference's dict for one env.
     A step that ends an episode reports that episode's final values, the next step those of the restarted episode.  ``reset``
     returns no payload (the tensors are written by steps).  Without keys ``infos`` is what it is without this argument.
+
+    ``time_averaged_stats``: the reference's TimeAveragedStatsHandler (simulator/time_averaged_stats.py:17-41) for every env,
+    accumulated on the device (``BatchedMettaGrid.set_time_averages``; needs ``episode_stats``).  The aggregate ``infos`` gets
+    ``"time_averaged_game": {key: sum of the episodes' averages / episodes}`` — the rule of multi_episode/summary.py:72-74:
+    divided by the number of episodes, not by the number holding the key — and ``"time_averaged_count"`` (and ``"time_averaged_partial": n`` when n of the window's episodes were partial: they are in
+    ``infos["episodes"]`` but in neither of the two); every
+    ``episode_infos()`` entry gets ``"time_averaged_game_stats"`` (and ``"time_averaged_partial": True`` when the accumulation did
+    not cover the whole episode); ``save_state`` / ``load_state`` carry the accumulators in ``EnvState.extra["time_avg"]``.  Off: ``infos`` and ``episode_infos()`` are what they are without this argument.
     """
 
     def __init__(self, prog: Program, num_envs: int, map_fn: Optional[Callable[[int, int], np.ndarray]] = None,
@@ -268,7 +276,10 @@ class MettaGridBatchedEnv:
                  episode_log: int = 0, log_per_agent: bool = False, specialize="auto", replay_envs=None,
                  replay_dir: Optional[str] = None, replay_words_per_env: Optional[int] = None, replay_interval: int = 64,
                  replay_capacity_groups: Optional[dict] = None, map_gen=None, map_seed: int = 0,
-                 map_seed_stride: int = 1 << 16, step_info_keys=None) -> None:
+                 map_seed_stride: int = 1 << 16, step_info_keys=None, time_averaged_stats: bool = False) -> None:
+        if time_averaged_stats and not episode_stats:
+            raise ValueError("time_averaged_stats needs episode_stats")
+        self.time_averaged_stats = bool(time_averaged_stats)
         self._si_keys = parse_step_info_keys(step_info_keys)
         # the game columns of the readout: the distinct stat names, then the step counter when an attribute key asks for it
         self._si_game_columns = list(dict.fromkeys(stat for _, stat in self._si_keys[0]))
@@ -406,6 +417,8 @@ class MettaGridBatchedEnv:
                                          buffers=self._kind, specialize=self.specialize)
         if self.episode_stats:
             self._eng.set_episode_stats(True, self.episode_log, self.log_per_agent)
+            if self.time_averaged_stats:
+                self._eng.set_time_averages(True, self.episode_log)
         self._steps = 0
         if self._si_on and (self._si_game_columns or self._si_keys[2]):
             self._eng.set_step_stats(self._si_game_columns, self._si_keys[2])
@@ -461,17 +474,40 @@ class MettaGridBatchedEnv:
                 "terminated": int(tot["terminated"]),
                 "attributes": {"map_w": int(words[4]), "map_h": int(words[3]), "max_steps": int(words[11]), "seed": self._seed}}
 
+    def _with_time_averages(self, infos: dict, ta: Optional[dict]) -> dict:
+        """The batch's time-averaged game stats beside the aggregate (summary.py:72-74: sum over episodes / episodes).  The two
+        snapshots are requested together, so they cover the same episodes; partial episodes are in neither value."""
+        if ta and ta["episodes"] > 0:
+            infos = dict(infos, time_averaged_game={k: v / ta["episodes"] for k, v in ta["sum"].items()},
+                         time_averaged_count=ta["count"])
+        if ta and ta["partial"] > 0:   # counted in infos["episodes"], in neither time_averaged_game nor its divisor
+            infos = dict(infos, time_averaged_partial=ta["partial"])
+        return infos
+
     def _step_infos(self) -> dict:
         if not self.episode_stats:
             return {}
         eng = self.engine
         self._steps += 1
+        ta_on = self.time_averaged_stats
         if not self._device_restarts or self._kind != "device":   # these paths synchronise with the device every step anyway
-            return self._infos_from_totals(eng.drain_episode_stats()) if self._steps % self.stats_interval == 0 else {}
+            if self._steps % self.stats_interval != 0:
+                return {}
+            out = self._infos_from_totals(eng.drain_episode_stats())
+            return self._with_time_averages(out, eng.drain_time_averages()) if ta_on else out
         out = {}
         if self._steps % self.stats_interval == 0:
-            out = self._infos_from_totals(eng.fetch_episode_stats(wait=False))   # the snapshot requested one interval ago
+            if ta_on:
+                # the two snapshots are requested back to back and fetched as a pair: the time averages' copy lands last, so
+                # once it is there the other one is too (no wait), and until then neither is taken
+                ta = eng.fetch_time_averages(wait=False)
+                if ta is not None:
+                    out = self._with_time_averages(self._infos_from_totals(eng.fetch_episode_stats(wait=True)), ta)
+            else:
+                out = self._infos_from_totals(eng.fetch_episode_stats(wait=False))   # the snapshot requested one interval ago
             eng.request_episode_stats()
+            if ta_on:
+                eng.request_time_averages()
         return out
 
     def check_actions(self, wait: bool = True) -> None:
@@ -525,15 +561,26 @@ class MettaGridBatchedEnv:
         steps, max_steps) + ``env`` / ``episode`` / ``map_index``.  Needs ``episode_log`` > 0; synchronises with the device."""
         self.flush_replays()
         recs, dropped = self.engine.drain_episode_log()
+        ta = None
+        if self.time_averaged_stats:
+            # the two logs have the same capacity, fill at the same finish points and are drained together: joined by position
+            # (an env can finish several episodes between two drains, and without a pool every record says episode 0)
+            ta = self.engine.drain_time_average_log()[0]
+            if len(ta) != len(recs) or any((t["env"], t["steps"]) != (r["env"], r["steps"]) for t, r in zip(ta, recs)):
+                raise RuntimeError("episode_infos: the episode log and the time-average log do not hold the same episodes")
         words = self.prog.words
         out = []
-        for r in recs:
+        for k, r in enumerate(recs):
             info = {"game": r["game"], "agent": r["agent"], "episode_rewards": r["episode_rewards"],
                     "attributes": {"seed": r["seed"], "map_w": int(words[4]), "map_h": int(words[3]), "steps": r["steps"],
                                    "max_steps": int(words[11])},
                     "env": r["env"], "episode": r["episode"], "map_index": r["map_index"]}
             if "per_agent" in r:
                 info["per_agent"] = {str(i): dct for i, dct in enumerate(r["per_agent"])}
+            if ta is not None:
+                info["time_averaged_game_stats"] = ta[k]["time_averaged_game_stats"]
+                if ta[k]["partial"]:
+                    info["time_averaged_partial"] = True
             if (r["env"], r["episode"]) in self.replay_paths:
                 info["replay_path"] = self.replay_paths[(r["env"], r["episode"])]
             out.append(info)
@@ -616,6 +663,10 @@ class MettaGridBatchedEnv:
         st = self.engine.save_envs(lst)
         if not self._device_restarts:
             st.extra["episode"] = self.episode[lst].copy()
+        if self.time_averaged_stats:   # not part of the engine's record: a resumed episode continues its average
+            # one uint32 array [n][2 * NG + seen words + 1] (f64 sums as word pairs, seen bits, steps): survives EnvState.to_dict
+            t = self.engine.time_average_state(lst)
+            st.extra["time_avg"] = np.concatenate([t["sum"].view(np.uint32).reshape(len(lst), -1), t["seen"], t["steps"][:, None]], axis=1)
         return st
 
     def load_state(self, state, envs=None) -> None:
@@ -623,6 +674,11 @@ class MettaGridBatchedEnv:
         from .engine import env_list
         lst = env_list(state.envs if envs is None else envs, self.E, "load_state", unique=True)
         self.engine.load_envs(state, lst)
+        if self.time_averaged_stats and "time_avg" in state.extra:   # (without them the episode ends flagged partial)
+            t = np.ascontiguousarray(state.extra["time_avg"], dtype=np.uint32)
+            ng = len(self.prog.game_stat_names)
+            self.engine.put_time_average_state(lst, {"sum": np.ascontiguousarray(t[:, :2 * ng]).view(np.float64).reshape(len(lst), ng),
+                                                     "seen": t[:, 2 * ng:-1], "steps": t[:, -1]})
         if not self._device_restarts and "episode" in state.extra:
             self.episode[lst] = np.asarray(state.extra["episode"], dtype=np.int64)
 
