@@ -280,6 +280,53 @@ int mgx_drain_time_average_log(mgx_engine* e, uint32_t* records, int32_t max_rec
 int mgx_get_time_average_state(mgx_engine* e, const int32_t* envs, int32_t n, double* sums, uint32_t* steps, uint32_t* seen);
 int mgx_put_time_average_state(mgx_engine* e, const int32_t* envs, int32_t n, const double* sums, const uint32_t* steps, const uint32_t* seen);
 
+/* ---- Per-policy episode statistics (policy_summaries / per_episode_per_policy_avg_rewards of the reference's summary) -------
+ * Reference: build_multi_episode_rollout_summaries (python/src/mettagrid/simulator/multi_episode/summary.py:38-130) splits every
+ * episode's agents by `assignments`, the policy index of each agent: summed_policy_stats[p][key] += float(value) over the
+ * agents of p in agent order (:60-67); per_policy_totals[p] += float(reward), per_policy_counts[p] += 1 and the episode's row
+ * totals[p] / counts[p], or None for a policy without agents (:81-94); avg_agent_metrics = the sums over all episodes divided
+ * by the agent count of the first episode's assignments (:48, 96-103).
+ * Here the caller gives the policy index of every agent row (u8 [E][A], values < num_policies <= MGX_MAX_POLICIES).  On the
+ * done list (auto-reset, or mgx_record_episodes), behind the episode statistics — whose launch flushes the integer counters
+ * into the stat cells first — each finished env gets a record (csrc/mgx_policy_stats.h): per policy and agent-stat column the
+ * f64 sum, started at +0.0, of (double)value over the policy's agents in agent order — the reference's bits for one episode —
+ * a "key exists" bit (touched bit OR value != 0 on some agent of the policy, the rule of mgx_get_stats), the f64 sum of the
+ * policy's agents' episode rewards in agent order and their number.  Records go into a bounded log and into batch totals
+ * accumulated in the order of the episode totals (list order, chunks of 256, chunk sums in chunk order).
+ * The table is SLOT-owned: agent rows are routed to policies by row index, so it is not part of an env's saved state —
+ * mgx_save_envs, mgx_load_envs and mgx_copy_envs never touch it — and an episode is attributed by the table as it stands when
+ * the episode ends.  Needs episode statistics (MGX_ERR_BAD_ARG otherwise); switching those off or setting them again switches
+ * this off.  Off: no kernel is enqueued and no layout word of the other statistics moves. */
+#define MGX_MAX_POLICIES 16   /* the record kernel keeps one f64 sum per policy in registers: 32 VGPRs at 16 */
+/* Totals (doubles): [MGX_PST_EPISODES]; per policy p at MGX_PST_HEADER + MGX_PST_POLICY_WORDS * p the MGX_PSP_* words (AVG_REWARD_*:
+ * over the episodes in which p had an agent, of reward sum / agent count, summary.py:94; min +inf / max -inf without one); at
+ * TOTALS_OFF_SUM [P][NS] sums; at TOTALS_OFF_COUNT [P][NS] counts of episodes in which some agent of p held the key. */
+enum { MGX_PST_EPISODES = 0, MGX_PST_HEADER };
+enum { MGX_PSP_EPISODES = 0, MGX_PSP_AGENT_EPISODES, MGX_PSP_AVG_REWARD_SUM, MGX_PSP_AVG_REWARD_MIN, MGX_PSP_AVG_REWARD_MAX, MGX_PST_POLICY_WORDS };
+/* enabled = 0 frees everything.  Refused before anything is touched (a table set earlier stays in force): num_policies outside
+ * [1, MGX_MAX_POLICIES], an assignment >= num_policies, a negative log capacity (summary.py:48 bincount(minlength)). */
+int mgx_set_policy_stats(mgx_engine* e, int32_t enabled, int32_t num_policies, const uint8_t* assignments /* host u8 [E][A] */,
+                         int32_t log_capacity);
+/* Replace the rows of n slots (no env twice), ordered behind the steps enqueued so far: matchmaking per slot between episodes.
+ * Episodes that end afterwards are attributed by the new rows (summary.py:60-61 reads each episode's own assignments). */
+int mgx_set_policy_assignments(mgx_engine* e, const int32_t* envs, int32_t n, const uint8_t* rows /* host u8 [n][A] */);
+/* Layout words (int32 [MGX_PSL_COUNT]).  A record is REC_WORDS uint32: [0] env [1] episodes the env had finished before
+ * [2] steps [3] flags (as the episode record's: bit 0 every agent terminal, 1 truncated, 2 early end); OFF_REWARD: f64 [P] reward
+ * sums; OFF_COUNT: u32 [P] agents; OFF_SUM: f64 [P][NS]; OFF_BITS: u32 [P][SEEN_WORDS] key-exists bits (summary.py:60-67, 81-94).
+ * mgx_policy_stats_layout_of is a TEST AID: the same words without an engine, so that the layout can be checked on a host
+ * without a GPU; integrations call the first form. */
+enum { MGX_PSL_NS = 0, MGX_PSL_A, MGX_PSL_P, MGX_PSL_SEEN_WORDS, MGX_PSL_REC_WORDS, MGX_PSL_LOG_WORDS, MGX_PSL_HEADER_WORDS, MGX_PSL_OFF_REWARD,
+       MGX_PSL_OFF_COUNT, MGX_PSL_OFF_SUM, MGX_PSL_OFF_BITS, MGX_PSL_TOTALS_WORDS, MGX_PSL_TOTALS_HEADER, MGX_PSL_TOTALS_POLICY_WORDS,
+       MGX_PSL_TOTALS_OFF_SUM, MGX_PSL_TOTALS_OFF_COUNT, MGX_PSL_LOG_CAPACITY, MGX_PSL_COUNT };
+int mgx_policy_stats_layout(mgx_engine* e, int32_t* out /* [MGX_PSL_COUNT] */);
+int mgx_policy_stats_layout_of(int32_t num_agent_stats, int32_t num_agents, int32_t num_policies, int32_t log_capacity,
+                               int32_t* out /* [MGX_PSL_COUNT] */);
+/* Snapshot-and-clear of the totals, as mgx_request_episode_stats / mgx_fetch_episode_stats (summary.py:96-103 divides these). */
+int mgx_request_policy_stats(mgx_engine* e);
+int mgx_fetch_policy_stats(mgx_engine* e, int32_t wait, double* totals /* [MGX_PSL_TOTALS_WORDS] */, int32_t* ready);
+/* The log (oldest first) to host memory, emptied; `records` must hold log_capacity records (summary.py:81-94: one row each). */
+int mgx_drain_policy_log(mgx_engine* e, uint32_t* records, int32_t max_records, int32_t* n_records, int32_t* n_dropped);
+
 /* ---- Chosen stats of every env and agent after every step (the per-step `infos` of MettaGridPufferEnv.step) ----------------
  * Reference: MettaGridPufferEnv(step_info_keys=...) (python/src/mettagrid/envs/mettagrid_puffer_env.py:81, 132-183) reads the
  * chosen game stats, attributes, per-agent stats and the step / episode rewards after every sim.step() and returns them as the

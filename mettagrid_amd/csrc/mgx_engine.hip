@@ -26,6 +26,7 @@
 #include "mgx_mapgen.h"     // the random map builder on the device (mgx_set_map_generator)
 #include "mgx_step_stats.h" // chosen stats of every env / agent read out behind every step (mgx_set_step_stats)
 #include "mgx_time_avg.h"   // time-averaged game stats of every episode (mgx_set_time_averages)
+#include "mgx_policy_stats.h"  // per-policy episode statistics (mgx_set_policy_stats)
 
 
 // Territory ownership map (TerritoryTracker::compute_cell_ownership, core/territory_tracker.cpp:215-252) of every cell,
@@ -301,6 +302,22 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
   size_t ta_block_bytes = 0;
   hipEvent_t ta_ev = nullptr;       // recorded behind the snapshot copy
   bool ta_pending = false;
+  // per-policy episode statistics (mgx_set_policy_stats; csrc/mgx_policy_stats.h): the assignment table belongs to the slots
+  bool ps_on = false;
+  MgxPolicyStats ps{};              // layout + assign u8 [E][A]
+  uint32_t* d_ps_rec = nullptr;     // [E][ps.L.rec_words] records of the envs that finished in the last step
+  double* d_ps_partial = nullptr;   // [ceil(E / 256)][tot_words] chunk sums
+  double* d_ps_totals = nullptr;    // [tot_words] batch totals since the last snapshot
+  double* d_ps_snap = nullptr;      // [tot_words] snapshot taken by mgx_request_policy_stats
+  double* h_ps_snap = nullptr;      // pinned host copy of the snapshot
+  uint32_t* d_ps_ticket = nullptr;  // [1]
+  uint32_t* d_ps_log = nullptr;     // [ps_log_cap][ps.L.rec_words] records kept for mgx_drain_policy_log
+  uint32_t* d_ps_log_state = nullptr;  // [2] records in the log, records dropped
+  int ps_log_cap = 0;
+  uint8_t* d_ps_rows = nullptr;     // [E][A] staging of mgx_set_policy_assignments: the rows of the listed envs
+  int32_t* d_ps_list = nullptr;     // [E] ... and the list
+  hipEvent_t ps_ev = nullptr;       // recorded behind the snapshot copy
+  bool ps_pending = false;
   unsigned long long* d_digest = nullptr;   // [E] mgx_state_digests
   // saved env state (mgx_env_state.h): the record layout, the device segment table, the staging of mgx_copy_envs
   MgxEnvStateLayout es;
@@ -614,8 +631,20 @@ static void free_time_averages(mgx_engine* e) {
   e->d_ta_log = nullptr; e->d_ta_log_state = nullptr; e->d_ta_block = nullptr; e->h_ta_snap = nullptr; e->ta_ev = nullptr;
   e->ta_on = false; e->ta_pending = false; e->ta_log_cap = 0; e->ta_block_bytes = 0;
 }
+static void free_policy_stats(mgx_engine* e) {
+  for (void* p : {(void*)e->ps.assign, (void*)e->d_ps_rec, (void*)e->d_ps_partial, (void*)e->d_ps_totals, (void*)e->d_ps_snap, (void*)e->d_ps_ticket,
+                  (void*)e->d_ps_log, (void*)e->d_ps_log_state, (void*)e->d_ps_rows, (void*)e->d_ps_list})
+    if (p) (void)hipFree(p);
+  if (e->h_ps_snap) (void)hipHostFree(e->h_ps_snap);
+  if (e->ps_ev) (void)hipEventDestroy(e->ps_ev);
+  e->ps = MgxPolicyStats{};
+  e->d_ps_rec = nullptr; e->d_ps_partial = nullptr; e->d_ps_totals = nullptr; e->d_ps_snap = nullptr; e->d_ps_ticket = nullptr;
+  e->d_ps_log = nullptr; e->d_ps_log_state = nullptr; e->d_ps_rows = nullptr; e->d_ps_list = nullptr; e->h_ps_snap = nullptr; e->ps_ev = nullptr;
+  e->ps_on = false; e->ps_pending = false; e->ps_log_cap = 0;
+}
 static void free_episode_stats(mgx_engine* e) {
   free_time_averages(e);   // (the time averages are finished on the episode statistics' done list)
+  free_policy_stats(e);    // (... and so are the per-policy records)
   for (void* p : {(void*)e->d_ep_rec, (void*)e->d_ep_partial, (void*)e->d_ep_totals, (void*)e->d_ep_snap, (void*)e->d_ep_ticket,
                   (void*)e->d_ep_log, (void*)e->d_ep_log_state})
     if (p) (void)hipFree(p);
@@ -647,6 +676,7 @@ static int launch_time_avg_accum(mgx_engine*) { return MGX_OK; }
 static int launch_time_avg_finish(mgx_engine*) { return MGX_OK; }
 static int clear_time_avg(mgx_engine*, const int32_t*, const uint32_t*, int, const uint8_t*) { return MGX_OK; }
 static int move_time_avg(mgx_engine*, const int32_t*, int, int) { return MGX_OK; }
+static int launch_policy_stats(mgx_engine*) { return MGX_OK; }
 static int launch_replay(mgx_engine*) { return MGX_OK; }
 static int mark_replay(mgx_engine*, const int32_t*, int, uint32_t) { return MGX_OK; }
 static int launch_mapgen_envs(mgx_engine*, const MgxList&, const uint32_t*) { return MGX_OK; }
@@ -733,6 +763,26 @@ static int move_time_avg(mgx_engine* e, const int32_t* dlist, int n, int dir) {
   const long long lanes = (long long)n * std::max(1, e->ta.L.NG);
   hipLaunchKernelGGL(mgx_time_avg_move_kernel, dim3((unsigned)std::min<long long>((lanes + 255) / 256, 1024)), dim3(256), 0, e->stream, e->ta,
                      dlist, n, e->d_ta_block, dir);
+  HIP_TRY(hipGetLastError());
+  return MGX_OK;
+}
+// Per-policy episode statistics (csrc/mgx_policy_stats.h) of the envs of the done list: records (+ log), then batch totals in
+// the fixed chunk order.  Behind launch_episode_stats, which has flushed the integer counters into the stat cells.
+static int launch_policy_stats(mgx_engine* e) {
+  MgxList dl;
+  dl.n_host = -1;
+  const int P = e->ps.L.P;
+  auto kernel = P <= 2 ? mgx_policy_record_kernel<2> : P <= 4 ? mgx_policy_record_kernel<4> : P <= 8 ? mgx_policy_record_kernel<8>
+                                                                                                    : mgx_policy_record_kernel<MGX_PS_MAX_POLICIES>;
+  hipLaunchKernelGGL(kernel, dim3((list_grid(e, dl, 128, 2048) + 3) / 4), dim3(256), 0, e->stream, dev_copy(e), e->ps,
+                     (const int32_t*)e->d_done_list, (const uint32_t*)e->d_done_n, e->d_ps_rec, e->d_ps_log, (const uint32_t*)e->d_ps_log_state,
+                     e->ps_log_cap, (const uint32_t*)e->d_early, (const uint32_t*)e->d_episodes);
+  HIP_TRY(hipGetLastError());
+  const int nchunks_max = (e->d.E + MGX_EP_CHUNK - 1) / MGX_EP_CHUNK;
+  const unsigned groups = (unsigned)((P * e->ps.L.NS + P + 255) / 256);   // work items: the (policy, column) sums, then the policy headers
+  hipLaunchKernelGGL(mgx_policy_total_kernel, dim3((unsigned)std::min(nchunks_max, 16), groups), dim3(256), 0, e->stream, e->ps.L,
+                     (const uint32_t*)e->d_done_n, (const uint32_t*)e->d_ps_rec, e->d_ps_partial, e->d_ps_totals, e->d_ps_ticket,
+                     e->d_ps_log_state, e->ps_log_cap, e->d_ps_log ? 1 : 0);
   HIP_TRY(hipGetLastError());
   return MGX_OK;
 }
@@ -1654,6 +1704,7 @@ int mgx_record_episodes(mgx_engine* e, const uint8_t* env_mask) {
   HIP_TRY(hipMemcpyAsync(e->d_done_list, idx.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(e->d_done_n, &n, 4, hipMemcpyHostToDevice, e->stream));
   int rc = launch_episode_stats(e);
+  if (!rc && e->ps_on) rc = launch_policy_stats(e);
   if (!rc && e->ta_on) rc = launch_time_avg_finish(e);
   if (!rc) rc = mark_replay(e, e->d_done_list, (int)n, 0);
   if (rc) return rc;
@@ -1821,6 +1872,163 @@ int mgx_drain_time_average_log(mgx_engine* e, uint32_t* records, int32_t max_rec
   HIP_TRY(hipStreamSynchronize(e->stream));
   if (st[0]) HIP_TRY(hipMemcpyAsync(records, e->d_ta_log, (size_t)st[0] * e->ta.L.rec_words * 4, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemsetAsync(e->d_ta_log_state, 0, 8, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  *n_records = (int32_t)st[0];
+  if (n_dropped) *n_dropped = (int32_t)st[1];
+  return MGX_OK;
+}
+
+// ---- per-policy episode statistics (csrc/mgx_policy_stats.h) ----------------------------------------------------------------
+static void ps_layout_words(const MgxPsLayout& L, int log_cap, int32_t* out) {
+  const int32_t v[MGX_PSL_COUNT] = {L.NS, L.A, L.P, L.NSW, L.rec_words, L.rec_words, MGX_PS_HDR, L.off_rew, L.off_cnt, L.off_sum, L.off_bits,
+                                    L.tot_words, MGX_PS_TOT_HDR, MGX_PS_TOT_POLICY, L.tot_off_sum, L.tot_off_cnt, log_cap};
+  memcpy(out, v, sizeof(v));
+}
+static int ps_check_policies(int32_t P, const char* who) {
+  static_assert(MGX_MAX_POLICIES == MGX_PS_MAX_POLICIES && MGX_PST_HEADER == MGX_PS_TOT_HDR && MGX_PST_POLICY_WORDS == MGX_PS_TOT_POLICY, "mgx.h");
+  if (P < 1 || P > MGX_MAX_POLICIES)
+    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": " + std::to_string(P) + " policies, outside [1, " + std::to_string(MGX_MAX_POLICIES) + "]");
+  return MGX_OK;
+}
+static int ps_check_rows(const uint8_t* rows, size_t n_rows, int A, int P, const char* who) {
+  for (size_t k = 0; k < n_rows * (size_t)A; k++)
+    if (rows[k] >= P)
+      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": row " + std::to_string(k / A) + ", agent " + std::to_string(k % A) + ": policy " +
+                                       std::to_string(rows[k]) + " of " + std::to_string(P));
+  return MGX_OK;
+}
+int mgx_policy_stats_layout_of(int32_t num_agent_stats, int32_t num_agents, int32_t num_policies, int32_t log_capacity, int32_t* out) {
+  if (!out || num_agent_stats < 0 || num_agents < 1 || log_capacity < 0)
+    return fail(MGX_ERR_BAD_ARG, "mgx_policy_stats_layout_of: null / negative argument");
+  { int rc = ps_check_policies(num_policies, "mgx_policy_stats_layout_of"); if (rc) return rc; }
+  ps_layout_words(mgx_ps_layout(num_agent_stats, num_agents, num_agent_stats, num_policies), log_capacity, out);
+  return MGX_OK;
+}
+int mgx_policy_stats_layout(mgx_engine* e, int32_t* out) {
+  if (!e || !out) return fail(MGX_ERR_BAD_ARG, "mgx_policy_stats_layout: null argument");
+  if (!e->ps_on) return fail(MGX_ERR_BAD_ARG, "mgx_policy_stats_layout: policy statistics are off (mgx_set_policy_stats)");
+  ps_layout_words(e->ps.L, e->ps_log_cap, out);
+  return MGX_OK;
+}
+
+int mgx_set_policy_stats(mgx_engine* e, int32_t enabled, int32_t num_policies, const uint8_t* assignments, int32_t log_capacity) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_policy_stats: null engine");
+  if (enabled) {   // every refusal comes before anything is touched
+    if (!e->ep_stats)
+      return fail(MGX_ERR_BAD_ARG, "mgx_set_policy_stats: episode statistics are off (mgx_set_episode_stats): the records are written on their done list");
+    if (!assignments) return fail(MGX_ERR_BAD_ARG, "mgx_set_policy_stats: null assignment table");
+    if (log_capacity < 0) return fail(MGX_ERR_BAD_ARG, "mgx_set_policy_stats: negative log capacity");
+    int rc = ps_check_policies(num_policies, "mgx_set_policy_stats");
+    if (!rc) rc = ps_check_rows(assignments, (size_t)e->d.E, e->d.A, num_policies, "mgx_set_policy_stats");
+    if (rc) return rc;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  free_policy_stats(e);
+  if (!enabled) return MGX_OK;
+#ifdef MGX_CPU_EMU
+  return fail(MGX_ERR_BAD_ARG, "mgx_set_policy_stats: not part of the sanitizer build");
+#else
+  const MgxDev& d = e->d;
+  e->ps.L = mgx_ps_layout(d.NS, d.A, d.NSP, num_policies);
+  const MgxPsLayout& L = e->ps.L;
+  const size_t E = (size_t)d.E, TW = (size_t)L.tot_words, nch = (E + MGX_EP_CHUNK - 1) / MGX_EP_CHUNK, table = E * d.A;
+  HIP_TRY(hipMalloc((void**)&e->ps.assign, table));
+  HIP_TRY(hipMalloc((void**)&e->d_ps_rows, table));
+  HIP_TRY(hipMalloc((void**)&e->d_ps_list, E * 4));
+  HIP_TRY(hipMalloc((void**)&e->d_ps_rec, E * L.rec_words * 4));
+  HIP_TRY(hipMalloc((void**)&e->d_ps_partial, nch * TW * 8));
+  HIP_TRY(hipMalloc((void**)&e->d_ps_totals, TW * 8));
+  HIP_TRY(hipMalloc((void**)&e->d_ps_snap, TW * 8));
+  HIP_TRY(hipMalloc((void**)&e->d_ps_ticket, 4));
+  HIP_TRY(hipMalloc((void**)&e->d_ps_log_state, 8));
+  HIP_TRY(hipHostMalloc((void**)&e->h_ps_snap, TW * 8, hipHostMallocDefault));
+  HIP_TRY(hipEventCreateWithFlags(&e->ps_ev, hipEventDisableTiming));
+  HIP_TRY(hipMemcpyAsync(e->ps.assign, assignments, table, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemsetAsync(e->d_ps_ticket, 0, 4, e->stream));
+  HIP_TRY(hipMemsetAsync(e->d_ps_log_state, 0, 8, e->stream));
+  if (log_capacity > 0) {
+    HIP_TRY(hipMalloc((void**)&e->d_ps_log, (size_t)log_capacity * L.rec_words * 4));
+    e->ps_log_cap = log_capacity;
+  }
+  // totals start as a cleared snapshot would leave them
+  hipLaunchKernelGGL(mgx_policy_snapshot_kernel, dim3(1), dim3(256), 0, e->stream, e->d_ps_totals, e->d_ps_snap, L);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (`assignments` is the caller's)
+  e->ps_on = true;
+  return MGX_OK;
+#endif
+}
+
+int mgx_set_policy_assignments(mgx_engine* e, const int32_t* envs, int32_t n, const uint8_t* rows) {
+  if (!e || !rows) return fail(MGX_ERR_BAD_ARG, "mgx_set_policy_assignments: null argument");
+  if (!e->ps_on) return fail(MGX_ERR_BAD_ARG, "mgx_set_policy_assignments: policy statistics are off (mgx_set_policy_stats)");
+  if (!envs || n <= 0) return fail(MGX_ERR_BAD_ARG, "mgx_set_policy_assignments: empty env list");
+  std::vector<uint8_t> dup((size_t)e->d.E, 0);
+  for (int32_t k = 0; k < n; k++) {
+    if (envs[k] < 0 || envs[k] >= e->d.E)
+      return fail(MGX_ERR_BAD_ARG, "mgx_set_policy_assignments: env index " + std::to_string(envs[k]) + " out of range [0, " + std::to_string(e->d.E) + ")");
+    if (dup[envs[k]]++) return fail(MGX_ERR_BAD_ARG, "mgx_set_policy_assignments: env " + std::to_string(envs[k]) + " listed twice");
+  }
+  { int rc = ps_check_rows(rows, (size_t)n, e->d.A, e->ps.L.P, "mgx_set_policy_assignments"); if (rc) return rc; }
+#ifndef MGX_CPU_EMU
+  HIP_TRY(hipSetDevice(e->device));
+  const long long cells = (long long)n * e->d.A;
+  HIP_TRY(hipMemcpyAsync(e->d_ps_list, envs, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_ps_rows, rows, (size_t)cells, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(mgx_policy_assign_kernel, dim3((unsigned)std::min<long long>((cells + 255) / 256, 1024)), dim3(256), 0, e->stream, e->ps.assign,
+                     (const int32_t*)e->d_ps_list, (int)n, (const uint8_t*)e->d_ps_rows, e->d.A);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (`envs` and `rows` are the caller's, and the staging is reused by the next call)
+#endif
+  return MGX_OK;
+}
+
+int mgx_request_policy_stats(mgx_engine* e) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_request_policy_stats: null engine");
+  if (!e->ps_on) return fail(MGX_ERR_BAD_ARG, "mgx_request_policy_stats: policy statistics are off (mgx_set_policy_stats)");
+  if (e->ps_pending) return MGX_OK;   // the snapshot already under way is fetched first; the totals keep accumulating
+#ifndef MGX_CPU_EMU
+  HIP_TRY(hipSetDevice(e->device));
+  const int TW = e->ps.L.tot_words;
+  hipLaunchKernelGGL(mgx_policy_snapshot_kernel, dim3(1), dim3(256), 0, e->stream, e->d_ps_totals, e->d_ps_snap, e->ps.L);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(e->h_ps_snap, e->d_ps_snap, (size_t)TW * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipEventRecord(e->ps_ev, e->stream));
+  e->ps_pending = true;
+#endif
+  return MGX_OK;
+}
+
+int mgx_fetch_policy_stats(mgx_engine* e, int32_t wait, double* totals, int32_t* ready) {
+  if (!e || !totals || !ready) return fail(MGX_ERR_BAD_ARG, "mgx_fetch_policy_stats: null argument");
+  *ready = 0;
+  if (!e->ps_on) return fail(MGX_ERR_BAD_ARG, "mgx_fetch_policy_stats: policy statistics are off (mgx_set_policy_stats)");
+  if (!e->ps_pending) return MGX_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  if (wait) {
+    HIP_TRY(hipEventSynchronize(e->ps_ev));
+  } else {
+    const hipError_t q = hipEventQuery(e->ps_ev);
+    if (q == hipErrorNotReady) return MGX_OK;
+    if (q != hipSuccess) return fail(MGX_ERR_HIP, std::string("hipEventQuery: ") + hipGetErrorString(q));
+  }
+  memcpy(totals, e->h_ps_snap, (size_t)e->ps.L.tot_words * 8);
+  e->ps_pending = false;
+  *ready = 1;
+  return MGX_OK;
+}
+
+int mgx_drain_policy_log(mgx_engine* e, uint32_t* records, int32_t max_records, int32_t* n_records, int32_t* n_dropped) {
+  if (!e || !records || !n_records) return fail(MGX_ERR_BAD_ARG, "mgx_drain_policy_log: null argument");
+  if (!e->ps_on || !e->d_ps_log) return fail(MGX_ERR_BAD_ARG, "mgx_drain_policy_log: no log (mgx_set_policy_stats)");
+  if (max_records < e->ps_log_cap) return fail(MGX_ERR_BAD_ARG, "mgx_drain_policy_log: the buffer must hold the whole log (log_capacity records)");
+  HIP_TRY(hipSetDevice(e->device));
+  uint32_t st[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(st, e->d_ps_log_state, 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (st[0]) HIP_TRY(hipMemcpyAsync(records, e->d_ps_log, (size_t)st[0] * e->ps.L.rec_words * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemsetAsync(e->d_ps_log_state, 0, 8, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   *n_records = (int32_t)st[0];
   if (n_dropped) *n_dropped = (int32_t)st[1];
@@ -2092,6 +2300,7 @@ int mgx_step(mgx_engine* e) {
                        e->d_counters + 1, e->d_done_list, e->d_done_n);
     HIP_TRY(hipGetLastError());
     if (e->ep_stats) { int erc = launch_episode_stats(e); if (erc) return erc; }
+    if (e->ps_on) { int prc = launch_policy_stats(e); if (prc) return prc; }
     if (e->ta_on) { int trc = launch_time_avg_finish(e); if (trc) return trc; }
   }
   if (e->rpl_n) { int prc = launch_replay(e); if (prc) return prc; }

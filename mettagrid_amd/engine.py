@@ -179,6 +179,13 @@ def load_lib():
     L.mgx_drain_time_average_log.argtypes = [vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.mgx_get_time_average_state.argtypes = [vp, vp, i32, vp, vp, vp]
     L.mgx_put_time_average_state.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.mgx_set_policy_stats.argtypes = [vp, i32, i32, vp, i32]
+    L.mgx_set_policy_assignments.argtypes = [vp, vp, i32, vp]
+    L.mgx_policy_stats_layout.argtypes = [vp, vp]
+    L.mgx_policy_stats_layout_of.argtypes = [i32, i32, i32, i32, vp]
+    L.mgx_request_policy_stats.argtypes = [vp]
+    L.mgx_fetch_policy_stats.argtypes = [vp, i32, vp, C.POINTER(i32)]
+    L.mgx_drain_policy_log.argtypes = [vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.mgx_count_objects_with_tag.argtypes = [vp, i32, i32, C.POINTER(i32)]
     L.mgx_set_profiling.argtypes = [vp, i32]
     L.mgx_get_step_timing.argtypes = [vp, vp]
@@ -514,6 +521,7 @@ class BatchedMettaGrid:
         _check(self.L.mgx_set_episode_stats(self.h, 1 if enabled else 0, int(log_capacity), 1 if log_per_agent else 0))
         self._epl = None
         self._tal = None   # (the engine switches the time averages off with the statistics they ride on)
+        self._psl = None   # (... and the per-policy statistics)
         if enabled:
             out = np.zeros(len(self.EPL), np.int32)
             _check(self.L.mgx_episode_stats_layout(self.h, out.ctypes.data))
@@ -719,6 +727,119 @@ class BatchedMettaGrid:
                         "partial": bool(int(r[4]) & self.TA_PARTIAL),
                         "time_averaged_game_stats": self._ta_keys(avg, r[Lw["OFF_SEEN"]:Lw["OFF_SEEN"] + Lw["SEEN_WORDS"]])})
         return out, dropped.value
+
+    # ---- per-policy episode statistics (include/mgx.h "Per-policy episode statistics"; multi_episode/summary.py:38-130) ----
+    PSL = ("NS", "A", "P", "SEEN_WORDS", "REC_WORDS", "LOG_WORDS", "HEADER_WORDS", "OFF_REWARD", "OFF_COUNT", "OFF_SUM", "OFF_BITS",
+           "TOTALS_WORDS", "TOTALS_HEADER", "TOTALS_POLICY_WORDS", "TOTALS_OFF_SUM", "TOTALS_OFF_COUNT", "LOG_CAPACITY")
+    MAX_POLICIES = 16   # MGX_MAX_POLICIES
+
+    def _policy_rows(self, rows, n: int, what: str) -> np.ndarray:
+        """Assignments as a contiguous u8 [n][A]: one row for all (``[A]``) or one per env."""
+        a = np.asarray(rows)
+        if a.ndim == 1:
+            a = np.broadcast_to(a, (n, len(a)))
+        if a.shape != (n, self.A) or a.size == 0:
+            raise ValueError(f"{what}: assignments of shape {np.asarray(rows).shape} for {n} envs of {self.A} agents")
+        if (a < 0).any() or (a > 255).any():
+            raise ValueError(f"{what}: a policy index outside [0, 255]")
+        return np.ascontiguousarray(a, dtype=np.uint8)
+
+    def set_policy_stats(self, enabled: bool = True, num_policies: int = 0, assignments=None, log_capacity: int = 0) -> None:
+        """Reduce every finished episode's agent stats and returns per policy on the device; ``assignments``: the policy index
+        of every agent row, ``[A]`` or ``[E][A]``.  Needs ``set_episode_stats``.  A refused call leaves the earlier setting."""
+        if not enabled:
+            _check(self.L.mgx_set_policy_stats(self.h, 0, 0, None, 0))
+            self._psl = None
+            return
+        rows = self._policy_rows(assignments, self.E, "set_policy_stats")
+        _check(self.L.mgx_set_policy_stats(self.h, 1, int(num_policies), rows.ctypes.data, int(log_capacity)))
+        out = np.zeros(len(self.PSL), np.int32)
+        _check(self.L.mgx_policy_stats_layout(self.h, out.ctypes.data))
+        self._psl = {k: int(v) for k, v in zip(self.PSL, out)}
+
+    def _ps_layout(self) -> dict:
+        if getattr(self, "_psl", None) is None:
+            raise ValueError("policy statistics are off: set_policy_stats()")
+        return self._psl
+
+    def set_policy_assignments(self, envs, rows) -> None:
+        """Replace the assignment rows of ``envs`` (``rows``: ``[A]`` or ``[n][A]``), behind the steps enqueued so far."""
+        self._ps_layout()
+        lst = env_list(envs, self.E, "set_policy_assignments", unique=True)
+        r = self._policy_rows(rows, len(lst), "set_policy_assignments")
+        _check(self.L.mgx_set_policy_assignments(self.h, lst.ctypes.data, len(lst), r.ctypes.data))
+
+    def request_policy_stats(self) -> None:
+        _check(self.L.mgx_request_policy_stats(self.h))
+
+    def _fetch_ps_raw(self, wait: bool):
+        out = np.zeros(self._ps_layout()["TOTALS_WORDS"], np.float64)
+        ready = C.c_int32(0)
+        _check(self.L.mgx_fetch_policy_stats(self.h, 1 if wait else 0, out.ctypes.data, C.byref(ready)))
+        return out if ready.value else None
+
+    def fetch_policy_stats(self, wait: bool = False):
+        """The snapshot requested last as a dict (see ``policy_totals_dict``), or None while its copy is in flight."""
+        raw = self._fetch_ps_raw(wait)
+        return None if raw is None else self.policy_totals_dict(raw)
+
+    def drain_policy_stats(self) -> dict:
+        """Everything finished up to now, synchronously; a snapshot still in flight is merged with a fresh one (sums and
+        counts add, minima / maxima combine)."""
+        first = self._fetch_ps_raw(True)
+        self.request_policy_stats()
+        tot = self._fetch_ps_raw(True)
+        if first is not None:
+            Lw = self._psl
+            base = Lw["TOTALS_HEADER"] + Lw["TOTALS_POLICY_WORDS"] * np.arange(Lw["P"])
+            lo, hi = base + 3, base + 4   # MGX_PSP_AVG_REWARD_MIN / _MAX
+            merged = first + tot
+            merged[lo] = np.minimum(first[lo], tot[lo])
+            merged[hi] = np.maximum(first[hi], tot[hi])
+            tot = merged
+        return self.policy_totals_dict(tot)
+
+    def policy_totals_dict(self, totals: np.ndarray) -> dict:
+        """Raw totals -> {"episodes", "policies": [{"episodes", "agent_episodes", "avg_reward_sum", "avg_reward_min",
+        "avg_reward_max", "agent_sum": {key: f64}, "agent_count": {key: episodes}}]} (only keys some agent of the policy held)."""
+        Lw = self._ps_layout()
+        NS, P, H, W = Lw["NS"], Lw["P"], Lw["TOTALS_HEADER"], Lw["TOTALS_POLICY_WORDS"]
+        names = self.prog.agent_stat_names
+        pols = []
+        for p in range(P):
+            h = totals[H + W * p:H + W * (p + 1)]
+            s = totals[Lw["TOTALS_OFF_SUM"] + p * NS:Lw["TOTALS_OFF_SUM"] + (p + 1) * NS]
+            c = totals[Lw["TOTALS_OFF_COUNT"] + p * NS:Lw["TOTALS_OFF_COUNT"] + (p + 1) * NS]
+            pols.append({"episodes": int(h[0]), "agent_episodes": int(h[1]), "avg_reward_sum": float(h[2]), "avg_reward_min": float(h[3]),
+                         "avg_reward_max": float(h[4]),
+                         "agent_sum": {names[i]: float(s[i]) for i in range(NS) if c[i]},
+                         "agent_count": {names[i]: int(c[i]) for i in range(NS) if c[i]}})
+        return {"episodes": int(totals[0]), "policies": pols}
+
+    def drain_policy_log(self):
+        """(list of per-episode dicts, dropped count); see ``policy_record_dict``."""
+        Lw = self._ps_layout()
+        cap, W = Lw["LOG_CAPACITY"], Lw["LOG_WORDS"]
+        if cap <= 0:
+            raise ValueError("no policy log: set_policy_stats(log_capacity=...)")
+        raw = np.zeros((cap, W), np.uint32)
+        n, dropped = C.c_int32(0), C.c_int32(0)
+        _check(self.L.mgx_drain_policy_log(self.h, raw.ctypes.data, cap, C.byref(n), C.byref(dropped)))
+        return [self.policy_record_dict(raw[i]) for i in range(n.value)], dropped.value
+
+    def policy_record_dict(self, rec: np.ndarray) -> dict:
+        """One record -> env, episode, steps, flags, reward_sum (f64 [P]), agents (int [P]), avg_rewards ([P] float or None:
+        the episode's row of per_episode_per_policy_avg_rewards), policies [P] of {key: f64 sum over the policy's agents}."""
+        Lw = self._ps_layout()
+        NS, P, SW = Lw["NS"], Lw["P"], Lw["SEEN_WORDS"]
+        names = self.prog.agent_stat_names
+        rew = np.ascontiguousarray(rec[Lw["OFF_REWARD"]:Lw["OFF_REWARD"] + 2 * P]).view(np.float64).copy()
+        cnt = rec[Lw["OFF_COUNT"]:Lw["OFF_COUNT"] + P].astype(np.int64)
+        sums = np.ascontiguousarray(rec[Lw["OFF_SUM"]:Lw["OFF_SUM"] + 2 * P * NS]).view(np.float64).reshape(P, NS)
+        bits = rec[Lw["OFF_BITS"]:Lw["OFF_BITS"] + P * SW].reshape(P, SW)
+        return {"env": int(rec[0]), "episode": int(rec[1]), "steps": int(rec[2]), "flags": int(rec[3]), "reward_sum": rew, "agents": cnt,
+                "avg_rewards": [float(rew[p] / cnt[p]) if cnt[p] > 0 else None for p in range(P)],
+                "policies": [{names[i]: float(sums[p, i]) for i in range(NS) if (int(bits[p, i >> 5]) >> (i & 31)) & 1} for p in range(P)]}
 
     # ---- replays of watched envs (include/mgx.h "Replays"; mettagrid_amd/replay.py) ----
     RPL = ("NUM_ENVS", "WORDS_PER_ENV", "STEP_WORDS", "END_WORDS", "SLOT_WORDS", "AMOUNT_WORDS", "GROUPS", "OBJECT_SLOTS", "MAX_STEP_WORDS")

@@ -267,6 +267,17 @@ class MettaGridBatchedEnv:
     ``infos["episodes"]`` but in neither of the two); every
     ``episode_infos()`` entry gets ``"time_averaged_game_stats"`` (and ``"time_averaged_partial": True`` when the accumulation did
     not cover the whole episode); ``save_state`` / ``load_state`` carry the accumulators in ``EnvState.extra["time_avg"]``.  Off: ``infos`` and ``episode_infos()`` are what they are without this argument.
+
+    ``policy_assignments`` (``[A]``, every env alike, or ``[E][A]``) and ``num_policies`` (default: the largest index + 1): which
+    policy drives which agent row, for evaluating several policies in one game; every finished episode's agent stats and
+    returns are reduced per policy on the device (``BatchedMettaGrid.set_policy_stats``; needs ``episode_stats``), in the
+    arithmetic of multi_episode/summary.py:38-130.  The aggregate ``infos`` gets ``"policy"``: per policy ``episodes`` (those in
+    which it had an agent), ``agent_episodes``, ``avg_reward`` ({mean, min, max} of the per-episode average reward, or None),
+    ``agent_sum`` {key: f64 sum over its agents and the episodes} and ``agent_count`` {key: episodes}; every ``episode_infos()``
+    entry gets ``"assignments"`` (the row the episode ended under) and ``"policy_avg_rewards"`` ([P] floats or None: the
+    reference's per_episode_per_policy_avg_rewards row).  ``policy_ids`` (int64 [E * A]) and ``policy_rows(p)`` route
+    observations and actions; ``set_policy_assignments(envs, rows)`` rematches slots between episodes.  The table belongs to
+    the slots: ``save_state`` / ``load_state`` do not move it.  Off: ``infos`` and ``episode_infos()`` are unchanged.
     """
 
     def __init__(self, prog: Program, num_envs: int, map_fn: Optional[Callable[[int, int], np.ndarray]] = None,
@@ -276,9 +287,25 @@ class MettaGridBatchedEnv:
                  episode_log: int = 0, log_per_agent: bool = False, specialize="auto", replay_envs=None,
                  replay_dir: Optional[str] = None, replay_words_per_env: Optional[int] = None, replay_interval: int = 64,
                  replay_capacity_groups: Optional[dict] = None, map_gen=None, map_seed: int = 0,
-                 map_seed_stride: int = 1 << 16, step_info_keys=None, time_averaged_stats: bool = False) -> None:
+                 map_seed_stride: int = 1 << 16, step_info_keys=None, time_averaged_stats: bool = False,
+                 policy_assignments=None, num_policies: Optional[int] = None) -> None:
         if time_averaged_stats and not episode_stats:
             raise ValueError("time_averaged_stats needs episode_stats")
+        if policy_assignments is not None and not episode_stats:
+            raise ValueError("policy_assignments needs episode_stats")
+        if policy_assignments is None and num_policies is not None:
+            raise ValueError("num_policies needs policy_assignments")
+        self._policy_table = None         # host copy of the engine's assignment table, u8 [E][A]
+        if policy_assignments is not None:
+            a = np.asarray(policy_assignments)
+            if a.ndim == 1:
+                a = np.broadcast_to(a, (num_envs, len(a)))
+            if a.shape != (num_envs, prog.num_agents) or a.dtype.kind not in "iub" or (a < 0).any() or (a > 255).any():
+                raise ValueError(f"policy_assignments: integers in [0, 255] of shape [{prog.num_agents}] or [{num_envs}][{prog.num_agents}]")
+            self._policy_table = np.array(a, dtype=np.uint8)
+            self.num_policies = int(a.max()) + 1 if num_policies is None else int(num_policies)
+        self._policy_ids = None
+        self._pending_infos: list = []    # episodes drained by set_policy_assignments, returned by the next episode_infos()
         self.time_averaged_stats = bool(time_averaged_stats)
         self._si_keys = parse_step_info_keys(step_info_keys)
         # the game columns of the readout: the distinct stat names, then the step counter when an attribute key asks for it
@@ -419,6 +446,10 @@ class MettaGridBatchedEnv:
             self._eng.set_episode_stats(True, self.episode_log, self.log_per_agent)
             if self.time_averaged_stats:
                 self._eng.set_time_averages(True, self.episode_log)
+            if self._policy_table is not None:
+                self._eng.set_policy_stats(True, self.num_policies, self._policy_table, self.episode_log)
+        self._policy_ids = None
+        self._pending_infos = []
         self._steps = 0
         if self._si_on and (self._si_game_columns or self._si_keys[2]):
             self._eng.set_step_stats(self._si_game_columns, self._si_keys[2])
@@ -484,31 +515,88 @@ class MettaGridBatchedEnv:
             infos = dict(infos, time_averaged_partial=ta["partial"])
         return infos
 
+    @staticmethod
+    def _with_policies(infos: dict, ps: Optional[dict]) -> dict:
+        """The batch's per-policy totals beside the aggregate (requested with it, so over the same episodes)."""
+        if not ps or ps["episodes"] == 0:
+            return infos
+        pol = [{"episodes": p["episodes"], "agent_episodes": p["agent_episodes"],
+                "avg_reward": {"mean": p["avg_reward_sum"] / p["episodes"], "min": p["avg_reward_min"], "max": p["avg_reward_max"]}
+                if p["episodes"] else None,
+                "agent_sum": p["agent_sum"], "agent_count": p["agent_count"]} for p in ps["policies"]]
+        return dict(infos, policy=pol)
+
     def _step_infos(self) -> dict:
         if not self.episode_stats:
             return {}
         eng = self.engine
         self._steps += 1
-        ta_on = self.time_averaged_stats
+        ta_on, ps_on = self.time_averaged_stats, self._policy_table is not None
         if not self._device_restarts or self._kind != "device":   # these paths synchronise with the device every step anyway
             if self._steps % self.stats_interval != 0:
                 return {}
             out = self._infos_from_totals(eng.drain_episode_stats())
-            return self._with_time_averages(out, eng.drain_time_averages()) if ta_on else out
+            if ta_on:
+                out = self._with_time_averages(out, eng.drain_time_averages())
+            return self._with_policies(out, eng.drain_policy_stats()) if ps_on else out
         out = {}
         if self._steps % self.stats_interval == 0:
-            if ta_on:
-                # the two snapshots are requested back to back and fetched as a pair: the time averages' copy lands last, so
-                # once it is there the other one is too (no wait), and until then neither is taken
-                ta = eng.fetch_time_averages(wait=False)
-                if ta is not None:
-                    out = self._with_time_averages(self._infos_from_totals(eng.fetch_episode_stats(wait=True)), ta)
+            if ta_on or ps_on:
+                # the snapshots are requested back to back and fetched together: the copy of the one requested last lands
+                # last, so once it is there the others are too (no wait), and until then none is taken
+                ps = eng.fetch_policy_stats(wait=False) if ps_on else None
+                ta = eng.fetch_time_averages(wait=ps is not None) if ta_on and (ps is not None or not ps_on) else None
+                if (ps if ps_on else ta) is not None:
+                    out = self._infos_from_totals(eng.fetch_episode_stats(wait=True))
+                    if ta_on:
+                        out = self._with_time_averages(out, ta)
+                    out = self._with_policies(out, ps)
             else:
                 out = self._infos_from_totals(eng.fetch_episode_stats(wait=False))   # the snapshot requested one interval ago
             eng.request_episode_stats()
             if ta_on:
                 eng.request_time_averages()
+            if ps_on:
+                eng.request_policy_stats()
         return out
+
+    # ---- policies (policy_assignments) ----
+    @property
+    def policy_ids(self):
+        """The policy index of every agent row, int64 [E * A] where the buffers are (a device tensor with device buffers)."""
+        if self._policy_table is None:
+            raise ValueError("no policy_assignments")
+        if self._policy_ids is None:
+            flat = self._policy_table.reshape(-1).astype(np.int64)
+            if self._kind == "device":
+                import torch
+                self._policy_ids = torch.from_numpy(flat).to(self.engine.obs.device)
+            else:
+                self._policy_ids = flat
+        return self._policy_ids
+
+    def policy_rows(self, p: int):
+        """The agent rows policy ``p`` drives, ascending: the index of an ``index_select`` on observations or actions."""
+        ids = self.policy_ids
+        if self._kind == "device":
+            import torch
+            return torch.nonzero(ids == int(p)).reshape(-1)
+        return np.nonzero(ids == int(p))[0]
+
+    def set_policy_assignments(self, envs, rows) -> None:
+        """Replace the assignment rows of ``envs`` (``rows``: ``[A]`` or ``[n][A]``): episodes that end from now on are
+        attributed by them.  Synchronises; the episodes logged so far are kept, with the rows they ended under, for the next
+        ``episode_infos()``."""
+        if self._policy_table is None:
+            raise ValueError("no policy_assignments")
+        from .engine import env_list
+        lst = env_list(envs, self.E, "set_policy_assignments", unique=True)
+        if self.episode_log > 0:
+            self._pending_infos += self._drain_episode_infos()
+        self.engine.set_policy_assignments(lst, rows)
+        r = np.asarray(rows)
+        self._policy_table[lst] = r if r.ndim == 2 else np.broadcast_to(r, (len(lst), len(r)))
+        self._policy_ids = None
 
     def check_actions(self, wait: bool = True) -> None:
         """Raise the reference's ValueError for a joint action id the device-side decode found out of range
@@ -559,6 +647,11 @@ class MettaGridBatchedEnv:
         """The episodes that finished since the last call, one dict each in the reference's shape (stats_tracker.py:26-76):
         ``game``, ``agent``, ``per_agent`` (with ``log_per_agent``), ``episode_rewards``, ``attributes`` (seed, map_w, map_h,
         steps, max_steps) + ``env`` / ``episode`` / ``map_index``.  Needs ``episode_log`` > 0; synchronises with the device."""
+        out = self._pending_infos + self._drain_episode_infos()
+        self._pending_infos = []
+        return out
+
+    def _drain_episode_infos(self) -> list:
         self.flush_replays()
         recs, dropped = self.engine.drain_episode_log()
         ta = None
@@ -568,6 +661,11 @@ class MettaGridBatchedEnv:
             ta = self.engine.drain_time_average_log()[0]
             if len(ta) != len(recs) or any((t["env"], t["steps"]) != (r["env"], r["steps"]) for t, r in zip(ta, recs)):
                 raise RuntimeError("episode_infos: the episode log and the time-average log do not hold the same episodes")
+        ps = None
+        if self._policy_table is not None:   # joined by position, as the time-average log
+            ps = self.engine.drain_policy_log()[0]
+            if len(ps) != len(recs) or any((t["env"], t["steps"]) != (r["env"], r["steps"]) for t, r in zip(ps, recs)):
+                raise RuntimeError("episode_infos: the episode log and the policy log do not hold the same episodes")
         words = self.prog.words
         out = []
         for k, r in enumerate(recs):
@@ -581,6 +679,9 @@ class MettaGridBatchedEnv:
                 info["time_averaged_game_stats"] = ta[k]["time_averaged_game_stats"]
                 if ta[k]["partial"]:
                     info["time_averaged_partial"] = True
+            if ps is not None:
+                info["assignments"] = [int(x) for x in self._policy_table[r["env"]]]
+                info["policy_avg_rewards"] = ps[k]["avg_rewards"]
             if (r["env"], r["episode"]) in self.replay_paths:
                 info["replay_path"] = self.replay_paths[(r["env"], r["episode"])]
             out.append(info)

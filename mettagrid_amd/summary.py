@@ -73,3 +73,29 @@ def summarize_episodes(episodes: list, assignments, num_policies: int) -> dict:
 
     return {"episodes": n, "policy_summaries": policies, "avg_game_stats": avg_game, "avg_time_averaged_game_stats": avg_ta,
             "per_episode_per_policy_avg_rewards": per_episode}
+
+
+def summarize_policy_totals(window_totals, assignments_of_first_episode) -> dict:
+    """The per-policy half of the summary from the device's totals (``BatchedMettaGrid.policy_totals_dict``: one window's
+    dict, or a list of windows' dicts, added in list order) instead of per-agent log rows.
+
+    The reference's own rule is kept (summary.py:48, 96-103): ``agent_count`` = bincount of the FIRST episode's assignments and
+    ``avg_agent_metrics[key]`` = the sum over ALL episodes and agents of the policy / that count, keys sorted — not a
+    per-episode mean when assignments differ between episodes or there are several episodes.  ``agent_episodes`` (how many
+    agent rows the sums run over) is returned beside it, so a caller can form ``sum / agent_episodes``.
+    Returns ``{"episodes", "policy_summaries": [{"agent_count", "avg_agent_metrics", "action_timeouts", "agent_episodes"}]}``."""
+    windows = [window_totals] if isinstance(window_totals, dict) else list(window_totals)
+    num_policies = len(windows[0]["policies"]) if windows else 0
+    counts = np.bincount(np.asarray(list(assignments_of_first_episode), dtype=np.int64), minlength=num_policies)   # summary.py:48
+    policies = []
+    for p in range(num_policies):
+        summed: dict = {}
+        agent_episodes = 0
+        for w in windows:
+            for key, value in w["policies"][p]["agent_sum"].items():
+                summed[key] = summed.get(key, 0.0) + float(value)
+            agent_episodes += int(w["policies"][p]["agent_episodes"])
+        count = int(counts[p])
+        metrics = {k: v / count for k, v in sorted(summed.items())} if count > 0 else {}   # summary.py:96-103
+        policies.append({"agent_count": count, "avg_agent_metrics": metrics, "action_timeouts": 0, "agent_episodes": agent_episodes})
+    return {"episodes": sum(int(w["episodes"]) for w in windows), "policy_summaries": policies}
