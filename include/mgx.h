@@ -327,6 +327,55 @@ int mgx_fetch_policy_stats(mgx_engine* e, int32_t wait, double* totals /* [MGX_P
 /* The log (oldest first) to host memory, emptied; `records` must hold log_capacity records (summary.py:81-94: one row each). */
 int mgx_drain_policy_log(mgx_engine* e, uint32_t* records, int32_t max_records, int32_t* n_records, int32_t* n_dropped);
 
+/* ---- Weighted map-pool sampling and per-map episode statistics (csrc/mgx_pool_sample.h) -------------------------
+ * Reference: the map cache hands every new episode a uniformly random cached map (python/src/mettagrid/simulator/map_cache.py:
+ * 207-215: rng.integers(0, len(maps_list))), the trainers' curricula feed per-task returns back into the task distribution and
+ * StatsTracker reports per_label_rewards (python/src/mettagrid/envs/stats_tracker.py:59-60).  The two halves of that loop on the
+ * device; how scores become weights stays with the caller.
+ * THE DRAW.  With sampling on, the auto-reset that makes env slot e's episode counter k plays the pool map
+ *   m = the smallest m with u < edge[m],
+ *   u = Generator(PCG64(SeedSequence(sample_seed, spawn_key=(a, k)))).integers(0, 2**32, dtype=uint32), a = (env_offset + e) mod 2^32
+ * (numpy's own stream: the low half of its first output; sample_seed 12345, a 7, k 3 gives 652139049).  It depends on
+ * (sample_seed, a, k) alone, not on which envs restart together.  A kernel behind the restart's bump writes the index, so
+ * mgx_get_episodes, episode-log word [2] and replays carry it as they carry the rotation rule's.  Not affected: a slot's first
+ * episode (the maps of mgx_create, word [2] = -1), mgx_reset_envs_from_pool (the caller names the map) and generator mode (with a
+ * pool and a generator both set the pool is the source, as without sampling).  mgx_save_envs / mgx_load_envs / mgx_copy_envs
+ * move the episode counter and the current index as before (record_bytes is unchanged): a forked env draws with its
+ * destination slot and the moved count.  Seed, offset and thresholds belong to the slots.
+ * THRESHOLDS (host, f64): C_m = C_(m-1) + w_m sequentially; edge[m] = (uint64) floor(C_m / C_(M-1) * 4294967296.0) for m < M - 1,
+ * edge[M-1] = 2^32.  A zero weight has an empty interval and is never drawn; so may a positive weight below 2^-32 of the total.
+ * Refused with MGX_ERR_BAD_ARG before anything is touched (an earlier setting stays in force): a negative, NaN or infinite weight,
+ * a zero or infinite total, no map pool.  mgx_set_map_pool with another n_maps is refused while sampling or map statistics are
+ * on; the same size keeps them. */
+/* TEST AIDS without an engine, host only (the library loads on a host without a GPU): the thresholds of n weights, and the
+ * uniform words of n (a, k) keys — the source the device kernel runs. */
+int mgx_pool_quantise(const double* weights, int32_t n, uint64_t* edges /* [n] */);
+int mgx_pool_draw_words(uint32_t sample_seed, const uint32_t* a, const uint32_t* k, int32_t n, uint32_t* out);
+/* weights: f64 [n_maps of the pool] host memory, or NULL = off (the rotation rule of mgx_set_auto_reset again, from the next
+ * restart on).  Setting it again replaces thresholds, seed and offset. */
+int mgx_set_pool_sampling(mgx_engine* e, const double* weights, uint32_t sample_seed, uint32_t env_offset);
+/* Replace the thresholds, ordered on the engine's stream through pinned staging: the call does not wait for the device and the
+ * restarts of the next mgx_step draw with the new weights (steps enqueued earlier keep the old ones); of two calls with no step
+ * between them the last wins. */
+int mgx_set_pool_weights(mgx_engine* e, const double* weights);
+/* The device kernel on n caller-given (env slot, episode count) pairs (host memory) -> pool indices; no env is touched.  What
+ * mgx_generate_maps is to the generator: the map slot `env` plays as its episode `episodes[i]`. */
+int mgx_pool_draws(mgx_engine* e, const int32_t* envs, const uint32_t* episodes, int32_t n, int32_t* map_index_out);
+/* MAP STATISTICS.  Behind the episode records of every step (auto-reset, or mgx_record_episodes) one thread per record adds it to
+ * row m = record word [2], or to row n_maps ("unattributed") when that is -1 (a slot's first episode).  Columns (uint64, vector
+ * atomics: integer sums, minima and maxima commute, so the table is exact and order-free):
+ *   EPISODES, TERMINATED (flag bit 0: every agent terminal), LENGTH_SUM (steps),
+ *   Q_SUM: sum of q = (int64) rint(r * 2^20), round-half-even, two's complement — fixed point BY DEFINITION, which is what lets
+ *          the table be compared word for word; r = the record's f64 reward sum / A, the value MGX_EPT_RETURN_SUM sums (finite),
+ *   KEY_MIN / KEY_MAX: of key(r), the total-order map of an f64 (all bits flipped if negative, else the sign bit set).
+ * A cleared row is 0 0 0 0 ~0 0.  Needs episode statistics and a map pool (MGX_ERR_BAD_ARG otherwise); switching the episode
+ * statistics off or setting them again switches this off.  The table belongs to the slots.  Off: nothing is enqueued. */
+enum { MGX_MS_EPISODES = 0, MGX_MS_TERMINATED, MGX_MS_LENGTH_SUM, MGX_MS_Q_SUM, MGX_MS_KEY_MIN, MGX_MS_KEY_MAX, MGX_MS_COUNT };
+int mgx_set_map_stats(mgx_engine* e, int32_t enabled);
+/* Snapshot-and-clear of the table, as mgx_request_episode_stats / mgx_fetch_episode_stats. */
+int mgx_request_map_stats(mgx_engine* e);
+int mgx_fetch_map_stats(mgx_engine* e, int32_t wait, uint64_t* table /* [n_maps + 1][MGX_MS_COUNT] */, int32_t* ready);
+
 /* ---- Chosen stats of every env and agent after every step (the per-step `infos` of MettaGridPufferEnv.step) ----------------
  * Reference: MettaGridPufferEnv(step_info_keys=...) (python/src/mettagrid/envs/mettagrid_puffer_env.py:81, 132-183) reads the
  * chosen game stats, attributes, per-agent stats and the step / episode rewards after every sim.step() and returns them as the

@@ -27,6 +27,7 @@
 #include "mgx_step_stats.h" // chosen stats of every env / agent read out behind every step (mgx_set_step_stats)
 #include "mgx_time_avg.h"   // time-averaged game stats of every episode (mgx_set_time_averages)
 #include "mgx_policy_stats.h"  // per-policy episode statistics (mgx_set_policy_stats)
+#include "mgx_pool_sample.h"   // weighted draws of the next pool map, per-map episode statistics (mgx_set_pool_sampling)
 
 
 // Territory ownership map (TerritoryTracker::compute_cell_ownership, core/territory_tracker.cpp:215-252) of every cell,
@@ -318,6 +319,20 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
   int32_t* d_ps_list = nullptr;     // [E] ... and the list
   hipEvent_t ps_ev = nullptr;       // recorded behind the snapshot copy
   bool ps_pending = false;
+  // weighted pool sampling (mgx_set_pool_sampling; csrc/mgx_pool_sample.h): thresholds, seed and offset belong to the slots
+  bool smp_on = false;              // (false: the restarts enqueue nothing for it and the rotation rule stands)
+  uint32_t smp_seed = 0, smp_offset = 0;
+  unsigned long long* d_smp_edges = nullptr;   // [n_pool] thresholds the draw kernel reads
+  unsigned long long* h_smp_edges = nullptr;   // pinned [MGX_SMP_RING][n_pool] staging of mgx_set_pool_weights ...
+  hipEvent_t smp_ev[4] = {};                   // ... and the event behind each slot's upload: a slot is reused once it has landed
+  int smp_slot = 0;
+  // per-map episode statistics (mgx_set_map_stats): the table belongs to the slots
+  bool ms_on = false;               // (false: nothing is enqueued behind the episode records)
+  unsigned long long* d_ms_table = nullptr;    // [n_pool + 1][MGX_MS_COLS] since the last snapshot
+  unsigned long long* d_ms_snap = nullptr;     // snapshot taken by mgx_request_map_stats
+  unsigned long long* h_ms_snap = nullptr;     // pinned host copy of the snapshot
+  hipEvent_t ms_ev = nullptr;       // recorded behind the snapshot copy
+  bool ms_pending = false;
   unsigned long long* d_digest = nullptr;   // [E] mgx_state_digests
   // saved env state (mgx_env_state.h): the record layout, the device segment table, the staging of mgx_copy_envs
   MgxEnvStateLayout es;
@@ -642,9 +657,26 @@ static void free_policy_stats(mgx_engine* e) {
   e->d_ps_log = nullptr; e->d_ps_log_state = nullptr; e->d_ps_rows = nullptr; e->d_ps_list = nullptr; e->h_ps_snap = nullptr; e->ps_ev = nullptr;
   e->ps_on = false; e->ps_pending = false; e->ps_log_cap = 0;
 }
+#define MGX_SMP_RING 4
+static void free_pool_sampling(mgx_engine* e) {
+  if (e->d_smp_edges) (void)hipFree(e->d_smp_edges);
+  if (e->h_smp_edges) (void)hipHostFree(e->h_smp_edges);
+  for (hipEvent_t& ev : e->smp_ev) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
+  e->d_smp_edges = nullptr; e->h_smp_edges = nullptr;
+  e->smp_on = false; e->smp_slot = 0;
+}
+static void free_map_stats(mgx_engine* e) {
+  if (e->d_ms_table) (void)hipFree(e->d_ms_table);
+  if (e->d_ms_snap) (void)hipFree(e->d_ms_snap);
+  if (e->h_ms_snap) (void)hipHostFree(e->h_ms_snap);
+  if (e->ms_ev) (void)hipEventDestroy(e->ms_ev);
+  e->d_ms_table = nullptr; e->d_ms_snap = nullptr; e->h_ms_snap = nullptr; e->ms_ev = nullptr;
+  e->ms_on = false; e->ms_pending = false;
+}
 static void free_episode_stats(mgx_engine* e) {
   free_time_averages(e);   // (the time averages are finished on the episode statistics' done list)
   free_policy_stats(e);    // (... and so are the per-policy records)
+  free_map_stats(e);       // (... and the per-map table reads the episode records)
   for (void* p : {(void*)e->d_ep_rec, (void*)e->d_ep_partial, (void*)e->d_ep_totals, (void*)e->d_ep_snap, (void*)e->d_ep_ticket,
                   (void*)e->d_ep_log, (void*)e->d_ep_log_state})
     if (p) (void)hipFree(p);
@@ -677,6 +709,8 @@ static int launch_time_avg_finish(mgx_engine*) { return MGX_OK; }
 static int clear_time_avg(mgx_engine*, const int32_t*, const uint32_t*, int, const uint8_t*) { return MGX_OK; }
 static int move_time_avg(mgx_engine*, const int32_t*, int, int) { return MGX_OK; }
 static int launch_policy_stats(mgx_engine*) { return MGX_OK; }
+static int launch_map_stats(mgx_engine*) { return MGX_OK; }
+static int launch_pool_draw(mgx_engine*, const MgxList&) { return MGX_OK; }
 static int launch_replay(mgx_engine*) { return MGX_OK; }
 static int mark_replay(mgx_engine*, const int32_t*, int, uint32_t) { return MGX_OK; }
 static int launch_mapgen_envs(mgx_engine*, const MgxList&, const uint32_t*) { return MGX_OK; }
@@ -783,6 +817,27 @@ static int launch_policy_stats(mgx_engine* e) {
   hipLaunchKernelGGL(mgx_policy_total_kernel, dim3((unsigned)std::min(nchunks_max, 16), groups), dim3(256), 0, e->stream, e->ps.L,
                      (const uint32_t*)e->d_done_n, (const uint32_t*)e->d_ps_rec, e->d_ps_partial, e->d_ps_totals, e->d_ps_ticket,
                      e->d_ps_log_state, e->ps_log_cap, e->d_ps_log ? 1 : 0);
+  HIP_TRY(hipGetLastError());
+  return MGX_OK;
+}
+// Per-map episode statistics (csrc/mgx_pool_sample.h): the step's episode records -> the table, one thread per record.  Behind
+// launch_episode_stats, which wrote the records.
+static int launch_map_stats(mgx_engine* e) {
+  MgxList dl;
+  dl.n_host = -1;
+  hipLaunchKernelGGL(mgx_map_stats_kernel, dim3((list_grid(e, dl, 128, 2048) + 255) / 256), dim3(256), 0, e->stream, (const uint32_t*)e->d_done_n,
+                     (const uint32_t*)e->d_ep_rec, e->ep.rec_words, e->d.A, e->n_pool, e->d_ms_table);
+  HIP_TRY(hipGetLastError());
+  return MGX_OK;
+}
+// Weighted pool sampling (csrc/mgx_pool_sample.h): the listed envs' next pool map, behind the bump of mgx_clear_rows_kernel
+// (whose rotation-rule index it overwrites).
+static int launch_pool_draw(mgx_engine* e, const MgxList& l) {
+  if (!l.list) return fail(MGX_ERR_BAD_ARG, "pool sampling: the restart has no env list");
+  const MgxPoolSample s{e->d_smp_edges, e->n_pool, e->smp_seed, e->smp_offset};
+  hipLaunchKernelGGL(mgx_pool_draw_kernel, dim3((list_grid(e, l, 128, 2048) + 255) / 256), dim3(256), 0, e->stream, s, l.list,
+                     l.n_host >= 0 ? (const uint32_t*)nullptr : l.n, l.n_host >= 0 ? l.n_host : 0, (const uint32_t*)e->d_episodes,
+                     (const uint32_t*)nullptr, e->d_map_index);
   HIP_TRY(hipGetLastError());
   return MGX_OK;
 }
@@ -998,6 +1053,7 @@ void mgx_destroy(mgx_engine* e) {
   if (e->jit_obs.mod) (void)hipModuleUnload(e->jit_obs.mod);
   if (e->jit_actx.mod) (void)hipModuleUnload(e->jit_actx.mod);
   free_episode_stats(e);
+  free_pool_sampling(e);
   free_replay(e);
   free_step_stats(e);
   for (int i = 0; i <= MGX_T_COUNT; i++) if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
@@ -1094,6 +1150,7 @@ static int restart_masked(mgx_engine* e, const uint8_t* dmask, bool from_pool, b
                      e->pool_stride, ll.list, ll.n);
   HIP_TRY(hipGetLastError());
   if (e->ta_on) { rc = clear_time_avg(e, ll.list, ll.n, ll.n_host, dmask); if (rc) return rc; }   // on_episode_start (time_averaged_stats.py:26-28)
+  if (bump && from_pool && e->smp_on) { rc = launch_pool_draw(e, ll); if (rc) return rc; }   // (replaces the index the bump has just written)
   if (generate) {   // behind the bump: the map of seed base[env] + episodes[env] (or the caller's seeds) into dmaps[env]
     rc = launch_mapgen_envs(e, ll, gen_seeds);
     if (rc) return rc;
@@ -1215,6 +1272,9 @@ int mgx_reset_envs(mgx_engine* e, const uint8_t* env_mask, const uint16_t* class
 
 int mgx_set_map_pool(mgx_engine* e, const uint16_t* class_maps, int32_t n_maps) {
   if (!e || !class_maps || n_maps <= 0) return fail(MGX_ERR_BAD_ARG, "mgx_set_map_pool: null/empty argument");
+  if ((e->smp_on || e->ms_on) && n_maps != e->n_pool)   // (thresholds and table rows are per pool map; the same size keeps them)
+    return fail(MGX_ERR_BAD_ARG, "mgx_set_map_pool: " + std::to_string(n_maps) + " maps, but pool sampling / map statistics are on for " +
+                                     std::to_string(e->n_pool) + ": switch them off first (mgx_set_pool_sampling, mgx_set_map_stats)");
   HIP_TRY(hipSetDevice(e->device));
   const MgxDev& d = e->d;
   const size_t HW = (size_t)d.H * d.W;
@@ -1704,6 +1764,7 @@ int mgx_record_episodes(mgx_engine* e, const uint8_t* env_mask) {
   HIP_TRY(hipMemcpyAsync(e->d_done_list, idx.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(e->d_done_n, &n, 4, hipMemcpyHostToDevice, e->stream));
   int rc = launch_episode_stats(e);
+  if (!rc && e->ms_on) rc = launch_map_stats(e);
   if (!rc && e->ps_on) rc = launch_policy_stats(e);
   if (!rc && e->ta_on) rc = launch_time_avg_finish(e);
   if (!rc) rc = mark_replay(e, e->d_done_list, (int)n, 0);
@@ -2035,6 +2096,150 @@ int mgx_drain_policy_log(mgx_engine* e, uint32_t* records, int32_t max_records, 
   return MGX_OK;
 }
 
+#ifndef MGX_CPU_EMU
+// ---- weighted pool sampling and per-map episode statistics (csrc/mgx_pool_sample.h) ------------------------------------------
+int mgx_pool_quantise(const double* weights, int32_t n, uint64_t* edges) {
+  static_assert(sizeof(uint64_t) == sizeof(unsigned long long) && MGX_MS_COUNT == MGX_MS_COLS, "mgx.h");
+  if (const char* why = mgx_pool_quantise_host(weights, n, (unsigned long long*)edges)) return fail(MGX_ERR_BAD_ARG, std::string("mgx_pool_quantise: ") + why);
+  return MGX_OK;
+}
+int mgx_pool_draw_words(uint32_t sample_seed, const uint32_t* a, const uint32_t* k, int32_t n, uint32_t* out) {
+  if (!a || !k || !out || n < 0) return fail(MGX_ERR_BAD_ARG, "mgx_pool_draw_words: null / negative argument");
+  for (int32_t i = 0; i < n; i++) out[i] = mgx_pool_draw_word(sample_seed, a[i], k[i]);
+  return MGX_OK;
+}
+
+// Thresholds of `weights` through the next pinned slot to the device, ordered on the engine's stream.  The host waits only when
+// the slot's upload of MGX_SMP_RING calls ago has not landed yet.
+static int upload_pool_edges(mgx_engine* e, const std::vector<unsigned long long>& edges) {
+  const int slot = e->smp_slot;
+  e->smp_slot = (slot + 1) % MGX_SMP_RING;
+  HIP_TRY(hipEventSynchronize(e->smp_ev[slot]));   // (an event never recorded counts as complete)
+  unsigned long long* h = e->h_smp_edges + (size_t)slot * e->n_pool;
+  memcpy(h, edges.data(), edges.size() * 8);
+  HIP_TRY(hipMemcpyAsync(e->d_smp_edges, h, edges.size() * 8, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipEventRecord(e->smp_ev[slot], e->stream));
+  return MGX_OK;
+}
+
+int mgx_set_pool_sampling(mgx_engine* e, const double* weights, uint32_t sample_seed, uint32_t env_offset) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_pool_sampling: null engine");
+  std::vector<unsigned long long> edges;
+  if (weights) {   // every refusal comes before anything is touched
+    if (e->n_pool <= 0) return fail(MGX_ERR_BAD_ARG, "mgx_set_pool_sampling: no map pool (mgx_set_map_pool)");
+    edges.resize((size_t)e->n_pool);
+    if (const char* why = mgx_pool_quantise_host(weights, e->n_pool, edges.data()))
+      return fail(MGX_ERR_BAD_ARG, std::string("mgx_set_pool_sampling: ") + why);
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  if (!weights) {
+    if (e->smp_on) HIP_TRY(hipStreamSynchronize(e->stream));   // (restarts enqueued earlier still read the thresholds)
+    free_pool_sampling(e);
+    return MGX_OK;
+  }
+  if (!e->smp_on) {
+    HIP_TRY(hipMalloc((void**)&e->d_smp_edges, edges.size() * 8));
+    HIP_TRY(hipHostMalloc((void**)&e->h_smp_edges, (size_t)MGX_SMP_RING * edges.size() * 8, hipHostMallocDefault));
+    for (hipEvent_t& ev : e->smp_ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  }
+  int rc = upload_pool_edges(e, edges);
+  if (rc) { free_pool_sampling(e); return rc; }
+  e->smp_seed = sample_seed; e->smp_offset = env_offset;
+  e->smp_on = true;
+  return MGX_OK;
+}
+
+int mgx_set_pool_weights(mgx_engine* e, const double* weights) {
+  if (!e || !weights) return fail(MGX_ERR_BAD_ARG, "mgx_set_pool_weights: null argument");
+  if (!e->smp_on) return fail(MGX_ERR_BAD_ARG, "mgx_set_pool_weights: pool sampling is off (mgx_set_pool_sampling)");
+  std::vector<unsigned long long> edges((size_t)e->n_pool);
+  if (const char* why = mgx_pool_quantise_host(weights, e->n_pool, edges.data()))
+    return fail(MGX_ERR_BAD_ARG, std::string("mgx_set_pool_weights: ") + why);
+  HIP_TRY(hipSetDevice(e->device));
+  return upload_pool_edges(e, edges);
+}
+
+int mgx_pool_draws(mgx_engine* e, const int32_t* envs, const uint32_t* episodes, int32_t n, int32_t* map_index_out) {
+  if (!e || !envs || !episodes || !map_index_out) return fail(MGX_ERR_BAD_ARG, "mgx_pool_draws: null argument");
+  if (!e->smp_on) return fail(MGX_ERR_BAD_ARG, "mgx_pool_draws: pool sampling is off (mgx_set_pool_sampling)");
+  if (n <= 0) return n == 0 ? MGX_OK : fail(MGX_ERR_BAD_ARG, "mgx_pool_draws: negative count");
+  for (int32_t k = 0; k < n; k++)
+    if (envs[k] < 0 || envs[k] >= e->d.E)
+      return fail(MGX_ERR_BAD_ARG, "mgx_pool_draws: env index " + std::to_string(envs[k]) + " out of range [0, " + std::to_string(e->d.E) + ")");
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t col = ((size_t)n * 4 + 15) & ~(size_t)15;
+  int rc = stage(e, 3 * col);
+  if (rc) return rc;
+  uint8_t* st = (uint8_t*)e->d_stage;
+  HIP_TRY(hipMemcpyAsync(st, envs, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(st + col, episodes, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+  const MgxPoolSample s{e->d_smp_edges, e->n_pool, e->smp_seed, e->smp_offset};
+  hipLaunchKernelGGL(mgx_pool_draw_kernel, dim3((unsigned)std::min(((size_t)n + 255) / 256, (size_t)2048)), dim3(256), 0, e->stream, s, (const int32_t*)st,
+                     (const uint32_t*)nullptr, (int)n, (const uint32_t*)nullptr, (const uint32_t*)(st + col), (int32_t*)(st + 2 * col));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(map_index_out, st + 2 * col, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (the arrays are the caller's)
+  return MGX_OK;
+}
+
+int mgx_set_map_stats(mgx_engine* e, int32_t enabled) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_map_stats: null engine");
+  if (enabled) {   // every refusal comes before anything is touched
+    if (!e->ep_stats)
+      return fail(MGX_ERR_BAD_ARG, "mgx_set_map_stats: episode statistics are off (mgx_set_episode_stats): the table is built from their records");
+    if (e->n_pool <= 0) return fail(MGX_ERR_BAD_ARG, "mgx_set_map_stats: no map pool (mgx_set_map_pool)");
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  free_map_stats(e);
+  if (!enabled) return MGX_OK;
+  const size_t words = ((size_t)e->n_pool + 1) * MGX_MS_COLS;
+  HIP_TRY(hipMalloc((void**)&e->d_ms_table, words * 8));
+  HIP_TRY(hipMalloc((void**)&e->d_ms_snap, words * 8));
+  HIP_TRY(hipHostMalloc((void**)&e->h_ms_snap, words * 8, hipHostMallocDefault));
+  HIP_TRY(hipEventCreateWithFlags(&e->ms_ev, hipEventDisableTiming));
+  // the table starts as a cleared snapshot would leave it
+  hipLaunchKernelGGL(mgx_map_stats_snapshot_kernel, dim3(1), dim3(256), 0, e->stream, e->d_ms_table, e->d_ms_snap, (int)words);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->ms_on = true;
+  return MGX_OK;
+}
+
+int mgx_request_map_stats(mgx_engine* e) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_request_map_stats: null engine");
+  if (!e->ms_on) return fail(MGX_ERR_BAD_ARG, "mgx_request_map_stats: map statistics are off (mgx_set_map_stats)");
+  if (e->ms_pending) return MGX_OK;   // the snapshot already under way is fetched first; the table keeps accumulating
+  HIP_TRY(hipSetDevice(e->device));
+  const int words = (e->n_pool + 1) * MGX_MS_COLS;
+  hipLaunchKernelGGL(mgx_map_stats_snapshot_kernel, dim3(1), dim3(256), 0, e->stream, e->d_ms_table, e->d_ms_snap, words);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(e->h_ms_snap, e->d_ms_snap, (size_t)words * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipEventRecord(e->ms_ev, e->stream));
+  e->ms_pending = true;
+  return MGX_OK;
+}
+
+int mgx_fetch_map_stats(mgx_engine* e, int32_t wait, uint64_t* table, int32_t* ready) {
+  if (!e || !table || !ready) return fail(MGX_ERR_BAD_ARG, "mgx_fetch_map_stats: null argument");
+  *ready = 0;
+  if (!e->ms_on) return fail(MGX_ERR_BAD_ARG, "mgx_fetch_map_stats: map statistics are off (mgx_set_map_stats)");
+  if (!e->ms_pending) return MGX_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  if (wait) {
+    HIP_TRY(hipEventSynchronize(e->ms_ev));
+  } else {
+    const hipError_t q = hipEventQuery(e->ms_ev);
+    if (q == hipErrorNotReady) return MGX_OK;
+    if (q != hipSuccess) return fail(MGX_ERR_HIP, std::string("hipEventQuery: ") + hipGetErrorString(q));
+  }
+  memcpy(table, e->h_ms_snap, ((size_t)e->n_pool + 1) * MGX_MS_COLS * 8);
+  e->ms_pending = false;
+  *ready = 1;
+  return MGX_OK;
+}
+#endif  // MGX_CPU_EMU
+
 int mgx_set_replay(mgx_engine* e, const int32_t* envs, int32_t n_envs, int32_t words_per_env, const int32_t* static_type_ids,
                    int32_t n_static) {
   if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_replay: null engine");
@@ -2300,6 +2505,7 @@ int mgx_step(mgx_engine* e) {
                        e->d_counters + 1, e->d_done_list, e->d_done_n);
     HIP_TRY(hipGetLastError());
     if (e->ep_stats) { int erc = launch_episode_stats(e); if (erc) return erc; }
+    if (e->ms_on) { int mrc = launch_map_stats(e); if (mrc) return mrc; }
     if (e->ps_on) { int prc = launch_policy_stats(e); if (prc) return prc; }
     if (e->ta_on) { int trc = launch_time_avg_finish(e); if (trc) return trc; }
   }

@@ -65,19 +65,25 @@ struct MgxMapScene {
 
 #ifndef MGX_CPU_EMU
 struct MgxU128 { unsigned long long hi, lo; };
-__device__ __forceinline__ MgxU128 mgx_mul128(MgxU128 a, MgxU128 b) {   // low 128 bits of the product
-  return {__umul64hi(a.lo, b.lo) + a.hi * b.lo + a.lo * b.hi, a.lo * b.lo};
+// (the seeding is __host__ __device__: csrc/mgx_pool_sample.h runs it on the host too, from this one source)
+__host__ __device__ __forceinline__ MgxU128 mgx_mul128(MgxU128 a, MgxU128 b) {   // low 128 bits of the product
+#ifdef __HIP_DEVICE_COMPILE__
+  const unsigned long long hi = __umul64hi(a.lo, b.lo);
+#else
+  const unsigned long long hi = (unsigned long long)(((unsigned __int128)a.lo * b.lo) >> 64);
+#endif
+  return {hi + a.hi * b.lo + a.lo * b.hi, a.lo * b.lo};
 }
-__device__ __forceinline__ MgxU128 mgx_add128(MgxU128 a, MgxU128 b) {
+__host__ __device__ __forceinline__ MgxU128 mgx_add128(MgxU128 a, MgxU128 b) {
   const unsigned long long lo = a.lo + b.lo;
   return {a.hi + b.hi + (lo < a.lo ? 1ull : 0ull), lo};
 }
 #define MGX_PCG_MULT (MgxU128{0x2360ED051FC65DA4ull, 0x4385DF649FCCF645ull})
 
-// SeedSequence(seed).generate_state(4, uint64) -> PCG64 state and increment after pcg64_set_seed.  KEYED: of
-// SeedSequence(seed, spawn_key=(key,)).
-template <bool KEYED = false>
-__device__ __forceinline__ void mgx_pcg64_seed(uint32_t seed, MgxU128& state, MgxU128& inc, uint32_t key = 0) {
+// SeedSequence(seed).generate_state(4, uint64) -> PCG64 state and increment after pcg64_set_seed.  NKEYS words of `keys`: of
+// SeedSequence(seed, spawn_key=keys), one mix(pool[d], hashmix(word)) round over the pool per word, in key order.
+template <int NKEYS>
+__host__ __device__ __forceinline__ void mgx_pcg64_seed_keys(uint32_t seed, MgxU128& state, MgxU128& inc, const uint32_t* keys) {
   uint32_t hc = 0x43b0d7e5u;
   auto hashmix = [&](uint32_t v) {
     v ^= hc; hc *= 0x931e8875u; v *= hc;
@@ -96,9 +102,10 @@ __device__ __forceinline__ void mgx_pcg64_seed(uint32_t seed, MgxU128& state, Mg
 #pragma unroll
     for (int d = 0; d < 4; d++)
       if (s != d) pool[d] = mix(pool[d], hashmix(pool[s]));
-  if (KEYED)
 #pragma unroll
-    for (int d = 0; d < 4; d++) pool[d] = mix(pool[d], hashmix(key));
+  for (int q = 0; q < NKEYS; q++)
+#pragma unroll
+    for (int d = 0; d < 4; d++) pool[d] = mix(pool[d], hashmix(keys[q]));
   uint32_t hb = 0x8b51f9ddu, w[8];
 #pragma unroll
   for (int i = 0; i < 8; i++) {
@@ -113,6 +120,11 @@ __device__ __forceinline__ void mgx_pcg64_seed(uint32_t seed, MgxU128& state, Mg
   MgxU128 s = inc;                                   // state 0 stepped once
   s = mgx_add128(s, MgxU128{v64[0], v64[1]});
   state = mgx_add128(mgx_mul128(s, MGX_PCG_MULT), inc);
+}
+// KEYED: of SeedSequence(seed, spawn_key=(key,)).
+template <bool KEYED = false>
+__device__ __forceinline__ void mgx_pcg64_seed(uint32_t seed, MgxU128& state, MgxU128& inc, uint32_t key = 0) {
+  mgx_pcg64_seed_keys<KEYED ? 1 : 0>(seed, state, inc, &key);
 }
 
 // The draw consumer: a PCG64 stream handed out in rounds of 64 outputs = 128 halves (lane l computes output l of the round

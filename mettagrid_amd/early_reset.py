@@ -14,7 +14,8 @@ def seedseq_pool(seeds, key=None):
     """SeedSequence(int seed < 2**32).pool for many seeds at once (numpy/random/bit_generator.pyx).  ``key`` (an int <
     2**32): the pool of ``SeedSequence(seed, spawn_key=(key,))``, the key-th child of ``spawn`` — the one-word entropy is
     padded with zeros to the pool size, the key is the fifth word, and mix_entropy hash-mixes every word past the pool into
-    each pool word after the 4 x 4 mixing."""
+    each pool word after the 4 x 4 mixing.  A tuple of ints or of [n] arrays: ``spawn_key=key``, one such round per word in key
+    order (pool_sampling.draw_words keys a stream by (env, episode))."""
     n = len(seeds)
     INIT_A, MULT_A = 0x43b0d7e5, 0x931e8875
     MIX_L, MIX_R = np.uint64(0xca01f9dd), np.uint64(0x4973f715)
@@ -33,8 +34,8 @@ def seedseq_pool(seeds, key=None):
         for d in range(4):
             if s != d:
                 pool[d] = mix(pool[d], hashmix(pool[s]))
-    if key is not None:
-        word = np.full(n, int(key), np.uint64)
+    for k in (() if key is None else key if isinstance(key, tuple) else (key,)):
+        word = np.broadcast_to(np.asarray(k, dtype=np.uint64), (n,))
         for d in range(4):
             pool[d] = mix(pool[d], hashmix(word))
     return pool

@@ -220,6 +220,16 @@ def load_lib():
         L.mgx_generate_maps.argtypes = [vp, vp, i32, vp, i32]
         L.mgx_reset_envs_generated.argtypes = [vp, vp, vp, vp]
         L.mgx_get_map_seeds.argtypes = [vp, vp]
+    if hasattr(L, "mgx_set_pool_sampling"):   # (absent from the CPU sanitizer build)
+        u32 = C.c_uint32
+        L.mgx_pool_quantise.argtypes = [vp, i32, vp]
+        L.mgx_pool_draw_words.argtypes = [u32, vp, vp, i32, vp]
+        L.mgx_set_pool_sampling.argtypes = [vp, vp, u32, u32]
+        L.mgx_set_pool_weights.argtypes = [vp, vp]
+        L.mgx_pool_draws.argtypes = [vp, vp, vp, i32, vp]
+        L.mgx_set_map_stats.argtypes = [vp, i32]
+        L.mgx_request_map_stats.argtypes = [vp]
+        L.mgx_fetch_map_stats.argtypes = [vp, i32, vp, C.POINTER(i32)]
     _lib = L
     return L
 
@@ -510,6 +520,77 @@ class BatchedMettaGrid:
         _check(self.L.mgx_get_map_seeds(self.h, out.ctypes.data))
         return out
 
+    # ---- weighted pool sampling and per-map statistics (include/mgx.h "Weighted map-pool sampling"; pool_sampling.py) ----
+    def _pool_weights(self, weights) -> np.ndarray:
+        M = getattr(self, "pool_size", 0)
+        if M <= 0:
+            raise ValueError("no map pool (set_map_pool)")
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (M,):
+            raise ValueError(f"weights must have shape [{M}], one per pool map")
+        return w
+
+    def set_pool_sampling(self, weights, sample_seed: int = 0, env_offset: int = 0) -> None:
+        """Auto-resets draw the next pool map with probability proportional to ``weights`` (f64 [M]; ``None``: the rotation rule
+        again): episode ``k`` of slot ``e`` plays ``pool_sampling.draws(weights, sample_seed, env_offset, [e], [k])``.
+        ``env_offset``: the slot's global env index minus its index here (engines that share one batch)."""
+        if weights is None:
+            _check(self.L.mgx_set_pool_sampling(self.h, None, 0, 0))
+            return
+        w = self._pool_weights(weights)
+        _check(self.L.mgx_set_pool_sampling(self.h, w.ctypes.data, int(sample_seed) & 0xFFFFFFFF, int(env_offset) & 0xFFFFFFFF))
+
+    def set_pool_weights(self, weights) -> None:
+        """New weights from the next step's restarts on; does not wait for the device."""
+        w = self._pool_weights(weights)
+        _check(self.L.mgx_set_pool_weights(self.h, w.ctypes.data))
+
+    def pool_draws(self, envs, episodes) -> np.ndarray:
+        """int32 [n]: the pool map slot ``envs[i]`` plays as its episode ``episodes[i]``, computed by the device kernel."""
+        ev = np.ascontiguousarray(np.asarray(envs, dtype=np.int32).reshape(-1))
+        ep = np.ascontiguousarray(np.asarray(episodes, dtype=np.uint32).reshape(-1))
+        if ev.size != ep.size:
+            raise ValueError("envs and episodes must have the same length")
+        out = np.empty(ev.size, np.int32)
+        _check(self.L.mgx_pool_draws(self.h, ev.ctypes.data, ep.ctypes.data, int(ev.size), out.ctypes.data))
+        return out
+
+    def set_map_stats(self, enabled: bool = True) -> None:
+        """Per-map episode statistics reduced on the device (needs ``set_episode_stats`` and a pool)."""
+        _check(self.L.mgx_set_map_stats(self.h, 1 if enabled else 0))
+        self._ms_on = bool(enabled)
+
+    def request_map_stats(self) -> None:
+        _check(self.L.mgx_request_map_stats(self.h))
+
+    def _fetch_ms_raw(self, wait: bool):
+        out = np.zeros((self.pool_size + 1, 6), np.uint64)
+        ready = C.c_int32(0)
+        _check(self.L.mgx_fetch_map_stats(self.h, 1 if wait else 0, out.ctypes.data, C.byref(ready)))
+        return out if ready.value else None
+
+    def fetch_map_stats(self, wait: bool = False, raw: bool = False):
+        """The snapshot requested last: one dict per pool map plus a last one for episodes without a pool index (a slot's first
+        episode) — ``episodes``, ``terminated``, ``length_sum``, ``return_sum`` (= q_sum / 2**20), ``return_min``,
+        ``return_max`` — or, with ``raw``, the uint64 [M + 1][6] table; None while its copy is still in flight."""
+        from .pool_sampling import table_dicts
+        t = self._fetch_ms_raw(wait)
+        return None if t is None else t if raw else table_dicts(t)
+
+    def drain_map_stats(self, raw: bool = False):
+        """Everything recorded up to now, synchronously; a snapshot still in flight is merged with a fresh one."""
+        from .pool_sampling import table_dicts
+        first = self._fetch_ms_raw(True)       # None unless a request was pending
+        self.request_map_stats()
+        t = self._fetch_ms_raw(True)
+        if first is not None:
+            with np.errstate(over="ignore"):
+                merged = first + t             # (two's complement: the q sums add like the counts)
+            merged[:, 4] = np.minimum(first[:, 4], t[:, 4])
+            merged[:, 5] = np.maximum(first[:, 5], t[:, 5])
+            t = merged
+        return t if raw else table_dicts(t)
+
     # ---- episode-end statistics (include/mgx.h "Episode-end statistics"; the reference's StatsTracker.on_episode_end) ----
     EPL = ("NG", "NS", "A", "TOTALS_WORDS", "REC_WORDS", "LOG_WORDS", "OFF_GAME", "OFF_GAME_BITS", "OFF_AGENT", "OFF_AGENT_BITS",
            "OFF_REWARDS", "OFF_PA", "OFF_PA_BITS", "OFF_INVK", "OFF_INVN", "PER_AGENT", "LOG_CAPACITY")
@@ -522,6 +603,7 @@ class BatchedMettaGrid:
         self._epl = None
         self._tal = None   # (the engine switches the time averages off with the statistics they ride on)
         self._psl = None   # (... and the per-policy statistics)
+        self._ms_on = False  # (... and the per-map table)
         if enabled:
             out = np.zeros(len(self.EPL), np.int32)
             _check(self.L.mgx_episode_stats_layout(self.h, out.ctypes.data))

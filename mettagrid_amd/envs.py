@@ -278,6 +278,18 @@ class MettaGridBatchedEnv:
     reference's per_episode_per_policy_avg_rewards row).  ``policy_ids`` (int64 [E * A]) and ``policy_rows(p)`` route
     observations and actions; ``set_policy_assignments(envs, rows)`` rematches slots between episodes.  The table belongs to
     the slots: ``save_state`` / ``load_state`` do not move it.  Off: ``infos`` and ``episode_infos()`` are unchanged.
+
+    ``map_weights`` (with ``map_pool``; f64 [M], or ``"uniform"``: equal weights, the distribution of the reference's map cache,
+    simulator/map_cache.py:207-215): auto-resets draw the next pool map with probability proportional to the weights instead of
+    rotating (``BatchedMettaGrid.set_pool_sampling``; the draw is ``pool_sampling.draws(weights, map_sample_seed,
+    map_env_offset, [env], [episode])``, reproducible bit for bit); ``set_map_weights(w)`` replaces them between steps without
+    waiting for the device — the curriculum's half of the loop.  The first episode's maps stay ``arange(E) % M``.
+    ``map_env_offset``: the global index of env 0 when several wrappers share one batch (``dist.env_shard(...).start``).
+    ``map_stats`` (needs ``episode_stats`` and ``map_pool``): per-map episode statistics reduced on the device; the aggregate
+    ``infos`` gets ``"per_map"``, a list with one dict per pool map, and ``"unattributed"``, one more such dict for the episodes
+    without a pool index (every slot's first): each with ``episodes``, ``terminated``, ``length_sum``, ``return_sum`` (fixed point, 2**-20), ``return_min``, ``return_max`` over the
+    same window, and with ``map_labels`` (one label per pool map) ``"per_label_rewards": {label: return_sum / episodes}`` over the
+    window's episodes of that label's maps (stats_tracker.py:59-60 for a batch).  Off: ``infos`` is unchanged.
     """
 
     def __init__(self, prog: Program, num_envs: int, map_fn: Optional[Callable[[int, int], np.ndarray]] = None,
@@ -288,7 +300,30 @@ class MettaGridBatchedEnv:
                  replay_dir: Optional[str] = None, replay_words_per_env: Optional[int] = None, replay_interval: int = 64,
                  replay_capacity_groups: Optional[dict] = None, map_gen=None, map_seed: int = 0,
                  map_seed_stride: int = 1 << 16, step_info_keys=None, time_averaged_stats: bool = False,
-                 policy_assignments=None, num_policies: Optional[int] = None) -> None:
+                 policy_assignments=None, num_policies: Optional[int] = None, map_weights=None, map_sample_seed: int = 0,
+                 map_stats: bool = False, map_labels=None, map_env_offset: int = 0) -> None:
+        if map_weights is not None and map_pool is None:
+            raise ValueError("map_weights needs map_pool")
+        if map_stats and (not episode_stats or map_pool is None):
+            raise ValueError("map_stats needs episode_stats and map_pool")
+        if map_labels is not None and not map_stats:
+            raise ValueError("map_labels needs map_stats")
+        if map_labels is not None and len(map_labels) != len(map_pool):
+            raise ValueError("map_labels: one label per pool map")
+        if isinstance(map_weights, str):
+            if map_weights != "uniform":
+                raise ValueError('map_weights: an array of one weight per pool map, or "uniform"')
+            map_weights = np.ones(len(map_pool), np.float64)
+        if map_weights is not None:
+            from .pool_sampling import quantise
+            map_weights = np.array(map_weights, dtype=np.float64)
+            if map_weights.shape != (len(map_pool),):
+                raise ValueError("map_weights: one weight per pool map")
+            quantise(map_weights)   # (refuses what the engine would refuse at reset())
+        self.map_weights = map_weights
+        self.map_sample_seed, self.map_env_offset = int(map_sample_seed), int(map_env_offset)
+        self.map_stats = bool(map_stats)
+        self.map_labels = None if map_labels is None else list(map_labels)
         if time_averaged_stats and not episode_stats:
             raise ValueError("time_averaged_stats needs episode_stats")
         if policy_assignments is not None and not episode_stats:
@@ -430,6 +465,8 @@ class MettaGridBatchedEnv:
                                          specialize=self.specialize)
             self._eng.set_map_pool(self.map_pool)
             self._eng.set_auto_reset(True, self.pool_stride, self.early_end_steps() if self.desync else None)
+            if self.map_weights is not None:
+                self._eng.set_pool_sampling(self.map_weights, self.map_sample_seed, self.map_env_offset)
         elif self.map_gen is not None:
             from .mapgen import generated_class_maps
             # capacities are sized from the create maps, and every map of a recipe holds the same cells: one host-built map
@@ -448,6 +485,8 @@ class MettaGridBatchedEnv:
                 self._eng.set_time_averages(True, self.episode_log)
             if self._policy_table is not None:
                 self._eng.set_policy_stats(True, self.num_policies, self._policy_table, self.episode_log)
+            if self.map_stats:
+                self._eng.set_map_stats(True)
         self._policy_ids = None
         self._pending_infos = []
         self._steps = 0
@@ -526,31 +565,52 @@ class MettaGridBatchedEnv:
                 "agent_sum": p["agent_sum"], "agent_count": p["agent_count"]} for p in ps["policies"]]
         return dict(infos, policy=pol)
 
+    def _with_maps(self, infos: dict, ms: Optional[list]) -> dict:
+        """The window's per-map table beside the aggregate (requested with it, so over the same episodes)."""
+        if not ms or not any(m["episodes"] for m in ms):
+            return infos
+        infos = dict(infos, per_map=ms[:-1], unattributed=ms[-1])
+        if self.map_labels is not None:
+            tot: dict = {}
+            for label, m in zip(self.map_labels, ms):
+                if m["episodes"]:
+                    t = tot.setdefault(label, [0.0, 0])
+                    t[0] += m["return_sum"]
+                    t[1] += m["episodes"]
+            infos["per_label_rewards"] = {label: t[0] / t[1] for label, t in tot.items()}
+        return infos
+
     def _step_infos(self) -> dict:
         if not self.episode_stats:
             return {}
         eng = self.engine
         self._steps += 1
-        ta_on, ps_on = self.time_averaged_stats, self._policy_table is not None
+        ta_on, ps_on, ms_on = self.time_averaged_stats, self._policy_table is not None, self.map_stats
         if not self._device_restarts or self._kind != "device":   # these paths synchronise with the device every step anyway
             if self._steps % self.stats_interval != 0:
                 return {}
             out = self._infos_from_totals(eng.drain_episode_stats())
             if ta_on:
                 out = self._with_time_averages(out, eng.drain_time_averages())
-            return self._with_policies(out, eng.drain_policy_stats()) if ps_on else out
+            if ps_on:
+                out = self._with_policies(out, eng.drain_policy_stats())
+            return self._with_maps(out, eng.drain_map_stats()) if ms_on else out
         out = {}
         if self._steps % self.stats_interval == 0:
-            if ta_on or ps_on:
+            if ta_on or ps_on or ms_on:
                 # the snapshots are requested back to back and fetched together: the copy of the one requested last lands
                 # last, so once it is there the others are too (no wait), and until then none is taken
-                ps = eng.fetch_policy_stats(wait=False) if ps_on else None
-                ta = eng.fetch_time_averages(wait=ps is not None) if ta_on and (ps is not None or not ps_on) else None
-                if (ps if ps_on else ta) is not None:
+                ms = eng.fetch_map_stats(wait=False) if ms_on else None
+                landed = ms is not None
+                ps = eng.fetch_policy_stats(wait=landed) if ps_on and (landed or not ms_on) else None
+                landed = landed or ps is not None
+                ta = eng.fetch_time_averages(wait=landed) if ta_on and (landed or not (ms_on or ps_on)) else None
+                if landed or ta is not None:
                     out = self._infos_from_totals(eng.fetch_episode_stats(wait=True))
                     if ta_on:
                         out = self._with_time_averages(out, ta)
                     out = self._with_policies(out, ps)
+                    out = self._with_maps(out, ms)
             else:
                 out = self._infos_from_totals(eng.fetch_episode_stats(wait=False))   # the snapshot requested one interval ago
             eng.request_episode_stats()
@@ -558,7 +618,17 @@ class MettaGridBatchedEnv:
                 eng.request_time_averages()
             if ps_on:
                 eng.request_policy_stats()
+            if ms_on:
+                eng.request_map_stats()
         return out
+
+    def set_map_weights(self, weights) -> None:
+        """New sampling weights (``map_weights``) from the next step's restarts on; does not wait for the device."""
+        if self.map_weights is None:
+            raise ValueError("no map_weights")
+        w = np.array(weights, dtype=np.float64)
+        self.engine.set_pool_weights(w)
+        self.map_weights = w
 
     # ---- policies (policy_assignments) ----
     @property

@@ -92,6 +92,12 @@ class EnvGroups:
         for eng in self.engines:
             eng.set_profiling(on)
 
+    def set_pool_sampling(self, weights, sample_seed: int = 0, env_offset: int = 0) -> None:
+        """``BatchedMettaGrid.set_pool_sampling`` on every group (each holds its own map pool), keyed by GLOBAL env index: group g
+        draws with offset ``env_offset + g * envs_per_group``, so the maps do not depend on how the batch is cut."""
+        for g, eng in enumerate(self.engines):
+            eng.set_pool_sampling(weights, sample_seed, env_offset + g * self.envs_per_group)
+
     def engine_of(self, env: int):
         """(engine, local env index) of a global env."""
         return self.engines[env // self.envs_per_group], env % self.envs_per_group
