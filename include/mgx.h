@@ -402,6 +402,41 @@ int mgx_set_step_stats(mgx_engine* e, const int32_t* game_cols, int32_t n_game, 
  * (cpp/bindings/mettagrid_py.cpp:181-197: StatsTracker::get_if_present); it has no such split.  Diagnostic. */
 int mgx_step_stats_columns(mgx_engine* e, int32_t* kinds_out);
 
+/* ---- Global state rows: every env's objects as tokens, written on the device behind every step ----------------------------
+ * What a centralised critic, a league's value baseline or a tool that looks at all envs at once needs, and what PettingZoo
+ * calls state(): the reference keeps a stub there (python/src/mettagrid/envs/pettingzoo_env.py:178-190 returns zeros).  A
+ * kernel at the end of every mgx_step (csrc/mgx_global_state.h: one wavefront per env) writes into caller-owned DEVICE memory
+ *   tokens       u32 [E][max_tokens]  one dword per token: row | col << 8 | feature << 16 | value << 24 — as bytes (r, c, f, v)
+ *                                     with ABSOLUTE coordinates (maps are at most 255 x 255: 0xFFFFFFFF is never a token);
+ *                                     every dword behind an env's last token is 0xFFFFFFFF
+ *   counts       u32 [E]              the UNTRUNCATED number of tokens of the env: token k is stored iff k < max_tokens,
+ *                                     counts[e] > max_tokens says the row overflowed; nothing is stored outside the row
+ *   agent_start  i32 [E][A] or NULL   index of the first token of agent i's object; -1 if its class is filtered out or the
+ *                                     object starts at or behind max_tokens
+ * Order across objects: grid cells in row-major order — the grid decides what is on the map; a dead slot or an object removed
+ * from the grid has no cell and no tokens.  Order inside an object: exactly the (feature, value) list the observation
+ * encoder emits for it to any observer (core/grid_object.cpp:178-203, objects/agent.cpp:142-154,
+ * observation_encoder.hpp:198-225): tag tokens in ascending tag id, `vibe` if not 0, the inventory items in iteration order
+ * (base digit, then the :pK digits in token_value_base; none for an object created at run time, which has no encoder), and
+ * for agents agent:group, then agent_id.  Static classes show their tags only.  The per-observer tokens are NOT in the row:
+ * the cell.visited staleness token, the territory aoe_mask token, the location-0xFE global tokens.
+ * class_include (host, u8 [classes], NULL = all): 0 = objects of the class emit nothing (e.g. walls, which never change).
+ * mgx_set_global_state fills the rows with 0xFF once and writes the current state; tokens == NULL switches the feature off:
+ * mgx_step then enqueues nothing for it.  With lazy auto-reset a row shows what the returned observations show: a finished
+ * env's final state, and after the next step the restarted env after its first tick.  The rows are derived state: they are in
+ * no saved env record, and mgx_reset_envs*, mgx_load_envs, mgx_copy_envs and mgx_set_inventory leave them stale until the
+ * next step or mgx_write_global_state (env_mask: host, u8 [E], NULL = all; on the engine's stream; rows of unmarked envs are
+ * not touched).  The engine keeps each row's previous length and never rewrites the 0xFF tail: a caller that writes into the
+ * rows sets them again.  They are outputs like the bound buffers: mgx_wait_before_outputs covers them.
+ * mgx_global_state_bound: a max_tokens no env of this engine can exceed under the filter, from the program and the slot count
+ * (per object its class's tag bound, and for a non-static class 1 + the digits of every resource + 2 for agents).
+ * MGX_ERR_BAD_ARG, before anything is changed: MGX_MEM_HOST buffers, max_tokens < 1, null counts.
+ * Not part of the CPU sanitizer build. */
+int mgx_global_state_bound(mgx_engine* e, const uint8_t* class_include, int32_t* max_tokens);
+int mgx_set_global_state(mgx_engine* e, uint32_t* tokens, int32_t max_tokens, uint32_t* counts, int32_t* agent_start,
+                         const uint8_t* class_include);
+int mgx_write_global_state(mgx_engine* e, const uint8_t* env_mask);
+
 /* Forget what the engine knows about the content of the bound observation buffer (enqueued on the engine's stream): the
  * next observation pass rewrites every row it touches in full, 0xFF padding included, as after mgx_set_buffers.  For callers
  * that wrote into the buffer themselves.  MGX_OBS_FULL_ROWS=1 in the environment at mgx_create makes every pass behave so. */

@@ -28,6 +28,7 @@
 #include "mgx_time_avg.h"   // time-averaged game stats of every episode (mgx_set_time_averages)
 #include "mgx_policy_stats.h"  // per-policy episode statistics (mgx_set_policy_stats)
 #include "mgx_pool_sample.h"   // weighted draws of the next pool map, per-map episode statistics (mgx_set_pool_sampling)
+#include "mgx_global_state.h"  // every env's objects as one token row, written behind every step (mgx_set_global_state)
 
 
 // Territory ownership map (TerritoryTracker::compute_cell_ownership, core/territory_tracker.cpp:215-252) of every cell,
@@ -350,6 +351,11 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
   MgxStepStats ss{};                // the kernel's argument: column table (device), the four output tensors
   bool ss_on = false;               // (false: mgx_step enqueues nothing for it)
   int32_t ss_kinds[2 * MGX_SS_MAX_COLUMNS] = {};   // resolved kind of each column, game columns first (mgx_step_stats_columns)
+  // global state rows (mgx_set_global_state; csrc/mgx_global_state.h): the rows are the caller's; the previous row lengths, the
+  // class filter and the staging of mgx_write_global_state's env mask are the slot's (one device block: used | include | mask)
+  MgxGlobalState gs{};              // the kernel's argument
+  bool gs_on = false;               // (false: mgx_step enqueues nothing for it)
+  uint8_t* d_gs_mask = nullptr;     // [E] inside the block behind gs.used
   // device map generator (mgx_set_map_generator; csrc/mgx_mapgen.h): the recipe and the base seeds belong to the slot, never
   // to a saved env state
   MgxMapGen gen{};                  // device pointers into d_gen_recipe + the shape
@@ -700,8 +706,16 @@ static void free_step_stats(mgx_engine* e) {
   e->ss_on = false;
 }
 
+static void free_global_state(mgx_engine* e) {
+  if (e->gs.used) (void)hipFree(e->gs.used);
+  e->gs = MgxGlobalState{};
+  e->d_gs_mask = nullptr;
+  e->gs_on = false;
+}
+
 #ifdef MGX_CPU_EMU   // the sanitizer build has no episode statistics, no replay recorder, no map generator and no step stats
 static int launch_step_stats(mgx_engine*) { return MGX_OK; }
+static int launch_global_state(mgx_engine*, const uint8_t*) { return MGX_OK; }
 static int flush_shadow(mgx_engine*, const int32_t*, const uint32_t*, unsigned) { return MGX_OK; }
 static int launch_episode_stats(mgx_engine*) { return MGX_OK; }
 static int launch_time_avg_accum(mgx_engine*) { return MGX_OK; }
@@ -863,6 +877,16 @@ static int launch_step_stats(mgx_engine* e) {
   const long long pairs = (long long)e->d.E * e->d.A * e->ss.KA + (long long)e->d.E * e->ss.KG;
   const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>((pairs + 255) / 256, 2048));
   hipLaunchKernelGGL(mgx_step_stats_kernel, dim3(grid), dim3(256), 0, e->stream, dev_copy(e), e->ss);
+  HIP_TRY(hipGetLastError());
+  return MGX_OK;
+}
+// Every env's objects -> the caller's token rows (csrc/mgx_global_state.h): one wavefront per env, four envs per workgroup;
+// `dmask` (device, u8 [E]) restricts the pass to the marked envs.  Nothing while the feature is off.
+static int launch_global_state(mgx_engine* e, const uint8_t* dmask) {
+  if (!e->gs_on) return MGX_OK;
+  { int frc = consume_out_fence(e); if (frc) return frc; }   // (the rows are outputs like the bound buffers)
+  const unsigned per = 256 / MGX_WAVE;
+  hipLaunchKernelGGL(mgx_global_state_kernel, dim3(((unsigned)e->d.E + per - 1) / per), dim3(256), 0, e->stream, dev_copy(e), e->gs, dmask);
   HIP_TRY(hipGetLastError());
   return MGX_OK;
 }
@@ -1056,6 +1080,7 @@ void mgx_destroy(mgx_engine* e) {
   free_pool_sampling(e);
   free_replay(e);
   free_step_stats(e);
+  free_global_state(e);
   for (int i = 0; i <= MGX_T_COUNT; i++) if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
   if (e->world_done) (void)hipEventDestroy(e->world_done);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -2410,6 +2435,79 @@ int mgx_step_stats_columns(mgx_engine* e, int32_t* kinds_out) {
   memcpy(kinds_out, e->ss_kinds, (size_t)(e->ss.KG + e->ss.KA) * sizeof(int32_t));
   return MGX_OK;
 }
+
+// ---- global state rows (csrc/mgx_global_state.h) ---------------------------------------------------------------------------
+// Worst-case tokens of one env under a class filter: per object its class's tag bound, and for a non-static class the vibe,
+// every digit of R resources and an agent's two tokens; at most min(S, H*W) objects, at most A of them agents.
+static int global_state_bound(const mgx_engine* e, const uint8_t* include) {
+  const MgxDev& d = e->d;
+  const int nc = e->prog[MGX_H_NUM_CLASSES], digits = mgx_gs_amount_digits(d.base);
+  long long agent_max = 0, other_max = 0;
+  for (int c = 0; c < nc; c++) {
+    if (include && !include[c]) continue;
+    const uint32_t ci = e->cls_tokinfo[(size_t)c];
+    const bool is_static = (ci >> 31) != 0, is_agent = (ci & 0x40000000u) != 0;
+    long long n = (long long)((ci >> 24) & 0x3Fu);
+    if (!is_static) n += e->prog[MGX_H_NUM_MATQ_TAGS] + 1 + (long long)d.R * digits + (is_agent ? 2 : 0);   // (+ the tags materialized queries may add)
+    (is_agent ? agent_max : other_max) = std::max(is_agent ? agent_max : other_max, n);
+  }
+  const long long objs = std::min<long long>(d.S, (long long)d.H * d.W), agents = std::min<long long>(d.A, objs);
+  const long long bound = agent_max > other_max ? agents * agent_max + (objs - agents) * other_max : objs * other_max;
+  return (int)std::max<long long>(1, std::min<long long>(bound, 0x7FFFFFFF));
+}
+
+int mgx_global_state_bound(mgx_engine* e, const uint8_t* class_include, int32_t* max_tokens) {
+  if (!e || !max_tokens) return fail(MGX_ERR_BAD_ARG, "mgx_global_state_bound: null argument");
+  *max_tokens = global_state_bound(e, class_include);
+  return MGX_OK;
+}
+
+int mgx_set_global_state(mgx_engine* e, uint32_t* tokens, int32_t max_tokens, uint32_t* counts, int32_t* agent_start,
+                         const uint8_t* class_include) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_global_state: null engine");
+  HIP_TRY(hipSetDevice(e->device));
+  const MgxDev& d = e->d;
+  if (!tokens) {   // off: the step enqueues nothing for it any more
+    HIP_TRY(hipStreamSynchronize(e->stream));   // (a kernel in flight still reads the filter and the row lengths)
+    free_global_state(e);
+    return MGX_OK;
+  }
+  if (e->mem_kind == MGX_MEM_HOST)
+    return fail(MGX_ERR_BAD_ARG, "mgx_set_global_state: the engine is bound to host buffers (MGX_MEM_HOST); the rows need device buffers");
+  if (max_tokens < 1) return fail(MGX_ERR_BAD_ARG, "mgx_set_global_state: the row length must be at least 1 (got " + std::to_string(max_tokens) + ")");
+  if (!counts) return fail(MGX_ERR_BAD_ARG, "mgx_set_global_state: null counts");
+  const size_t E = (size_t)d.E, nc = (size_t)e->prog[MGX_H_NUM_CLASSES];
+  const size_t inc_off = E * 4, mask_off = (inc_off + nc + 15) & ~(size_t)15, bytes = mask_off + E;
+  std::vector<uint8_t> inc(nc, 1);
+  if (class_include) memcpy(inc.data(), class_include, nc);
+  uint8_t* block = nullptr;
+  HIP_TRY(hipMalloc((void**)&block, bytes));
+  hipError_t he = hipMemsetAsync(block, 0, bytes, e->stream);   // previous row lengths 0: the rows are filled below
+  if (he == hipSuccess) he = hipMemcpyAsync(block + inc_off, inc.data(), nc, hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipMemsetAsync(tokens, 0xFF, E * (size_t)max_tokens * 4, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);   // `inc` is a local; a kernel in flight still reads the old block
+  if (he != hipSuccess) {
+    (void)hipFree(block);
+    return fail(MGX_ERR_HIP, std::string("mgx_set_global_state: ") + hipGetErrorString(he));
+  }
+  free_global_state(e);
+  e->gs.tokens = tokens; e->gs.counts = counts; e->gs.agent_start = agent_start; e->gs.TG = max_tokens;
+  e->gs.n_classes = (int)nc; e->gs.n_cls_tok = (int)e->cls_tok.size();
+  e->gs.used = (uint32_t*)block; e->gs.include = block + inc_off; e->d_gs_mask = block + mask_off;
+  e->gs_on = true;
+  return launch_global_state(e, nullptr);   // the current state
+}
+
+int mgx_write_global_state(mgx_engine* e, const uint8_t* env_mask) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_write_global_state: null engine");
+  if (!e->gs_on) return fail(MGX_ERR_BAD_ARG, "mgx_write_global_state: no rows set (mgx_set_global_state)");
+  HIP_TRY(hipSetDevice(e->device));
+  if (!env_mask) return launch_global_state(e, nullptr);
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (an earlier masked pass may still read the staged mask)
+  HIP_TRY(hipMemcpyAsync(e->d_gs_mask, env_mask, (size_t)e->d.E, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));   // the caller's mask has been read
+  return launch_global_state(e, e->d_gs_mask);
+}
 #endif  // MGX_CPU_EMU
 
 int mgx_step(mgx_engine* e) {
@@ -2511,6 +2609,7 @@ int mgx_step(mgx_engine* e) {
   }
   if (e->rpl_n) { int prc = launch_replay(e); if (prc) return prc; }
   if (e->ss_on) { int src = launch_step_stats(e); if (src) return src; }   // (behind the episode statistics: a step that ends an episode reports its final values)
+  if (e->gs_on) { int grc = launch_global_state(e, nullptr); if (grc) return grc; }   // (the restart is lazy: a finished env still shows its final state, as its observations do)
   if (e->mem_kind == MGX_MEM_HOST) {
     rc = copy_out(e, 0, (size_t)d.E);
     if (rc) return rc;

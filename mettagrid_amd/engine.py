@@ -214,6 +214,10 @@ def load_lib():
     if hasattr(L, "mgx_set_step_stats"):      # (absent from the CPU sanitizer build)
         L.mgx_set_step_stats.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp]
         L.mgx_step_stats_columns.argtypes = [vp, vp]
+    if hasattr(L, "mgx_set_global_state"):    # (absent from the CPU sanitizer build)
+        L.mgx_global_state_bound.argtypes = [vp, vp, C.POINTER(i32)]
+        L.mgx_set_global_state.argtypes = [vp, vp, i32, vp, vp, vp]
+        L.mgx_write_global_state.argtypes = [vp, vp]
     if hasattr(L, "mgx_set_map_generator"):   # (absent from the CPU sanitizer build, like the packed rows)
         L.mgx_set_map_generator.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, vp]
         L.mgx_set_map_scene_generator.argtypes = [vp] + [i32] * 10 + [vp, i32, vp, vp, i32, vp]
@@ -1019,6 +1023,69 @@ class BatchedMettaGrid:
         names = [self.SSK[int(v)] for v in out]
         return names[:len(gk)], names[len(gk):]
 
+    # ---- global state rows (include/mgx.h mgx_set_global_state; csrc/mgx_global_state.h; mettagrid_amd/global_state.py) ----
+    def global_state_bound(self, exclude=()) -> int:
+        """A row length no env of this engine can exceed when the classes in ``exclude`` (class ids, cell or type names such
+        as ``"wall"``) are left out: from the program and the slot count (include/mgx.h mgx_global_state_bound)."""
+        from .global_state import class_include
+        inc = class_include(self.prog, exclude)
+        out = C.c_int32(0)
+        _check(self.L.mgx_global_state_bound(self.h, inc.ctypes.data, C.byref(out)))
+        return out.value
+
+    def set_global_state(self, max_tokens=None, exclude=(), agent_start: bool = True):
+        """From now on a kernel behind every step writes the tokens of every object on every env's grid into device tensors,
+        which are returned (and kept as ``global_state``): ``tokens`` uint32 [E, TG] (``row | col << 8 | feature << 16 |
+        value << 24``; 0xFFFFFFFF behind an env's last token), ``counts`` uint32 [E] (untruncated: more than TG
+        says the row overflowed) and ``agent_start`` int32 [E, A] (or None).  Format and order: ``mettagrid_amd/global_state.py``.
+        ``max_tokens``: TG, default ``global_state_bound(exclude)``.  ``max_tokens=0`` switches the feature off.  The rows
+        show the state after the last step; after ``reset_envs*`` / ``load_envs`` / ``copy_envs`` / ``set_inventory`` call
+        ``write_global_state``.  Device buffers only."""
+        import torch
+        from .global_state import class_include
+        if max_tokens is not None and int(max_tokens) == 0:
+            _check(self.L.mgx_set_global_state(self.h, None, 0, None, None, None))
+            self._global_state = None
+            return None
+        inc = class_include(self.prog, exclude)
+        tg = self.global_state_bound(exclude) if max_tokens is None else int(max_tokens)
+        if tg < 1:
+            raise ValueError(f"set_global_state: max_tokens must be at least 1 (got {tg})")
+        if self.kind != "device":
+            raise ValueError("set_global_state: the engine is bound to host buffers; the rows need device buffers")
+        dev = torch.device("cuda", self.device)
+        t = (torch.empty((self.E, tg), dtype=torch.int32, device=dev).view(torch.uint32),
+             torch.zeros(self.E, dtype=torch.int32, device=dev).view(torch.uint32),
+             torch.full((self.E, self.A), -1, dtype=torch.int32, device=dev) if agent_start else None)
+        self.bind_global_state(*t, include=inc)
+        return self._global_state
+
+    def bind_global_state(self, tokens, counts, agent_start=None, include=None) -> None:
+        """``set_global_state`` with the caller's own contiguous device tensors (4-byte elements; ``tokens`` [E, TG])."""
+        import torch
+        torch.cuda.synchronize(torch.device("cuda", self.device))   # (the engine's stream writes them from now on)
+        inc = None if include is None else np.ascontiguousarray(include, dtype=np.uint8)
+        _check(self.L.mgx_set_global_state(self.h, tokens.data_ptr(), int(tokens.shape[-1]), counts.data_ptr(),
+                                           agent_start.data_ptr() if agent_start is not None else None,
+                                           inc.ctypes.data if inc is not None else None))
+        self._global_state = (tokens, counts, agent_start)   # (the old tensors are released only now)
+
+    @property
+    def global_state(self):
+        """(tokens, counts, agent_start) of ``set_global_state``, ordered on the engine's stream (``caller_waits``); None
+        while the feature is off."""
+        return getattr(self, "_global_state", None)
+
+    def write_global_state(self, envs=None) -> None:
+        """Rewrite the rows of ``envs`` (indices; None = all) from the current state, on the engine's stream: after
+        ``reset_envs*``, ``load_envs``, ``copy_envs`` and ``set_inventory``, which leave them stale."""
+        if envs is None:
+            _check(self.L.mgx_write_global_state(self.h, None))
+            return
+        mask = np.zeros(self.E, np.uint8)
+        mask[env_list(envs, self.E, "write_global_state")] = 1
+        _check(self.L.mgx_write_global_state(self.h, mask.ctypes.data))
+
     @property
     def stream(self) -> int:
         return int(self.L.mgx_stream(self.h) or 0)
@@ -1361,11 +1428,13 @@ class MettaGrid:
     ``Program`` or a ``GameSpec``).  Buffers are caller-visible numpy arrays, stored by reference like the
     reference does (cpp/bindings/mettagrid_c.cpp:1165-1184): ``step()`` writes into them."""
 
-    def __init__(self, env_cfg, map, seed: int, device: int = 0) -> None:  # noqa: A002 - reference argument name
+    def __init__(self, env_cfg, map, seed: int, device: int = 0, buffers: str = "host") -> None:  # noqa: A002 - reference argument name
+        """``buffers="device"``: the buffers are the engine's torch tensors instead (what the device-side features need, e.g.
+        ``set_global_state``); ``set_buffers`` stays a host-array call."""
         H, W = len(map), len(map[0])
         prog = env_cfg if isinstance(env_cfg, Program) else compile_spec(env_cfg, H, W)
         self.prog = prog
-        self._b = BatchedMettaGrid(prog, prog.class_map(map), [int(seed) & 0xFFFFFFFF], device=device, buffers="host")
+        self._b = BatchedMettaGrid(prog, prog.class_map(map), [int(seed) & 0xFFFFFFFF], device=device, buffers=buffers)
         w = prog.words
         self.obs_width, self.obs_height = int(w[K.H_OBS_WIDTH]), int(w[K.H_OBS_HEIGHT])
         self.max_steps = int(w[K.H_MAX_STEPS])

@@ -290,6 +290,12 @@ class MettaGridBatchedEnv:
     without a pool index (every slot's first): each with ``episodes``, ``terminated``, ``length_sum``, ``return_sum`` (fixed point, 2**-20), ``return_min``, ``return_max`` over the
     same window, and with ``map_labels`` (one label per pool map) ``"per_label_rewards": {label: return_sum / episodes}`` over the
     window's episodes of that label's maps (stats_tracker.py:59-60 for a batch).  Off: ``infos`` is unchanged.
+    ``global_state`` (device buffers): every env's whole state as a token row on the device — what a centralised critic
+    reads (``BatchedMettaGrid.set_global_state``; format: ``mettagrid_amd/global_state.py``).  ``env.global_state`` is
+    ``(tokens uint32 [E, TG], counts uint32 [E], agent_start int32 [E, A])``: device tensors that ``step`` updates in place,
+    and ``reset`` / ``load_state`` through ``write_global_state``.  ``global_state_exclude``: classes left out (cell or type
+    names such as ``"wall"``, class ids); ``global_state_tokens``: TG (default: the engine's bound).  With device restarts a
+    finished env's row shows its final state, like its observations, and the restarted env after its first step.
     """
 
     def __init__(self, prog: Program, num_envs: int, map_fn: Optional[Callable[[int, int], np.ndarray]] = None,
@@ -301,7 +307,12 @@ class MettaGridBatchedEnv:
                  replay_capacity_groups: Optional[dict] = None, map_gen=None, map_seed: int = 0,
                  map_seed_stride: int = 1 << 16, step_info_keys=None, time_averaged_stats: bool = False,
                  policy_assignments=None, num_policies: Optional[int] = None, map_weights=None, map_sample_seed: int = 0,
-                 map_stats: bool = False, map_labels=None, map_env_offset: int = 0) -> None:
+                 map_stats: bool = False, map_labels=None, map_env_offset: int = 0, global_state: bool = False,
+                 global_state_exclude=(), global_state_tokens: Optional[int] = None) -> None:
+        if global_state and buffers != "device":
+            raise ValueError("global_state needs device buffers")
+        self._gs_on, self._gs_exclude, self._gs_tokens = bool(global_state), tuple(global_state_exclude), global_state_tokens
+        self.global_state = None          # (tokens, counts, agent_start) once reset() has made the engine
         if map_weights is not None and map_pool is None:
             raise ValueError("map_weights needs map_pool")
         if map_stats and (not episode_stats or map_pool is None):
@@ -493,6 +504,7 @@ class MettaGridBatchedEnv:
         if self._si_on and (self._si_game_columns or self._si_keys[2]):
             self._eng.set_step_stats(self._si_game_columns, self._si_keys[2])
         self._step_info = StepInfo(self) if self._si_on else None   # (one object: the engine rewrites its tensors every step)
+        self.global_state = self._eng.set_global_state(self._gs_tokens, self._gs_exclude) if self._gs_on else None
         if self.replay_envs:
             from .replay import ReplayAssembler
             import os
@@ -770,6 +782,7 @@ class MettaGridBatchedEnv:
                     self.flush_replays()
                 self.episode[idx] += 1
                 eng.reset_envs(done, self._maps(idx), self._seeds())
+                # (no write_global_state: the step below rewrites every row)
         if self._kind == "device":
             import torch
             a = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(np.asarray(actions), device=eng.obs.device)
@@ -852,6 +865,9 @@ class MettaGridBatchedEnv:
                                                      "seen": t[:, 2 * ng:-1], "steps": t[:, -1]})
         if not self._device_restarts and "episode" in state.extra:
             self.episode[lst] = np.asarray(state.extra["episode"], dtype=np.int64)
+        if self._gs_on:   # the rows are derived state: rebuilt from what was loaded
+            self.engine.write_global_state(lst)
+            self.engine.caller_waits()
 
     def close(self) -> None:
         if self._eng is not None:
@@ -867,9 +883,19 @@ class MettaGridParallelEnv:
     agent id, finished agents dropped from ``agents``, one shared observation / action space for all agents.  pettingzoo and
     gymnasium themselves are not imported: spaces are described by shape / size."""
 
-    def __init__(self, env_cfg, map, seed: int = 0, device: int = 0) -> None:  # noqa: A002 - reference argument name
+    def __init__(self, env_cfg, map, seed: int = 0, device: int = 0, global_state: bool = False,  # noqa: A002 - reference argument name
+                 global_state_exclude=(), global_state_tokens: Optional[int] = None) -> None:
+        """``global_state=True``: ``state()`` returns the env's global state row (``mettagrid_amd/global_state.py``) instead of
+        the reference's zero vector; the engine then runs on device buffers and the dicts hold host copies."""
         from .engine import MettaGrid
-        self._make = lambda s: MettaGrid(env_cfg, map, s, device=device)
+        self._gs_on = bool(global_state)
+
+        def make(s):
+            sim = MettaGrid(env_cfg, map, s, device=device, buffers="device" if self._gs_on else "host")
+            if self._gs_on:
+                sim._b.set_global_state(global_state_tokens, global_state_exclude, agent_start=False)
+            return sim
+        self._make = make
         self._seed = seed
         self._sim = self._make(seed)
         names = self._sim.prog.action_names
@@ -884,20 +910,34 @@ class MettaGridParallelEnv:
         self._sim._b.close()
         self._sim = self._make(self._seed)
         self.agents = list(self.possible_agents)
-        obs = self._sim.observations()
+        obs = self._host(self._sim.observations())
         return {a: obs[a] for a in self.agents}, {a: {} for a in self.agents}
+
+    def _host(self, x):
+        """A bound buffer as a numpy array (device buffers: a host copy behind the engine's stream)."""
+        if isinstance(x, np.ndarray):
+            return x
+        self._sim._b.sync()
+        return x.cpu().numpy()
 
     def step(self, actions: dict):
         sim = self._sim
-        arr = sim.actions()
+        arr = sim.actions() if not self._gs_on else np.zeros(len(self.possible_agents), np.int32)
         for a in self.agents:
             if a in actions:
                 idx = int(np.asarray(actions[a], dtype=np.int32).reshape(()).item())
                 if idx < 0 or idx >= len(self._action_indices):
                     raise ValueError(f"Action index {idx} out of range for PettingZoo action space.")
                 arr[a] = self._action_indices[idx]
+        if self._gs_on:   # device buffers: the agents that sent nothing keep their previous action, as in the host array
+            import torch
+            sent = np.zeros(len(arr), np.bool_)
+            sent[[a for a in self.agents if a in actions]] = True
+            dev = sim.actions().device
+            sim.actions().copy_(torch.where(torch.as_tensor(sent, device=dev), torch.as_tensor(arr, device=dev), sim.actions()))
+            torch.cuda.synchronize(dev)
         sim.step()
-        obs, rew, term, trunc = sim.observations(), sim.rewards(), sim.terminals(), sim.truncations()
+        obs, rew, term, trunc = (self._host(x) for x in (sim.observations(), sim.rewards(), sim.terminals(), sim.truncations()))
         out = ({a: obs[a] for a in self.agents}, {a: float(rew[a]) for a in self.agents}, {a: bool(term[a]) for a in self.agents},
                {a: bool(trunc[a]) for a in self.agents}, {a: {} for a in self.agents})
         self.agents = [a for a in self.agents if not (out[2][a] or out[3][a])]
@@ -909,7 +949,12 @@ class MettaGridParallelEnv:
     def action_space_n(self, agent: int) -> int:
         return len(self._action_indices)
 
-    def state(self) -> np.ndarray:   # pettingzoo_env.py:178-190: a zero vector of the flattened observation size
+    def state(self) -> np.ndarray:
+        """Default: the reference's stub, a zero vector of the flattened observation size (pettingzoo_env.py:178-190).  With
+        ``global_state=True``: the env's global state row as u8 [TG][4] = (row, col, feature, value), 0xFF behind the last
+        token (``mettagrid_amd/global_state.py``)."""
+        if self._gs_on:
+            return self._host(self._sim._b.global_state[0][0]).view(np.uint8).reshape(-1, 4).copy()
         return np.zeros(len(self.possible_agents) * int(np.prod(self.observation_shape)), np.uint8)
 
     @property
