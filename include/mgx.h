@@ -194,6 +194,32 @@ int mgx_set_map_scene_generator(mgx_engine* e, int32_t room_height, int32_t room
                                 int32_t border_width, int32_t instance_border_width, int32_t border_code, int32_t instance_border_code,
                                 int32_t first_on_root, const uint16_t* symbols, int32_t n_sym, const uint16_t* rename,
                                 const int32_t* rename_off, int32_t n_teams, const uint32_t* map_seed_base);
+/* mgx_set_map_maze_generator — the third recipe kind: the reference's MapGen with a Maze instance scene
+ *   (python/src/mettagrid/mapgen/scenes/maze.py) whose one child is a Random scene over the whole room (where = "full").  Room
+ *   grid, borders, rename tables, symbols [n_inst][n_sym] and the seed rule are those of mgx_set_map_scene_generator.  Every
+ *   room k < n_inst is overwritten by a maze of wall_code (class index + 1, not 0) and empty cells: rs = max(1, min(room_size,
+ *   room_width, room_height)), ws = max(1, wall_size), maze cell (i, j) is the rs x rs block at x = i * (rs + ws),
+ *   y = j * (rs + ws), with (room_width + ws) / (rs + ws) cells per row and (room_height + ws) / (rs + ws) per column.
+ *   algorithm 0 = kruskal: empty room, wall strips between the cell columns and rows (a remainder past the last cell stays
+ *   empty), one Generator.shuffle of the wall list, each wall opened whose cells are not connected yet.  1 = dfs: all wall
+ *   (a remainder stays wall), the depth-first walk from cell (0, 0), choosing among the unvisited neighbours in the order up,
+ *   down, right, left by Generator.integers(0, count) (no draw for a count of 1).  Then the Random child: the symbols are
+ *   shuffled, the room's EMPTY cells in row-major order are shuffled on the same generator, and symbol q lands on empty cell
+ *   q; n_sym = 0 draws nothing.  n_sym must not exceed the empty cells of a room's maze, which are the same for every seed
+ *   (a maze is a spanning tree of its cells).
+ *   Generators: the Maze scene of instance k draws from default_rng(seed) itself when k == 0 and first_on_root != 0, else
+ *   from PCG64(SeedSequence(seed, spawn_key=(k + key_offset,))); key_offset is 1 when num_agents is set (the pre-rendered
+ *   instance's child and its transplant each took a spawn of the root, mapgen.py:199-241), else 0.  Its Random child draws
+ *   from the Maze scene's key with one more word 0: (0,), or (k + key_offset, 0) (mapgen/scene.py:199).
+ *   One recipe per engine, of any of the three kinds; everything said above about replacing, switching off, validation
+ *   before anything is touched and the users of a recipe holds.  The capacity checks run on one comb maze with symbol q on
+ *   its q-th empty cell.  LDS: the map, the wall permutation or the walk's stack (max(walls, maze cells)), a label or flag
+ *   per maze cell, the room's empty cells and the symbols, 2 B each, against 160 KB (MGX_MAPGEN_LDS_BYTES as above). */
+int mgx_set_map_maze_generator(mgx_engine* e, int32_t room_height, int32_t room_width, int32_t n_inst, int32_t rows, int32_t cols,
+                               int32_t border_width, int32_t instance_border_width, int32_t border_code, int32_t instance_border_code,
+                               int32_t algorithm, int32_t room_size, int32_t wall_size, int32_t wall_code, int32_t first_on_root,
+                               int32_t key_offset, const uint16_t* symbols, int32_t n_sym, const uint16_t* rename,
+                               const int32_t* rename_off, int32_t n_teams, const uint32_t* map_seed_base);
 int mgx_generate_maps(mgx_engine* e, const uint32_t* map_seeds, int32_t n, uint16_t* out, int32_t out_is_device);
 int mgx_reset_envs_generated(mgx_engine* e, const uint8_t* env_mask, const uint32_t* map_seeds, const uint32_t* seeds);
 int mgx_get_map_seeds(mgx_engine* e, uint32_t* out);

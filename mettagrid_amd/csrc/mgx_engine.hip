@@ -361,6 +361,8 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
   MgxMapGen gen{};                  // device pointers into d_gen_recipe + the shape
   MgxMapScene gen_scene{};          // ... of the scene recipe (gen_is_scene; an engine holds one recipe of either kind)
   bool gen_is_scene = false;
+  MgxMapMaze gen_maze{};            // ... of the maze recipe (gen_is_maze)
+  bool gen_is_maze = false;
   bool gen_on = false;              // (false: mgx_step and the restarts enqueue nothing for it)
   size_t gen_lds = 0;               // dynamic LDS of mgx_mapgen_kernel: the inner array (scene: map, indices, symbols)
   void* d_gen_recipe = nullptr;     // inner (scene: symbols) | rename | rename_off
@@ -1381,17 +1383,22 @@ static void free_map_generator(mgx_engine* e) {
   e->gen = MgxMapGen{};
   e->gen_scene = MgxMapScene{};
   e->gen_is_scene = false;
+  e->gen_maze = MgxMapMaze{};
+  e->gen_is_maze = false;
   e->gen_on = false;
   e->gen_lds = 0;
 }
 static int raise_mapgen_lds(mgx_engine* e, size_t bytes) {
   static MgxLdsLimit limit;
-  return raise_lds(limit, {(const void*)mgx_mapgen_kernel, (const void*)mgx_mapscene_kernel}, e, bytes);
+  return raise_lds(limit, {(const void*)mgx_mapgen_kernel, (const void*)mgx_mapscene_kernel, (const void*)mgx_maze_kernel}, e, bytes);
 }
 // The kernel of the recipe that is set: map k of `grid`-strided n (or *n_dev) maps (mgx_mapgen_kernel's arguments).
 static int launch_mapgen(mgx_engine* e, unsigned grid, const uint32_t* seeds, const uint32_t* base, const uint32_t* episodes,
                          const int32_t* env_list, const uint32_t* n_dev, int n, uint16_t* out, uint32_t* cur_seed) {
-  if (e->gen_is_scene)
+  if (e->gen_is_maze)
+    hipLaunchKernelGGL(mgx_maze_kernel, dim3(grid), dim3(MGX_WAVE), e->gen_lds, e->stream, e->gen_maze, seeds, base, episodes, env_list, n_dev,
+                       n, out, cur_seed);
+  else if (e->gen_is_scene)
     hipLaunchKernelGGL(mgx_mapscene_kernel, dim3(grid), dim3(MGX_WAVE), e->gen_lds, e->stream, e->gen_scene, seeds, base, episodes, env_list,
                        n_dev, n, out, cur_seed);
   else
@@ -1541,6 +1548,35 @@ int mgx_set_map_generator(mgx_engine* e, const uint16_t* inner, int32_t n_inner,
   return MGX_OK;
 }
 
+// The room grid of MapGen.prepare_grid (mapgen.py:305-315), in 64 bits: rows x cols for n_inst rooms, adding up to the program's map.
+static int check_room_grid(const mgx_engine* e, const char* who, int rh, int rw, int n_inst, int rows, int cols, int b, int ibw) {
+  const MgxDev& d = e->d;
+  int want_rows = 1;
+  while ((long long)want_rows * want_rows < n_inst) want_rows++;
+  const int want_cols = (n_inst + want_rows - 1) / want_rows;
+  const long long wantH = (long long)rows * rh + (long long)(rows - 1) * ibw + 2LL * b, wantW = (long long)cols * rw + (long long)(cols - 1) * ibw + 2LL * b;
+  if (rows != want_rows || cols != want_cols || wantH != d.H || wantW != d.W)
+    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": " + std::to_string(n_inst) + " instances are a grid of " + std::to_string(want_rows) + " x " +
+                                     std::to_string(want_cols) + " rooms, and rooms, instance borders and the outer border must add up to the program's " +
+                                     std::to_string(d.H) + " x " + std::to_string(d.W) + " map (they give " + std::to_string(wantH) + " x " +
+                                     std::to_string(wantW) + ")");
+  return MGX_OK;
+}
+// The representative map of a scene or maze recipe: its team cells renamed in row-major order over the whole map.
+static int rename_one_map(const char* who, std::vector<uint16_t>& one, const uint16_t* rename, const int32_t* rename_off, int32_t n_teams) {
+  std::vector<int> seen((size_t)std::max(n_teams, 1), 0);
+  for (uint16_t& v : one) {   // row-major over the whole map
+    if (v < MGX_MAPGEN_TEAM0) continue;
+    const int t = v - MGX_MAPGEN_TEAM0;
+    if (t >= n_teams) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": a symbol names team " + std::to_string(t) + " of " + std::to_string(n_teams));
+    const int k = seen[t]++;
+    if (k >= rename_off[t + 1] - rename_off[t])
+      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": more cells of team " + std::to_string(t) + " than entries in its rename table");
+    v = rename[rename_off[t] + k];
+  }
+  return MGX_OK;
+}
+
 int mgx_set_map_scene_generator(mgx_engine* e, int32_t room_height, int32_t room_width, int32_t n_inst, int32_t rows, int32_t cols,
                                 int32_t border_width, int32_t instance_border_width, int32_t border_code, int32_t instance_border_code,
                                 int32_t first_on_root, const uint16_t* symbols, int32_t n_sym, const uint16_t* rename,
@@ -1554,21 +1590,12 @@ int mgx_set_map_scene_generator(mgx_engine* e, int32_t room_height, int32_t room
   if (!map_seed_base || rh <= 0 || rw <= 0 || rh > d.H || rw > d.W || b < 0 || ibw < 0 || ibw > 0xFFFF || n_inst < 1 || rows < 1 || cols < 1 || n_sym < 0 ||
       (n_sym > 0 && !symbols))
     return fail(MGX_ERR_BAD_ARG, std::string(who) + ": null / negative argument, or base seeds not given");
-  {   // MapGen.prepare_grid (mapgen.py:305-315), in 64 bits
-    int want_rows = 1;
-    while ((long long)want_rows * want_rows < n_inst) want_rows++;
-    const int want_cols = (n_inst + want_rows - 1) / want_rows;
-    const long long wantH = (long long)rows * rh + (long long)(rows - 1) * ibw + 2LL * b, wantW = (long long)cols * rw + (long long)(cols - 1) * ibw + 2LL * b;
-    if (rows != want_rows || cols != want_cols || wantH != d.H || wantW != d.W)
-      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": " + std::to_string(n_inst) + " instances are a grid of " + std::to_string(want_rows) + " x " +
-                                       std::to_string(want_cols) + " rooms, and rooms, instance borders and the outer border must add up to the program's " +
-                                       std::to_string(d.H) + " x " + std::to_string(d.W) + " map (they give " + std::to_string(wantH) + " x " +
-                                       std::to_string(wantW) + ")");
-  }
+  int rc = check_room_grid(e, who, rh, rw, n_inst, rows, cols, b, ibw);
+  if (rc) return rc;
   const int area = rh * rw;
   if (n_sym > area)
     return fail(MGX_ERR_BAD_ARG, std::string(who) + ": " + std::to_string(n_sym) + " symbols do not fit the " + std::to_string(area) + " cells of a room");
-  int rc = check_rename_tables(e, who, rename, rename_off, n_teams);
+  rc = check_rename_tables(e, who, rename, rename_off, n_teams);
   if (rc) return rc;
   for (int code : {border_code, instance_border_code})
     if (code < 0 || code > nc)
@@ -1585,18 +1612,8 @@ int mgx_set_map_scene_generator(mgx_engine* e, int32_t room_height, int32_t room
   for (int k = 0; k < n_inst; k++)
     for (int i = 0; i < n_sym; i++)
       one[(size_t)(b + (k / cols) * ph + i / rw) * d.W + b + (k % cols) * pw + i % rw] = symbols[(size_t)k * n_sym + i];
-  {
-    std::vector<int> seen((size_t)std::max(n_teams, 1), 0);
-    for (uint16_t& v : one) {   // row-major over the whole map
-      if (v < MGX_MAPGEN_TEAM0) continue;
-      const int t = v - MGX_MAPGEN_TEAM0;
-      if (t >= n_teams) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": a symbol names team " + std::to_string(t) + " of " + std::to_string(n_teams));
-      const int k = seen[t]++;
-      if (k >= rename_off[t + 1] - rename_off[t])
-        return fail(MGX_ERR_BAD_ARG, std::string(who) + ": more cells of team " + std::to_string(t) + " than entries in its rename table");
-      v = rename[rename_off[t] + k];
-    }
-  }
+  rc = rename_one_map(who, one, rename, rename_off, n_teams);
+  if (rc) return rc;
   const size_t lds = MGX_MAPSCENE_LDS_BYTES((size_t)d.H * d.W, area, n_sym);
   const MgxRecipeBlob blob_host = pack_map_recipe(symbols, (size_t)n_inst * n_sym, rename, rename_off, n_teams);
   rc = accept_map_recipe(e, who, one, lds, "the map of " + std::to_string(d.H * d.W) + " cells with a room of " + std::to_string(area) + " and " +
@@ -1611,6 +1628,93 @@ int mgx_set_map_scene_generator(mgx_engine* e, int32_t room_height, int32_t room
   g.n_teams = n_teams; g.first_on_root = first_on_root ? 1 : 0;
   g.border_code = (uint32_t)border_code; g.iborder_code = (uint32_t)instance_border_code;
   e->gen_is_scene = true;
+  e->gen_on = true;
+  return MGX_OK;
+}
+
+int mgx_set_map_maze_generator(mgx_engine* e, int32_t room_height, int32_t room_width, int32_t n_inst, int32_t rows, int32_t cols,
+                               int32_t border_width, int32_t instance_border_width, int32_t border_code, int32_t instance_border_code,
+                               int32_t algorithm, int32_t room_size, int32_t wall_size, int32_t wall_code, int32_t first_on_root,
+                               int32_t key_offset, const uint16_t* symbols, int32_t n_sym, const uint16_t* rename,
+                               const int32_t* rename_off, int32_t n_teams, const uint32_t* map_seed_base) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_map_maze_generator: null engine");
+  HIP_TRY(hipSetDevice(e->device));
+  const MgxDev& d = e->d;
+  const char* who = "mgx_set_map_maze_generator";
+  const int nc = e->prog[MGX_H_NUM_CLASSES];
+  const int rh = room_height, rw = room_width, b = border_width, ibw = instance_border_width;
+  if (!map_seed_base || rh <= 0 || rw <= 0 || rh > d.H || rw > d.W || b < 0 || ibw < 0 || ibw > 0xFFFF || n_inst < 1 || rows < 1 || cols < 1 || n_sym < 0 ||
+      (n_sym > 0 && !symbols) || (key_offset != 0 && key_offset != 1))
+    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": null / negative argument, a key offset other than 0 or 1, or base seeds not given");
+  if (algorithm != MGX_MAZE_KRUSKAL && algorithm != MGX_MAZE_DFS)
+    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": algorithm " + std::to_string(algorithm) + " is neither kruskal (0) nor dfs (1)");
+  int rc = check_room_grid(e, who, rh, rw, n_inst, rows, cols, b, ibw);
+  if (rc) return rc;
+  // MazeGrid (mapgen/scenes/maze.py): the clamped sizes, the maze cells of a room and the walls between neighbouring cells
+  // (a wall as wide as the room's longer side or wider leaves one maze cell whatever its width: clamped, so that sums stay small)
+  const int rs = std::max(1, std::min(room_size, std::min(rw, rh))), ws = std::min(std::max(1, wall_size), std::max(rw, rh));
+  const int p = rs + ws, mcols = (rw + ws) / p, mrows = (rh + ws) / p;
+  const int cells = mcols * mrows, n_walls = mcols * (mrows - 1) + (mcols - 1) * mrows, area = rh * rw;
+  if (mcols < 1 || mrows < 1 || n_walls > 0xFFFF)
+    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": a room of " + std::to_string(rh) + " x " + std::to_string(rw) + " holds " + std::to_string(mrows) +
+                                     " x " + std::to_string(mcols) + " maze cells");
+  rc = check_rename_tables(e, who, rename, rename_off, n_teams);
+  if (rc) return rc;
+  for (int code : {border_code, instance_border_code, wall_code})
+    if (code < 0 || code > nc)
+      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": class map holds id " + std::to_string(code) + " but the program has " + std::to_string(nc) +
+                                       " classes");
+  if (wall_code == 0) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": the wall code is 0 (empty)");
+  // ONE generated map stands for all of them: every maze of a recipe is a spanning tree of the same maze cells, so all hold
+  // the same number of wall and empty cells, and every symbol is always placed.  The representative is a comb maze (every
+  // wall between vertical neighbours open, between horizontal neighbours in the top row only) with symbol q of an instance
+  // on the q-th empty cell of its room.
+  std::vector<uint16_t> room((size_t)area);
+  for (int i = 0; i < area; i++) {
+    const int x = i % rw, y = i / rw;
+    const bool strip = (x % p >= rs && x / p < mcols - 1) || (y % p >= rs && y / p < mrows - 1);
+    const bool cell = x % p < rs && x / p < mcols && y % p < rs && y / p < mrows;
+    const bool open_down = x % p < rs && x / p < mcols && y % p >= rs && y / p < mrows - 1;
+    const bool open_right = y < rs && x % p >= rs && x / p < mcols - 1;
+    const bool wall = algorithm == MGX_MAZE_KRUSKAL ? (strip && !open_down && !open_right) : !(cell || open_down || open_right);
+    room[(size_t)i] = wall ? (uint16_t)wall_code : (uint16_t)0;
+  }
+  std::vector<int> empties;
+  for (int i = 0; i < area; i++)
+    if (!room[(size_t)i]) empties.push_back(i);
+  const int n_empty = (int)empties.size();
+  if (n_sym > n_empty)
+    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": " + std::to_string(n_sym) + " symbols do not fit the " + std::to_string(n_empty) +
+                                     " empty cells of a room's maze");
+  std::vector<uint16_t> one((size_t)d.H * d.W, (uint16_t)border_code);
+  const int ph = rh + ibw, pw = rw + ibw;
+  for (int r = 0; r < d.H - 2 * b; r++)
+    for (int c = 0; c < d.W - 2 * b; c++)
+      one[(size_t)(r + b) * d.W + c + b] = (n_inst > 1 && (r % ph >= rh || c % pw >= rw)) ? (uint16_t)instance_border_code : (uint16_t)0;
+  for (int k = 0; k < n_inst; k++) {
+    uint16_t* at = one.data() + (size_t)(b + (k / cols) * ph) * d.W + b + (k % cols) * pw;
+    for (int i = 0; i < area; i++) at[(size_t)(i / rw) * d.W + i % rw] = room[(size_t)i];
+    for (int q = 0; q < n_sym; q++) at[(size_t)(empties[(size_t)q] / rw) * d.W + empties[(size_t)q] % rw] = symbols[(size_t)k * n_sym + q];
+  }
+  rc = rename_one_map(who, one, rename, rename_off, n_teams);
+  if (rc) return rc;
+  const int n_work = std::max(n_walls, cells);
+  const size_t lds = MGX_MAZE_LDS_BYTES((size_t)d.H * d.W, n_work, cells, area, n_sym);
+  const MgxRecipeBlob blob_host = pack_map_recipe(symbols, (size_t)n_inst * n_sym, rename, rename_off, n_teams);
+  rc = accept_map_recipe(e, who, one, lds, "the map of " + std::to_string(d.H * d.W) + " cells with a room of " + std::to_string(area) + ", " +
+                                               std::to_string(cells) + " maze cells, " + std::to_string(n_walls) + " walls and " +
+                                               std::to_string(n_sym) + " symbols", blob_host.host, map_seed_base);
+  if (rc) return rc;
+  const uint8_t* blob = (const uint8_t*)e->d_gen_recipe;
+  MgxMapMaze& g = e->gen_maze;
+  g.symbols = (const uint16_t*)blob;
+  g.rename = (const uint16_t*)(blob + blob_host.off_rename);
+  g.rename_off = (const int32_t*)(blob + blob_host.off_off);
+  g.n_sym = n_sym; g.rh = rh; g.rw = rw; g.n_inst = n_inst; g.rows = rows; g.cols = cols; g.border = b; g.ibw = ibw; g.H = d.H; g.W = d.W;
+  g.n_teams = n_teams; g.first_on_root = first_on_root ? 1 : 0; g.key_offset = key_offset;
+  g.algorithm = algorithm; g.rs = rs; g.ws = ws; g.mcols = mcols; g.mrows = mrows; g.n_walls = n_walls; g.n_work = n_work;
+  g.border_code = (uint32_t)border_code; g.iborder_code = (uint32_t)instance_border_code; g.wall_code = (uint32_t)wall_code;
+  e->gen_is_maze = true;
   e->gen_on = true;
   return MGX_OK;
 }

@@ -63,6 +63,20 @@ struct MgxMapScene {
   uint32_t border_code, iborder_code;   // outer wall; fill between the rooms (n_inst > 1)
 };
 
+struct MgxMapMaze {
+  const uint16_t* symbols;     // [n_inst][n_sym] as MgxMapScene's
+  const uint16_t* rename;
+  const int32_t* rename_off;   // [n_teams + 1]
+  int n_sym, rh, rw, n_inst, rows, cols, border, ibw, H, W, n_teams;
+  int first_on_root, key_offset;   // the Maze scene of instance k: default_rng(seed) for k == 0 with first_on_root, else key (k + key_offset,)
+  int algorithm;                   // MGX_MAZE_KRUSKAL / MGX_MAZE_DFS
+  int rs, ws, mcols, mrows;        // clamped room and wall size, maze cells per row and per column of a room
+  int n_walls, n_work;             // walls between neighbouring cells; max(n_walls, cells): the permutation / the stack
+  uint32_t border_code, iborder_code, wall_code;
+};
+#define MGX_MAZE_KRUSKAL 0
+#define MGX_MAZE_DFS 1
+
 #ifndef MGX_CPU_EMU
 struct MgxU128 { unsigned long long hi, lo; };
 // (the seeding is __host__ __device__: csrc/mgx_pool_sample.h runs it on the host too, from this one source)
@@ -161,6 +175,18 @@ struct MgxDraws {
       const uint16_t ai = a[i], aj = a[j];   // (every lane the same addresses: broadcast reads, same-value writes)
       a[i] = aj; a[j] = ai;
     }
+  }
+  // Generator.integers(0, m) for a wavefront-uniform scalar m <= 2^32 - 1: no draw for m <= 1, else Lemire's method on
+  // next_uint32 (the halves shuffle consumes): prod = half * m, redrawn while its low word is below (2^32 - m) mod m.  For
+  // m <= 4 (the maze walk) the redraw happens only for m == 3 with a half of 0.
+  __device__ __forceinline__ uint32_t integers(uint32_t m, const MgxU128& mulA, const MgxU128& mulG) {
+    if (m <= 1u) return 0u;
+    unsigned long long prod = (unsigned long long)half(mulA, mulG) * m;
+    if ((uint32_t)prod < m) {
+      const uint32_t thr = (0xFFFFFFFFu - (m - 1u)) % m;
+      while ((uint32_t)prod < thr) prod = (unsigned long long)half(mulA, mulG) * m;
+    }
+    return (uint32_t)(prod >> 32);
   }
 };
 
@@ -295,6 +321,178 @@ __global__ void __launch_bounds__(MGX_WAVE) mgx_mapscene_kernel(MgxMapScene g, c
     const uint32_t seed = seeds ? seeds[k] : base[env] + episodes[env];
     if (cur_seed && lane == 0) cur_seed[env] = seed;
     mgx_mapscene_one(g, seed, mulA, mulG, mgx_mapgen_lds, out + (size_t)env * HW);
+  }
+}
+
+// ---- the third recipe kind: MapGen with a Maze instance scene and a Random child (mgx_set_map_maze_generator) ----
+// LDS of the maze kernel, u16 each: the map [H * W], the wall permutation or the walk's stack [n_work], the component label or
+// the visited flag of every maze cell [cells], the room's empty cells [rh * rw], the symbols [n_sym].
+#define MGX_MAZE_LDS_BYTES(HW, n_work, cells, area, n_sym) \
+  ((((size_t)(HW) + (size_t)(n_work) + (size_t)(cells) + (size_t)(area) + (size_t)(n_sym)) * 2 + 15) & ~(size_t)15)
+
+// A value every lane read from the same LDS address, as a scalar: the maze's control flow is wavefront-uniform.
+__device__ __forceinline__ int mgx_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// Empty the bw x bh block at (x, y) of a room (row pitch W), lanes over its cells; nothing reads the room before the barrier
+// that follows the maze.
+__device__ __forceinline__ void mgx_maze_clear(uint16_t* room, int W, int rh, int rw, int x, int y, int bw, int bh) {
+  for (int i = threadIdx.x; i < bw * bh; i += MGX_WAVE) {
+    const int cx = x + i % bw, cy = y + i / bw;
+    if (cx < rw && cy < rh) room[cy * W + cx] = 0;
+  }
+}
+// The wall block between maze cell (i, j) and its neighbour (i + di, j + dj): rs x ws or ws x rs cells.
+__device__ __forceinline__ void mgx_maze_open(const MgxMapMaze& g, uint16_t* room, int i, int j, int di, int dj) {
+  const int p = g.rs + g.ws, x = (di < 0 ? i - 1 : i) * p, y = (dj < 0 ? j - 1 : j) * p;
+  if (di) mgx_maze_clear(room, g.W, g.rh, g.rw, x + g.rs, y, g.ws, g.rs);
+  else mgx_maze_clear(room, g.W, g.rh, g.rw, x, y + g.rs, g.rs, g.ws);
+}
+
+// Maze._render_kruskal (mapgen/scenes/maze.py): the room empty, wall strips between the cell columns and rows (a remainder
+// right of or below the last cell stays empty), one shuffle of the wall list — (col, row, down) for col, row < rows - 1, then
+// (col, row, right) for col < cols - 1, row — and every wall opened whose two cells are not connected yet.  Connectivity alone
+// decides the output: label[c] is the component of cell c, a union relabels one component with the lanes over the cells
+// (no find loop; n_walls serial steps, each at most ceil(cells / 64) passes).
+__device__ __forceinline__ void mgx_maze_kruskal(const MgxMapMaze& g, MgxDraws& d, const MgxU128& mulA, const MgxU128& mulG, uint16_t* room,
+                                                 uint16_t* perm, uint16_t* label) {
+  const int lane = threadIdx.x;
+  const int area = g.rh * g.rw, cells = g.mcols * g.mrows, p = g.rs + g.ws;
+  for (int i = lane; i < area; i += MGX_WAVE) {
+    const int x = i % g.rw, y = i / g.rw;
+    const bool wall = (x % p >= g.rs && x / p < g.mcols - 1) || (y % p >= g.rs && y / p < g.mrows - 1);
+    room[y * g.W + x] = wall ? (uint16_t)g.wall_code : (uint16_t)0;
+  }
+  for (int i = lane; i < g.n_walls; i += MGX_WAVE) perm[i] = (uint16_t)i;
+  for (int i = lane; i < cells; i += MGX_WAVE) label[i] = (uint16_t)i;
+  __syncthreads();
+  d.shuffle(perm, g.n_walls, mulA, mulG);
+  const int n_down = g.mcols * (g.mrows - 1);
+  for (int t = 0; t < g.n_walls; t++) {
+    const int w = mgx_uniform(perm[t]);
+    if (w >= g.n_walls) continue;   // (a permutation never holds one)
+    int col, row, di = 0, dj = 0;
+    if (w < n_down) { col = w / (g.mrows - 1); row = w % (g.mrows - 1); dj = 1; }
+    else { col = (w - n_down) / g.mrows; row = (w - n_down) % g.mrows; di = 1; }
+    const int la = mgx_uniform(label[row * g.mcols + col]), lb = mgx_uniform(label[(row + dj) * g.mcols + col + di]);
+    if (la == lb) continue;
+    mgx_maze_open(g, room, col, row, di, dj);
+    for (int c = lane; c < cells; c += MGX_WAVE)
+      if (label[c] == lb) label[c] = (uint16_t)la;
+    __syncthreads();   // (the next wall reads labels other lanes wrote)
+  }
+}
+
+// Maze._render_dfs: the room all wall, cell (0, 0) carved and pushed; at the top of the stack the unvisited neighbours inside
+// the maze in the order up, down, right, left; none: pop, else one of them by Generator.integers(0, count), its wall opened,
+// the cell carved and pushed.  Every cell is pushed once and popped once: at most 2 * cells iterations.
+__device__ __forceinline__ void mgx_maze_dfs(const MgxMapMaze& g, MgxDraws& d, const MgxU128& mulA, const MgxU128& mulG, uint16_t* room,
+                                             uint16_t* stack, uint16_t* visited) {
+  const int lane = threadIdx.x;
+  const int area = g.rh * g.rw, cells = g.mcols * g.mrows, p = g.rs + g.ws;
+  for (int i = lane; i < area; i += MGX_WAVE) room[(i / g.rw) * g.W + i % g.rw] = (uint16_t)g.wall_code;
+  for (int i = lane; i < cells; i += MGX_WAVE) visited[i] = 0;
+  __syncthreads();
+  if (cells <= 0) return;
+  mgx_maze_clear(room, g.W, g.rh, g.rw, 0, 0, g.rs, g.rs);
+  stack[0] = 0; visited[0] = 1;   // (every lane the same addresses and values, as in the shuffle)
+  int sp = 1;
+  for (int it = 0; it < 2 * cells && sp > 0; it++) {
+    const int cur = mgx_uniform(stack[sp - 1]);
+    if (cur >= cells) break;   // (the stack holds cell indices only)
+    const int i = cur % g.mcols, j = cur / g.mcols;
+    uint32_t dirs = 0, m = 0;   // 2 bits per open direction, in the reference's order
+    if (j > 0 && !mgx_uniform(visited[cur - g.mcols])) { dirs |= 0u << (2 * m); m++; }
+    if (j + 1 < g.mrows && !mgx_uniform(visited[cur + g.mcols])) { dirs |= 1u << (2 * m); m++; }
+    if (i + 1 < g.mcols && !mgx_uniform(visited[cur + 1])) { dirs |= 2u << (2 * m); m++; }
+    if (i > 0 && !mgx_uniform(visited[cur - 1])) { dirs |= 3u << (2 * m); m++; }
+    if (m == 0) { sp--; continue; }
+    const uint32_t dir = (dirs >> (2 * d.integers(m, mulA, mulG))) & 3u;
+    const int di = dir == 2u ? 1 : dir == 3u ? -1 : 0, dj = dir == 0u ? -1 : dir == 1u ? 1 : 0;
+    const int ni = i + di, nj = j + dj, next = nj * g.mcols + ni;
+    if (sp >= cells) break;    // (every cell is pushed once)
+    mgx_maze_open(g, room, i, j, di, dj);
+    mgx_maze_clear(room, g.W, g.rh, g.rw, ni * p, nj * p, g.rs, g.rs);
+    visited[next] = 1;
+    stack[sp++] = (uint16_t)next;
+  }
+}
+
+// One map of the maze recipe: border, fill and empty rooms in `map` (LDS, H * W u16) as the scene recipe's, then per instance
+// the maze on its own stream and — on the stream of that key with one more word 0 — the Random child: the shuffle of the
+// symbols, the shuffle of the room's empty cells in row-major order, symbol q on empty cell q.  Then the rename over the whole
+// map -> dst [H][W].  Called by all 64 lanes.
+__device__ __forceinline__ void mgx_maze_one(const MgxMapMaze& g, uint32_t seed, MgxU128 mulA, MgxU128 mulG, uint16_t* map,
+                                             uint16_t* __restrict__ dst) {
+  const int lane = threadIdx.x;
+  const int HW = g.H * g.W, area = g.rh * g.rw, n_sym = g.n_sym, cells = g.mcols * g.mrows;
+  uint16_t* work = map + HW;          // kruskal: the wall permutation; dfs: the stack
+  uint16_t* mark = work + g.n_work;   // kruskal: the component labels; dfs: the visited flags
+  uint16_t* emp = mark + cells;
+  uint16_t* sym = emp + area;
+  const int ph = g.rh + g.ibw, pw = g.rw + g.ibw;   // room pitch
+  const int inh = g.H - 2 * g.border, inw = g.W - 2 * g.border;
+  for (int i = lane; i < HW; i += MGX_WAVE) {
+    const int r = i / g.W - g.border, c = i % g.W - g.border;
+    uint32_t v = g.border_code;
+    if (r >= 0 && r < inh && c >= 0 && c < inw) v = (g.n_inst > 1 && (r % ph >= g.rh || c % pw >= g.rw)) ? g.iborder_code : 0u;
+    map[i] = (uint16_t)v;
+  }
+  for (int k = 0; k < g.n_inst; k++) {
+    __syncthreads();   // (the map is filled / the scatter of the instance before is done)
+    uint16_t* room = map + (g.border + (k / g.cols) * ph) * g.W + g.border + (k % g.cols) * pw;
+    const bool root = k == 0 && g.first_on_root;
+    const uint32_t keys[2] = {(uint32_t)(k + g.key_offset), 0u};
+    MgxDraws d;
+    if (root) mgx_pcg64_seed_keys<0>(seed, d.base, d.inc, keys);
+    else mgx_pcg64_seed_keys<1>(seed, d.base, d.inc, keys);
+    if (g.algorithm == MGX_MAZE_KRUSKAL) mgx_maze_kruskal(g, d, mulA, mulG, room, work, mark);
+    else mgx_maze_dfs(g, d, mulA, mulG, room, work, mark);
+    __syncthreads();
+    if (n_sym <= 0) continue;   // (no symbols: the child draws nothing)
+    int n_emp = 0;
+    for (int c0 = 0; c0 < area; c0 += MGX_WAVE) {   // row-major compaction: ballot + popcount over 64-cell chunks
+      const int i = c0 + lane;
+      const bool is = i < area && room[(i / g.rw) * g.W + i % g.rw] == 0;
+      const unsigned long long b = __ballot(is);
+      if (is) emp[n_emp + __popcll(b & ((1ull << lane) - 1ull))] = (uint16_t)i;
+      n_emp += __popcll(b);
+    }
+    for (int i = lane; i < n_sym; i += MGX_WAVE) sym[i] = g.symbols[(size_t)k * n_sym + i];
+    MgxDraws c;
+    if (root) mgx_pcg64_seed_keys<1>(seed, c.base, c.inc, keys + 1);
+    else mgx_pcg64_seed_keys<2>(seed, c.base, c.inc, keys);
+    __syncthreads();
+    c.shuffle(sym, n_sym, mulA, mulG);
+    c.shuffle(emp, n_emp, mulA, mulG);
+    __syncthreads();
+    for (int t = lane; t < n_sym && t < n_emp; t += MGX_WAVE) {   // (distinct targets: emp holds distinct cells)
+      const int v = emp[t];
+      if (v < area) room[(v / g.rw) * g.W + v % g.rw] = sym[t];
+    }
+  }
+  __syncthreads();
+  mgx_mapgen_rename(map, HW, g.rename, g.rename_off, g.n_teams);
+  __syncthreads();
+  for (int i = lane; i < HW; i += MGX_WAVE) dst[i] = map[i];
+  __syncthreads();   // (the next map of this wavefront refills `map`)
+}
+
+// mgx_mapgen_kernel for the maze recipe: the same launch arguments.
+__global__ void __launch_bounds__(MGX_WAVE) mgx_maze_kernel(MgxMapMaze g, const uint32_t* __restrict__ seeds, const uint32_t* __restrict__ base,
+                                                            const uint32_t* __restrict__ episodes, const int32_t* __restrict__ env_list,
+                                                            const uint32_t* __restrict__ n_dev, int n, uint16_t* __restrict__ out,
+                                                            uint32_t* __restrict__ cur_seed) {
+  extern __shared__ uint16_t mgx_mapgen_lds[];
+  const int lane = threadIdx.x;
+  MgxU128 mulA, mulG;
+  mgx_mapgen_multipliers(mulA, mulG);
+  const int count = n_dev ? (int)*n_dev : n;
+  const size_t HW = (size_t)g.H * g.W;
+  for (int k = blockIdx.x; k < count; k += gridDim.x) {
+    const int env = env_list ? env_list[k] : k;
+    const uint32_t seed = seeds ? seeds[k] : base[env] + episodes[env];
+    if (cur_seed && lane == 0) cur_seed[env] = seed;
+    mgx_maze_one(g, seed, mulA, mulG, mgx_mapgen_lds, out + (size_t)env * HW);
   }
 }
 #endif  // MGX_CPU_EMU

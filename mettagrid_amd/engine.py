@@ -221,6 +221,7 @@ def load_lib():
     if hasattr(L, "mgx_set_map_generator"):   # (absent from the CPU sanitizer build, like the packed rows)
         L.mgx_set_map_generator.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, vp]
         L.mgx_set_map_scene_generator.argtypes = [vp] + [i32] * 10 + [vp, i32, vp, vp, i32, vp]
+        L.mgx_set_map_maze_generator.argtypes = [vp] + [i32] * 15 + [vp, i32, vp, vp, i32, vp]
         L.mgx_generate_maps.argtypes = [vp, vp, i32, vp, i32]
         L.mgx_reset_envs_generated.argtypes = [vp, vp, vp, vp]
         L.mgx_get_map_seeds.argtypes = [vp, vp]
@@ -469,8 +470,9 @@ class BatchedMettaGrid:
     # ---- device map generator (include/mgx.h "Device map generator"; csrc/mgx_mapgen.h) ----
     def set_map_generator(self, spec, map_seed_base=0) -> None:
         """New episodes' maps from one of the reference's map builders on the device.  ``spec``: a ``mapgen.RandomMapSpec``
-        (RandomMapBuilder) or a ``mapgen.MapGenSpec`` (MapGen with a Random instance scene, the arena's builder), or what their
-        ``lower(prog)`` returns; the engine holds one recipe, so setting one replaces the other and ``None`` switches the
+        (RandomMapBuilder), a ``mapgen.MapGenSpec`` (MapGen with a Random instance scene, the arena's builder) or a
+        ``mapgen.MazeGenSpec`` (MapGen with a Maze instance scene and a Random child), or what their ``lower(prog)`` returns; the
+        engine holds one recipe, so setting one replaces the other and ``None`` switches the
         generator off; ``map_seed_base``: uint32 [E] (or one value for all)."""
         if spec is None:
             _check(self.L.mgx_set_map_generator(self.h, None, 0, 0, 0, None, None, 0, None))
@@ -480,6 +482,15 @@ class BatchedMettaGrid:
         off = np.ascontiguousarray(low.rename_off, dtype=np.int32)
         base = np.ascontiguousarray(np.broadcast_to(np.asarray(map_seed_base, dtype=np.uint32), (self.E,)))
         n_teams = int(off.size) - 1
+        if hasattr(low, "algorithm"):   # a mapgen.LoweredMaze
+            sym = np.ascontiguousarray(low.symbols, dtype=np.uint16)
+            _check(self.L.mgx_set_map_maze_generator(
+                self.h, int(low.room_height), int(low.room_width), int(low.n_inst), int(low.rows), int(low.cols), int(low.border_width),
+                int(low.instance_border_width), int(low.border_code), int(low.instance_border_code), int(low.algorithm),
+                int(low.room_size), int(low.wall_size), int(low.wall_code), int(bool(low.first_on_root)), int(low.key_offset),
+                sym.ctypes.data if sym.size else None, int(low.n_sym), rename.ctypes.data if rename.size else None,
+                off.ctypes.data if n_teams > 0 else None, n_teams, base.ctypes.data))
+            return
         if hasattr(low, "symbols"):   # a mapgen.LoweredScene
             sym = np.ascontiguousarray(low.symbols, dtype=np.uint16)
             _check(self.L.mgx_set_map_scene_generator(

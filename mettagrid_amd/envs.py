@@ -222,10 +222,11 @@ class MettaGridBatchedEnv:
       same step.
     * ``map_fn(env_index, episode_index) -> uint16 class map [H, W]``: maps built on the host once per episode, as in the
       reference (simulator.py:83); the done test then costs a device->host read per step.
-    * ``map_gen`` (a ``mapgen.RandomMapSpec`` or a ``mapgen.MapGenSpec``; ``mapgen.spec_from_config`` makes either from the dict
-      of a reference map builder config): a fresh map per episode like ``map_fn``, generated ON THE DEVICE at restart like
-      ``map_pool`` (``mgx_set_map_generator`` / ``mgx_set_map_scene_generator``): the reference's RandomMapBuilder, or its
-      MapGen with a Random instance scene (the arena's map builder), seeded ``base[e] + k`` for episode ``k`` of env ``e``
+    * ``map_gen`` (a ``mapgen.RandomMapSpec``, a ``mapgen.MapGenSpec`` or a ``mapgen.MazeGenSpec``; ``mapgen.spec_from_config``
+      makes any of them from the dict of a reference map builder config): a fresh map per episode like ``map_fn``, generated ON
+      THE DEVICE at restart like ``map_pool`` (``mgx_set_map_generator`` / ``mgx_set_map_scene_generator`` /
+      ``mgx_set_map_maze_generator``): the reference's RandomMapBuilder, or its MapGen with a Random instance scene (the arena's
+      map builder) or with a Maze instance scene and a Random child, seeded ``base[e] + k`` for episode ``k`` of env ``e``
       (simulator.py:403-409), ``base[e] = (map_seed + e * map_seed_stride) mod 2**32``.  ``map_seed_stride``
       defaults to 2**16, so the seed ranges of two envs do not overlap before an env has played 2**16 episodes (for up to
       2**16 envs; beyond that the bases wrap).  ``desync`` as for ``map_pool``.  ``engine.map_seeds()`` / episode-log records

@@ -215,6 +215,8 @@ class MapGenSpec:
     the Random scene from a generator of its own, inside an outer wall.  ``make_arena`` (builder/envs.py:54-67) builds its
     maps with this."""
 
+    _fills_its_area = False   # a Random scene writes only the cells it places; a Maze (MazeGenSpec) writes all of its room
+
     def __init__(self, width: int, height: int, objects: dict, agents: dict | int, num_agents: int | None = None,
                  instances: int | None = None, border_width: int = 5, instance_border_width: int = 5,
                  instance_border_object: str = "wall", set_team_by_instance: bool = False) -> None:
@@ -241,7 +243,7 @@ class MapGenSpec:
         # lone instance is the root scene on that generator (mapgen.py:340-368) unless set_team_by_instance wraps it in a Nop
         # scene, whose child it then is (mapgen.py:434-449), and every room of a room grid is a child scene.
         self.first_on_root = bool(num_agents) or (n == 1 and not self.set_team_by_instance)
-        if self.border_width == 0 and n == 1 and not num_agents and not self.refusal:
+        if self.border_width == 0 and n == 1 and not num_agents and not self.refusal and not self._fills_its_area:
             # mapgen.py:323-326 with a border of 0 turns the whole grid to wall ([-0:] is everything); a pre-rendered instance
             # or a room grid overwrites that, a lone scene finds no empty cell and fails on its assignment (random.py:67)
             self.refusal = "MapGenSpec: border_width 0 with one instance and no num_agents (the reference cannot build this map)"
@@ -343,6 +345,224 @@ class MapGenSpec:
                             np.array(rename, dtype=np.uint16), np.array(rename_off, dtype=np.int32))
 
 
+# ---- MapGen with a Maze instance scene (mapgen/scenes/maze.py) and a Random child over the whole room ----
+MAZE_ALGORITHMS = ("kruskal", "dfs")                # LoweredMaze.algorithm: the index
+MAZE_DIRS = ((0, -1), (0, 1), (1, 0), (-1, 0))      # (di, dj) in the order the walk lists them: up, down, right, left
+
+
+def maze_geometry(height: int, width: int, room_size: int, wall_size: int) -> tuple:
+    """(rs, ws, cols, rows) of a maze over a height x width room (maze.py MazeGrid, Maze.post_init): maze cell (i, j) is the
+    rs x rs block at x = i * (rs + ws), y = j * (rs + ws)."""
+    rs = max(1, min(int(room_size), width, height))
+    ws = max(1, int(wall_size))
+    return rs, ws, (width + ws) // (rs + ws), (height + ws) // (rs + ws)
+
+
+def maze_walls(cols: int, rows: int) -> list:
+    """The walls between neighbouring maze cells, (col, row, di, dj), in the order kruskal lists them before its shuffle."""
+    return ([(c, r, 0, 1) for c in range(cols) for r in range(rows - 1)] +
+            [(c, r, 1, 0) for c in range(cols - 1) for r in range(rows)])
+
+
+def _maze_open(g: np.ndarray, rs: int, ws: int, i: int, j: int, di: int, dj: int) -> None:
+    """Empty the wall block between maze cell (i, j) and its neighbour (i + di, j + dj): rs x ws or ws x rs cells."""
+    p = rs + ws
+    x, y = min(i, i + di) * p, min(j, j + dj) * p
+    if di:
+        g[y:y + rs, x + rs:x + p] = 0
+    else:
+        g[y + rs:y + p, x:x + rs] = 0
+
+
+def maze_kruskal(height: int, width: int, room_size: int, wall_size: int, order) -> np.ndarray:
+    """uint8 [height][width], 1 = wall: empty room, wall strips between the cell columns and rows (a remainder right of or below
+    the last cell stays empty), then the walls in ``order`` (a permutation of ``maze_walls``' indices) opened where the two cells
+    are not connected yet."""
+    rs, ws, cols, rows = maze_geometry(height, width, room_size, wall_size)
+    p = rs + ws
+    g = np.zeros((height, width), np.uint8)
+    for c in range(cols - 1):
+        g[:, p * c + rs:p * (c + 1)] = 1
+    for r in range(rows - 1):
+        g[p * r + rs:p * (r + 1), :] = 1
+    walls = maze_walls(cols, rows)
+    label = list(range(cols * rows))   # connectivity alone decides the output: the component id of every cell
+    for t in order:
+        c, r, di, dj = walls[int(t)]
+        a, b = label[r * cols + c], label[(r + dj) * cols + c + di]
+        if a != b:
+            _maze_open(g, rs, ws, c, r, di, dj)
+            label = [a if v == b else v for v in label]
+    return g
+
+
+def maze_dfs(height: int, width: int, room_size: int, wall_size: int, integers) -> np.ndarray:
+    """uint8 [height][width], 1 = wall: all wall, then the depth-first walk from cell (0, 0); ``integers(m)`` is the draw
+    ``Generator.integers(0, m)`` among the m >= 1 unvisited neighbours of the cell on top of the stack."""
+    walk = maze_dfs_walk(height, width, room_size, wall_size)
+    try:
+        m = next(walk)
+        while True:
+            m = walk.send(integers(m))
+    except StopIteration as done:
+        return done.value
+
+
+def maze_dfs_walk(height: int, width: int, room_size: int, wall_size: int):
+    """``maze_dfs`` as a generator: yields m at every decision, is sent the draw, and returns the grid."""
+    rs, ws, cols, rows = maze_geometry(height, width, room_size, wall_size)
+    p = rs + ws
+    g = np.ones((height, width), np.uint8)
+    seen = np.zeros((rows, cols), bool)
+    stack = [(0, 0)]
+    seen[0, 0] = True
+    g[0:rs, 0:rs] = 0
+    for _ in range(2 * cols * rows):   # every cell is pushed once and popped once
+        if not stack:
+            break
+        i, j = stack[-1]
+        dirs = [(di, dj) for di, dj in MAZE_DIRS if 0 <= i + di < cols and 0 <= j + dj < rows and not seen[j + dj, i + di]]
+        if not dirs:
+            stack.pop()
+            continue
+        di, dj = dirs[int((yield len(dirs)))]
+        _maze_open(g, rs, ws, i, j, di, dj)
+        i, j = i + di, j + dj
+        seen[j, i] = True
+        g[j * p:j * p + rs, i * p:i * p + rs] = 0
+        stack.append((i, j))
+    return g
+
+
+def _maze_key(rule, k: int):
+    """The spawn key of instance k's Maze scene under the key rule of a MazeGenSpec or LoweredMaze: None = the generator of
+    default_rng(seed) itself."""
+    return None if (k == 0 and rule.first_on_root) else (k + rule.key_offset,)
+
+
+class LoweredMaze:
+    """What ``MazeGenSpec.lower`` makes: the arguments of ``mgx_set_map_maze_generator``."""
+
+    def __init__(self, height, width, room_height, room_width, n_inst, rows, cols, border_width, instance_border_width, border_code,
+                 instance_border_code, first_on_root, key_offset, algorithm, room_size, wall_size, wall_code, n_empty, symbols, rename,
+                 rename_off):
+        self.height, self.width, self.room_height, self.room_width = height, width, room_height, room_width
+        self.n_inst, self.rows, self.cols = n_inst, rows, cols
+        self.border_width, self.instance_border_width = border_width, instance_border_width
+        self.border_code, self.instance_border_code = border_code, instance_border_code   # class index + 1, 0 = empty
+        # the key rule: the Maze scene of instance k draws from default_rng(seed) when k == 0 and first_on_root, else from spawn
+        # key (k + key_offset,); its Random child from that key with one more word 0
+        self.first_on_root, self.key_offset = first_on_root, key_offset
+        self.algorithm = algorithm                               # index into MAZE_ALGORITHMS
+        self.room_size, self.wall_size = room_size, wall_size    # as configured; maze_geometry clamps them
+        self.wall_code = wall_code                               # class index + 1 of "wall"
+        self.n_empty = n_empty                                   # empty cells of every room's maze: a constant of the recipe
+        self.symbols = symbols                                   # uint16 [n_inst][n_sym], as LoweredScene's
+        self.rename, self.rename_off = rename, rename_off
+
+    @property
+    def n_sym(self) -> int:
+        return self.symbols.shape[1]
+
+    @property
+    def n_teams(self) -> int:
+        return len(self.rename_off) - 1
+
+    def maze_key(self, k: int):
+        return _maze_key(self, k)
+
+
+class MazeGenSpec(MapGenSpec):
+    """The reference's ``MapGen.Config`` with a ``Maze.Config`` instance scene (mapgen/scenes/maze.py) whose one child is a
+    ``Random.Config`` scene over the whole room (``where="full"``), without its seed: every room is a maze built by ``algorithm``
+    ("kruskal" or "dfs") from a generator of its own, and the Random child puts ``objects`` and ``agents`` on the maze's empty
+    cells from the first spawn of that generator."""
+
+    _fills_its_area = True
+
+    def __init__(self, width: int, height: int, objects: dict, agents: dict | int, num_agents: int | None = None,
+                 instances: int | None = None, border_width: int = 5, instance_border_width: int = 5,
+                 instance_border_object: str = "wall", set_team_by_instance: bool = False, algorithm: str = "kruskal",
+                 room_size: int = 1, wall_size: int = 1) -> None:
+        if algorithm not in MAZE_ALGORITHMS:
+            raise ValueError(f"MazeGenSpec: algorithm {algorithm!r} is not one of {MAZE_ALGORITHMS}")
+        if isinstance(room_size, bool) or isinstance(wall_size, bool) or int(room_size) != room_size or int(wall_size) != wall_size:
+            raise ValueError("MazeGenSpec: room_size and wall_size are ints")
+        self.algorithm, self.room_size, self.wall_size = algorithm, int(room_size), int(wall_size)
+        super().__init__(width, height, objects, agents, num_agents, instances, border_width, instance_border_width,
+                         instance_border_object, set_team_by_instance)
+        # instance 0 on the builder's generator as for MapGenSpec; when num_agents is set the pre-rendered instance's child and
+        # its transplant each took one spawn of the root before instance 1 (mapgen.py:199-241), so instance k >= 1 is spawn k + 1
+        self.key_offset = 1 if num_agents else 0
+        _, _, cols, rows = maze_geometry(self.height, self.width, self.room_size, self.wall_size)
+        self.n_empty = int(np.count_nonzero(self._comb() == 0))
+        self.n_walls = len(maze_walls(cols, rows))
+
+    def _comb(self) -> np.ndarray:
+        """A maze of this recipe that needs no draw (the walls opened in list order; the walk always taking its first
+        direction).  Every maze of a recipe is a spanning tree of the same cells, so all hold as many empty cells as this one."""
+        if self.algorithm == "kruskal":
+            _, _, cols, rows = maze_geometry(self.height, self.width, self.room_size, self.wall_size)
+            return maze_kruskal(self.height, self.width, self.room_size, self.wall_size, range(len(maze_walls(cols, rows))))
+        return maze_dfs(self.height, self.width, self.room_size, self.wall_size, lambda m: 0)
+
+    def maze_key(self, k: int):
+        return _maze_key(self, k)
+
+    def _maze(self, rng: np.random.Generator) -> np.ndarray:
+        if self.algorithm == "kruskal":
+            _, _, cols, rows = maze_geometry(self.height, self.width, self.room_size, self.wall_size)
+            order = np.arange(len(maze_walls(cols, rows)))
+            rng.shuffle(order)   # (the swaps of shuffling the wall list itself; no draw below two walls)
+            return maze_kruskal(self.height, self.width, self.room_size, self.wall_size, order)
+        return maze_dfs(self.height, self.width, self.room_size, self.wall_size, lambda m: rng.integers(0, m))
+
+    def random_map(self, seed: int) -> np.ndarray:
+        """``MapGen(config with this seed).build().grid`` with numpy's own generators."""
+        if self.refusal:
+            raise ValueError(self.refusal)
+        H, W, b = self.map_height, self.map_width, self.border_width
+        grid = np.full((H, W), "wall", dtype="<U50")
+        grid[b:H - b, b:W - b] = self.instance_border_object if self.instances_count > 1 else "empty"
+        for k in range(self.rows * self.cols):
+            y, x = self.room_origin(k)
+            room = np.full(self.height * self.width, "empty", dtype="<U50")
+            if k < self.instances_count:
+                key = self.maze_key(k)
+                if key is None:
+                    rng = np.random.default_rng(int(seed))
+                else:
+                    rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence(int(seed), spawn_key=key)))
+                room[self._maze(rng).reshape(-1) != 0] = "wall"
+                sym = self.instance_symbols(k)
+                empty = np.flatnonzero(room == "empty")
+                if len(sym) > len(empty):
+                    raise ValueError(f"MazeGenSpec: {len(sym)} symbols do not fit the {len(empty)} empty cells of a room's maze")
+                if sym:
+                    child = np.random.Generator(np.random.PCG64(np.random.SeedSequence(int(seed), spawn_key=(key or ()) + (0,))))
+                    sym = np.array(sym).astype(str)
+                    child.shuffle(sym)
+                    child.shuffle(empty)
+                    room[empty[:len(sym)]] = sym
+            grid[y:y + self.height, x:x + self.width] = room.reshape(self.height, self.width)
+        return grid
+
+    def lower(self, prog) -> LoweredMaze:
+        """The seed-independent half: ``MapGenSpec.lower``'s symbol codes, rename tables, room grid and border codes, with the
+        maze's geometry, its wall code, the key rule and the number of empty cells every room's maze has."""
+        low = super().lower(prog)
+        if low.n_sym > self.n_empty:
+            raise ValueError(f"MazeGenSpec: {low.n_sym} symbols do not fit the {self.n_empty} empty cells of a room's maze (the "
+                             "reference would cap the objects with a draw of its own, or fail)")
+        wall = prog.cell_to_class["wall"] + 1
+        if wall >= TEAM0:
+            raise ValueError("MazeGenSpec: class ids reach the team codes")
+        return LoweredMaze(low.height, low.width, low.room_height, low.room_width, low.n_inst, low.rows, low.cols, low.border_width,
+                           low.instance_border_width, low.border_code, low.instance_border_code, low.first_on_root, self.key_offset,
+                           MAZE_ALGORITHMS.index(self.algorithm), self.room_size, self.wall_size, wall, self.n_empty, low.symbols,
+                           low.rename, low.rename_off)
+
+
 class UnsupportedMapBuilder(ValueError):
     """``spec_from_config``: the map builder config asks for something the device generators do not restate."""
 
@@ -350,11 +570,14 @@ class UnsupportedMapBuilder(ValueError):
 _RANDOM_BUILDER = "mettagrid.map_builder.random_map.RandomMapBuilder.Config"
 _MAPGEN = "mettagrid.mapgen.mapgen.MapGen.Config"
 _RANDOM_SCENE = "mettagrid.mapgen.scenes.random.Random.Config"
+_MAZE_SCENE = "mettagrid.mapgen.scenes.maze.Maze.Config"
 
 
 def spec_from_config(d: dict):
     """The spec of a reference map builder config, given as the plain dict its ``model_dump(mode="json")`` yields: a
-    ``RandomMapSpec`` for ``RandomMapBuilder.Config``, a ``MapGenSpec`` for ``MapGen.Config`` with a ``Random.Config`` instance.
+    ``RandomMapSpec`` for ``RandomMapBuilder.Config``, a ``MapGenSpec`` for ``MapGen.Config`` with a ``Random.Config`` instance, a
+    ``MazeGenSpec`` for ``MapGen.Config`` with a ``Maze.Config`` instance whose one child is a ``Random.Config`` scene over the
+    whole room.
     The config's own ``seed`` is not part of a spec (the seed rule of an episode's map is ``base + episodes so far``).
     Anything else raises ``UnsupportedMapBuilder`` naming the field."""
     def refuse(field, why):
@@ -369,11 +592,48 @@ def spec_from_config(d: dict):
     if not isinstance(inst, dict):
         refuse("instance", "is required")
     it = inst.get("type")
-    if it != _RANDOM_SCENE:
+    maze = it == _MAZE_SCENE
+    if maze and len(inst.get("children") or []) != 1:
+        refuse("instance.type", "is Maze.Config, which is supported only with exactly one entry in 'instance.children': a "
+               "Random.Config scene with where = 'full' (a maze alone places no agent)")
+    if it != _RANDOM_SCENE and not maze:
         if isinstance(it, str) and (it == _MAPGEN or ".map_builder." in it or it.endswith("MapBuilder.Config")):
-            refuse("instance", f"is a map builder ({it}); only a Random.Config scene is supported")
-        refuse("instance.type", f"is {it!r}: only the scene Random.Config is supported")
-    if inst.get("children"):
+            refuse("instance", f"is a map builder ({it}); only a Random.Config or a Maze.Config scene is supported")
+        refuse("instance.type", f"is {it!r}: only the scenes Random.Config and Maze.Config are supported")
+    placed, sizes = inst, {}
+    if maze:
+        act = inst["children"][0]
+        at = "instance.children[0]"
+        if not isinstance(act, dict) or not isinstance(act.get("scene"), dict):
+            refuse(at + ".scene", "is required")
+        placed = act["scene"]
+        if placed.get("type") != _RANDOM_SCENE:
+            refuse(at + ".scene.type", f"is {placed.get('type')!r}: only the scene Random.Config is supported under a maze")
+        if act.get("where") != "full":
+            refuse(at + ".where", f"is {act.get('where')!r}: only 'full' is supported (the child fills the whole room)")
+        for f in ("limit", "offset", "lock", "instance_id", "use_instance_id_for_team_assignment"):
+            if act.get(f) is not None:
+                refuse(f"{at}.{f}", "must not be set")
+        if act.get("order_by", "random") not in ("random", "first", "last"):
+            refuse(at + ".order_by", f"is {act['order_by']!r}")   # (with no limit none of the three draws)
+        if placed.get("children"):
+            refuse(at + ".scene.children", "must be empty")
+        if placed.get("transform", "identity") != "identity":
+            refuse(at + ".scene.transform", f"is {placed['transform']!r}: only 'identity' is supported")
+        if placed.get("seed") is not None:
+            refuse(at + ".scene.seed", "is set: a scene-level seed replaces the per-episode generator")
+        if inst.get("algorithm", "kruskal") not in MAZE_ALGORITHMS:
+            refuse("instance.algorithm", f"is {inst['algorithm']!r}: only {MAZE_ALGORITHMS} are known")
+        for f in ("room_size", "wall_size"):
+            v = inst.get(f, {"value": 1})
+            if isinstance(v, dict) and set(v) == {"value"}:
+                v = v["value"]
+            if isinstance(v, bool) or not isinstance(v, int):
+                # a uniform distribution would draw from the maze's generator, and the number of walls, so the cells of a map
+                # and the capacity check on one map, would vary from map to map
+                refuse("instance." + f, f"is {v!r}: only a constant is supported")
+            sizes[f] = v
+    elif inst.get("children"):
         refuse("instance.children", "must be empty")
     if inst.get("transform", "identity") != "identity":
         refuse("instance.transform", f"is {inst['transform']!r}: only 'identity' is supported")
@@ -386,17 +646,21 @@ def spec_from_config(d: dict):
     if d.get("instance_names") is not None:
         refuse("instance_names", "must not be set")
     if d.get("width") is None or d.get("height") is None:
-        refuse("width", "and 'height' must be set (a Random scene has no size of its own)")
-    return MapGenSpec(d["width"], d["height"], inst.get("objects", {}), inst.get("agents", 0), d.get("num_agents"), d.get("instances"),
-                      d.get("border_width", 5), d.get("instance_border_width", 5), d.get("instance_border_object", "wall"),
-                      d.get("set_team_by_instance", False))
+        refuse("width", "and 'height' must be set (a Random or Maze scene has no size of its own)")
+    args = (d["width"], d["height"], placed.get("objects", {}), placed.get("agents", 0), d.get("num_agents"), d.get("instances"),
+            d.get("border_width", 5), d.get("instance_border_width", 5), d.get("instance_border_object", "wall"),
+            d.get("set_team_by_instance", False))
+    if maze:
+        return MazeGenSpec(*args, algorithm=inst.get("algorithm", "kruskal"), **sizes)
+    return MapGenSpec(*args)
 
 
 class _Streams:
     """One PCG64 per row, as ``default_rng(seed)`` (key None) or ``Generator(PCG64(SeedSequence(seed, spawn_key=(key,))))``
     seeds it, with ``next_uint32``'s buffered high half.  ``shuffle`` is ``Generator.shuffle`` of a 1-d array — for i = n-1 .. 1:
     j = random_interval(i), swap a[i], a[j] — with random_interval's masked rejection on the buffered 32-bit halves (low half
-    of each 64-bit output first).  Shuffles on one object continue one stream, as two calls on one numpy generator do."""
+    of each 64-bit output first).  Shuffles on one object continue one stream, as two calls on one numpy generator do, and so
+    does ``integers``.  ``key`` may be a tuple: ``spawn_key=key``, as a child of a child has it."""
 
     def __init__(self, seeds, key=None) -> None:
         from . import early_reset as er
@@ -414,9 +678,8 @@ class _Streams:
         self.hi_half = np.zeros(S, u64)
 
     def shuffle(self, out: np.ndarray) -> None:
-        er, u64 = self.er, np.uint64
+        u64 = np.uint64
         S, n = out.shape
-        sh, sl, ih, il, have_hi, hi_half = self.sh, self.sl, self.ih, self.il, self.have_hi, self.hi_half
         rows = np.arange(S)
         with np.errstate(over="ignore"):
             for i in range(n - 1, 0, -1):
@@ -424,24 +687,55 @@ class _Streams:
                 j = np.zeros(S, np.int64)
                 todo = rows
                 while len(todo):
-                    use_hi = have_hi[todo]
-                    fresh = todo[~use_hi]
-                    nh, nl = er.step(sh[fresh], sl[fresh], ih[fresh], il[fresh])
-                    sh[fresh], sl[fresh] = nh, nl
-                    x = nh ^ nl
-                    rot = nh >> u64(58)
-                    o = (x >> rot) | (x << ((u64(64) - rot) & u64(63)))
-                    half = hi_half[todo].copy()
-                    half[~use_hi] = o & er.M32
-                    hi_half[fresh] = o >> u64(32)
-                    have_hi[todo] = ~use_hi
-                    val = half & mask
+                    val = self.halves(todo) & mask
                     ok = val <= u64(i)
                     j[todo[ok]] = val[ok].astype(np.int64)
                     todo = todo[~ok]
                 ai = out[:, i].copy()
                 out[:, i] = out[rows, j]
                 out[rows, j] = ai
+
+    def halves(self, todo: np.ndarray) -> np.ndarray:
+        """``next_uint32`` of the rows ``todo`` (distinct indices): the buffered high half, or the low half of a new output."""
+        er, u64 = self.er, np.uint64
+        with np.errstate(over="ignore"):
+            use_hi = self.have_hi[todo]
+            fresh = todo[~use_hi]
+            nh, nl = er.step(self.sh[fresh], self.sl[fresh], self.ih[fresh], self.il[fresh])
+            self.sh[fresh], self.sl[fresh] = nh, nl
+            x = nh ^ nl
+            rot = nh >> u64(58)
+            o = (x >> rot) | (x << ((u64(64) - rot) & u64(63)))
+            half = self.hi_half[todo].copy()
+            half[~use_hi] = o & er.M32
+            self.hi_half[fresh] = o >> u64(32)
+            self.have_hi[todo] = ~use_hi
+        return half
+
+    def integers(self, m, halves=None) -> np.ndarray:
+        """``Generator.integers(0, m[row])`` per row for scalar bounds m <= 2**32 - 1 -> int64 [S]; a row with m <= 1 draws nothing
+        and gets 0.  Lemire's method on ``next_uint32`` (the buffered halves ``shuffle`` uses): prod = half * m, and where the low
+        word of prod is below m it is redrawn while below (2**32 - m) mod m.  ``halves``: the source of halves, for tests."""
+        u64 = np.uint64
+        halves = halves or self.halves
+        m = np.broadcast_to(np.asarray(m, dtype=np.int64), (self.S,))
+        out = np.zeros(self.S, np.int64)
+        todo = np.nonzero(m > 1)[0]
+        if not len(todo):
+            return out
+        mm = m[todo].astype(u64)
+        prod = halves(todo) * mm
+        out[todo] = (prod >> u64(32)).astype(np.int64)
+        left = prod & self.er.M32
+        thr = (u64(0xFFFFFFFF) - (mm - u64(1))) % mm
+        again = (left < mm) & (left < thr)
+        while again.any():
+            rows = todo[again]
+            prod = halves(rows) * m[rows].astype(u64)
+            out[rows] = (prod >> u64(32)).astype(np.int64)
+            redo = (prod & self.er.M32) < thr[again]
+            again[np.nonzero(again)[0][~redo]] = False
+        return out
 
 
 def shuffled_rows(base: np.ndarray, seeds, then=None, key=None):
@@ -471,13 +765,73 @@ def _rename_rows(cells: np.ndarray, rename, rename_off) -> np.ndarray:
     return cells
 
 
+def _maze_rooms(low: LoweredMaze, seeds: np.ndarray, key) -> np.ndarray:
+    """uint8 [S][h][w], 1 = wall: the maze every seed's stream ``key`` builds in a room.  The draws are vectorised over the
+    seeds (one shuffle of the wall indices, or the walks in lockstep, one ``integers`` per round of decisions); the union-find
+    and the walk themselves run per seed."""
+    h, w, S = low.room_height, low.room_width, len(seeds)
+    _, _, cols, rows = maze_geometry(h, w, low.room_size, low.wall_size)
+    if MAZE_ALGORITHMS[low.algorithm] == "kruskal":
+        order = shuffled_rows(np.arange(len(maze_walls(cols, rows)), dtype=np.int64), seeds, key=key)
+        return np.stack([maze_kruskal(h, w, low.room_size, low.wall_size, order[s]) for s in range(S)])
+    st = _Streams(seeds, key)
+    walks = [maze_dfs_walk(h, w, low.room_size, low.wall_size) for _ in range(S)]
+    out, m = [None] * S, np.zeros(S, np.int64)
+
+    def advance(s, draw):
+        try:
+            m[s] = next(walks[s]) if draw is None else walks[s].send(draw)
+        except StopIteration as done:
+            out[s], m[s] = done.value, 0
+    for s in range(S):
+        advance(s, None)
+    for _ in range(cols * rows):   # a walk makes cells - 1 decisions
+        if not m.any():
+            break
+        draws = st.integers(m)
+        for s in np.nonzero(m)[0]:
+            advance(s, int(draws[s]))
+    return np.stack(out)
+
+
+def _maze_class_maps(low: LoweredMaze, seeds: np.ndarray) -> np.ndarray:
+    """The host restatement of mgx_maze_kernel: per instance the maze from one stream, then — from that stream's key with one
+    more word 0 — the shuffle of the symbols and the shuffle of the room's empty cells in row-major order."""
+    S = len(seeds)
+    H, W, b, h, w = low.height, low.width, low.border_width, low.room_height, low.room_width
+    out = np.full((S, H, W), low.border_code, dtype=np.uint16)
+    out[:, b:H - b, b:W - b] = low.instance_border_code if low.n_inst > 1 else 0
+    flat = out.reshape(S, H * W)
+    for k in range(low.rows * low.cols):
+        y0, x0 = b + (k // low.cols) * (h + low.instance_border_width), b + (k % low.cols) * (w + low.instance_border_width)
+        out[:, y0:y0 + h, x0:x0 + w] = 0
+        if k >= low.n_inst or S == 0:
+            continue
+        key = low.maze_key(k)
+        walls = _maze_rooms(low, seeds, key)
+        out[:, y0:y0 + h, x0:x0 + w] = np.where(walls != 0, np.uint16(low.wall_code), np.uint16(0))
+        if low.n_sym == 0:
+            continue
+        empty = np.stack([np.flatnonzero(walls[s].reshape(-1) == 0) for s in range(S)])   # [S][n_empty]: the same count for all
+        sym = np.tile(low.symbols[k], (S, 1))
+        st = _Streams(seeds, (key or ()) + (0,))
+        st.shuffle(sym)
+        st.shuffle(empty)
+        idx = empty[:, :low.n_sym]
+        flat[np.arange(S)[:, None], (y0 + idx // w) * W + x0 + idx % w] = sym
+    return _rename_rows(flat, low.rename, low.rename_off).reshape(S, H, W)
+
+
 def generated_class_maps(spec, prog, seeds) -> np.ndarray:
     """``prog.class_map(spec.random_map(seed))`` for many seeds (< 2**32) -> uint16 [n][H][W], without a numpy generator per
     map: the host restatement of mgx_mapgen_kernel (a ``RandomMapSpec``, with the halving rule) or of mgx_mapscene_kernel (a
-    ``MapGenSpec``: per instance one stream, the shuffle of the symbols, then the shuffle of the room's cell indices)."""
+    ``MapGenSpec``: per instance one stream, the shuffle of the symbols, then the shuffle of the room's cell indices) or of
+    mgx_maze_kernel (a ``MazeGenSpec``: ``_maze_class_maps``)."""
     low = spec.lower(prog)
     seeds = np.asarray(seeds, dtype=np.uint64).reshape(-1)
     S = len(seeds)
+    if isinstance(low, LoweredMaze):
+        return _maze_class_maps(low, seeds)
     if isinstance(low, LoweredScene):
         H, W, b, h, w = low.height, low.width, low.border_width, low.room_height, low.room_width
         out = np.full((S, H, W), low.border_code, dtype=np.uint16)

@@ -16,6 +16,11 @@ variant the median over the rounds with min / max and the coefficient of variati
            Then the wrapper's ms per step with the 4-instance recipe on rung-3 rules at min(envs, 16 384) envs, map_pool (16 maps)
            against map_gen.
   all      gen, then wrapper, then scene (the default).
+  maze     the maze recipe (MapGen + Maze scene with a Random child, mgx_maze_kernel; not part of `all`): 25 x 25 rooms, border 6,
+           1 and 4 instances, kruskal and dfs, each beside its yardstick in the same process, the scene recipe (a Random instance)
+           on rooms of the same size with the same symbols; generate_maps of `envs` and of 64 maps as in `gen`, and the ratios.
+           Then the wrapper's ms per step with the 4-instance kruskal recipe on rung-3 rules at min(envs, 8 192) envs, map_pool
+           (16 maps) against map_gen.
 A plain `python bench.py` of this tree against its parent is run by hand, the two alternating.
 Prints one JSON line.  Usage (GPU box): python scripts/mapgen_timing.py [envs] [steps] [rounds] [mode] [trace csv]"""
 import csv
@@ -65,7 +70,7 @@ from mettagrid_amd import presets  # noqa: E402
 from mettagrid_amd.compiler import compile_spec  # noqa: E402
 from mettagrid_amd.engine import BatchedMettaGrid  # noqa: E402
 from mettagrid_amd.envs import MettaGridBatchedEnv  # noqa: E402
-from mettagrid_amd.mapgen import MapGenSpec, RandomMapSpec, generated_class_maps, random_class_maps  # noqa: E402
+from mettagrid_amd.mapgen import MapGenSpec, MazeGenSpec, RandomMapSpec, generated_class_maps, random_class_maps  # noqa: E402
 
 spec3 = presets.rung3_spec()
 spec3.max_steps = 128
@@ -190,5 +195,70 @@ if mode in ("scene", "all"):
     for k, v in wms.items():
         out[f"wrapper_arena4_{k}_ms_per_step"] = stats(v)
         out[f"wrapper_arena4_{k}_ms_rounds"] = [round(float(x), 4) for x in v]
+        envs[k].close()
+
+if mode == "maze":
+    rooms = {1: dict(agents={"red": 8, "blue": 8}), 4: dict(agents={"red": 2, "blue": 2})}
+    common = dict(num_agents=16, border_width=6, instance_border_width=0)
+    recipes = {}
+    for n, kw in rooms.items():
+        recipes[f"scene{n}"] = MapGenSpec(25, 25, {"wall": 10}, **kw, **common)   # the yardstick
+        for alg in ("kruskal", "dfs"):
+            recipes[f"maze{n}_{alg}"] = MazeGenSpec(25, 25, {"wall": 10}, **kw, **common, algorithm=alg)
+    shapes = {name: (rec.map_height, rec.map_width) for name, rec in recipes.items()}
+    progs = {name: compile_spec(spec3, *shapes[name], max_objects=4096) for name in recipes}   # (1 344 border + 4 x 298 maze walls)
+    order = [(name, n) for name in recipes for n in (E, 64)]
+    engs = {}
+    for name, rec in recipes.items():
+        engs[name] = BatchedMettaGrid(progs[name], generated_class_maps(rec, progs[name], [0]), [0], buffers="device", specialize=False)
+        engs[name].set_map_generator(rec, [0])
+    bufs = {(name, n): torch.zeros((n,) + shapes[name], dtype=torch.int16, device="cuda") for name, n in order}
+    seeds = {E: (np.arange(E, dtype=np.uint64) * 2654435761 % (1 << 32)).astype(np.uint32), 64: np.arange(64, dtype=np.uint32) + 12345}
+    ms = {k: [] for k in order}
+    for r in range(rounds + 1):   # (round 0 warms up)
+        for name, n in order:
+            eng = engs[name]
+            st = eng._ext_stream()
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record(st)
+            eng.generate_maps(seeds[n], out=bufs[(name, n)])
+            t1.record(st)
+            t1.synchronize()
+            if r:
+                ms[(name, n)].append(t0.elapsed_time(t1))
+    for (name, n), v in ms.items():
+        out[f"generate_{name}_{n}_ms"] = stats(v, n)
+    for name in recipes:
+        if name.startswith("maze"):
+            for n in (E, 64):
+                yard = "scene" + name[4]
+                out[f"ratio_{name}_{n}"] = round(out[f"generate_{name}_{n}_ms"]["median"] / out[f"generate_{yard}_{n}_ms"]["median"], 3)
+    for eng in engs.values():
+        eng.close()
+    del bufs
+    maze4, prog = recipes["maze4_kruskal"], progs["maze4_kruskal"]
+    pool = generated_class_maps(maze4, prog, range(16))
+    EW = min(E, 8192)   # (4 096 object slots per env)
+    out["wrapper_maze4_envs"] = EW
+    envs = {"map_pool": MettaGridBatchedEnv(prog, EW, map_pool=pool, desync=True, episode_stats=False, specialize=False),
+            "map_gen": MettaGridBatchedEnv(prog, EW, map_gen=maze4, desync=True, episode_stats=False, specialize=False)}
+    g = torch.Generator(device="cuda").manual_seed(1)
+    for env in envs.values():
+        env.reset()
+    acts = [torch.randint(0, envs["map_gen"].transport_action_n, (EW * prog.num_agents,), generator=g, device="cuda", dtype=torch.int32) for _ in range(8)]
+    wms = {k: [] for k in envs}
+    for r in range(rounds + 1):
+        for k, env in envs.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for t in range(steps):
+                env.step(acts[t % 8])
+            t1.record()
+            t1.synchronize()
+            if r:
+                wms[k].append(t0.elapsed_time(t1) / steps)
+    for k, v in wms.items():
+        out[f"wrapper_maze4_{k}_ms_per_step"] = stats(v)
+        out[f"wrapper_maze4_{k}_ms_rounds"] = [round(float(x), 4) for x in v]
         envs[k].close()
 print(json.dumps(out), flush=True)
