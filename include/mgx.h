@@ -533,6 +533,19 @@ int mgx_decode_obs(mgx_engine* e, const uint8_t* tokens, int64_t n_rows, float* 
  * box; 2 = bfloat16 = that float32 box rounded to nearest even; 0 (or box = NULL) switches back to token rows.  scale: float
  * [256] host memory as for mgx_decode_obs.  Token statistics (tokens_written ...) are kept as on the token path. */
 int mgx_set_box_output(mgx_engine* e, void* box, int32_t dtype, int32_t num_features, const float* scale);
+/* Token-bag features — the input of the reference's token baseline, TokenPolicyNet._encode_tokens,
+ * python/src/mettagrid/policy/token_encoder.py:88-114, without its learned tables: token rows u8 [n_rows][T][3] ->
+ * bag [n_rows][32 + num_features] and counts int32 [n_rows], both DEVICE memory.  For every token with coord != 0xFF and
+ * feature < num_features, s = (float)value / (scale[feature] + 1e-6f) (the reference's float32 term) is added to the columns
+ * coord & 15, 16 + (coord >> 4) and 32 + feature, and the token is counted; coord 0xFE is x = 14, y = 15 as in the
+ * reference net, not the centre cell of mgx_decode_obs.  The net's summary is then
+ * (bag @ concat(pos_x[:16], pos_y[:16], feature[:num_features])) / sqrt(max(counts, 1)).  Every column of every row is
+ * written; the order of the float32 additions within a column is unspecified.  dtype: 1 = float32, 2 = bfloat16 = the
+ * float32 sum rounded to nearest even (MGX_BOX_F32 / MGX_BOX_BF16).  tokens, n_rows, scale: as for mgx_decode_obs;
+ * tokens = NULL is refused while box output is on (the observation rows are not written then).  MGX_ERR_BAD_ARG before
+ * anything is enqueued; MGX_ERR_PROGRAM when T and num_features do not fit the kernel's LDS.  Enqueued on the engine's stream. */
+int mgx_token_bag(mgx_engine* e, const uint8_t* tokens, int64_t n_rows, void* bag, int32_t dtype, int32_t* counts, int32_t num_features,
+                  const float* scale);
 
 /* One 64-bit digest per env (uint64 [E], host memory) of everything the episode signature is made of: the
  * mgx_get_objects records of the live slots, every stat value and "key exists" flag (mgx_get_stats), episode rewards,

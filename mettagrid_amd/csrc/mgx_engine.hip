@@ -3278,23 +3278,51 @@ int mgx_poll_action_errors(mgx_engine* e, int32_t wait, uint32_t* flags, int64_t
   return MGX_OK;
 }
 
-int mgx_decode_obs(mgx_engine* e, const uint8_t* tokens, int64_t n_rows, float* box, int32_t num_features, const float* scale) {
-  if (!e || !box || !scale || num_features < 1 || num_features > 256) return fail(MGX_ERR_BAD_ARG, "mgx_decode_obs: bad argument");
-  HIP_TRY(hipSetDevice(e->device));
-  const MgxDev& d = e->d;
-  if (!tokens) { tokens = d.obs; n_rows = (int64_t)d.E * d.A; }
-  if (n_rows <= 0) return fail(MGX_ERR_BAD_ARG, "mgx_decode_obs: no rows");
+// e->d_scale = the caller's float[256] scale table, uploaded on the engine's stream when it differs from the last one
+static int upload_scale(mgx_engine* e, const float* scale) {
   if (!e->d_scale) { int rc = e->alloc(&e->d_scale, 256); if (rc) return rc; }
   if (!e->scale_valid || memcmp(e->scale_host, scale, sizeof e->scale_host) != 0) {
     memcpy(e->scale_host, scale, sizeof e->scale_host);
     HIP_TRY(hipMemcpyAsync(e->d_scale, e->scale_host, sizeof e->scale_host, hipMemcpyHostToDevice, e->stream));
     e->scale_valid = true;
   }
+  return MGX_OK;
+}
+
+int mgx_decode_obs(mgx_engine* e, const uint8_t* tokens, int64_t n_rows, float* box, int32_t num_features, const float* scale) {
+  if (!e || !box || !scale || num_features < 1 || num_features > 256) return fail(MGX_ERR_BAD_ARG, "mgx_decode_obs: bad argument");
+  HIP_TRY(hipSetDevice(e->device));
+  const MgxDev& d = e->d;
+  if (!tokens) { tokens = d.obs; n_rows = (int64_t)d.E * d.A; }
+  if (n_rows <= 0) return fail(MGX_ERR_BAD_ARG, "mgx_decode_obs: no rows");
+  if (int rc = upload_scale(e, scale)) return rc;
   const int rc = mgx_launch_decode(e->stream, tokens, box, e->d_scale, (long long)n_rows, d.T, num_features, e->prog[MGX_H_OBS_HEIGHT],
                                    e->prog[MGX_H_OBS_WIDTH]);
   if (rc == -1) return fail(MGX_ERR_PROGRAM, "mgx_decode_obs: the box of one agent does not fit the decode kernel's LDS");
   if (rc) return fail(MGX_ERR_HIP, "mgx_decode_obs: launch failed");
   return MGX_OK;
+}
+
+int mgx_token_bag(mgx_engine* e, const uint8_t* tokens, int64_t n_rows, void* bag, int32_t dtype, int32_t* counts, int32_t num_features,
+                  const float* scale) {
+  if (!e || !bag || !counts || !scale || num_features < 1 || num_features > 256 || (dtype != MGX_BOX_F32 && dtype != MGX_BOX_BF16))
+    return fail(MGX_ERR_BAD_ARG, "mgx_token_bag: bad argument");
+  const MgxDev& d = e->d;
+  if (!tokens) {
+    if (e->box_dtype != MGX_BOX_OFF) return fail(MGX_ERR_BAD_ARG, "mgx_token_bag: box output is on (mgx_set_box_output): no observation rows");
+    tokens = d.obs; n_rows = (int64_t)d.E * d.A;
+  }
+  if (n_rows <= 0) return fail(MGX_ERR_BAD_ARG, "mgx_token_bag: no rows");
+#ifdef MGX_CPU_EMU   // (wavefront-cooperative: ballot, LDS float adds)
+  return fail(MGX_ERR_PROGRAM, "mgx_token_bag: the token-bag kernel is not part of the sanitizer build");
+#else
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = upload_scale(e, scale)) return rc;
+  const int rc = mgx_launch_token_bag(e->stream, tokens, bag, dtype == MGX_BOX_BF16, counts, e->d_scale, (long long)n_rows, d.T, num_features);
+  if (rc == -1) return fail(MGX_ERR_PROGRAM, "mgx_token_bag: one row's tokens and bins do not fit the kernel's LDS");
+  if (rc) return fail(MGX_ERR_HIP, "mgx_token_bag: launch failed");
+  return MGX_OK;
+#endif
 }
 
 int mgx_set_box_output(mgx_engine* e, void* box, int32_t dtype, int32_t num_features, const float* scale) {

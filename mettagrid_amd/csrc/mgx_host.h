@@ -135,5 +135,8 @@ bool mgx_aoe_set_lds(int nstat, int prog_words);
 void mgx_aoe_collect_stats(const int32_t* program, bool with_on_tick, bool with_coverage, std::vector<int16_t>& out);
 // token decode kernel (mgx_decode.hip)
 int mgx_launch_decode(hipStream_t stream, const uint8_t* tokens, float* box, const float* scale_dev, long long rows, int T, int C, int H, int W);
+// token-bag kernel (mgx_token_bag.hip): -1 = T / C do not fit the LDS, -2 = the runtime refused
+int mgx_launch_token_bag(hipStream_t stream, const uint8_t* tokens, void* bag, int bf16, int32_t* counts, const float* scale_dev, long long rows,
+                         int T, int C);
 
 #endif  // MGX_HOST_H_

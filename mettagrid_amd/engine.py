@@ -160,6 +160,7 @@ def load_lib():
     L.mgx_set_inventory.argtypes = [vp, i32, i32, vp, vp, i32]
     L.mgx_decode_obs.argtypes = [vp, vp, i64, vp, i32, vp]
     L.mgx_set_box_output.argtypes = [vp, vp, i32, i32, vp]
+    L.mgx_token_bag.argtypes = [vp, vp, i64, vp, i32, vp, i32, vp]
     L.mgx_state_digests.argtypes = [vp, vp]
     L.mgx_set_map_pool.argtypes = [vp, vp, i32]
     L.mgx_reset_envs_from_pool.argtypes = [vp, vp, vp, vp]
@@ -1315,6 +1316,43 @@ class BatchedMettaGrid:
             tok_ptr = tokens.data_ptr()
         _check(self.L.mgx_decode_obs(self.h, tok_ptr, rows, out.data_ptr(), Cn, scale.ctypes.data))
         return out
+
+    def token_bag(self, out=None, counts=None, tokens=None, num_features=None):
+        """Token-bag features of the current observations (include/mgx.h mgx_token_bag): ``(bag, counts)``,
+        ``bag`` [rows, 32 + C] = per row the sums of ``value / (scale[feature] + 1e-6)`` by x nibble, by y nibble and by
+        feature — everything ``token_bag.TokenBagEmbedding`` needs of a row — and ``counts`` int32 [rows], the row's tokens.
+        Computed on the GPU, ordered on the engine's stream.  ``out``: contiguous float32 or bfloat16 CUDA tensor to fill
+        (float32 allocated if None); ``counts``: contiguous int32 [rows]; ``tokens``: another token tensor u8 [rows, T, 3] on
+        the device instead of the engine's own observation buffer; ``num_features``: C, default the program's feature count
+        (tokens of a feature >= C are skipped and not counted)."""
+        import torch
+        Cn = len(self.prog.feature_norms) if num_features is None else int(num_features)
+        if not 1 <= Cn <= 256:
+            raise ValueError("num_features must be in [1, 256]")
+        dev = torch.device("cuda", self.device)
+        tok_ptr = None
+        if tokens is not None:
+            if (not isinstance(tokens, torch.Tensor) or tokens.dtype != torch.uint8 or tokens.ndim != 3 or tokens.shape[0] < 1
+                    or tuple(tokens.shape[1:]) != (self.T, 3) or not tokens.is_contiguous() or tokens.device != dev):
+                raise ValueError(f"tokens must be a contiguous uint8 tensor [rows >= 1, {self.T}, 3] on {dev}")
+            tok_ptr = tokens.data_ptr()
+        elif getattr(self, "_box", None) is not None:
+            raise ValueError("token_bag: box output is on (set_box_output): the observation rows are not written")
+        rows = self.E * self.A if tokens is None else int(tokens.shape[0])
+        if out is None:
+            out = torch.empty((rows, 32 + Cn), dtype=torch.float32, device=dev)
+        if counts is None:
+            counts = torch.empty((rows,), dtype=torch.int32, device=dev)
+        if (not isinstance(out, torch.Tensor) or tuple(out.shape) != (rows, 32 + Cn) or out.dtype not in (torch.float32, torch.bfloat16)
+                or not out.is_contiguous() or out.device != dev):
+            raise ValueError(f"out must be a contiguous float32 / bfloat16 tensor of shape {(rows, 32 + Cn)} on {dev}")
+        if (not isinstance(counts, torch.Tensor) or tuple(counts.shape) != (rows,) or counts.dtype != torch.int32
+                or not counts.is_contiguous() or counts.device != dev):
+            raise ValueError(f"counts must be a contiguous int32 tensor of shape {(rows,)} on {dev}")
+        scale = self.feature_scale()
+        _check(self.L.mgx_token_bag(self.h, tok_ptr, rows, out.data_ptr(), 1 if out.dtype == torch.float32 else 2, counts.data_ptr(), Cn,
+                                    scale.ctypes.data))
+        return out, counts
 
     def set_profiling(self, on: bool) -> None:
         _check(self.L.mgx_set_profiling(self.h, 1 if on else 0))

@@ -297,6 +297,11 @@ class MettaGridBatchedEnv:
     and ``reset`` / ``load_state`` through ``write_global_state``.  ``global_state_exclude``: classes left out (cell or type
     names such as ``"wall"``, class ids); ``global_state_tokens``: TG (default: the engine's bound).  With device restarts a
     finished env's row shows its final state, like its observations, and the restarted env after its first step.
+    ``token_bag`` (device buffers): ``True`` or ``"float32"`` / ``"bfloat16"`` — the token-bag features of every observation
+    row (``BatchedMettaGrid.token_bag``; ``mettagrid_amd/token_bag.py``), what a token policy's ``TokenBagEmbedding`` reads.
+    ``env.token_bag`` is ``(bag [E*A, 32 + C], counts int32 [E*A])``: device tensors written behind every ``step``'s
+    observations and by ``reset`` / ``load_state``, in place, ordered on the caller's stream like the other returned tensors.
+    With device restarts a finished env's rows follow its observation rows.
     """
 
     def __init__(self, prog: Program, num_envs: int, map_fn: Optional[Callable[[int, int], np.ndarray]] = None,
@@ -309,9 +314,15 @@ class MettaGridBatchedEnv:
                  map_seed_stride: int = 1 << 16, step_info_keys=None, time_averaged_stats: bool = False,
                  policy_assignments=None, num_policies: Optional[int] = None, map_weights=None, map_sample_seed: int = 0,
                  map_stats: bool = False, map_labels=None, map_env_offset: int = 0, global_state: bool = False,
-                 global_state_exclude=(), global_state_tokens: Optional[int] = None) -> None:
+                 global_state_exclude=(), global_state_tokens: Optional[int] = None, token_bag=False) -> None:
         if global_state and buffers != "device":
             raise ValueError("global_state needs device buffers")
+        if token_bag not in (False, True, "float32", "bfloat16"):
+            raise ValueError('token_bag: False, True, "float32" or "bfloat16"')
+        if token_bag and buffers != "device":
+            raise ValueError("token_bag needs device buffers")
+        self._tb_dtype = None if not token_bag else "bfloat16" if token_bag == "bfloat16" else "float32"
+        self.token_bag = None             # (bag, counts) once reset() has made the engine
         self._gs_on, self._gs_exclude, self._gs_tokens = bool(global_state), tuple(global_state_exclude), global_state_tokens
         self.global_state = None          # (tokens, counts, agent_start) once reset() has made the engine
         if map_weights is not None and map_pool is None:
@@ -506,6 +517,14 @@ class MettaGridBatchedEnv:
             self._eng.set_step_stats(self._si_game_columns, self._si_keys[2])
         self._step_info = StepInfo(self) if self._si_on else None   # (one object: the engine rewrites its tensors every step)
         self.global_state = self._eng.set_global_state(self._gs_tokens, self._gs_exclude) if self._gs_on else None
+        self.token_bag = None
+        if self._tb_dtype is not None:
+            import torch
+            rows, dev = self.E * self.prog.num_agents, self._eng.obs.device
+            bag = torch.empty((rows, 32 + len(self.prog.feature_norms)), dtype=getattr(torch, self._tb_dtype), device=dev)
+            counts = torch.empty((rows,), dtype=torch.int32, device=dev)
+            self._eng.wait_for_caller()   # (the allocator may hand out memory the caller's stream still uses)
+            self.token_bag = self._eng.token_bag(bag, counts)
         if self.replay_envs:
             from .replay import ReplayAssembler
             import os
@@ -814,6 +833,8 @@ class MettaGridBatchedEnv:
                     eng.vibe_actions.zero_()    # (mettagrid_puffer_env.py:389-391)
                 eng.wait_for_caller()   # the engine's kernels read the actions written on the caller's stream ...
             eng.step()
+            if self.token_bag is not None:
+                eng.token_bag(*self.token_bag)
             eng.caller_waits()      # ... and whatever the caller enqueues next sees this step's results
             if self.supervisor is not None:
                 self._compute_supervisor_actions()
@@ -868,6 +889,9 @@ class MettaGridBatchedEnv:
             self.episode[lst] = np.asarray(state.extra["episode"], dtype=np.int64)
         if self._gs_on:   # the rows are derived state: rebuilt from what was loaded
             self.engine.write_global_state(lst)
+            self.engine.caller_waits()
+        if self.token_bag is not None:   # ... and so are the bags of the loaded observation rows
+            self.engine.token_bag(*self.token_bag)
             self.engine.caller_waits()
 
     def close(self) -> None:
