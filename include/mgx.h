@@ -629,6 +629,15 @@ int32_t mgx_is_extended(const mgx_engine* e);
  * disjoint (MgxDev::duo, csrc/mgx_world.h) — chosen at mgx_create under the conditions of the lane-per-agent dispatch.
  * Same results. Diagnostic. */
 int32_t mgx_dispatch_pairs(const mgx_engine* e);
+/* Non-zero: the lean lane-per-env kernel resolves every agent's move target in its staging pass and runs consecutive
+ * trivial actions of an env's order (noop, move off the map / into an empty cell / into an object without on_use) without a
+ * load (MgxDev::move_fast, csrc/mgx_world.h) — chosen at mgx_create for programs whose move handlers have the reference's
+ * default shape and that dispatch pairs; 0 under env MGX_NO_MOVE_FAST.  Same results.  Diagnostic. */
+int32_t mgx_move_fast(const mgx_engine* e);
+/* With env MGX_MOVE_FAST_COUNT set at mgx_create: out[0] = actions the run-ahead consumed, out[1] = resolved entries found
+ * stale (the action then took the general path), summed over all envs and steps so far.  Synchronises the engine's stream.
+ * Without the switch (or without move_fast): both 0.  Diagnostic (tests). */
+int mgx_move_fast_counts(mgx_engine* e, uint64_t* out);
 /* Non-zero: the counters of the per-action bookkeeping (actions/action_handler.hpp:78-105: action.<kind>.success / .failed,
  * action.failed, status.max_steps_without_motion; bit 0) and the two coverage stats (objects/agent.cpp:49-57; bit 1, lean
  * lane-per-env dispatch only) are kept as integers beside the agents' stat rows and written into them before anything reads

@@ -53,6 +53,17 @@ struct MgxDev {
                           //    batched per-agent passes (clears, staging, vibe pass, tail_shadow): lane l of trip t takes element
                           //    64 t + l, so every access is coalesced (mgx_world.h; 0 under env MGX_WORLD_PASSES_PER_ENV).  Engine
                           //    configuration, not env state: it changes speed only and is in no record
+  int move_fast;          // bit 0: the move-handler table has the canonical shape (relocate into an empty cell, else use the
+                          //    target) and the lean lane-per-env kernel resolves every agent's move target in its staging pass
+                          //    and runs consecutive trivial actions of an env's order without a load (mgx_world.h, "run-ahead";
+                          //    0 under env MGX_NO_MOVE_FAST).  bit 1: there is no use-target handler: an occupied cell always fails.
+                          //    Engine configuration like coop_passes: it changes speed only
+  int mf_lds_off;         // ... byte offset of its LDS behind everything else of the kernel: resolved actions u8[A][64] (cell ahead: 0 empty,
+                          //    1 an object whose class has no on_use, 2 one with | kind << 2 | orientation << 4 | off the map << 7) | dirty cells of the tick u32[mf_dirty_words][64]
+  int mf_dirty_words;     // words per env of the dirty set: an exact bitmap of the map (mf_exact) or a hashed mask (a power of two)
+  int mf_exact;
+  uint32_t* mf_count;     // [E][2] run-ahead actions | stale entries sent down the general path, summed over the steps; nullptr
+                          //    unless env MGX_MOVE_FAST_COUNT asks for them (tests)
   int act_ngset;          // game-scope stats the action-phase handlers SET (StatsMutation): applied in agent order at the end
   int act_gset_ids[4];
   int act_lds_extra;      // bytes per workgroup behind the game-stat cells: footprints u32[A'][EPG] | cell map u8[EPG][H*W] (0: no cell map)

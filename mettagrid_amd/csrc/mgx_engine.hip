@@ -933,6 +933,8 @@ static void report_plan(const mgx_engine* e, size_t program_words) {
           (int)e->prog_in_lds, e->lds_world);
   if (d.X) fprintf(stderr, "[mgx] action-phase handlers on the %s VM\n", d.flat_top ? "register" : "LDS");
   fprintf(stderr, "[mgx] handler code: %s\n", d.gen_prog ? "generated for this program at build()" : "interpreter");
+  fprintf(stderr, "[mgx] lean dispatch: move targets %s\n", !d.move_fast ? "read by every move" : d.mf_exact ?
+          "resolved in the staging pass, trivial actions run ahead (exact dirty bitmap)" : "resolved in the staging pass, trivial actions run ahead (hashed dirty mask)");
   fprintf(stderr, "[mgx] lean dispatch: %s\n", d.duo ? "two agents of an env at a time (disjoint footprints)" : "one agent at a time");
   fprintf(stderr, "[mgx] action dispatch: one lane per %s\n", d.act_par ? "agent (conflict-ordered rounds)" : "env");
   if (d.X) fprintf(stderr, "[mgx] extended world kernel: %zu bytes of private memory per lane\n", mgx_world_x_private_bytes());
@@ -977,6 +979,7 @@ int mgx_create(const int32_t* program, size_t program_words, const uint16_t* cla
   // not an env state array: a restart keeps the rows and so their counts; whatever may break "0xFF behind the count" resets
   // them to 0xFFFF (invalidate_obs)
   if (sw.obs_tail) A_(e->alloc(&d.obs_used, rows, 0xFF));
+  if (d.move_fast && sw.move_fast_count) A_(e->alloc(&d.mf_count, E * 2));
   A_(e->alloc(&e->own_term, rows));
   A_(e->alloc(&e->own_trunc, rows));
   A_(e->alloc(&e->own_rew, rows));
@@ -3387,6 +3390,18 @@ int32_t mgx_world_prog_in_lds(const mgx_engine* e) { return e && e->prog_in_lds 
 int32_t mgx_is_extended(const mgx_engine* e) { return e && e->d.X ? 1 : 0; }
 int32_t mgx_dispatch_pairs(const mgx_engine* e) { return e && e->d.duo ? 1 : 0; }
 int32_t mgx_integer_bookkeeping(const mgx_engine* e) { return e ? e->d.shadow : 0; }
+int32_t mgx_move_fast(const mgx_engine* e) { return e ? e->d.move_fast : 0; }
+int mgx_move_fast_counts(mgx_engine* e, uint64_t* out) {
+  if (!e || !out) return fail(MGX_ERR_BAD_ARG, "mgx_move_fast_counts: null argument");
+  out[0] = out[1] = 0;
+  if (!e->d.mf_count) return MGX_OK;
+  std::vector<uint32_t> h((size_t)e->d.E * 2);
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipMemcpyAsync(h.data(), e->d.mf_count, h.size() * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (size_t i = 0; i < h.size(); i += 2) { out[0] += h[i]; out[1] += h[i + 1]; }
+  return MGX_OK;
+}
 int32_t mgx_create_paths(const mgx_engine* e) {
   if (!e) return 0;
   const MgxDev& d = e->d;

@@ -22,7 +22,7 @@
 // the engine's lifetime: a later reset that grows the token pool sizes the observation kernel with the same ones.
 struct MgxSwitches {   // (mgx_read_switches: which switch sets or clears each)
   bool verbose, prog_lds, aoe_local, tick_in_aoe, aoe_prog_lds, flat_top, tick_split, rewards_mid, obs_512, obs_preset, act_lean,
-      act_par, act_map, act_replay, duo, coop_passes, shadow, gen, obs_tail;
+      act_par, act_map, act_replay, duo, coop_passes, move_fast, move_fast_count, shadow, gen, obs_tail;
 };
 inline MgxSwitches mgx_read_switches() {
   auto on = [](const char* name) { return getenv(name) != nullptr; };
@@ -44,6 +44,8 @@ inline MgxSwitches mgx_read_switches() {
   s.act_replay = on("MGX_ACT_SHUFFLE_REPLAY");      // the shuffle always takes its serial replay path (tests)
   s.duo = !on("MGX_NO_DUO");
   s.coop_passes = !on("MGX_WORLD_PASSES_PER_ENV");  // the lean kernel's batched per-agent passes one lane per env
+  s.move_fast = !on("MGX_NO_MOVE_FAST");            // the lean kernel resolves no move target up front: every action takes the trip loop
+  s.move_fast_count = on("MGX_MOVE_FAST_COUNT");    // ... and counts run-ahead actions and stale entries per env (tests)
   s.shadow = !on("MGX_NO_SHADOW");                  // no integer bookkeeping
   s.gen = !on("MGX_NO_GEN");                        // handlers on the interpreter
   s.obs_tail = !on("MGX_OBS_FULL_ROWS");            // every observation pass rewrites whole rows (no MgxDev::obs_used)
@@ -51,6 +53,7 @@ inline MgxSwitches mgx_read_switches() {
   // the sanitizer build runs work-items one by one: no LDS program copies (they need a workgroup barrier), no flush kernel
   // for the integer bookkeeping, no wavefront-cooperative (ballot / readlane) lane-per-agent dispatch
   s.prog_lds = s.aoe_prog_lds = s.shadow = s.act_par = false;
+  s.move_fast = false;   // (like coop_passes it needs the helper lanes of the GPU build)
 #endif
   return s;
 }
@@ -604,6 +607,45 @@ inline int mgx_plan(const int32_t* P, size_t words, const uint16_t* class_maps, 
     d.duo = duo ? 1 : 0;
     d.coop_passes = (!d.X && sw.coop_passes) ? 1 : 0;
     d.act_replay = sw.act_replay ? 1 : 0;
+    {  // MgxDev::move_fast: the move-handler table has the shape of the reference's default move — [0] relocate when the cell
+       // ahead is empty, optionally [1] use the target when it is not, both one cell ahead — so the outcome of a move follows
+       // from the grid entry ahead and its class's on_use alone (a class without on_use fails UseTarget with no side effect:
+       // run_handler, the generated h1_L0).  Needs the paired dispatch's analysis (writes stay inside footprints) and the
+       // deferred bookkeeping (a consumed action leaves a result byte, no stat update).
+      const int n_hd = mgx_sec_cnt(P, MGX_SEC_HANDLERS), n_atoms = mgx_sec_cnt(P, MGX_SEC_ATOMS);
+      auto leaf = [&](int h, int fop, int mop) {   // one filter atom `fop`, one mutation `mop`
+        if (h < 0 || h >= n_hd) return false;
+        const int32_t* hd = P + d.sec[MGX_SEC_HANDLERS] + h * MGX_HD_WORDS;
+        const int pc = hd[MGX_HD_FILTER_PC];
+        if (hd[MGX_HD_KIND] != MGX_HK_LEAF || hd[MGX_HD_MUT_COUNT] != 1 || pc < 0 || pc >= n_atoms) return false;
+        const int32_t* a = P + d.sec[MGX_SEC_ATOMS] + pc * MGX_AT_WORDS;
+        if (a[MGX_AT_OP] != fop || a[MGX_AT_ON_TRUE] != MGX_PC_PASS || a[MGX_AT_ON_FALSE] != MGX_PC_FAIL) return false;
+        return (P + d.sec[MGX_SEC_MUTS] + hd[MGX_HD_MUT_START] * MGX_MU_WORDS)[MGX_MU_OP] == mop;
+      };
+      const int nm = d.n_move_handlers;
+      bool mf = sw.move_fast && duo && d.defer_book && range1 && (nm == 1 || nm == 2) && mh[MGX_MH_ACCEPTS_EMPTY] != 0 &&
+                leaf(mh[MGX_MH_HANDLER], MGX_FOP_TARGET_LOC_EMPTY, MGX_MOP_RELOCATE) &&
+                (nm == 1 || leaf(mh[MGX_MH_WORDS + MGX_MH_HANDLER], MGX_FOP_TARGET_IS_USABLE, MGX_MOP_USE_TARGET));
+      if (mf) {
+        // LDS behind everything else of the kernel (the program copy included): an exact bitmap of the map up to 1 024 cells,
+        // a 128-bit hashed mask above that or where only the bitmap would cost the kernel its fourth workgroup per CU (40 KB).
+        // The fast path never moves a kernel across the 64 KB opt-in or past the CU's 160 KB: it stays off there.
+        const size_t hw = (size_t)d.H * d.W, pre = ((size_t)d.A * MGX_WORLD_EPG + 15) & ~(size_t)15;
+        const size_t cap = p.lds_world <= 64 * 1024 ? 64 * 1024 : 160 * 1024;
+        int words = hw <= 1024 ? (int)((hw + 31) / 32) : 4;
+        bool exact = hw <= 1024;
+        if (exact && words > 4 && p.lds_world + pre + (size_t)4 * 4 * MGX_WORLD_EPG <= 40 * 1024 &&
+            p.lds_world + pre + (size_t)4 * words * MGX_WORLD_EPG > 40 * 1024) { words = 4; exact = false; }
+        if (p.lds_world + pre + (size_t)4 * words * MGX_WORLD_EPG > cap) mf = false;
+        else {
+          d.mf_lds_off = (int)p.lds_world;
+          d.mf_dirty_words = words;
+          d.mf_exact = exact ? 1 : 0;
+          p.lds_world += pre + (size_t)4 * words * MGX_WORLD_EPG;
+        }
+      }
+      d.move_fast = mf ? (nm == 1 ? 3 : 1) : 0;
+    }
     // game-stat SETs are applied in agent order through per-env cells (the paired dispatch too)
     const std::vector<int>& sets = par ? gset : duo ? act_sets : std::vector<int>();
     d.act_ngset = (int)sets.size();

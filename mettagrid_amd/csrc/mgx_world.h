@@ -76,9 +76,11 @@ struct MgxALds {
 MGX_DBG_LINKAGE __device__ unsigned long long mgx_dbg_cycles[16];
 #define MGX_TICK(k) do { unsigned long long _n = clock64(); if (threadIdx.x == 0) atomicAdd(&mgx_dbg_cycles[k], _n - _t); _t = _n; } while (0)
 #define MGX_TICK0() unsigned long long _t = clock64()
+#define MGX_COUNT(k, n) atomicAdd(&mgx_dbg_cycles[k], (unsigned long long)(n))   // plain event counts beside the cycle totals
 #else
 #define MGX_TICK(k)
 #define MGX_TICK0()
+#define MGX_COUNT(k, n)
 #endif
 
 // MGX_BIG: inlining policy of the large interpreter functions.  The lean world kernel is built in its own translation
@@ -295,6 +297,26 @@ struct MgxEnvT {  // per-lane view of one env
   __device__ __forceinline__ void flag(uint32_t bit) const { atomicOr(&d.err[envi()], bit); }   // (two lanes of an env may flag at once)
 #else
   __device__ __forceinline__ void flag(uint32_t bit) const { d.err[envi()] |= bit; }
+#endif
+
+  // MgxDev::move_fast: the cells a grid write of this tick's action phase touched, per env in LDS ([word][env]): an exact
+  // bitmap of the map or a hashed mask.  A move target resolved in the staging pass is used only while neither the acting
+  // agent's own cell (it was not displaced) nor the target is in the set; a false positive sends the action down the general
+  // path, so results do not depend on the mask size.  Two lanes of an env may mark at once (paired dispatch): LDS atomics.
+#if MGX_HELPERS_ON
+  __device__ __forceinline__ uint8_t* mf_pre() const { return mgx_dyn_lds + d.mf_lds_off; }
+  __device__ __forceinline__ uint32_t* mf_dirty() const { return (uint32_t*)(mf_pre() + ((d.A * MGX_WORLD_EPG + 15) & ~15)); }
+  __device__ __forceinline__ uint32_t mf_bit(int r, int c) const {
+    const uint32_t cellidx = (uint32_t)(r * d.W + c);
+    return d.mf_exact ? cellidx : (cellidx & (uint32_t)(d.mf_dirty_words * 32 - 1));
+  }
+  __device__ __forceinline__ void mf_mark(int r, int c) const {
+    if constexpr (!X) {
+      if (d.move_fast) { const uint32_t b = mf_bit(r, c); atomicOr(mf_dirty() + (b >> 5) * MGX_WORLD_EPG + mgx_world_lane(), 1u << (b & 31)); }
+    }
+  }
+#else
+  __device__ __forceinline__ void mf_mark(int, int) const {}
 #endif
 
   // ---- stats (systems/stats_tracker.hpp:69-90) ----
@@ -863,6 +885,7 @@ struct MgxEnvT {  // per-lane view of one env
     cell(r, c) = (uint16_t)(slot + 1);
     cell(rc >> 8, rc & 0xFF) = 0;
     grid_dirty = 1;
+    mf_mark(r, c); mf_mark(rc >> 8, rc & 0xFF);
     d.obj_rc[so(slot)] = (uint16_t)((r << 8) | c);
     {
       const int a = slot == cur_slot ? cur_agent : agent_of(slot);
@@ -953,7 +976,7 @@ struct MgxEnvT {  // per-lane view of one env
       }
     }
     uint16_t rc = d.obj_rc[so(slot)];
-    cell(rc >> 8, rc & 0xFF) = 0; grid_dirty = 1;
+    cell(rc >> 8, rc & 0xFF) = 0; grid_dirty = 1; mf_mark(rc >> 8, rc & 0xFF);
     d.obj_flags[so(slot)] |= 1;
     for (int t = 0; t < 256 && d.NL > 0; t++) {  // TagIndex::unregister_object (core/tag_index.cpp:21-31)
       if (!has_tag(slot, t)) continue;
@@ -1055,6 +1078,7 @@ struct MgxEnvT {  // per-lane view of one env
         uint16_t rx = d.obj_rc[so(c.actor)], ry = d.obj_rc[so(c.target)];
         cell(rx >> 8, rx & 0xFF) = (uint16_t)(c.target + 1);
         cell(ry >> 8, ry & 0xFF) = (uint16_t)(c.actor + 1); grid_dirty = 1;
+        mf_mark(rx >> 8, rx & 0xFF); mf_mark(ry >> 8, ry & 0xFF);
         d.obj_rc[so(c.actor)] = ry;
         d.obj_rc[so(c.target)] = rx;
         d.ag_rc[ao(xa)] = ry;
@@ -2303,6 +2327,18 @@ __device__ __forceinline__ void mgx_shuffle_order(const ENV& e, uint8_t* order, 
   }
 }
 
+// The cell a staged action `a` of an agent standing on `own` ((r << 8) | c) acts on: (r << 8) | c of the cell ahead for a move
+// that stays on the map, -1 otherwise (orientation.hpp:28-48).
+template <class PP>
+__device__ __forceinline__ int mgx_move_target(const MgxDev& d, PP acts, int a, uint32_t own) {
+  if (a < 0 || a >= d.nact || acts[a * MGX_AC_WORDS + MGX_AC_KIND] != MGX_AK_MOVE) return -1;
+  const int orient = acts[a * MGX_AC_WORDS + MGX_AC_ARG];
+  const int dx = (orient == 2 || orient == 4 || orient == 6) ? -1 : (orient == 3 || orient == 5 || orient == 7) ? 1 : 0;
+  const int dy = (orient == 0 || orient == 4 || orient == 5) ? -1 : (orient == 1 || orient == 6 || orient == 7) ? 1 : 0;
+  const int r = (int)(own >> 8) + dy, c = (int)(own & 0xFF) + dx;
+  return (r >= 0 && c >= 0 && r < d.H && c < d.W) ? ((r << 8) | c) : -1;
+}
+
 // One agent's action of one stream (the body of the dispatch loop, mettagrid_c.cpp:966-999): invalid-index bookkeeping,
 // the stream / kind check, ActionHandler::handle_action and the executed / success rows.
 template <class ENV, class PP>
@@ -2466,6 +2502,56 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
   }
   e.al_ = al;
   MGX_TICK(0);
+  PP acts = P + d.sec[MGX_SEC_ACTIONS];
+  // MgxDev::move_fast: what every agent's primary action will meet, resolved here for all agents of the run at once — the grid
+  // entry of the cell ahead, then for an occupied one its class's on_use handler: two levels of independent loads per step
+  // instead of two dependent round trips at the head of every move of the ordered loop.  Each lane resolves the elements it
+  // staged itself (its own LDS writes: program order).  The dirty set of the tick starts empty.
+  bool mf = false;
+#if MGX_HELPERS_ON
+  if constexpr (HELP) {
+    mf = d.move_fast != 0 && d.duo != 0 && act;
+    if (mf) {
+      uint8_t* pre = e.mf_pre();
+      uint32_t* dirty = e.mf_dirty();
+      if (!helper)
+        for (int w = 0; w < d.mf_dirty_words; w++) dirty[w * MGX_WORLD_EPG + lane] = 0u;
+      const size_t HW = (size_t)d.H * d.W;
+      const int n_el = coop ? n_flat : a_hi;
+      for (int i0 = coop ? 0 : a_lo; i0 < (coop ? (n_flat + MGX_WAVE - 1) / MGX_WAVE : a_hi); i0 += 8) {
+        int li8[8];
+        uint32_t cv8[8], cls8[8], kd8[8];
+        size_t env8[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) {   // level 1: the cell ahead
+          const int p = coop ? (i0 + q) * MGX_WAVE + wl : i0 + q;
+          li8[q] = -1; cv8[q] = 0u; kd8[q] = 0u; env8[q] = (size_t)env;
+          if (p < n_el) {
+            int ew = 0;
+            const int li = coop ? flat_li(p, &ew) : p * MGX_WORLD_EPG + lane;
+            if (coop) env8[q] = (size_t)(genv0 + ew);
+            li8[q] = li;
+            const int a = al.act[li];
+            const int kind = (a < 0 || a >= d.nact) ? 3 : min((int)acts[a * MGX_AC_WORDS + MGX_AC_KIND], 3);
+            const int t = mgx_move_target(d, acts, a, al.rc[li]);
+            kd8[q] = (uint32_t)(kind << 2);
+            if (kind == MGX_AK_MOVE) kd8[q] |= ((uint32_t)acts[a * MGX_AC_WORDS + MGX_AC_ARG] & 7u) << 4 | (t < 0 ? 0x80u : 0u);
+            if (t >= 0) cv8[q] = d.grid[env8[q] * HW + (size_t)((t >> 8) * d.W + (t & 0xFF))];
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < 8; q++) cls8[q] = cv8[q] ? (uint32_t)d.obj_cls[env8[q] * d.S + (cv8[q] - 1u)] : 0u;   // level 2
+#pragma unroll
+        for (int q = 0; q < 8; q++)
+          if (li8[q] >= 0) {   // cell ahead (0 empty, 1 no on_use, 2 on_use) | kind << 2 (3: general path) | orientation << 4 | off the map << 7
+            const int h = cv8[q] ? e.cls((int)cls8[q])[MGX_C_ON_USE] : -1;
+            pre[li8[q]] = (uint8_t)((cv8[q] == 0u ? 0u : h < 0 ? 1u : 2u) | kd8[q]);
+          }
+      }
+    }
+  }
+#endif
+  MGX_TICK(8);
   if constexpr (HELP) {   // the helper's half of the staging is read by the env's own lane below (same wavefront: program order)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __builtin_amdgcn_wave_barrier();
@@ -2476,7 +2562,6 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
   // over the primary then the vibe stream.  Every real action handler has priority 0 and the only thing the
   // higher (empty) levels do is repeat the invalid-index bookkeeping, so one pass per stream with the invalid-index
   // stats added (max_priority + 1) times is equivalent — the stat keys involved are touched by nothing else.
-  PP acts = P + d.sec[MGX_SEC_ACTIONS];
   const int repeats = d.max_priority + 1;
   MGX_TICK(1);
   // MgxDev::duo (MGX_WORLD_HELPERS): the env's own lane runs the next agent a of the order and its helper lane the agent b
@@ -2560,9 +2645,101 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
       }
     }
     int q = 0;   // this env's place in its order (the same in both lanes of a pair)
+    uint32_t mf_ran = 0, mf_stale = 0;   // (MgxDev::mf_count)
+#ifdef MGX_WORLD_TIMING
+    uint32_t mf_slow = 0;
+#endif
     for (;;) {
+#if MGX_HELPERS_ON
+      if constexpr (HELP) {
+        // Run-ahead (MgxDev::move_fast): the env's own lane consumes consecutive agents of its order whose outcome is known
+        // from the staging pass and needs no handler — a noop, a wrong-stream id, a move off the map, into a wall-like object
+        // (its class has no on_use: UseTarget fails, nothing is written) or into an empty cell — exactly as handle_action +
+        // do_move would, with LDS updates and fire-and-forget stores only.  A resolved entry counts while neither the agent's
+        // own cell nor the target is in the tick's dirty set.  The first agent that meets an object with an on_use handler,
+        // has a stale entry or an invalid id ends the run and goes through the dispatch below, pairing rule included.  One
+        // lane, in order: the reference's serial order is kept.
+        if (mf && stream == 0) {
+          const int q0 = q;
+          // Everything the run needs from the engine's table and the LDS layout is read once per trip and pinned in scalar
+          // registers.  Under this kernel's register pressure a table field used inside the loop is re-read there by a vector
+          // load, and a load behind the run's stores waits for every one of them (measured: one store round trip per
+          // consumed agent, slower than the trip loop it replaces).  The loop itself issues LDS accesses and stores only.
+          int mW = d.W, mHW = d.H * d.W, mA = A, mS = d.S, mFl = d.move_fast, mMask = d.mf_exact ? -1 : d.mf_dirty_words * 32 - 1;
+          const int alds0 = (A * MGX_WORLD_EPG + 15) & ~15;   // (mgx_world_alds)
+          int oSwm = alds0, oAct = alds0 + A * MGX_WORLD_EPG * 4, oSlot = alds0 + A * MGX_WORLD_EPG * 8;
+          int oPre = d.mf_lds_off;
+          uint16_t* gGrid = d.grid; uint16_t* gObjRc = d.obj_rc; uint16_t* gAgRc = d.ag_rc;
+          int32_t* gEx = d.executed; uint8_t* gSu = d.success;
+          asm volatile("" : "+s"(mW), "+s"(mHW), "+s"(mA), "+s"(mS), "+s"(mFl), "+s"(mMask), "+s"(oSwm), "+s"(oAct), "+s"(oSlot), "+s"(oPre));
+          asm volatile("" : "+s"(gGrid), "+s"(gObjRc), "+s"(gAgRc), "+s"(gEx), "+s"(gSu));
+          if (!helper) {
+            const int oRc = oSlot + mA * MGX_WORLD_EPG * 2, oPrev = oRc + mA * MGX_WORLD_EPG * 2;
+            const int oDirty = oPre + ((mA * MGX_WORLD_EPG + 15) & ~15);
+            auto dirty_word = [&](uint32_t b) { return (uint32_t*)(mgx_dyn_lds + oDirty) + (b >> 5) * MGX_WORLD_EPG + lane; };
+            while (q < mA) {
+              const int ai = order[q * MGX_WORLD_EPG + lane], li = ai * MGX_WORLD_EPG + lane;
+              const uint32_t w = mgx_dyn_lds[oPre + li];   // cell ahead (2 bits) | kind << 2 | orientation << 4 | off the map << 7
+              const int kind = (int)((w >> 2) & 3u);
+              if (kind == 3) break;   // invalid index (or a kind of action this path does not know): the general path
+              int16_t* actp = (int16_t*)(mgx_dyn_lds + oAct) + li;
+              if (kind == MGX_AK_VIBE) { *actp = 0; q++; continue; }   // wrong stream: no call, empty result byte
+              uint16_t* rcp = (uint16_t*)(mgx_dyn_lds + oRc) + li;
+              uint32_t rc = *rcp;
+              bool ok = true;
+              if (kind == MGX_AK_MOVE) {
+                const int r0 = (int)(rc >> 8), c0 = (int)(rc & 0xFF);
+                const uint32_t b0 = (uint32_t)(r0 * mW + c0) & (uint32_t)mMask;
+                if ((*dirty_word(b0) >> (b0 & 31)) & 1u) { mf_stale++; break; }   // displaced by a swap
+                if (w & 0x80u) ok = false;   // off the map: every handler's line scan ends at once
+                else {
+                  const int orient = (int)((w >> 4) & 7u);   // orientation.hpp:28-48
+                  const int dx = (orient == 2 || orient == 4 || orient == 6) ? -1 : (orient == 3 || orient == 5 || orient == 7) ? 1 : 0;
+                  const int dy = (orient == 0 || orient == 4 || orient == 5) ? -1 : (orient == 1 || orient == 6 || orient == 7) ? 1 : 0;
+                  const int r = r0 + dy, c = c0 + dx;
+                  const uint32_t b1 = (uint32_t)(r * mW + c) & (uint32_t)mMask;
+                  if ((*dirty_word(b1) >> (b1 & 31)) & 1u) { mf_stale++; break; }
+                  if ((w & 3u) == 0u) {   // empty: the relocate handler = Grid::move_object of the agent's own object
+                    const uint32_t slot = ((uint16_t*)(mgx_dyn_lds + oSlot))[li];
+                    const uint16_t nrc = (uint16_t)((r << 8) | c);
+                    uint16_t* g = gGrid + (size_t)env * mHW;
+                    g[r * mW + c] = (uint16_t)(slot + 1u);
+                    g[r0 * mW + c0] = 0;
+                    gObjRc[(size_t)env * mS + slot] = nrc;
+                    gAgRc[(size_t)env * mA + ai] = nrc;
+                    *rcp = nrc; rc = nrc;
+                    atomicOr(dirty_word(b0), 1u << (b0 & 31)); atomicOr(dirty_word(b1), 1u << (b1 & 31));
+                  } else if ((w & 3u) == 1u || (mFl & 2)) ok = false;   // nothing to use
+                  else break;   // an on_use handler chain
+                }
+              }
+              const int a = *actp;
+              uint16_t* prevp = (uint16_t*)(mgx_dyn_lds + oPrev) + li;   // handle_action's bookkeeping, deferred form
+              uint32_t* swmp = (uint32_t*)(mgx_dyn_lds + oSwm) + li;
+              const bool moved = rc != *prevp;
+              if (moved) { *swmp = 0; *prevp = (uint16_t)rc; }
+              else *swmp += 1;
+              *actp = (int16_t)(1 | (kind << 1) | (ok ? 8 : 0) | (moved ? 16 : 0));
+              if (ok) { gEx[(size_t)env * mA + ai] = a; gSu[(size_t)env * mA + ai] = 1; }
+              q++;
+            }
+            mf_ran += (uint32_t)(q - q0);
+          }
+          // the helper lane may read cells the run wrote (its agent's cell ahead): visible before the pair's actions
+          if (__ballot(q != q0) != 0ull) {
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+          }
+          const int qo = __shfl_xor(q, 32);
+          if (helper) q = qo;
+        }
+      }
+#endif
       const bool more = q < A && (duo || !helper);
       if (__ballot(more) == 0ull) break;
+#ifdef MGX_WORLD_TIMING
+      if (stream == 0 && threadIdx.x == 0) MGX_COUNT(9, 1);   // trips of the workgroup's first wavefront
+#endif
       bool run = more && !helper;
       int k = q, adv = 1;
 #if MGX_HELPERS_ON
@@ -2595,6 +2772,9 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
         }
       }
 #endif
+#ifdef MGX_WORLD_TIMING
+      if (stream == 0 && run) mf_slow++;   // actions through the general path
+#endif
       if (run) mgx_dispatch_one(e, d, acts, al, order[k * MGX_WORLD_EPG + lane], stream, lane, repeats);
 #if MGX_HELPERS_ON
       if constexpr (HELP) {
@@ -2606,6 +2786,20 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
 #endif
       q += adv;
     }
+#if MGX_HELPERS_ON
+    if constexpr (HELP) {
+      if (mf && stream == 0 && !helper) {
+        if (d.mf_count) { d.mf_count[2 * (size_t)env] += mf_ran; d.mf_count[2 * (size_t)env + 1] += mf_stale; }
+      }
+    }
+#endif
+#ifdef MGX_WORLD_TIMING
+    if (stream == 0) {   // event counts of the workgroup's first wavefront (one atomic each: nothing for the fences to wait for)
+      uint32_t c0 = mf_ran, c1 = mf_slow, c2 = mf_stale;
+      for (int o = 32; o > 0; o >>= 1) { c0 += __shfl_xor((int)c0, o); c1 += __shfl_xor((int)c1, o); c2 += __shfl_xor((int)c2, o); }
+      if (threadIdx.x == 0) { MGX_COUNT(10, c0); MGX_COUNT(11, c1); MGX_COUNT(12, c2); }
+    }
+#endif
     MGX_TICK(2 + stream);
   }
 #if MGX_HELPERS_ON

@@ -199,9 +199,10 @@ def load_lib():
         L.mgx_unpack_rows.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     for name in ("mgx_num_envs", "mgx_num_agents", "mgx_num_tokens", "mgx_obs_variant", "mgx_act_variant", "mgx_handler_variant",
                  "mgx_world_prog_in_lds", "mgx_is_extended", "mgx_dispatch_pairs", "mgx_integer_bookkeeping",
-                 "mgx_create_paths"):
+                 "mgx_create_paths", "mgx_move_fast"):
         getattr(L, name).argtypes = [vp]
         getattr(L, name).restype = i32
+    L.mgx_move_fast_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.mgx_state_bytes.argtypes = [vp]
     L.mgx_state_bytes.restype = i64
     L.mgx_env_state_layout.argtypes = [vp, C.c_size_t, vp, i32, C.POINTER(EnvStateInfo)]
@@ -1390,6 +1391,18 @@ class BatchedMettaGrid:
     def dispatch_pairs(self) -> int:
         """1: the lean lane-per-env dispatch runs two agents of an env per trip where their footprints are disjoint."""
         return int(self.L.mgx_dispatch_pairs(self.h))
+
+    @property
+    def move_fast(self) -> int:
+        """Non-zero: the lean kernel resolves move targets in its staging pass and runs trivial actions ahead (same results)."""
+        return int(self.L.mgx_move_fast(self.h))
+
+    def move_fast_counts(self) -> tuple:
+        """(actions the run-ahead consumed, resolved entries found stale) over all envs and steps; needs env
+        MGX_MOVE_FAST_COUNT at create, else (0, 0)."""
+        out = (C.c_uint64 * 2)()
+        _check(self.L.mgx_move_fast_counts(self.h, out))
+        return int(out[0]), int(out[1])
 
     @property
     def integer_bookkeeping(self) -> int:

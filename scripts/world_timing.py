@@ -35,10 +35,17 @@ for t in range(5 + steps):
         eng.step()
 eng.sync()
 lib.mgx_debug_world_cycles(out, 0)
-names = ["stage agents", "shuffle", "stream0 (move/noop)", "stream1 (vibe)", "on_tick", "coverage", "  do_move (in streams)", "  action bookkeeping"]
+names = ["stage agents", "shuffle", "stream0 (move/noop)", "stream1 (vibe)", "on_tick", "coverage", "  do_move (in streams)", "  action bookkeeping",
+         "resolve move targets"]
 waves = (E + 63) // 64
+print(f"move_fast {eng.move_fast}")
 for k, nm in enumerate(names):
     print(f"{nm:28s} {out[k] / steps / waves:12.0f} cycles / wave / step")
+# event counts of the primary stream (MGX_COUNT), first wavefront of every workgroup (32 envs) like the cycle totals
+print(f"{'stream0 trips':28s} {out[9] / steps / waves:12.2f} / wave / step")
+print(f"{'run-ahead actions':28s} {out[10] / steps / waves / 32:12.2f} / env / step   (of {A} agents)")
+print(f"{'general-path dispatches':28s} {out[11] / steps / waves / 32:12.2f} / env / step")
+print(f"{'  of them stale entries':28s} {out[12] / steps / waves / 32:12.3f} / env / step")
 lib.mgx_debug_obs_cycles(out2, 0)
 print("observation kernel, thread 0 of every workgroup:")
 for k, nm in [(8, "stage grid/agents"), (9, "object token cache"), (10, "first observer"), (11, "encode 4 agents"),
