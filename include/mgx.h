@@ -547,6 +547,29 @@ int mgx_set_box_output(mgx_engine* e, void* box, int32_t dtype, int32_t num_feat
 int mgx_token_bag(mgx_engine* e, const uint8_t* tokens, int64_t n_rows, void* bag, int32_t dtype, int32_t* counts, int32_t num_features,
                   const float* scale);
 
+/* Rendering — what MettaGridPufferEnv.render() (envs/mettagrid_puffer_env.py:505-524) and an rgb_array of
+ * watched envs are made of, without a grid_objects() round trip per env.
+ * mgx_render_cells: one uint32 per cell of every listed env, out u32 [n][H][W] HOST memory: 0 for an empty cell, else
+ * (class + 1) | agent_id << 16 | vibe << 24 of the object the grid holds there (agent_id 0xFF for a non-agent; class = the
+ * engine's class index, the [1] of mgx_get_objects).  envs: int32 [n] host memory, any order, repeats allowed.  A
+ * synchronous getter like mgx_get_objects_batch (one kernel into engine-owned scratch that grows on demand, one copy, a
+ * wait); host and device buffers alike.  MGX_ERR_BAD_ARG before anything is enqueued: n < 1, an env out of range, NULL. */
+int mgx_render_cells(mgx_engine* e, const int32_t* envs, int32_t n, uint32_t* out);
+/* The tile atlas of mgx_render_rgb, all HOST memory: tiles u8 [n_tiles][tile_px][tile_px][3] (1 <= tile_px <= 32, 1 <=
+ * n_tiles <= 65536; tile 0 is the empty cell), class_tile u16 [classes], agent_tile u16 [A], vibe_rgb u8 [n_vibes][3] or NULL
+ * (no vibe marker; n_vibes <= 256).  MGX_ERR_BAD_ARG, an earlier atlas staying in force: a size out of range, a tile index >=
+ * n_tiles, a NULL table.  tiles = NULL frees the atlas.  The atlas belongs to the slot: it is in no saved env record. */
+int mgx_set_render_tiles(mgx_engine* e, const uint8_t* tiles, int32_t n_tiles, int32_t tile_px, const uint16_t* class_tile,
+                         const uint16_t* agent_tile, const uint8_t* vibe_rgb, int32_t n_vibes);
+/* RGB frames of the listed envs into caller-owned DEVICE memory, frames u8 [n][H * s][W * s][3] (s = tile_px), on the
+ * engine's stream; every byte of every frame is written by every launch.  With cell = the mgx_render_cells word of envs[k]
+ * at (y / s, x / s) and t = 0 for an empty cell, agent_tile[agent] for an agent, else class_tile[class]:
+ *   frames[k][y][x][:] = tiles[t][y % s][x % s][:], and then, q = s / 3, where vibe_rgb is set, 0 < vibe < n_vibes,
+ *   y % s < q and x % s >= s - q (the top right corner; nothing for s < 3):  frames[k][y][x][:] = vibe_rgb[vibe].
+ * envs: int32 [n] host memory (repeats allowed), uploaded by the call when it differs from the last list; frames: any
+ * alignment.  MGX_ERR_BAD_ARG before anything is enqueued: no atlas, n < 1, an env out of range, NULL. */
+int mgx_render_rgb(mgx_engine* e, const int32_t* envs, int32_t n, uint8_t* frames);
+
 /* One 64-bit digest per env (uint64 [E], host memory) of everything the episode signature is made of: the
  * mgx_get_objects records of the live slots, every stat value and "key exists" flag (mgx_get_stats), episode rewards,
  * action_success, current_stat_reward (mgx_get_reward_state) and the current step — FNV-1a over 32-bit words, restated in

@@ -29,6 +29,7 @@
 #include "mgx_policy_stats.h"  // per-policy episode statistics (mgx_set_policy_stats)
 #include "mgx_pool_sample.h"   // weighted draws of the next pool map, per-map episode statistics (mgx_set_pool_sampling)
 #include "mgx_global_state.h"  // every env's objects as one token row, written behind every step (mgx_set_global_state)
+#include "mgx_render.h"        // the tile atlas of mgx_render_rgb (the kernels: mgx_render.hip)
 
 
 // Territory ownership map (TerritoryTracker::compute_cell_ownership, core/territory_tracker.cpp:215-252) of every cell,
@@ -370,6 +371,16 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
   uint32_t* d_gen_seed = nullptr;   // [E] seed of the map each env's most recent generated restart built
   int32_t* d_objs = nullptr;        // mgx_get_objects_batch: env list | counts | packed records
   size_t objs_cap = 0;              // envs the buffer holds
+  // rendering (mgx_render_cells / mgx_set_render_tiles / mgx_render_rgb; csrc/mgx_render.h): slot-owned, in no env record
+  MgxRenderAtlas rnd{};             // device pointers into d_rnd_atlas (tiles == nullptr: no atlas)
+  void* d_rnd_atlas = nullptr;      // tiles | class_tile | agent_tile | vibe_rgb
+  int32_t* d_rnd_envs = nullptr;    // the env list of the last render call ...
+  size_t rnd_envs_cap = 0;
+  std::vector<int32_t> rnd_envs_host;   // ... as uploaded (an equal list is not uploaded again) ...
+  hipEvent_t rnd_ev = nullptr;      // ... recorded behind that upload: the vector is rewritten once it has completed
+  bool rnd_ev_pending = false;
+  uint32_t* d_rnd_cells = nullptr;  // mgx_render_cells: scratch u32 [rnd_cells_cap]
+  size_t rnd_cells_cap = 0;
   float* d_scale = nullptr;         // per-feature scale of the token decode (mgx_decode_obs)
   float scale_host[256] = {};
   bool scale_valid = false;
@@ -1076,6 +1087,10 @@ void mgx_destroy(mgx_engine* e) {
   if (e->d_objs) (void)hipFree(e->d_objs);
   if (e->d_es_buf) (void)hipFree(e->d_es_buf);
   if (e->es_ev) (void)hipEventDestroy(e->es_ev);
+  if (e->d_rnd_atlas) (void)hipFree(e->d_rnd_atlas);
+  if (e->d_rnd_envs) (void)hipFree(e->d_rnd_envs);
+  if (e->d_rnd_cells) (void)hipFree(e->d_rnd_cells);
+  if (e->rnd_ev) (void)hipEventDestroy(e->rnd_ev);
   if (e->h_flags) (void)hipHostFree(e->h_flags);
   if (e->h_act_err) (void)hipHostFree(e->h_act_err);
   if (e->jit_world.mod) (void)hipModuleUnload(e->jit_world.mod);
@@ -3324,6 +3339,130 @@ int mgx_token_bag(mgx_engine* e, const uint8_t* tokens, int64_t n_rows, void* ba
   const int rc = mgx_launch_token_bag(e->stream, tokens, bag, dtype == MGX_BOX_BF16, counts, e->d_scale, (long long)n_rows, d.T, num_features);
   if (rc == -1) return fail(MGX_ERR_PROGRAM, "mgx_token_bag: one row's tokens and bins do not fit the kernel's LDS");
   if (rc) return fail(MGX_ERR_HIP, "mgx_token_bag: launch failed");
+  return MGX_OK;
+#endif
+}
+
+// ---- rendering (csrc/mgx_render.h, mgx_render.hip) ---------------------------------------------------------------------------
+#ifndef MGX_CPU_EMU
+// e->d_rnd_envs = the caller's env list (checked by the caller), uploaded on the engine's stream when it differs from the
+// last one.
+static int upload_render_envs(mgx_engine* e, const int32_t* envs, int32_t n) {
+  if (e->rnd_envs_host.size() == (size_t)n && memcmp(e->rnd_envs_host.data(), envs, (size_t)n * 4) == 0) return MGX_OK;
+  if (!e->rnd_ev) HIP_TRY(hipEventCreateWithFlags(&e->rnd_ev, hipEventDisableTiming));
+  if (e->rnd_ev_pending) { HIP_TRY(hipEventSynchronize(e->rnd_ev)); e->rnd_ev_pending = false; }
+  e->rnd_envs_host.clear();   // (whatever fails below, the next call uploads again)
+  if ((size_t)n > e->rnd_envs_cap) {
+    HIP_TRY(hipStreamSynchronize(e->stream));   // (a kernel in flight still reads the old list)
+    if (e->d_rnd_envs) (void)hipFree(e->d_rnd_envs);
+    e->d_rnd_envs = nullptr;
+    e->rnd_envs_cap = 0;
+    HIP_TRY(hipMalloc((void**)&e->d_rnd_envs, (size_t)n * 4));
+    e->rnd_envs_cap = (size_t)n;
+  }
+  std::vector<int32_t> list(envs, envs + n);
+  HIP_TRY(hipMemcpyAsync(e->d_rnd_envs, list.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+  e->rnd_envs_host.swap(list);   // (the upload reads this buffer: it stays as it is until rnd_ev has completed)
+  HIP_TRY(hipEventRecord(e->rnd_ev, e->stream));
+  e->rnd_ev_pending = true;
+  return MGX_OK;
+}
+#endif
+
+static int check_render_envs(const mgx_engine* e, const int32_t* envs, int32_t n, const char* who) {
+  if (!envs || n < 1) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": bad argument (env list, n >= 1)");
+  for (int32_t k = 0; k < n; k++)
+    if (envs[k] < 0 || envs[k] >= e->d.E)
+      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": env index " + std::to_string(envs[k]) + " out of range [0, " + std::to_string(e->d.E) + ")");
+  return MGX_OK;
+}
+
+int mgx_render_cells(mgx_engine* e, const int32_t* envs, int32_t n, uint32_t* out) {
+  if (!e || !out) return fail(MGX_ERR_BAD_ARG, "mgx_render_cells: null argument");
+  if (int rc = check_render_envs(e, envs, n, "mgx_render_cells")) return rc;
+#ifdef MGX_CPU_EMU
+  return fail(MGX_ERR_PROGRAM, "mgx_render_cells: the render kernels are not part of the sanitizer build");
+#else
+  HIP_TRY(hipSetDevice(e->device));
+  const MgxDev& d = e->d;
+  const size_t words = (size_t)n * (size_t)d.H * (size_t)d.W;
+  if (words > e->rnd_cells_cap) {
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->d_rnd_cells) (void)hipFree(e->d_rnd_cells);
+    e->d_rnd_cells = nullptr;
+    e->rnd_cells_cap = 0;
+    HIP_TRY(hipMalloc((void**)&e->d_rnd_cells, words * 4));
+    e->rnd_cells_cap = words;
+  }
+  if (int rc = upload_render_envs(e, envs, n)) return rc;
+  const int rc = mgx_launch_render_cells(e->stream, dev_copy(e), e->d_rnd_envs, n, d.H, d.W, e->d_rnd_cells);
+  if (rc == -1) return fail(MGX_ERR_BAD_ARG, "mgx_render_cells: too many envs for one launch");
+  if (rc) return fail(MGX_ERR_HIP, "mgx_render_cells: launch failed");
+  HIP_TRY(hipMemcpyAsync(out, e->d_rnd_cells, words * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return MGX_OK;
+#endif
+}
+
+int mgx_set_render_tiles(mgx_engine* e, const uint8_t* tiles, int32_t n_tiles, int32_t tile_px, const uint16_t* class_tile,
+                         const uint16_t* agent_tile, const uint8_t* vibe_rgb, int32_t n_vibes) {
+  if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_render_tiles: null engine");
+  HIP_TRY(hipSetDevice(e->device));
+  if (!tiles) {   // off: the atlas is freed once the frames in flight are written
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->d_rnd_atlas) (void)hipFree(e->d_rnd_atlas);
+    e->d_rnd_atlas = nullptr;
+    e->rnd = MgxRenderAtlas{};
+    return MGX_OK;
+  }
+  // every refusal comes before anything is touched: an atlas that is set stays in force
+  const int nc = e->prog[MGX_H_NUM_CLASSES], A = e->d.A;
+  if (n_tiles < 1 || n_tiles > 65536 || tile_px < 1 || tile_px > MGX_RENDER_MAX_TILE_PX || !class_tile || !agent_tile)
+    return fail(MGX_ERR_BAD_ARG, "mgx_set_render_tiles: bad argument (1 <= n_tiles <= 65536, 1 <= tile_px <= 32, class and agent tables)");
+  if (vibe_rgb && (n_vibes < 1 || n_vibes > 256)) return fail(MGX_ERR_BAD_ARG, "mgx_set_render_tiles: n_vibes must be in [1, 256]");
+  for (int c = 0; c < nc; c++)
+    if (class_tile[c] >= n_tiles) return fail(MGX_ERR_BAD_ARG, "mgx_set_render_tiles: class_tile[" + std::to_string(c) + "] is not a tile of the atlas");
+  for (int a = 0; a < A; a++)
+    if (agent_tile[a] >= n_tiles) return fail(MGX_ERR_BAD_ARG, "mgx_set_render_tiles: agent_tile[" + std::to_string(a) + "] is not a tile of the atlas");
+#ifdef MGX_CPU_EMU
+  return fail(MGX_ERR_PROGRAM, "mgx_set_render_tiles: the render kernels are not part of the sanitizer build");
+#else
+  // one block: tiles | class_tile | agent_tile | vibe_rgb (the u16 tables on an even offset)
+  const size_t tile_bytes = (size_t)n_tiles * tile_px * tile_px * 3, off_cls = (tile_bytes + 15) & ~(size_t)15;
+  const size_t off_ag = off_cls + (((size_t)nc * 2 + 15) & ~(size_t)15), off_vibe = off_ag + (((size_t)A * 2 + 15) & ~(size_t)15);
+  std::vector<uint8_t> host(off_vibe + (vibe_rgb ? (size_t)n_vibes * 3 : 0) + 16, 0);
+  memcpy(host.data(), tiles, tile_bytes);
+  memcpy(host.data() + off_cls, class_tile, (size_t)nc * 2);
+  memcpy(host.data() + off_ag, agent_tile, (size_t)A * 2);
+  if (vibe_rgb) memcpy(host.data() + off_vibe, vibe_rgb, (size_t)n_vibes * 3);
+  uint8_t* block = nullptr;
+  HIP_TRY(hipMalloc((void**)&block, host.size()));
+  hipError_t he = hipMemcpyAsync(block, host.data(), host.size(), hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);   // `host` is a local; frames in flight read the old atlas
+  if (he != hipSuccess) { (void)hipFree(block); return fail(MGX_ERR_HIP, std::string("mgx_set_render_tiles: ") + hipGetErrorString(he)); }
+  if (e->d_rnd_atlas) (void)hipFree(e->d_rnd_atlas);
+  e->d_rnd_atlas = block;
+  e->rnd.tiles = block;
+  e->rnd.class_tile = (const uint16_t*)(block + off_cls);
+  e->rnd.agent_tile = (const uint16_t*)(block + off_ag);
+  e->rnd.vibe_rgb = vibe_rgb ? block + off_vibe : nullptr;
+  e->rnd.n_tiles = n_tiles; e->rnd.s = tile_px; e->rnd.n_vibes = vibe_rgb ? n_vibes : 0; e->rnd.n_classes = nc;
+  return MGX_OK;
+#endif
+}
+
+int mgx_render_rgb(mgx_engine* e, const int32_t* envs, int32_t n, uint8_t* frames) {
+  if (!e || !frames) return fail(MGX_ERR_BAD_ARG, "mgx_render_rgb: null argument");
+  if (int rc = check_render_envs(e, envs, n, "mgx_render_rgb")) return rc;
+  if (!e->rnd.tiles) return fail(MGX_ERR_BAD_ARG, "mgx_render_rgb: no atlas (mgx_set_render_tiles)");
+#ifdef MGX_CPU_EMU
+  return fail(MGX_ERR_PROGRAM, "mgx_render_rgb: the render kernels are not part of the sanitizer build");
+#else
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = upload_render_envs(e, envs, n)) return rc;
+  const int rc = mgx_launch_render_rgb(e->stream, dev_copy(e), e->rnd, e->d_rnd_envs, n, e->d.H, e->d.W, frames);
+  if (rc == -1) return fail(MGX_ERR_BAD_ARG, "mgx_render_rgb: too many envs for one launch");
+  if (rc) return fail(MGX_ERR_HIP, "mgx_render_rgb: launch failed");
   return MGX_OK;
 #endif
 }

@@ -138,5 +138,10 @@ int mgx_launch_decode(hipStream_t stream, const uint8_t* tokens, float* box, con
 // token-bag kernel (mgx_token_bag.hip): -1 = T / C do not fit the LDS, -2 = the runtime refused
 int mgx_launch_token_bag(hipStream_t stream, const uint8_t* tokens, void* bag, int bf16, int32_t* counts, const float* scale_dev, long long rows,
                          int T, int C);
+// render kernels (mgx_render.hip; mgx_render.h): -1 = the launch does not fit a grid, -2 = the runtime refused
+struct MgxRenderAtlas;
+int mgx_launch_render_cells(hipStream_t stream, const MgxDev* dev_copy, const int32_t* envs_dev, int n, int H, int W, uint32_t* out_dev);
+int mgx_launch_render_rgb(hipStream_t stream, const MgxDev* dev_copy, const MgxRenderAtlas& atlas, const int32_t* envs_dev, int n, int H, int W,
+                          uint8_t* frames_dev);
 
 #endif  // MGX_HOST_H_

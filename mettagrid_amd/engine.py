@@ -161,6 +161,9 @@ def load_lib():
     L.mgx_decode_obs.argtypes = [vp, vp, i64, vp, i32, vp]
     L.mgx_set_box_output.argtypes = [vp, vp, i32, i32, vp]
     L.mgx_token_bag.argtypes = [vp, vp, i64, vp, i32, vp, i32, vp]
+    L.mgx_render_cells.argtypes = [vp, vp, i32, vp]
+    L.mgx_set_render_tiles.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32]
+    L.mgx_render_rgb.argtypes = [vp, vp, i32, vp]
     L.mgx_state_digests.argtypes = [vp, vp]
     L.mgx_set_map_pool.argtypes = [vp, vp, i32]
     L.mgx_reset_envs_from_pool.argtypes = [vp, vp, vp, vp]
@@ -1354,6 +1357,82 @@ class BatchedMettaGrid:
         _check(self.L.mgx_token_bag(self.h, tok_ptr, rows, out.data_ptr(), 1 if out.dtype == torch.float32 else 2, counts.data_ptr(), Cn,
                                     scale.ctypes.data))
         return out, counts
+
+    # ---- rendering (include/mgx.h mgx_render_cells / mgx_set_render_tiles / mgx_render_rgb) ----
+    @property
+    def map_shape(self) -> tuple:
+        return int(self.prog.words[K.H_HEIGHT]), int(self.prog.words[K.H_WIDTH])
+
+    def render_cells(self, envs) -> np.ndarray:
+        """The cell words of the listed envs (any order, repeats allowed), uint32 [n, H, W]: 0 for an empty cell, else
+        ``(class + 1) | agent_id << 16 | vibe << 24`` (``mettagrid_amd/render.py``: ``ansi`` makes the reference's text frame
+        of them, ``cells_from_objects`` the same words from ``grid_objects()``).  One kernel, one copy; a synchronous getter."""
+        idx = env_list(list(envs) if not isinstance(envs, np.ndarray) else envs, self.E, "render_cells")
+        H, W = self.map_shape
+        out = np.empty((idx.size, H, W), np.uint32)
+        _check(self.L.mgx_render_cells(self.h, idx.ctypes.data, int(idx.size), out.ctypes.data))
+        return out
+
+    def set_render_tiles(self, tiles=None, class_tile=None, agent_tile=None, vibe_rgb=None, scale=None) -> None:
+        """The tile atlas ``render_rgb`` draws with: ``tiles`` uint8 [n_tiles, s, s, 3] (s in 1..32; tile 0: the empty cell),
+        ``class_tile`` [classes] and ``agent_tile`` [A] tile indices, ``vibe_rgb`` uint8 [n_vibes, 3] or None (no vibe marker).
+        ``set_render_tiles(scale=8)``: the atlas of ``render.default_tiles``.  ``set_render_tiles()``: frees the atlas."""
+        from . import render
+        if scale is not None:
+            if tiles is not None:
+                raise ValueError("set_render_tiles: give tiles or scale, not both")
+            tiles, class_tile, agent_tile, vibe_rgb = render.default_tiles(self.prog, scale)
+        if tiles is None:
+            _check(self.L.mgx_set_render_tiles(self.h, None, 0, 0, None, None, None, 0))
+            self.render_tiles = None
+            return
+        nc = int(self.prog.words[K.H_NUM_CLASSES])
+        t = np.asarray(tiles)
+        if t.dtype != np.uint8 or t.ndim != 4 or t.shape[0] < 1 or t.shape[0] > 65536 or t.shape[1] != t.shape[2] or t.shape[3] != 3:
+            raise ValueError("set_render_tiles: tiles must be uint8 [1 <= n_tiles <= 65536, s, s, 3]")
+        if not 1 <= t.shape[1] <= 32:
+            raise ValueError(f"set_render_tiles: the tile size must be in [1, 32] (got {t.shape[1]})")
+        if class_tile is None or agent_tile is None:
+            raise ValueError("set_render_tiles: class_tile and agent_tile are needed")
+        tables = []
+        for name, tab, n in (("class_tile", class_tile, nc), ("agent_tile", agent_tile, self.A)):
+            a = np.asarray(tab)
+            if a.shape != (n,) or a.dtype.kind not in "iu":
+                raise ValueError(f"set_render_tiles: {name} must hold {n} integers")
+            if a.size and (a.min() < 0 or a.max() >= t.shape[0]):
+                raise ValueError(f"set_render_tiles: {name} names a tile outside the atlas of {t.shape[0]} tiles")
+            tables.append(np.ascontiguousarray(a, dtype=np.uint16))
+        v = None
+        if vibe_rgb is not None:
+            v = np.asarray(vibe_rgb)
+            if v.dtype != np.uint8 or v.ndim != 2 or v.shape[1] != 3 or not 1 <= v.shape[0] <= 256:
+                raise ValueError("set_render_tiles: vibe_rgb must be uint8 [1 <= n_vibes <= 256, 3]")
+            v = np.ascontiguousarray(v)
+        t = np.ascontiguousarray(t)
+        _check(self.L.mgx_set_render_tiles(self.h, t.ctypes.data, int(t.shape[0]), int(t.shape[1]), tables[0].ctypes.data, tables[1].ctypes.data,
+                                           v.ctypes.data if v is not None else None, int(v.shape[0]) if v is not None else 0))
+        self.render_tiles = (t, tables[0], tables[1], v)   # host copies: what render.rgb_host needs to restate a frame
+
+    def render_rgb(self, envs, out=None):
+        """RGB frames of the listed envs (any order, repeats allowed) on the device: uint8 CUDA tensor [n, H * s, W * s, 3], written
+        on the engine's stream (``caller_waits`` orders the caller's stream behind it); every byte is written by every call.
+        ``out``: a contiguous uint8 CUDA tensor with exactly that many elements to fill instead (any storage offset).  Needs
+        ``set_render_tiles``."""
+        import torch
+        idx = env_list(list(envs) if not isinstance(envs, np.ndarray) else envs, self.E, "render_rgb")
+        if getattr(self, "render_tiles", None) is None:
+            raise ValueError("render_rgb: no atlas (set_render_tiles)")
+        H, W = self.map_shape
+        s = int(self.render_tiles[0].shape[1])
+        shape = (int(idx.size), H * s, W * s, 3)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous()
+                or out.numel() != int(np.prod(shape))):
+            raise ValueError(f"render_rgb: out must be a contiguous uint8 tensor of {int(np.prod(shape))} elements {shape} on {dev}")
+        _check(self.L.mgx_render_rgb(self.h, idx.ctypes.data, int(idx.size), out.data_ptr()))
+        return out.view(shape)
 
     def set_profiling(self, on: bool) -> None:
         _check(self.L.mgx_set_profiling(self.h, 1 if on else 0))

@@ -302,6 +302,12 @@ class MettaGridBatchedEnv:
     ``env.token_bag`` is ``(bag [E*A, 32 + C], counts int32 [E*A])``: device tensors written behind every ``step``'s
     observations and by ``reset`` / ``load_state``, in place, ordered on the caller's stream like the other returned tensors.
     With device restarts a finished env's rows follow its observation rows.
+    ``render_envs`` (device buffers) and ``render_scale`` (tile size s, default 8): ``env.frames`` is a device tensor uint8
+    [n, H * s, W * s, 3] with one RGB frame per listed env (``BatchedMettaGrid.render_rgb`` with the atlas of
+    ``render.default_tiles``; ``engine.set_render_tiles`` replaces it), kept current in place behind every ``step``, ``reset``
+    and ``load_state`` and ordered on the caller's stream like ``token_bag``.  With device restarts a finished env's frame
+    shows its final state, and the restarted env appears after its first step, as its observations do.  ``render()`` works
+    without it.
     """
 
     def __init__(self, prog: Program, num_envs: int, map_fn: Optional[Callable[[int, int], np.ndarray]] = None,
@@ -314,7 +320,8 @@ class MettaGridBatchedEnv:
                  map_seed_stride: int = 1 << 16, step_info_keys=None, time_averaged_stats: bool = False,
                  policy_assignments=None, num_policies: Optional[int] = None, map_weights=None, map_sample_seed: int = 0,
                  map_stats: bool = False, map_labels=None, map_env_offset: int = 0, global_state: bool = False,
-                 global_state_exclude=(), global_state_tokens: Optional[int] = None, token_bag=False) -> None:
+                 global_state_exclude=(), global_state_tokens: Optional[int] = None, token_bag=False,
+                 render_envs=None, render_scale: int = 8) -> None:
         if global_state and buffers != "device":
             raise ValueError("global_state needs device buffers")
         if token_bag not in (False, True, "float32", "bfloat16"):
@@ -323,6 +330,16 @@ class MettaGridBatchedEnv:
             raise ValueError("token_bag needs device buffers")
         self._tb_dtype = None if not token_bag else "bfloat16" if token_bag == "bfloat16" else "float32"
         self.token_bag = None             # (bag, counts) once reset() has made the engine
+        self.render_scale = int(render_scale)
+        if not 1 <= self.render_scale <= 32:
+            raise ValueError("render_scale must be in [1, 32]")
+        self.render_envs = None           # int32 list of the envs whose frames are kept current, or None
+        self.frames = None                # uint8 [n, H * s, W * s, 3] once reset() has made the engine
+        if render_envs is not None:
+            from .engine import env_list
+            if buffers != "device":
+                raise ValueError("render_envs needs device buffers")
+            self.render_envs = env_list(list(render_envs), num_envs, "render_envs")
         self._gs_on, self._gs_exclude, self._gs_tokens = bool(global_state), tuple(global_state_exclude), global_state_tokens
         self.global_state = None          # (tokens, counts, agent_start) once reset() has made the engine
         if map_weights is not None and map_pool is None:
@@ -525,6 +542,11 @@ class MettaGridBatchedEnv:
             counts = torch.empty((rows,), dtype=torch.int32, device=dev)
             self._eng.wait_for_caller()   # (the allocator may hand out memory the caller's stream still uses)
             self.token_bag = self._eng.token_bag(bag, counts)
+        self.frames = None
+        if self.render_envs is not None:
+            self._eng.set_render_tiles(scale=self.render_scale)
+            self._eng.wait_for_caller()   # (as above: the frames may be memory the caller's stream still uses)
+            self.frames = self._eng.render_rgb(self.render_envs)
         if self.replay_envs:
             from .replay import ReplayAssembler
             import os
@@ -835,6 +857,8 @@ class MettaGridBatchedEnv:
             eng.step()
             if self.token_bag is not None:
                 eng.token_bag(*self.token_bag)
+            if self.frames is not None:
+                eng.render_rgb(self.render_envs, self.frames)
             eng.caller_waits()      # ... and whatever the caller enqueues next sees this step's results
             if self.supervisor is not None:
                 self._compute_supervisor_actions()
@@ -893,6 +917,32 @@ class MettaGridBatchedEnv:
         if self.token_bag is not None:   # ... and so are the bags of the loaded observation rows
             self.engine.token_bag(*self.token_bag)
             self.engine.caller_waits()
+        if self.frames is not None:      # ... and the frames of the watched envs
+            self.engine.render_rgb(self.render_envs, self.frames)
+            self.engine.caller_waits()
+
+    # ---- looking at an env (mettagrid_amd/render.py) ----
+    @property
+    def render_mode(self) -> str:
+        """``"ansi"``, as the reference's MettaGridPufferEnv (envs/mettagrid_puffer_env.py:505-508)."""
+        return "ansi"
+
+    def render(self, env: int = 0, mode: str = "ansi", symbols=None):
+        """Env ``env`` as the reference's text frame (``mode="ansi"``, mettagrid_puffer_env.py:510-524; ``symbols``: the
+        overrides the reference reads from ``game.render.symbols``) or as a host uint8 array [H * s, W * s, 3]
+        (``mode="rgb_array"``, s = ``render_scale``, the atlas the engine holds or else the default one)."""
+        from . import render
+        eng = self.engine
+        if mode == "ansi":
+            return render.ansi(eng.render_cells([int(env)])[0], render.class_type_names(self.prog), symbols)
+        if mode != "rgb_array":
+            raise ValueError('render: mode must be "ansi" or "rgb_array"')
+        if getattr(eng, "render_tiles", None) is None:
+            eng.set_render_tiles(scale=self.render_scale)
+        eng.wait_for_caller()   # (the new frame may be memory the caller's stream still uses)
+        frame = eng.render_rgb([int(env)])
+        eng.sync()
+        return frame[0].cpu().numpy()
 
     def close(self) -> None:
         if self._eng is not None:
@@ -909,10 +959,18 @@ class MettaGridParallelEnv:
     gymnasium themselves are not imported: spaces are described by shape / size."""
 
     def __init__(self, env_cfg, map, seed: int = 0, device: int = 0, global_state: bool = False,  # noqa: A002 - reference argument name
-                 global_state_exclude=(), global_state_tokens: Optional[int] = None) -> None:
+                 global_state_exclude=(), global_state_tokens: Optional[int] = None, render_mode: Optional[str] = None,
+                 render_scale: int = 8, render_symbols=None) -> None:
         """``global_state=True``: ``state()`` returns the env's global state row (``mettagrid_amd/global_state.py``) instead of
-        the reference's zero vector; the engine then runs on device buffers and the dicts hold host copies."""
+        the reference's zero vector; the engine then runs on device buffers and the dicts hold host copies.
+        ``render_mode``: what ``render()`` returns — None: nothing, ``"ansi"``: the reference's text frame (``render_symbols``:
+        symbol overrides), ``"rgb_array"``: a uint8 array [H * s, W * s, 3] with s = ``render_scale``."""
         from .engine import MettaGrid
+        if render_mode not in (None, "ansi", "rgb_array"):
+            raise ValueError('render_mode: None, "ansi" or "rgb_array"')
+        if not 1 <= int(render_scale) <= 32:
+            raise ValueError("render_scale must be in [1, 32]")
+        self.render_mode, self._render_scale, self._render_symbols = render_mode, int(render_scale), render_symbols
         self._gs_on = bool(global_state)
 
         def make(s):
@@ -990,8 +1048,20 @@ class MettaGridParallelEnv:
     def max_steps(self) -> int:
         return self._sim.max_steps
 
-    def render(self) -> None:
-        pass
+    def render(self):
+        """None without a ``render_mode``; the text frame for ``"ansi"``; the RGB frame (host array) for ``"rgb_array"``."""
+        if self.render_mode is None:
+            return None
+        from . import render
+        b = self._sim._b
+        if self.render_mode == "ansi":
+            return render.ansi(b.render_cells([0])[0], render.class_type_names(b.prog), self._render_symbols)
+        if getattr(b, "render_tiles", None) is None:
+            b.set_render_tiles(scale=self._render_scale)
+        b.wait_for_caller()   # (the new frame may be memory the caller's stream still uses)
+        frame = b.render_rgb([0])
+        b.sync()
+        return frame[0].cpu().numpy()
 
     def close(self) -> None:
         if self._sim is not None:

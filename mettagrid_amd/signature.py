@@ -50,7 +50,8 @@ def objects_from_raw(prog, raw: np.ndarray, current_stat_reward=None) -> dict:
         d = {"id": oid, "type_name": prog.type_names[int(C[K.C_TYPE_ID])], "r": r, "c": c, "location": (c, r),
              "tag_ids": tags, "vibe": vibe,
              "inventory": {i: int(amounts[i]) for i in range(_MAXR) if amounts[i] > 0},
-             "inventory_order": [int(x) for x in rec[8:8 + norder]]}
+             "inventory_order": [int(x) for x in rec[8:8 + norder]],
+             "class_id": cls}   # (not a reference field: several classes share a type name; render.cells_from_objects reads it)
         if agent_id >= 0:
             d["agent_id"] = agent_id
             d["group_id"] = int(C[K.C_GROUP])
