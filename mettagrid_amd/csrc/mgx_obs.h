@@ -397,10 +397,83 @@ static __device__ __forceinline__ void mgx_obs_env(const MgxDev& d, const int en
       for (size_t i = tid; i < env_bytes / 2; i += NTH) ((uint16_t*)eb)[i] = 0;
     }
   }
-  // The classification of object slot `tid` (phase 0b) needs only global data: its loads are issued first, so they
-  // are in flight together with the staging loads below instead of one barrier later.
+  // ---- phase 0a: stage the env (coalesced), in three parts: (1) every global load of this thread that depends on nothing
+  // loaded is ISSUED into registers, with no LDS store and no other use of a loaded value in between; (2) the loads that
+  // need a value of part one are issued behind one wait; (3) the LDS writes and the classification (phase 0b).  A wavefront
+  // then waits for two memory round trips in front of the first barrier, not for one per staging job: a job written as
+  // `if (tid < n) lds[tid] = global[tid];` ends with a wait for its own load before the next job's load is issued.
+  // Only the first pass of a run-time loop (a grid of more than 16 * NTH bytes, S or A above NTH ...) is hoisted like that;
+  // further passes are plain loops in part three.
+  // Which thread takes which job: object slots and the grid start at thread 0; the agents, the program block and the
+  // class-tag table start at the first wavefront with no object slot to classify (FREE; thread 0 again when S fills the
+  // workgroup); the window offsets end at the last thread.  j* is this thread's item of such a job.
+  static_assert((NTH & (NTH - 1)) == 0, "job rotation by masking");
+  const int FREE = S < NTH ? (((S + MGX_WAVE - 1) & ~(MGX_WAVE - 1)) & (NTH - 1)) : 0;
+  const int jf = (tid - FREE) & (NTH - 1);
+  const int jw = (tid + min(CP, NTH)) & (NTH - 1);
+  const int n16 = (HW * 2) / 16;
+  const uint4* gsrc = (const uint4*)(d.grid + (size_t)env * HW);
+  const int gtail = n16 * 8 + tid;   // the cells behind the last whole 16 bytes: fewer than eight
+  const int4* bsrc = (const int4*)(d.P + blk_start);
+  const int32_t* offs = d.P + d.sec[MGX_SEC_OBS_OFFSETS];
+  const bool pool_once = pool_prefix <= NTH;   // (uniform) one guarded load per thread instead of a loop
+  // what phase 0a keeps of one agent
+  struct AgStage { uint32_t slot, rwi; int32_t ex, used; uint16_t sprev, spawn, rc; float vs; };
+  // every load of an agent is independent: the cell and the class's reward records come from the per-agent mirrors
+  // (MgxDev::ag_rc, ag_rwinfo), the cell.visited stat is loaded whatever the step (and dropped at step 0, below)
+  auto ag_load = [&](int i) -> AgStage {
+    AgStage g;
+    const size_t a = e.ao(i);
+    g.slot = d.ag_obj[a];
+    g.ex = d.executed[a];
+    g.sprev = d.ag_stepprev[a];
+    g.spawn = d.ag_spawn[a];
+    g.vs = e.astat_get(i, sid_visited);
+    g.rc = d.ag_rc[a];
+    g.rwi = d.ag_rwinfo[a];
+    // tokens the previous pass left in the agent's row (0xFFFF = unknown: the whole row is rewritten), parked in s_written[i]
+    // until the row's encode replaces it with this pass's count
+    g.used = 0xFFFF;
+    if constexpr (!BOX) { if (d.obs_used) g.used = (int)d.obs_used[a]; }
+    return g;
+  };
+  // X: the observer's own tag bitset (friend / foe of a cell's owner tag), once per env — behind the agent's slot (and
+  // behind its class, where tags are static)
+  auto ag_tags_load = [&](uint32_t slot, uint32_t* t) {
+    const int32_t* C = d.obj_tags ? nullptr : mgx_cls(d, d.obj_cls[e.so(slot)]);
+#pragma unroll
+    for (int w = 0; w < MGX_TAG_WORDS; w++)
+      if (w < TW) t[w] = d.obj_tags ? d.obj_tags[e.so(slot) * MGX_TAG_WORDS + w] : (uint32_t)C[MGX_C_TAGS + w];
+  };
+  auto ag_store = [&](int i, const AgStage& g, const uint32_t* t) {
+    s_agents[i] = g.slot | ((uint32_t)g.rc << 16);
+    s_aginfo[i] = ((uint32_t)g.ex & 0xFF) | (g.rc != g.sprev ? 0x100u : 0u);
+    s_spawn[i] = g.spawn;
+    s_vstat[i] = step > 0 ? g.vs : 0.f;
+    s_rwinfo[i] = g.rwi;
+    if constexpr (!BOX) s_written[i] = g.used;
+    if constexpr (X) {
+      if (want_mask) {
+#pragma unroll
+        for (int w = 0; w < MGX_TAG_WORDS; w++)
+          if (w < TW) s_agtags[i * TW + w] = t[w];
+      }
+    }
+  };
+  // The territory owner of a cell (X; TerritoryTracker::compute_observability_at :254-273: the first territory type with an
+  // owner decides; mgx_terr_kernel keeps the per-type maps current)
+  auto terr_rest = [&](int cellidx, uint16_t owner) -> uint16_t {
+    for (int ti = 1; ti < dNT && owner == 0xFFFF; ti++) owner = d.terr_owner[((size_t)env * dNT + ti) * (size_t)HW + cellidx];
+    return owner;
+  };
+
+  // -- part one: first-level loads.  The classification pair first: part two waits for it alone.
   uint16_t pre_cls = MGX_DEAD_CLASS;
   uint32_t pre_vis = 0, pre_cinfo = 0;
+  if (tid < S) {
+    pre_cls = d.obj_cls[e.so(tid)];
+    pre_vis = d.obj_visited[e.so(tid)];
+  }
   // the two game stats the tail adds to (nothing else in this kernel writes them): loaded now, so the last thing a
   // workgroup does is not an HBM round trip that keeps its LDS occupied
   float pre_tw = 0.f, pre_tf = 0.f;
@@ -409,73 +482,91 @@ static __device__ __forceinline__ void mgx_obs_env(const MgxDev& d, const int en
     pre_tw = gs0[d.wk[MGX_S_GAME_TOKENS_WRITTEN]];
     pre_tf = gs0[d.wk[MGX_S_GAME_TOKENS_FREE]];
   }
-  if (tid < S) {
-    pre_cls = d.obj_cls[e.so(tid)];
-    pre_vis = d.obj_visited[e.so(tid)];
-    if (pre_cls != MGX_DEAD_CLASS) pre_cinfo = d.cls_tokinfo[pre_cls];
+  uint4 g0 = make_uint4(0u, 0u, 0u, 0u);
+  if (tid < n16) g0 = gsrc[tid];
+  uint16_t g1 = 0;
+  if (gtail < HW) g1 = d.grid[(size_t)env * HW + gtail];
+  int4 b0 = make_int4(0, 0, 0, 0);
+  if constexpr (PL) { if (jf < blk_words / 4) b0 = bsrc[jf]; }
+  uint16_t p0 = 0;
+  if (pool_once && jf < pool_prefix) p0 = d.cls_tok[jf];
+  int orow0 = 0, ocol0 = 0;
+  if (jw < CP) { const int ii = min(jw, NOFF - 1); orow0 = offs[ii * 2]; ocol0 = offs[ii * 2 + 1]; }
+  AgStage a0 = {};
+  if (jf < A) a0 = ag_load(jf);
+  uint16_t own0 = 0xFFFF;
+  uint32_t ov0 = 0;
+  if constexpr (X) {
+    // the first territory type of this thread's cell and the query-backed obs values (mgx_values_kernel, one env per lane,
+    // wrote them right before this kernel): plain per-env data, staged with the grid
+    if (want_mask && tid < HW) own0 = d.terr_owner[(size_t)env * dNT * (size_t)HW + tid];
+    if (d.obsval && tid < A * NOV) ov0 = d.obsval[(size_t)env * A * NOV + tid];
   }
-  // ---- phase 0a: stage the env (coalesced) ----
+  // -- part two: the loads behind a value of part one
+  if (tid < S && pre_cls != MGX_DEAD_CLASS) pre_cinfo = d.cls_tokinfo[pre_cls];
+  uint32_t t0[MGX_TAG_WORDS] = {};
+  if constexpr (X) {
+    if (want_mask && jf < A) ag_tags_load(a0.slot, t0);
+    if (want_mask && tid < HW) own0 = terr_rest(tid, own0);   // (a cell no type owns yet: one more round trip per type)
+  }
+  // -- part three: LDS writes; the further passes of the run-time loops.  Its conditions are those of part one, tested
+  // AGAIN on a copy of the thread index the compiler cannot see through: kept, the lane masks of part one cost 14 scalar
+  // registers across the waits, which took the rung-3 instance from 95 to 102 SGPRs and from eight to seven wavefronts per
+  // SIMD by the compiler's count; a compare each is free in a stretch that waits for memory.
   {
-    const uint4* src = (const uint4*)(d.grid + (size_t)env * HW);
+    int tid3 = tid;
+    asm volatile("" : "+v"(tid3));
+    const int tid = tid3, jf = (tid3 - FREE) & (NTH - 1), jw = (tid3 + min(CP, NTH)) & (NTH - 1), gtail = n16 * 8 + tid3;   // (shadow part one's)
     uint4* dst = (uint4*)s_grid;
-    const int n16 = (HW * 2) / 16;
-    for (int i = tid; i < n16; i += NTH) dst[i] = src[i];
-    for (int i = n16 * 8 + tid; i < HW; i += NTH) s_grid[i] = d.grid[(size_t)env * HW + i];
-    if constexpr (PL) {
-      const int4* bsrc = (const int4*)(d.P + blk_start);
-      int4* bdst = (int4*)(smem + L.blk);
-      for (int i = tid; i < blk_words / 4; i += NTH) bdst[i] = bsrc[i];
+    if (tid < n16) dst[tid] = g0;
+    if (gtail < HW) s_grid[gtail] = g1;
+    if constexpr (PL) { if (jf < blk_words / 4) ((int4*)(smem + L.blk))[jf] = b0; }
+    if (pool_once && jf < pool_prefix) s_pool[jf] = p0;
+    if (jw < CP) {
+      if (jw < NOFF) s_offs[jw] = make_char2((char)orow0, (char)ocol0);
+      s_loc[jw] = (uint8_t)(((orow0 + hr) << 4) | (ocol0 + wr));
     }
-    for (int i = tid; i < pool_prefix; i += NTH) s_pool[i] = d.cls_tok[i];
-    const int32_t* offs = d.P + d.sec[MGX_SEC_OBS_OFFSETS];
-    for (int i = tid; i < CP; i += NTH) {
-      const int ii = min(i, NOFF - 1);
-      const int orow = offs[ii * 2], ocol = offs[ii * 2 + 1];
-      if (i < NOFF) s_offs[i] = make_char2((char)orow, (char)ocol);
-      s_loc[i] = (uint8_t)(((orow + hr) << 4) | (ocol + wr));
-    }
-    for (int i = tid; i < A; i += NTH) {
-      const uint32_t slot = d.ag_obj[e.ao(i)];
-      const int32_t ex = d.executed[e.ao(i)];
-      const uint16_t sprev = d.ag_stepprev[e.ao(i)];
-      const uint16_t spawn = d.ag_spawn[e.ao(i)];
-      const float vs = step > 0 ? e.astat_get(i, sid_visited) : 0.f;
-      // the agent's cell and its class's reward records from the per-agent mirrors (MgxDev::ag_rc, ag_rwinfo): every load of
-      // this loop is independent — one memory round trip in front of the first barrier instead of three (slot -> object row ->
-      // class record)
-      const uint16_t rc = d.ag_rc[e.ao(i)];
-      const uint32_t rwi = d.ag_rwinfo[e.ao(i)];
-      s_agents[i] = slot | ((uint32_t)rc << 16);
-      s_aginfo[i] = ((uint32_t)ex & 0xFF) | (rc != sprev ? 0x100u : 0u);
-      s_spawn[i] = spawn;
-      s_vstat[i] = vs;
-      s_rwinfo[i] = rwi;
-      // tokens the previous pass left in the agent's row (0xFFFF = unknown: the whole row is rewritten), parked in s_written[i]
-      // until the row's encode replaces it with this pass's count — loaded here, with everything else the env stages
-      if constexpr (!BOX) s_written[i] = d.obs_used ? (int)d.obs_used[e.ao(i)] : 0xFFFF;
-      if constexpr (X) {
-        if (want_mask) {   // the observer's own tag bitset (friend / foe of a cell's owner tag), once per env
-          const int32_t* C = d.obj_tags ? nullptr : mgx_cls(d, d.obj_cls[e.so(slot)]);
-          for (int w = 0; w < TW; w++)
-            s_agtags[i * TW + w] = d.obj_tags ? d.obj_tags[e.so(slot) * MGX_TAG_WORDS + w] : (uint32_t)C[MGX_C_TAGS + w];
-        }
-      }
-    }
+    if (jf < A) ag_store(jf, a0, t0);
     if constexpr (X) {
-      // The territory owner of every cell (TerritoryTracker::compute_observability_at :254-273: the first territory type
-      // with an owner decides; mgx_terr_kernel keeps the per-type maps current) and the query-backed obs values are plain
-      // per-env data: staged here with the grid, one round trip, instead of behind a barrier of their own in the middle
-      // of the kernel.
-      if (want_mask)
-        for (int cellidx = tid; cellidx < HW; cellidx += NTH) {
-          uint16_t owner = 0xFFFF;
-          for (int ti = 0; ti < dNT && owner == 0xFFFF; ti++) owner = d.terr_owner[((size_t)env * dNT + ti) * (size_t)HW + cellidx];
-          if (owner8) s_owner8[cellidx] = (uint8_t)owner; else s_owner[cellidx] = owner;  // (0xFFFF -> 0xFF: tag ids stop at 254 then)
-        }
-      if (d.obsval)  // evaluated by mgx_values_kernel (one env per lane) right before this kernel
-        for (int i = tid; i < A * NOV; i += NTH) s_obsval[i] = d.obsval[(size_t)env * A * NOV + i];
+      if (want_mask && tid < HW) { if (owner8) s_owner8[tid] = (uint8_t)own0; else s_owner[tid] = own0; }  // (0xFFFF -> 0xFF: tag ids stop at 254 then)
+      if (d.obsval && tid < A * NOV) s_obsval[tid] = ov0;
     }
     if (tid == 0) { s_misc[0] = (uint32_t)pool_prefix; if (S > NTH) s_misc[1] = 0; }  // pool top, number of per-step lists (S <= NTH: a count byte per wavefront, below)
+    if (n16 > NTH)
+      for (int i = tid + NTH; i < n16; i += NTH) dst[i] = gsrc[i];
+    if constexpr (PL) {
+      if (blk_words / 4 > NTH)
+        for (int i = jf + NTH; i < blk_words / 4; i += NTH) ((int4*)(smem + L.blk))[i] = bsrc[i];
+    }
+    if (!pool_once) {
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+      for (int i = tid; i < pool_prefix; i += NTH) s_pool[i] = d.cls_tok[i];
+    }
+    if (CP > NTH)
+      for (int i = jw + NTH; i < CP; i += NTH) {
+        const int ii = min(i, NOFF - 1);
+        const int orow = offs[ii * 2], ocol = offs[ii * 2 + 1];
+        if (i < NOFF) s_offs[i] = make_char2((char)orow, (char)ocol);
+        s_loc[i] = (uint8_t)(((orow + hr) << 4) | (ocol + wr));
+      }
+    if (A > NTH)
+      for (int i = jf + NTH; i < A; i += NTH) {
+        const AgStage g = ag_load(i);
+        uint32_t t[MGX_TAG_WORDS] = {};
+        if constexpr (X) { if (want_mask) ag_tags_load(g.slot, t); }
+        ag_store(i, g, t);
+      }
+    if constexpr (X) {
+      if (want_mask && HW > NTH) {
+        for (int cellidx = tid + NTH; cellidx < HW; cellidx += NTH) {
+          const uint16_t owner = terr_rest(cellidx, d.terr_owner[(size_t)env * dNT * (size_t)HW + cellidx]);
+          if (owner8) s_owner8[cellidx] = (uint8_t)owner; else s_owner[cellidx] = owner;
+        }
+      }
+      if (d.obsval && A * NOV > NTH) {
+        for (int i = tid + NTH; i < A * NOV; i += NTH) s_obsval[i] = d.obsval[(size_t)env * A * NOV + i];
+      }
+    }
   }
   const bool dyn_tags = X && d.obj_tags != nullptr;
   // ---- phase 0b: classify the object slots.  Static classes show their class tag list (pool prefix); everything
