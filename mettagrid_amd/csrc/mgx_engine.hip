@@ -212,6 +212,126 @@ static int fail(int code, const std::string& msg) {
       return fail(MGX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));                 \
   } while (0)
 
+// ---- what the statistics reducers share on the host (on the device: csrc/mgx_totals.h) --------------------------
+// Totals that live on the device and are read by SNAPSHOT: one kernel launch copies them to d_snap and clears them, an async
+// copy brings d_snap to pinned memory, an event says when it has landed.  One snapshot at a time.  Elements are 8 bytes.
+struct MgxSnapshot {
+  void* d_totals = nullptr;   // [bytes] since the last snapshot
+  void* d_snap = nullptr;     // [bytes] the snapshot taken by request()
+  void* h_snap = nullptr;     // pinned host copy of the snapshot
+  size_t bytes = 0;
+  hipEvent_t ev = nullptr;    // recorded behind the snapshot copy
+  bool pending = false;       // a snapshot has been requested and not fetched yet
+
+  int create(size_t n_bytes) {
+    bytes = n_bytes;
+    HIP_TRY(hipMalloc(&d_totals, bytes));
+    HIP_TRY(hipMalloc(&d_snap, bytes));
+    HIP_TRY(hipHostMalloc(&h_snap, bytes, hipHostMallocDefault));
+    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    return MGX_OK;
+  }
+  void destroy() {   // (also of a half-created one)
+    if (d_totals) (void)hipFree(d_totals);
+    if (d_snap) (void)hipFree(d_snap);
+    if (h_snap) (void)hipHostFree(h_snap);
+    if (ev) (void)hipEventDestroy(ev);
+    *this = MgxSnapshot{};
+  }
+  // launch(): the owner's snapshot kernel, enqueued on `stream`; returns MGX_OK or its failure.
+  template <class Launch>
+  int request(int device, hipStream_t stream, Launch launch) {
+    if (pending) return MGX_OK;   // the snapshot already under way is fetched first; the totals keep accumulating
+    HIP_TRY(hipSetDevice(device));
+    { int rc = launch(); if (rc) return rc; }
+    HIP_TRY(hipMemcpyAsync(h_snap, d_snap, bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(ev, stream));
+    pending = true;
+    return MGX_OK;
+  }
+  // *ready (0 on entry) = 1 and `out` filled once the requested snapshot has landed; nothing without a request.
+  int fetch(int device, int32_t wait, void* out, int32_t* ready) {
+    if (!pending) return MGX_OK;
+    HIP_TRY(hipSetDevice(device));
+    if (wait) {
+      HIP_TRY(hipEventSynchronize(ev));
+    } else {
+      const hipError_t q = hipEventQuery(ev);
+      if (q == hipErrorNotReady) return MGX_OK;
+      if (q != hipSuccess) return fail(MGX_ERR_HIP, std::string("hipEventQuery: ") + hipGetErrorString(q));
+    }
+    memcpy(out, h_snap, bytes);
+    pending = false;
+    *ready = 1;
+    return MGX_OK;
+  }
+};
+
+// A bounded device log of per-episode records; the total kernel of each step advances d_state (csrc/mgx_totals.h).
+struct MgxEpisodeLog {
+  uint32_t* d_log = nullptr;     // [cap][words] records kept for the drain, or nullptr (no log)
+  uint32_t* d_state = nullptr;   // [2] records in the log, records dropped since the last drain
+  int cap = 0, words = 0;
+
+  int create(hipStream_t stream, int log_cap, int log_words) {
+    words = log_words;
+    HIP_TRY(hipMalloc((void**)&d_state, 8));
+    HIP_TRY(hipMemsetAsync(d_state, 0, 8, stream));
+    if (log_cap > 0) {
+      HIP_TRY(hipMalloc((void**)&d_log, (size_t)log_cap * words * 4));
+      cap = log_cap;
+    }
+    return MGX_OK;
+  }
+  void destroy() {
+    if (d_log) (void)hipFree(d_log);
+    if (d_state) (void)hipFree(d_state);
+    *this = MgxEpisodeLog{};
+  }
+  // The log's records -> `records` (room for `cap` of them), the log emptied; waits for the device.
+  int drain(int device, hipStream_t stream, uint32_t* records, int32_t* n_records, int32_t* n_dropped) {
+    HIP_TRY(hipSetDevice(device));
+    uint32_t st[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(st, d_state, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (st[0]) HIP_TRY(hipMemcpyAsync(records, d_log, (size_t)st[0] * words * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemsetAsync(d_state, 0, 8, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *n_records = (int32_t)st[0];
+    if (n_dropped) *n_dropped = (int32_t)st[1];
+    return MGX_OK;
+  }
+};
+
+// One reducer: the step's records -> chunk sums -> f64 batch totals (read by snapshot) + the log.
+struct MgxReducer {
+  uint32_t* rec = nullptr;      // [E][rec_words] records of the envs that finished in the last step
+  double* partial = nullptr;    // [ceil(E / MGX_EP_CHUNK)][tot_words] chunk sums
+  uint32_t* ticket = nullptr;   // [1]
+  MgxSnapshot snap;             // [tot_words] doubles
+  MgxEpisodeLog log;
+  double* totals() const { return (double*)snap.d_totals; }
+
+  // The totals are left as allocated: the owner runs its snapshot kernel once, which leaves them cleared.
+  int create(hipStream_t stream, size_t E, int rec_words, int tot_words, int log_cap, int log_words) {
+    const size_t nch = (E + MGX_EP_CHUNK - 1) / MGX_EP_CHUNK;
+    HIP_TRY(hipMalloc((void**)&rec, E * rec_words * 4));
+    HIP_TRY(hipMalloc((void**)&partial, nch * tot_words * 8));
+    HIP_TRY(hipMalloc((void**)&ticket, 4));
+    HIP_TRY(hipMemsetAsync(ticket, 0, 4, stream));
+    { int rc = snap.create((size_t)tot_words * 8); if (rc) return rc; }
+    return log.create(stream, log_cap, log_words);
+  }
+  void destroy() {
+    if (rec) (void)hipFree(rec);
+    if (partial) (void)hipFree(partial);
+    if (ticket) (void)hipFree(ticket);
+    snap.destroy();
+    log.destroy();
+    *this = MgxReducer{};
+  }
+};
+
 struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layout) + the resources behind it
   MgxSwitches sw{};            // the create-time switches, for the rest of the engine's life
   MgxDev* d_dev = nullptr;     // copy of `d` in device memory for the kernels that take it by pointer (extended path)
@@ -277,50 +397,20 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
   // episode-end statistics (mgx_set_episode_stats; csrc/mgx_episode.h)
   bool ep_stats = false;
   MgxEpLayout ep{};
-  uint32_t* d_ep_rec = nullptr;     // [E][ep.rec_words] records of the envs that finished in the last step
-  double* d_ep_partial = nullptr;   // [ceil(E / 256)][TW] chunk sums
-  double* d_ep_totals = nullptr;    // [TW] batch totals since the last snapshot
-  double* d_ep_snap = nullptr;      // [TW] snapshot taken by mgx_request_episode_stats
-  double* h_ep_snap = nullptr;      // pinned host copy of the snapshot
-  uint32_t* d_ep_ticket = nullptr;  // [1]
-  uint32_t* d_ep_log = nullptr;     // [ep_log_cap][ep.log_words] per-episode records kept for mgx_drain_episode_log
-  uint32_t* d_ep_log_state = nullptr;  // [2] records in the log, records dropped
-  int ep_log_cap = 0;
-  hipEvent_t ep_ev = nullptr;       // recorded behind the snapshot copy
-  bool ep_pending = false;          // a snapshot has been requested and not fetched yet
+  MgxReducer ep_red;                // records [E][ep.rec_words], totals [ep_tw()], log records of ep.log_words
   int ep_tw() const { return MGX_EP_TOT_HDR + 2 * (ep.NG + ep.NS); }
   // time-averaged game stats (mgx_set_time_averages; csrc/mgx_time_avg.h): slot-side arrays outside the saved env record
   bool ta_on = false;
   MgxTimeAvg ta{};                  // layout + ta_sum [E][NG], ta_seen [E][NGW], ta_steps [E]
-  uint32_t* d_ta_rec = nullptr;     // [E][ta.L.rec_words] records of the envs that finished in the last step
-  double* d_ta_partial = nullptr;   // [ceil(E / 256)][tot_words] chunk sums
-  double* d_ta_totals = nullptr;    // [tot_words] batch totals since the last snapshot
-  double* d_ta_snap = nullptr;      // [tot_words] snapshot taken by mgx_request_time_averages
-  double* h_ta_snap = nullptr;      // pinned host copy of the snapshot
-  uint32_t* d_ta_ticket = nullptr;  // [1]
-  uint32_t* d_ta_log = nullptr;     // [ta_log_cap][ta.L.rec_words] records kept for mgx_drain_time_average_log
-  uint32_t* d_ta_log_state = nullptr;  // [2] records in the log, records dropped
-  int ta_log_cap = 0;
+  MgxReducer ta_red;                // records [E][ta.L.rec_words], totals [ta.L.tot_words], log records as the records
   uint8_t* d_ta_block = nullptr;    // staging of mgx_copy_envs / get / put: packed accumulators of a list of envs
   size_t ta_block_bytes = 0;
-  hipEvent_t ta_ev = nullptr;       // recorded behind the snapshot copy
-  bool ta_pending = false;
   // per-policy episode statistics (mgx_set_policy_stats; csrc/mgx_policy_stats.h): the assignment table belongs to the slots
   bool ps_on = false;
   MgxPolicyStats ps{};              // layout + assign u8 [E][A]
-  uint32_t* d_ps_rec = nullptr;     // [E][ps.L.rec_words] records of the envs that finished in the last step
-  double* d_ps_partial = nullptr;   // [ceil(E / 256)][tot_words] chunk sums
-  double* d_ps_totals = nullptr;    // [tot_words] batch totals since the last snapshot
-  double* d_ps_snap = nullptr;      // [tot_words] snapshot taken by mgx_request_policy_stats
-  double* h_ps_snap = nullptr;      // pinned host copy of the snapshot
-  uint32_t* d_ps_ticket = nullptr;  // [1]
-  uint32_t* d_ps_log = nullptr;     // [ps_log_cap][ps.L.rec_words] records kept for mgx_drain_policy_log
-  uint32_t* d_ps_log_state = nullptr;  // [2] records in the log, records dropped
-  int ps_log_cap = 0;
+  MgxReducer ps_red;                // records [E][ps.L.rec_words], totals [ps.L.tot_words], log records as the records
   uint8_t* d_ps_rows = nullptr;     // [E][A] staging of mgx_set_policy_assignments: the rows of the listed envs
   int32_t* d_ps_list = nullptr;     // [E] ... and the list
-  hipEvent_t ps_ev = nullptr;       // recorded behind the snapshot copy
-  bool ps_pending = false;
   // weighted pool sampling (mgx_set_pool_sampling; csrc/mgx_pool_sample.h): thresholds, seed and offset belong to the slots
   bool smp_on = false;              // (false: the restarts enqueue nothing for it and the rotation rule stands)
   uint32_t smp_seed = 0, smp_offset = 0;
@@ -330,11 +420,7 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
   int smp_slot = 0;
   // per-map episode statistics (mgx_set_map_stats): the table belongs to the slots
   bool ms_on = false;               // (false: nothing is enqueued behind the episode records)
-  unsigned long long* d_ms_table = nullptr;    // [n_pool + 1][MGX_MS_COLS] since the last snapshot
-  unsigned long long* d_ms_snap = nullptr;     // snapshot taken by mgx_request_map_stats
-  unsigned long long* h_ms_snap = nullptr;     // pinned host copy of the snapshot
-  hipEvent_t ms_ev = nullptr;       // recorded behind the snapshot copy
-  bool ms_pending = false;
+  MgxSnapshot ms_snap;              // the table: uint64 [n_pool + 1][MGX_MS_COLS]
   unsigned long long* d_digest = nullptr;   // [E] mgx_state_digests
   // saved env state (mgx_env_state.h): the record layout, the device segment table, the staging of mgx_copy_envs
   MgxEnvStateLayout es;
@@ -655,26 +741,20 @@ static int init_buffers(mgx_engine* e) {
 }
 
 static void free_time_averages(mgx_engine* e) {
-  for (void* p : {(void*)e->ta.sum, (void*)e->ta.seen, (void*)e->ta.steps, (void*)e->d_ta_rec, (void*)e->d_ta_partial, (void*)e->d_ta_totals,
-                  (void*)e->d_ta_snap, (void*)e->d_ta_ticket, (void*)e->d_ta_log, (void*)e->d_ta_log_state, (void*)e->d_ta_block})
+  for (void* p : {(void*)e->ta.sum, (void*)e->ta.seen, (void*)e->ta.steps, (void*)e->d_ta_block})
     if (p) (void)hipFree(p);
-  if (e->h_ta_snap) (void)hipHostFree(e->h_ta_snap);
-  if (e->ta_ev) (void)hipEventDestroy(e->ta_ev);
+  e->ta_red.destroy();
   e->ta = MgxTimeAvg{};
-  e->d_ta_rec = nullptr; e->d_ta_partial = nullptr; e->d_ta_totals = nullptr; e->d_ta_snap = nullptr; e->d_ta_ticket = nullptr;
-  e->d_ta_log = nullptr; e->d_ta_log_state = nullptr; e->d_ta_block = nullptr; e->h_ta_snap = nullptr; e->ta_ev = nullptr;
-  e->ta_on = false; e->ta_pending = false; e->ta_log_cap = 0; e->ta_block_bytes = 0;
+  e->d_ta_block = nullptr;
+  e->ta_on = false; e->ta_block_bytes = 0;
 }
 static void free_policy_stats(mgx_engine* e) {
-  for (void* p : {(void*)e->ps.assign, (void*)e->d_ps_rec, (void*)e->d_ps_partial, (void*)e->d_ps_totals, (void*)e->d_ps_snap, (void*)e->d_ps_ticket,
-                  (void*)e->d_ps_log, (void*)e->d_ps_log_state, (void*)e->d_ps_rows, (void*)e->d_ps_list})
+  for (void* p : {(void*)e->ps.assign, (void*)e->d_ps_rows, (void*)e->d_ps_list})
     if (p) (void)hipFree(p);
-  if (e->h_ps_snap) (void)hipHostFree(e->h_ps_snap);
-  if (e->ps_ev) (void)hipEventDestroy(e->ps_ev);
+  e->ps_red.destroy();
   e->ps = MgxPolicyStats{};
-  e->d_ps_rec = nullptr; e->d_ps_partial = nullptr; e->d_ps_totals = nullptr; e->d_ps_snap = nullptr; e->d_ps_ticket = nullptr;
-  e->d_ps_log = nullptr; e->d_ps_log_state = nullptr; e->d_ps_rows = nullptr; e->d_ps_list = nullptr; e->h_ps_snap = nullptr; e->ps_ev = nullptr;
-  e->ps_on = false; e->ps_pending = false; e->ps_log_cap = 0;
+  e->d_ps_rows = nullptr; e->d_ps_list = nullptr;
+  e->ps_on = false;
 }
 #define MGX_SMP_RING 4
 static void free_pool_sampling(mgx_engine* e) {
@@ -685,25 +765,15 @@ static void free_pool_sampling(mgx_engine* e) {
   e->smp_on = false; e->smp_slot = 0;
 }
 static void free_map_stats(mgx_engine* e) {
-  if (e->d_ms_table) (void)hipFree(e->d_ms_table);
-  if (e->d_ms_snap) (void)hipFree(e->d_ms_snap);
-  if (e->h_ms_snap) (void)hipHostFree(e->h_ms_snap);
-  if (e->ms_ev) (void)hipEventDestroy(e->ms_ev);
-  e->d_ms_table = nullptr; e->d_ms_snap = nullptr; e->h_ms_snap = nullptr; e->ms_ev = nullptr;
-  e->ms_on = false; e->ms_pending = false;
+  e->ms_snap.destroy();
+  e->ms_on = false;
 }
 static void free_episode_stats(mgx_engine* e) {
   free_time_averages(e);   // (the time averages are finished on the episode statistics' done list)
   free_policy_stats(e);    // (... and so are the per-policy records)
   free_map_stats(e);       // (... and the per-map table reads the episode records)
-  for (void* p : {(void*)e->d_ep_rec, (void*)e->d_ep_partial, (void*)e->d_ep_totals, (void*)e->d_ep_snap, (void*)e->d_ep_ticket,
-                  (void*)e->d_ep_log, (void*)e->d_ep_log_state})
-    if (p) (void)hipFree(p);
-  if (e->h_ep_snap) (void)hipHostFree(e->h_ep_snap);
-  if (e->ep_ev) (void)hipEventDestroy(e->ep_ev);
-  e->d_ep_rec = nullptr; e->d_ep_partial = nullptr; e->d_ep_totals = nullptr; e->d_ep_snap = nullptr; e->d_ep_ticket = nullptr;
-  e->d_ep_log = nullptr; e->d_ep_log_state = nullptr; e->h_ep_snap = nullptr; e->ep_ev = nullptr;
-  e->ep_stats = false; e->ep_pending = false; e->ep_log_cap = 0;
+  e->ep_red.destroy();
+  e->ep_stats = false;
 }
 static void free_replay(mgx_engine* e) {
   for (const void* p : {(const void*)e->rpl.envs, (const void*)e->rpl.log, (const void*)e->rpl.cursor, (const void*)e->rpl.state,
@@ -750,6 +820,13 @@ static int flush_shadow(mgx_engine* e, const int32_t* list, const uint32_t* list
   HIP_TRY(hipGetLastError());
   return MGX_OK;
 }
+// A reducer's f64 totals -> its snapshot buffer, the totals cleared by the reducer's column rule (csrc/mgx_totals.h).
+template <class Kind>
+static int launch_totals_snapshot(mgx_engine* e, MgxSnapshot& s, const Kind kind) {
+  hipLaunchKernelGGL(mgx_totals_snapshot_kernel<Kind>, dim3(1), dim3(256), 0, e->stream, kind, (double*)s.d_totals, (double*)s.d_snap, (int)(s.bytes / 8));
+  HIP_TRY(hipGetLastError());
+  return MGX_OK;
+}
 // Episode-end statistics of the envs in the done list (csrc/mgx_episode.h): records, then batch totals (+ log).
 static int launch_episode_stats(mgx_engine* e) {
   const MgxDev& d = e->d;
@@ -760,14 +837,14 @@ static int launch_episode_stats(mgx_engine* e) {
     if (frc) return frc;
   }
   hipLaunchKernelGGL(mgx_episode_record_kernel, dim3((list_grid(e, dl, 128, 2048) + 3) / 4), dim3(256), 0, e->stream, dev_copy(e), e->ep,
-                     (const int32_t*)e->d_done_list, (const uint32_t*)e->d_done_n, e->d_ep_rec, e->d_ep_log, (const uint32_t*)e->d_ep_log_state,
-                     e->ep_log_cap, (const uint32_t*)e->d_early, (const uint32_t*)e->d_episodes, (const int32_t*)(e->n_pool > 0 ? e->d_map_index : nullptr),
+                     (const int32_t*)e->d_done_list, (const uint32_t*)e->d_done_n, e->ep_red.rec, e->ep_red.log.d_log, (const uint32_t*)e->ep_red.log.d_state,
+                     e->ep_red.log.cap, (const uint32_t*)e->d_early, (const uint32_t*)e->d_episodes, (const int32_t*)(e->n_pool > 0 ? e->d_map_index : nullptr),
                      (const uint32_t*)e->dseeds);
   HIP_TRY(hipGetLastError());
   const int nchunks_max = (d.E + MGX_EP_CHUNK - 1) / MGX_EP_CHUNK;
   hipLaunchKernelGGL(mgx_episode_accum_kernel, dim3((unsigned)std::min(nchunks_max, 16)), dim3(256), 0, e->stream, e->ep,
-                     (const uint32_t*)e->d_done_n, (const uint32_t*)e->d_ep_rec, e->d_ep_partial, e->d_ep_totals, e->d_ep_ticket,
-                     e->d_ep_log_state, e->ep_log_cap, e->d_ep_log ? 1 : 0);
+                     (const uint32_t*)e->d_done_n, (const uint32_t*)e->ep_red.rec, e->ep_red.partial, e->ep_red.totals(), e->ep_red.ticket,
+                     e->ep_red.log.d_state, e->ep_red.log.cap, e->ep_red.log.d_log ? 1 : 0);
   HIP_TRY(hipGetLastError());
   return MGX_OK;
 }
@@ -785,13 +862,13 @@ static int launch_time_avg_finish(mgx_engine* e) {
   MgxList dl;
   dl.n_host = -1;
   hipLaunchKernelGGL(mgx_time_avg_finish_kernel, dim3((list_grid(e, dl, 128, 2048) + 3) / 4), dim3(256), 0, e->stream, dev_copy(e), e->ta,
-                     (const int32_t*)e->d_done_list, (const uint32_t*)e->d_done_n, e->d_ta_rec, e->d_ta_log, (const uint32_t*)e->d_ta_log_state,
-                     e->ta_log_cap, (const uint32_t*)e->d_episodes);
+                     (const int32_t*)e->d_done_list, (const uint32_t*)e->d_done_n, e->ta_red.rec, e->ta_red.log.d_log, (const uint32_t*)e->ta_red.log.d_state,
+                     e->ta_red.log.cap, (const uint32_t*)e->d_episodes);
   HIP_TRY(hipGetLastError());
   const int nchunks_max = (e->d.E + MGX_EP_CHUNK - 1) / MGX_EP_CHUNK;
   hipLaunchKernelGGL(mgx_time_avg_total_kernel, dim3((unsigned)std::min(nchunks_max, 16)), dim3(256), 0, e->stream, e->ta.L,
-                     (const uint32_t*)e->d_done_n, (const uint32_t*)e->d_ta_rec, e->d_ta_partial, e->d_ta_totals, e->d_ta_ticket,
-                     e->d_ta_log_state, e->ta_log_cap, e->d_ta_log ? 1 : 0);
+                     (const uint32_t*)e->d_done_n, (const uint32_t*)e->ta_red.rec, e->ta_red.partial, e->ta_red.totals(), e->ta_red.ticket,
+                     e->ta_red.log.d_state, e->ta_red.log.cap, e->ta_red.log.d_log ? 1 : 0);
   HIP_TRY(hipGetLastError());
   return MGX_OK;
 }
@@ -836,14 +913,14 @@ static int launch_policy_stats(mgx_engine* e) {
   auto kernel = P <= 2 ? mgx_policy_record_kernel<2> : P <= 4 ? mgx_policy_record_kernel<4> : P <= 8 ? mgx_policy_record_kernel<8>
                                                                                                     : mgx_policy_record_kernel<MGX_PS_MAX_POLICIES>;
   hipLaunchKernelGGL(kernel, dim3((list_grid(e, dl, 128, 2048) + 3) / 4), dim3(256), 0, e->stream, dev_copy(e), e->ps,
-                     (const int32_t*)e->d_done_list, (const uint32_t*)e->d_done_n, e->d_ps_rec, e->d_ps_log, (const uint32_t*)e->d_ps_log_state,
-                     e->ps_log_cap, (const uint32_t*)e->d_early, (const uint32_t*)e->d_episodes);
+                     (const int32_t*)e->d_done_list, (const uint32_t*)e->d_done_n, e->ps_red.rec, e->ps_red.log.d_log, (const uint32_t*)e->ps_red.log.d_state,
+                     e->ps_red.log.cap, (const uint32_t*)e->d_early, (const uint32_t*)e->d_episodes);
   HIP_TRY(hipGetLastError());
   const int nchunks_max = (e->d.E + MGX_EP_CHUNK - 1) / MGX_EP_CHUNK;
   const unsigned groups = (unsigned)((P * e->ps.L.NS + P + 255) / 256);   // work items: the (policy, column) sums, then the policy headers
   hipLaunchKernelGGL(mgx_policy_total_kernel, dim3((unsigned)std::min(nchunks_max, 16), groups), dim3(256), 0, e->stream, e->ps.L,
-                     (const uint32_t*)e->d_done_n, (const uint32_t*)e->d_ps_rec, e->d_ps_partial, e->d_ps_totals, e->d_ps_ticket,
-                     e->d_ps_log_state, e->ps_log_cap, e->d_ps_log ? 1 : 0);
+                     (const uint32_t*)e->d_done_n, (const uint32_t*)e->ps_red.rec, e->ps_red.partial, e->ps_red.totals(), e->ps_red.ticket,
+                     e->ps_red.log.d_state, e->ps_red.log.cap, e->ps_red.log.d_log ? 1 : 0);
   HIP_TRY(hipGetLastError());
   return MGX_OK;
 }
@@ -853,7 +930,15 @@ static int launch_map_stats(mgx_engine* e) {
   MgxList dl;
   dl.n_host = -1;
   hipLaunchKernelGGL(mgx_map_stats_kernel, dim3((list_grid(e, dl, 128, 2048) + 255) / 256), dim3(256), 0, e->stream, (const uint32_t*)e->d_done_n,
-                     (const uint32_t*)e->d_ep_rec, e->ep.rec_words, e->d.A, e->n_pool, e->d_ms_table);
+                     (const uint32_t*)e->ep_red.rec, e->ep.rec_words, e->d.A, e->n_pool, (unsigned long long*)e->ms_snap.d_totals);
+  HIP_TRY(hipGetLastError());
+  return MGX_OK;
+}
+// The per-map table -> its snapshot buffer, the table cleared.
+static int launch_map_stats_snapshot(mgx_engine* e) {
+  MgxSnapshot& s = e->ms_snap;
+  hipLaunchKernelGGL(mgx_map_stats_snapshot_kernel, dim3(1), dim3(256), 0, e->stream, (unsigned long long*)s.d_totals, (unsigned long long*)s.d_snap,
+                     (int)(s.bytes / 8));
   HIP_TRY(hipGetLastError());
   return MGX_OK;
 }
@@ -1863,26 +1948,11 @@ int mgx_set_episode_stats(mgx_engine* e, int32_t enabled, int32_t log_capacity, 
   if (log_capacity < 0) return fail(MGX_ERR_BAD_ARG, "mgx_set_episode_stats: negative log capacity");
   const MgxDev& d = e->d;
   e->ep = mgx_ep_layout(d.NG, d.NS, d.A, d.NSP, log_per_agent ? 1 : 0);
-  const size_t TW = (size_t)e->ep_tw(), nch = ((size_t)d.E + MGX_EP_CHUNK - 1) / MGX_EP_CHUNK;
-  HIP_TRY(hipMalloc((void**)&e->d_ep_rec, (size_t)d.E * e->ep.rec_words * 4));
-  HIP_TRY(hipMalloc((void**)&e->d_ep_partial, nch * TW * 8));
-  HIP_TRY(hipMalloc((void**)&e->d_ep_totals, TW * 8));
-  HIP_TRY(hipMalloc((void**)&e->d_ep_snap, TW * 8));
-  HIP_TRY(hipMalloc((void**)&e->d_ep_ticket, 4));
-  HIP_TRY(hipMalloc((void**)&e->d_ep_log_state, 8));
-  HIP_TRY(hipHostMalloc((void**)&e->h_ep_snap, TW * 8, hipHostMallocDefault));
-  HIP_TRY(hipEventCreateWithFlags(&e->ep_ev, hipEventDisableTiming));
-  HIP_TRY(hipMemsetAsync(e->d_ep_ticket, 0, 4, e->stream));
-  HIP_TRY(hipMemsetAsync(e->d_ep_log_state, 0, 8, e->stream));
-  if (log_capacity > 0) {
-    HIP_TRY(hipMalloc((void**)&e->d_ep_log, (size_t)log_capacity * e->ep.log_words * 4));
-    e->ep_log_cap = log_capacity;
-  }
+  { int rc = e->ep_red.create(e->stream, (size_t)d.E, e->ep.rec_words, e->ep_tw(), log_capacity, e->ep.log_words); if (rc) return rc; }
   if (!e->d_done_list) { int rc = e->alloc(&e->d_done_list, (size_t)d.E); if (rc) return rc; }
   if (!e->d_done_n) { int rc = e->alloc(&e->d_done_n, 4); if (rc) return rc; }
   // totals start as a cleared snapshot would leave them
-  hipLaunchKernelGGL(mgx_episode_snapshot_kernel, dim3(1), dim3(256), 0, e->stream, e->d_ep_totals, e->d_ep_snap, (int)TW);
-  HIP_TRY(hipGetLastError());
+  { int rc = launch_totals_snapshot(e, e->ep_red.snap, MgxEpKind{}); if (rc) return rc; }
   HIP_TRY(hipStreamSynchronize(e->stream));
   e->ep_stats = true;
   return MGX_OK;
@@ -1894,7 +1964,7 @@ int mgx_episode_stats_layout(mgx_engine* e, int32_t* out) {
   if (!e->ep_stats) return fail(MGX_ERR_BAD_ARG, "mgx_episode_stats_layout: episode statistics are off (mgx_set_episode_stats)");
   const MgxEpLayout& L = e->ep;
   const int32_t v[MGX_EPL_COUNT] = {L.NG, L.NS, L.A, e->ep_tw(), L.rec_words, L.log_words, L.off_game, L.off_gbits, L.off_agent, L.off_abits,
-                                    L.off_rew, L.off_pa, L.off_pabits, L.off_invk, L.off_invn, L.per_agent, e->ep_log_cap};
+                                    L.off_rew, L.off_pa, L.off_pabits, L.off_invk, L.off_invn, L.per_agent, e->ep_red.log.cap};
   memcpy(out, v, sizeof(v));
   return MGX_OK;
 }
@@ -1924,52 +1994,25 @@ int mgx_record_episodes(mgx_engine* e, const uint8_t* env_mask) {
 int mgx_request_episode_stats(mgx_engine* e) {
   if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_request_episode_stats: null engine");
   if (!e->ep_stats) return fail(MGX_ERR_BAD_ARG, "mgx_request_episode_stats: episode statistics are off (mgx_set_episode_stats)");
-  if (e->ep_pending) return MGX_OK;   // the snapshot already under way is fetched first; the totals keep accumulating
-#ifndef MGX_CPU_EMU
-  HIP_TRY(hipSetDevice(e->device));
-  const int TW = e->ep_tw();
-  hipLaunchKernelGGL(mgx_episode_snapshot_kernel, dim3(1), dim3(256), 0, e->stream, e->d_ep_totals, e->d_ep_snap, TW);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(e->h_ep_snap, e->d_ep_snap, (size_t)TW * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipEventRecord(e->ep_ev, e->stream));
-  e->ep_pending = true;
-#endif
+#ifdef MGX_CPU_EMU
   return MGX_OK;
+#else
+  return e->ep_red.snap.request(e->device, e->stream, [e] { return launch_totals_snapshot(e, e->ep_red.snap, MgxEpKind{}); });
+#endif
 }
 
 int mgx_fetch_episode_stats(mgx_engine* e, int32_t wait, double* totals, int32_t* ready) {
   if (!e || !totals || !ready) return fail(MGX_ERR_BAD_ARG, "mgx_fetch_episode_stats: null argument");
   *ready = 0;
   if (!e->ep_stats) return fail(MGX_ERR_BAD_ARG, "mgx_fetch_episode_stats: episode statistics are off (mgx_set_episode_stats)");
-  if (!e->ep_pending) return MGX_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  if (wait) {
-    HIP_TRY(hipEventSynchronize(e->ep_ev));
-  } else {
-    const hipError_t q = hipEventQuery(e->ep_ev);
-    if (q == hipErrorNotReady) return MGX_OK;
-    if (q != hipSuccess) return fail(MGX_ERR_HIP, std::string("hipEventQuery: ") + hipGetErrorString(q));
-  }
-  memcpy(totals, e->h_ep_snap, (size_t)e->ep_tw() * 8);
-  e->ep_pending = false;
-  *ready = 1;
-  return MGX_OK;
+  return e->ep_red.snap.fetch(e->device, wait, totals, ready);
 }
 
 int mgx_drain_episode_log(mgx_engine* e, uint32_t* records, int32_t max_records, int32_t* n_records, int32_t* n_dropped) {
   if (!e || !records || !n_records) return fail(MGX_ERR_BAD_ARG, "mgx_drain_episode_log: null argument");
-  if (!e->ep_stats || !e->d_ep_log) return fail(MGX_ERR_BAD_ARG, "mgx_drain_episode_log: no episode log (mgx_set_episode_stats)");
-  if (max_records < e->ep_log_cap) return fail(MGX_ERR_BAD_ARG, "mgx_drain_episode_log: the buffer must hold the whole log (log_capacity records)");
-  HIP_TRY(hipSetDevice(e->device));
-  uint32_t st[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(st, e->d_ep_log_state, 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (st[0]) HIP_TRY(hipMemcpyAsync(records, e->d_ep_log, (size_t)st[0] * e->ep.log_words * 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemsetAsync(e->d_ep_log_state, 0, 8, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  *n_records = (int32_t)st[0];
-  if (n_dropped) *n_dropped = (int32_t)st[1];
-  return MGX_OK;
+  if (!e->ep_stats || !e->ep_red.log.d_log) return fail(MGX_ERR_BAD_ARG, "mgx_drain_episode_log: no episode log (mgx_set_episode_stats)");
+  if (max_records < e->ep_red.log.cap) return fail(MGX_ERR_BAD_ARG, "mgx_drain_episode_log: the buffer must hold the whole log (log_capacity records)");
+  return e->ep_red.log.drain(e->device, e->stream, records, n_records, n_dropped);
 }
 
 // ---- time-averaged game stats (csrc/mgx_time_avg.h) -----------------------------------------------------------------------
@@ -1985,7 +2028,7 @@ int mgx_time_average_layout_of(int32_t num_game_stats, int32_t log_capacity, int
 int mgx_time_average_layout(mgx_engine* e, int32_t* out) {
   if (!e || !out) return fail(MGX_ERR_BAD_ARG, "mgx_time_average_layout: null argument");
   if (!e->ta_on) return fail(MGX_ERR_BAD_ARG, "mgx_time_average_layout: time averages are off (mgx_set_time_averages)");
-  ta_layout_words(e->ta.L, e->ta_log_cap, out);
+  ta_layout_words(e->ta.L, e->ta_red.log.cap, out);
   return MGX_OK;
 }
 
@@ -2005,30 +2048,18 @@ int mgx_set_time_averages(mgx_engine* e, int32_t enabled, int32_t log_capacity) 
   const MgxDev& d = e->d;
   e->ta.L = mgx_ta_layout(d.NG);
   const MgxTaLayout& L = e->ta.L;
-  const size_t E = (size_t)d.E, TW = (size_t)L.tot_words, nch = (E + MGX_EP_CHUNK - 1) / MGX_EP_CHUNK;
+  const size_t E = (size_t)d.E;
   const size_t sum_bytes = std::max<size_t>(8, E * L.NG * 8), seen_bytes = std::max<size_t>(4, E * L.NGW * 4);
   HIP_TRY(hipMalloc((void**)&e->ta.sum, sum_bytes));
   HIP_TRY(hipMalloc((void**)&e->ta.seen, seen_bytes));
   HIP_TRY(hipMalloc((void**)&e->ta.steps, E * 4));
-  HIP_TRY(hipMalloc((void**)&e->d_ta_rec, E * L.rec_words * 4));
-  HIP_TRY(hipMalloc((void**)&e->d_ta_partial, nch * TW * 8));
-  HIP_TRY(hipMalloc((void**)&e->d_ta_totals, TW * 8));
-  HIP_TRY(hipMalloc((void**)&e->d_ta_snap, TW * 8));
-  HIP_TRY(hipMalloc((void**)&e->d_ta_ticket, 4));
-  HIP_TRY(hipMalloc((void**)&e->d_ta_log_state, 8));
-  HIP_TRY(hipHostMalloc((void**)&e->h_ta_snap, TW * 8, hipHostMallocDefault));
-  HIP_TRY(hipEventCreateWithFlags(&e->ta_ev, hipEventDisableTiming));
+  { int rc = e->ta_red.create(e->stream, E, L.rec_words, L.tot_words, log_capacity, L.rec_words); if (rc) return rc; }
   // an episode's accumulators are zero when it starts; an env inside an episode now finishes it as a partial one
   HIP_TRY(hipMemsetAsync(e->ta.sum, 0, sum_bytes, e->stream));
   HIP_TRY(hipMemsetAsync(e->ta.seen, 0, seen_bytes, e->stream));
   HIP_TRY(hipMemsetAsync(e->ta.steps, 0, E * 4, e->stream));
-  HIP_TRY(hipMemsetAsync(e->d_ta_totals, 0, TW * 8, e->stream));
-  HIP_TRY(hipMemsetAsync(e->d_ta_ticket, 0, 4, e->stream));
-  HIP_TRY(hipMemsetAsync(e->d_ta_log_state, 0, 8, e->stream));
-  if (log_capacity > 0) {
-    HIP_TRY(hipMalloc((void**)&e->d_ta_log, (size_t)log_capacity * L.rec_words * 4));
-    e->ta_log_cap = log_capacity;
-  }
+  // totals start as a cleared snapshot would leave them
+  { int rc = launch_totals_snapshot(e, e->ta_red.snap, MgxTaKind{}); if (rc) return rc; }
   HIP_TRY(hipStreamSynchronize(e->stream));
   e->ta_on = true;
   return MGX_OK;
@@ -2038,52 +2069,25 @@ int mgx_set_time_averages(mgx_engine* e, int32_t enabled, int32_t log_capacity) 
 int mgx_request_time_averages(mgx_engine* e) {
   if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_request_time_averages: null engine");
   if (!e->ta_on) return fail(MGX_ERR_BAD_ARG, "mgx_request_time_averages: time averages are off (mgx_set_time_averages)");
-  if (e->ta_pending) return MGX_OK;   // the snapshot already under way is fetched first; the totals keep accumulating
-#ifndef MGX_CPU_EMU
-  HIP_TRY(hipSetDevice(e->device));
-  const int TW = e->ta.L.tot_words;
-  hipLaunchKernelGGL(mgx_time_avg_snapshot_kernel, dim3(1), dim3(256), 0, e->stream, e->d_ta_totals, e->d_ta_snap, TW);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(e->h_ta_snap, e->d_ta_snap, (size_t)TW * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipEventRecord(e->ta_ev, e->stream));
-  e->ta_pending = true;
-#endif
+#ifdef MGX_CPU_EMU
   return MGX_OK;
+#else
+  return e->ta_red.snap.request(e->device, e->stream, [e] { return launch_totals_snapshot(e, e->ta_red.snap, MgxTaKind{}); });
+#endif
 }
 
 int mgx_fetch_time_averages(mgx_engine* e, int32_t wait, double* totals, int32_t* ready) {
   if (!e || !totals || !ready) return fail(MGX_ERR_BAD_ARG, "mgx_fetch_time_averages: null argument");
   *ready = 0;
   if (!e->ta_on) return fail(MGX_ERR_BAD_ARG, "mgx_fetch_time_averages: time averages are off (mgx_set_time_averages)");
-  if (!e->ta_pending) return MGX_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  if (wait) {
-    HIP_TRY(hipEventSynchronize(e->ta_ev));
-  } else {
-    const hipError_t q = hipEventQuery(e->ta_ev);
-    if (q == hipErrorNotReady) return MGX_OK;
-    if (q != hipSuccess) return fail(MGX_ERR_HIP, std::string("hipEventQuery: ") + hipGetErrorString(q));
-  }
-  memcpy(totals, e->h_ta_snap, (size_t)e->ta.L.tot_words * 8);
-  e->ta_pending = false;
-  *ready = 1;
-  return MGX_OK;
+  return e->ta_red.snap.fetch(e->device, wait, totals, ready);
 }
 
 int mgx_drain_time_average_log(mgx_engine* e, uint32_t* records, int32_t max_records, int32_t* n_records, int32_t* n_dropped) {
   if (!e || !records || !n_records) return fail(MGX_ERR_BAD_ARG, "mgx_drain_time_average_log: null argument");
-  if (!e->ta_on || !e->d_ta_log) return fail(MGX_ERR_BAD_ARG, "mgx_drain_time_average_log: no log (mgx_set_time_averages)");
-  if (max_records < e->ta_log_cap) return fail(MGX_ERR_BAD_ARG, "mgx_drain_time_average_log: the buffer must hold the whole log (log_capacity records)");
-  HIP_TRY(hipSetDevice(e->device));
-  uint32_t st[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(st, e->d_ta_log_state, 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (st[0]) HIP_TRY(hipMemcpyAsync(records, e->d_ta_log, (size_t)st[0] * e->ta.L.rec_words * 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemsetAsync(e->d_ta_log_state, 0, 8, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  *n_records = (int32_t)st[0];
-  if (n_dropped) *n_dropped = (int32_t)st[1];
-  return MGX_OK;
+  if (!e->ta_on || !e->ta_red.log.d_log) return fail(MGX_ERR_BAD_ARG, "mgx_drain_time_average_log: no log (mgx_set_time_averages)");
+  if (max_records < e->ta_red.log.cap) return fail(MGX_ERR_BAD_ARG, "mgx_drain_time_average_log: the buffer must hold the whole log (log_capacity records)");
+  return e->ta_red.log.drain(e->device, e->stream, records, n_records, n_dropped);
 }
 
 // ---- per-policy episode statistics (csrc/mgx_policy_stats.h) ----------------------------------------------------------------
@@ -2115,7 +2119,7 @@ int mgx_policy_stats_layout_of(int32_t num_agent_stats, int32_t num_agents, int3
 int mgx_policy_stats_layout(mgx_engine* e, int32_t* out) {
   if (!e || !out) return fail(MGX_ERR_BAD_ARG, "mgx_policy_stats_layout: null argument");
   if (!e->ps_on) return fail(MGX_ERR_BAD_ARG, "mgx_policy_stats_layout: policy statistics are off (mgx_set_policy_stats)");
-  ps_layout_words(e->ps.L, e->ps_log_cap, out);
+  ps_layout_words(e->ps.L, e->ps_red.log.cap, out);
   return MGX_OK;
 }
 
@@ -2140,28 +2144,14 @@ int mgx_set_policy_stats(mgx_engine* e, int32_t enabled, int32_t num_policies, c
   const MgxDev& d = e->d;
   e->ps.L = mgx_ps_layout(d.NS, d.A, d.NSP, num_policies);
   const MgxPsLayout& L = e->ps.L;
-  const size_t E = (size_t)d.E, TW = (size_t)L.tot_words, nch = (E + MGX_EP_CHUNK - 1) / MGX_EP_CHUNK, table = E * d.A;
+  const size_t E = (size_t)d.E, table = E * d.A;
   HIP_TRY(hipMalloc((void**)&e->ps.assign, table));
   HIP_TRY(hipMalloc((void**)&e->d_ps_rows, table));
   HIP_TRY(hipMalloc((void**)&e->d_ps_list, E * 4));
-  HIP_TRY(hipMalloc((void**)&e->d_ps_rec, E * L.rec_words * 4));
-  HIP_TRY(hipMalloc((void**)&e->d_ps_partial, nch * TW * 8));
-  HIP_TRY(hipMalloc((void**)&e->d_ps_totals, TW * 8));
-  HIP_TRY(hipMalloc((void**)&e->d_ps_snap, TW * 8));
-  HIP_TRY(hipMalloc((void**)&e->d_ps_ticket, 4));
-  HIP_TRY(hipMalloc((void**)&e->d_ps_log_state, 8));
-  HIP_TRY(hipHostMalloc((void**)&e->h_ps_snap, TW * 8, hipHostMallocDefault));
-  HIP_TRY(hipEventCreateWithFlags(&e->ps_ev, hipEventDisableTiming));
+  { int rc = e->ps_red.create(e->stream, E, L.rec_words, L.tot_words, log_capacity, L.rec_words); if (rc) return rc; }
   HIP_TRY(hipMemcpyAsync(e->ps.assign, assignments, table, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemsetAsync(e->d_ps_ticket, 0, 4, e->stream));
-  HIP_TRY(hipMemsetAsync(e->d_ps_log_state, 0, 8, e->stream));
-  if (log_capacity > 0) {
-    HIP_TRY(hipMalloc((void**)&e->d_ps_log, (size_t)log_capacity * L.rec_words * 4));
-    e->ps_log_cap = log_capacity;
-  }
   // totals start as a cleared snapshot would leave them
-  hipLaunchKernelGGL(mgx_policy_snapshot_kernel, dim3(1), dim3(256), 0, e->stream, e->d_ps_totals, e->d_ps_snap, L);
-  HIP_TRY(hipGetLastError());
+  { int rc = launch_totals_snapshot(e, e->ps_red.snap, MgxPsKind{L.tot_off_sum}); if (rc) return rc; }
   HIP_TRY(hipStreamSynchronize(e->stream));   // (`assignments` is the caller's)
   e->ps_on = true;
   return MGX_OK;
@@ -2195,52 +2185,26 @@ int mgx_set_policy_assignments(mgx_engine* e, const int32_t* envs, int32_t n, co
 int mgx_request_policy_stats(mgx_engine* e) {
   if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_request_policy_stats: null engine");
   if (!e->ps_on) return fail(MGX_ERR_BAD_ARG, "mgx_request_policy_stats: policy statistics are off (mgx_set_policy_stats)");
-  if (e->ps_pending) return MGX_OK;   // the snapshot already under way is fetched first; the totals keep accumulating
-#ifndef MGX_CPU_EMU
-  HIP_TRY(hipSetDevice(e->device));
-  const int TW = e->ps.L.tot_words;
-  hipLaunchKernelGGL(mgx_policy_snapshot_kernel, dim3(1), dim3(256), 0, e->stream, e->d_ps_totals, e->d_ps_snap, e->ps.L);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(e->h_ps_snap, e->d_ps_snap, (size_t)TW * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipEventRecord(e->ps_ev, e->stream));
-  e->ps_pending = true;
-#endif
+#ifdef MGX_CPU_EMU
   return MGX_OK;
+#else
+  return e->ps_red.snap.request(e->device, e->stream,
+                                [e] { return launch_totals_snapshot(e, e->ps_red.snap, MgxPsKind{e->ps.L.tot_off_sum}); });
+#endif
 }
 
 int mgx_fetch_policy_stats(mgx_engine* e, int32_t wait, double* totals, int32_t* ready) {
   if (!e || !totals || !ready) return fail(MGX_ERR_BAD_ARG, "mgx_fetch_policy_stats: null argument");
   *ready = 0;
   if (!e->ps_on) return fail(MGX_ERR_BAD_ARG, "mgx_fetch_policy_stats: policy statistics are off (mgx_set_policy_stats)");
-  if (!e->ps_pending) return MGX_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  if (wait) {
-    HIP_TRY(hipEventSynchronize(e->ps_ev));
-  } else {
-    const hipError_t q = hipEventQuery(e->ps_ev);
-    if (q == hipErrorNotReady) return MGX_OK;
-    if (q != hipSuccess) return fail(MGX_ERR_HIP, std::string("hipEventQuery: ") + hipGetErrorString(q));
-  }
-  memcpy(totals, e->h_ps_snap, (size_t)e->ps.L.tot_words * 8);
-  e->ps_pending = false;
-  *ready = 1;
-  return MGX_OK;
+  return e->ps_red.snap.fetch(e->device, wait, totals, ready);
 }
 
 int mgx_drain_policy_log(mgx_engine* e, uint32_t* records, int32_t max_records, int32_t* n_records, int32_t* n_dropped) {
   if (!e || !records || !n_records) return fail(MGX_ERR_BAD_ARG, "mgx_drain_policy_log: null argument");
-  if (!e->ps_on || !e->d_ps_log) return fail(MGX_ERR_BAD_ARG, "mgx_drain_policy_log: no log (mgx_set_policy_stats)");
-  if (max_records < e->ps_log_cap) return fail(MGX_ERR_BAD_ARG, "mgx_drain_policy_log: the buffer must hold the whole log (log_capacity records)");
-  HIP_TRY(hipSetDevice(e->device));
-  uint32_t st[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(st, e->d_ps_log_state, 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (st[0]) HIP_TRY(hipMemcpyAsync(records, e->d_ps_log, (size_t)st[0] * e->ps.L.rec_words * 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemsetAsync(e->d_ps_log_state, 0, 8, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  *n_records = (int32_t)st[0];
-  if (n_dropped) *n_dropped = (int32_t)st[1];
-  return MGX_OK;
+  if (!e->ps_on || !e->ps_red.log.d_log) return fail(MGX_ERR_BAD_ARG, "mgx_drain_policy_log: no log (mgx_set_policy_stats)");
+  if (max_records < e->ps_red.log.cap) return fail(MGX_ERR_BAD_ARG, "mgx_drain_policy_log: the buffer must hold the whole log (log_capacity records)");
+  return e->ps_red.log.drain(e->device, e->stream, records, n_records, n_dropped);
 }
 
 #ifndef MGX_CPU_EMU
@@ -2340,14 +2304,9 @@ int mgx_set_map_stats(mgx_engine* e, int32_t enabled) {
   HIP_TRY(hipStreamSynchronize(e->stream));
   free_map_stats(e);
   if (!enabled) return MGX_OK;
-  const size_t words = ((size_t)e->n_pool + 1) * MGX_MS_COLS;
-  HIP_TRY(hipMalloc((void**)&e->d_ms_table, words * 8));
-  HIP_TRY(hipMalloc((void**)&e->d_ms_snap, words * 8));
-  HIP_TRY(hipHostMalloc((void**)&e->h_ms_snap, words * 8, hipHostMallocDefault));
-  HIP_TRY(hipEventCreateWithFlags(&e->ms_ev, hipEventDisableTiming));
+  { int rc = e->ms_snap.create(((size_t)e->n_pool + 1) * MGX_MS_COLS * 8); if (rc) return rc; }
   // the table starts as a cleared snapshot would leave it
-  hipLaunchKernelGGL(mgx_map_stats_snapshot_kernel, dim3(1), dim3(256), 0, e->stream, e->d_ms_table, e->d_ms_snap, (int)words);
-  HIP_TRY(hipGetLastError());
+  { int rc = launch_map_stats_snapshot(e); if (rc) return rc; }
   HIP_TRY(hipStreamSynchronize(e->stream));
   e->ms_on = true;
   return MGX_OK;
@@ -2356,34 +2315,14 @@ int mgx_set_map_stats(mgx_engine* e, int32_t enabled) {
 int mgx_request_map_stats(mgx_engine* e) {
   if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_request_map_stats: null engine");
   if (!e->ms_on) return fail(MGX_ERR_BAD_ARG, "mgx_request_map_stats: map statistics are off (mgx_set_map_stats)");
-  if (e->ms_pending) return MGX_OK;   // the snapshot already under way is fetched first; the table keeps accumulating
-  HIP_TRY(hipSetDevice(e->device));
-  const int words = (e->n_pool + 1) * MGX_MS_COLS;
-  hipLaunchKernelGGL(mgx_map_stats_snapshot_kernel, dim3(1), dim3(256), 0, e->stream, e->d_ms_table, e->d_ms_snap, words);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(e->h_ms_snap, e->d_ms_snap, (size_t)words * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipEventRecord(e->ms_ev, e->stream));
-  e->ms_pending = true;
-  return MGX_OK;
+  return e->ms_snap.request(e->device, e->stream, [e] { return launch_map_stats_snapshot(e); });
 }
 
 int mgx_fetch_map_stats(mgx_engine* e, int32_t wait, uint64_t* table, int32_t* ready) {
   if (!e || !table || !ready) return fail(MGX_ERR_BAD_ARG, "mgx_fetch_map_stats: null argument");
   *ready = 0;
   if (!e->ms_on) return fail(MGX_ERR_BAD_ARG, "mgx_fetch_map_stats: map statistics are off (mgx_set_map_stats)");
-  if (!e->ms_pending) return MGX_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  if (wait) {
-    HIP_TRY(hipEventSynchronize(e->ms_ev));
-  } else {
-    const hipError_t q = hipEventQuery(e->ms_ev);
-    if (q == hipErrorNotReady) return MGX_OK;
-    if (q != hipSuccess) return fail(MGX_ERR_HIP, std::string("hipEventQuery: ") + hipGetErrorString(q));
-  }
-  memcpy(table, e->h_ms_snap, ((size_t)e->n_pool + 1) * MGX_MS_COLS * 8);
-  e->ms_pending = false;
-  *ready = 1;
-  return MGX_OK;
+  return e->ms_snap.fetch(e->device, wait, table, ready);
 }
 #endif  // MGX_CPU_EMU
 

@@ -17,12 +17,12 @@
 //                               over the chunk), chunk sums added to the totals in chunk order by the last workgroup.  Fixed
 //                               order => the totals are reproducible bit for bit (tests/test_gpu_episode_stats.py restates
 //                               the order on the host), and a step in which all 65 536 envs finish is still one parallel pass.
-//   mgx_episode_snapshot_kernel totals -> snapshot buffer, totals cleared (mgx_request_episode_stats): the host fetches the
-//                               snapshot asynchronously.
+// mgx_request_episode_stats takes the totals with mgx_totals_snapshot_kernel<MgxEpKind> (mgx_totals.h).
 #ifndef MGX_EPISODE_H_
 #define MGX_EPISODE_H_
 
 #include "mgx_device.h"
+#include "mgx_totals.h"
 
 #define MGX_EP_HDR 8        // record header words: env, episode, map index, seed, steps, flags, f64 return sum (2 words)
 #define MGX_EP_TOT_HDR 8    // totals header doubles (include/mgx.h MGX_EPT_*)
@@ -206,6 +206,9 @@ __device__ __forceinline__ double mgx_ep_f64(const uint32_t* w) {
 // totals / partial layout (doubles): [MGX_EP_TOT_HDR header][NG game sums][NG game key counts][NS agent sums][NS agent key counts]
 // header: 0 episodes, 1 sum of mean returns, 2 min, 3 max, 4 sum of lengths, 5 min, 6 max, 7 episodes that ended with every
 // agent terminal.
+struct MgxEpKind {
+  __device__ int operator()(int c) const { return (c == 2 || c == 5) ? MGX_TOT_MIN : (c == 3 || c == 6) ? MGX_TOT_MAX : MGX_TOT_SUM; }
+};
 __global__ void __launch_bounds__(256) mgx_episode_accum_kernel(const MgxEpLayout L, const uint32_t* __restrict__ list_n,
                                                                 const uint32_t* __restrict__ rec, double* __restrict__ partial,
                                                                 double* __restrict__ totals, uint32_t* __restrict__ ticket,
@@ -277,40 +280,7 @@ __global__ void __launch_bounds__(256) mgx_episode_accum_kernel(const MgxEpLayou
       P[0] = (double)(k1 - k0); P[1] = rs; P[2] = rmin; P[3] = rmax; P[4] = ls; P[5] = lmin; P[6] = lmax; P[7] = nterm;
     }
   }
-  __threadfence();
-  __syncthreads();
-  __shared__ uint32_t s_last;
-  if (threadIdx.x == 0) s_last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
-  for (int c = threadIdx.x; c < TW; c += blockDim.x) {   // totals += chunk sums, in chunk order
-    double t = totals[c];
-    const bool is_min = c == 2 || c == 5, is_max = c == 3 || c == 6;
-    for (int ch = 0; ch < nchunks; ch++) {
-      const double p = __longlong_as_double((long long)__hip_atomic_load((const unsigned long long*)(partial + (size_t)ch * TW + c),
-                                                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      t = is_min ? fmin(t, p) : is_max ? fmax(t, p) : t + p;
-    }
-    totals[c] = t;
-  }
-  if (threadIdx.x == 0) {
-    *ticket = 0;
-    if (has_log) {
-      const uint32_t have = log_state[0], room = (uint32_t)log_cap - have, take = (uint32_t)n < room ? (uint32_t)n : room;
-      log_state[0] = have + take;
-      log_state[1] += (uint32_t)n - take;
-    }
-  }
-}
-
-// totals -> snapshot, totals cleared (sums 0, minima +inf, maxima -inf).
-__global__ void __launch_bounds__(256) mgx_episode_snapshot_kernel(double* __restrict__ totals, double* __restrict__ snap, int TW) {
-  const double INF = __longlong_as_double(0x7FF0000000000000ll);
-  for (int c = threadIdx.x; c < TW; c += blockDim.x) {
-    snap[c] = totals[c];
-    totals[c] = (c == 2 || c == 5) ? INF : (c == 3 || c == 6) ? -INF : 0.0;
-  }
+  mgx_totals_fold(MgxEpKind{}, partial, totals, ticket, gridDim.x, nchunks, TW, log_state, log_cap, has_log, n);
 }
 #endif  // !MGX_CPU_EMU
 

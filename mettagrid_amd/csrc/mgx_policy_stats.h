@@ -22,7 +22,7 @@
 //   mgx_policy_total_kernel     records -> batch totals (f64) in the order of mgx_episode_accum_kernel: list order, chunks of
 //                               MGX_EP_CHUNK, chunk sums started at +0.0 and added in chunk order by the last workgroup.
 //                               One thread per (policy, column) and per policy header, spread over blockIdx.y.
-//   mgx_policy_snapshot_kernel  totals -> snapshot, totals cleared (sums 0, minima +inf, maxima -inf).
+//                               mgx_request_policy_stats takes the totals with mgx_totals_snapshot_kernel<MgxPsKind>.
 //   mgx_policy_assign_kernel    rows of the assignment table of a list of envs <- a packed block (mgx_set_policy_assignments).
 //
 // The assignment table (u8 [E][A]) is SLOT-owned: agent rows are routed to policies by row index, whichever episode or env
@@ -187,6 +187,13 @@ __global__ void __launch_bounds__(256) mgx_policy_record_kernel(const MgxDev* __
 // some agent of p held the key.  Work items: the P * NS columns, then the P policy headers, one thread each; blockIdx.x walks
 // the chunks, blockIdx.y the items in groups of blockDim.x, so that every item's serial pass over a chunk runs side by side
 // with the others' (the pass is a chain of load latencies: sixteen records' loads in flight at a time).
+struct MgxPsKind {   // field 3 of a policy header is a minimum, field 4 a maximum
+  int tot_off_sum;
+  __device__ int operator()(int c) const {
+    const int f = (c >= MGX_PS_TOT_HDR && c < tot_off_sum) ? (c - MGX_PS_TOT_HDR) % MGX_PS_TOT_POLICY : 0;
+    return f == 3 ? MGX_TOT_MIN : f == 4 ? MGX_TOT_MAX : MGX_TOT_SUM;
+  }
+};
 __global__ void __launch_bounds__(256) mgx_policy_total_kernel(const MgxPsLayout L, const uint32_t* __restrict__ list_n,
                                                                const uint32_t* __restrict__ rec, double* __restrict__ partial,
                                                                double* __restrict__ totals, uint32_t* __restrict__ ticket,
@@ -243,41 +250,7 @@ __global__ void __launch_bounds__(256) mgx_policy_total_kernel(const MgxPsLayout
       if (hp == 0) Pt[0] = (double)(k1 - k0);
     }
   }
-  __threadfence();
-  __syncthreads();
-  __shared__ uint32_t s_last;
-  if (threadIdx.x == 0) s_last = atomicAdd(ticket, 1u) == gridDim.x * gridDim.y - 1 ? 1u : 0u;
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
-  for (int c = threadIdx.x; c < TW; c += blockDim.x) {   // totals += chunk sums, in chunk order
-    double t = totals[c];
-    const int f = (c >= MGX_PS_TOT_HDR && c < L.tot_off_sum) ? (c - MGX_PS_TOT_HDR) % MGX_PS_TOT_POLICY : 0;
-    for (int ch = 0; ch < nchunks; ch++) {
-      const double p = __longlong_as_double((long long)__hip_atomic_load((const unsigned long long*)(partial + (size_t)ch * TW + c),
-                                                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      t = f == 3 ? fmin(t, p) : f == 4 ? fmax(t, p) : t + p;
-    }
-    totals[c] = t;
-  }
-  if (threadIdx.x == 0) {
-    *ticket = 0;
-    if (has_log) {
-      const uint32_t have = log_state[0], room = (uint32_t)log_cap - have, take = (uint32_t)n < room ? (uint32_t)n : room;
-      log_state[0] = have + take;
-      log_state[1] += (uint32_t)n - take;
-    }
-  }
-}
-
-// totals -> snapshot, totals cleared (sums 0, the policies' reward minima +inf, maxima -inf).
-__global__ void __launch_bounds__(256) mgx_policy_snapshot_kernel(double* __restrict__ totals, double* __restrict__ snap, const MgxPsLayout L) {
-  const double INF = __longlong_as_double(0x7FF0000000000000ll);
-  for (int c = threadIdx.x; c < L.tot_words; c += blockDim.x) {
-    const int f = (c >= MGX_PS_TOT_HDR && c < L.tot_off_sum) ? (c - MGX_PS_TOT_HDR) % MGX_PS_TOT_POLICY : 0;
-    snap[c] = totals[c];
-    totals[c] = f == 3 ? INF : f == 4 ? -INF : 0.0;
-  }
+  mgx_totals_fold(MgxPsKind{L.tot_off_sum}, partial, totals, ticket, gridDim.x * gridDim.y, nchunks, TW, log_state, log_cap, has_log, n);
 }
 
 // assign[list[i]][0..A) <- rows[i][0..A) for the n listed envs (no env twice).

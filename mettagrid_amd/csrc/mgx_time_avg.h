@@ -135,6 +135,9 @@ __global__ void __launch_bounds__(256) mgx_time_avg_finish_kernel(const MgxDev* 
 }
 
 // totals / partial layout (doubles): [0] episodes (not partial) [1] partial episodes [NG sums of the averages][NG key counts]
+struct MgxTaKind {
+  __device__ int operator()(int) const { return MGX_TOT_SUM; }
+};
 __global__ void __launch_bounds__(256) mgx_time_avg_total_kernel(const MgxTaLayout L, const uint32_t* __restrict__ list_n,
                                                                  const uint32_t* __restrict__ rec, double* __restrict__ partial,
                                                                  double* __restrict__ totals, uint32_t* __restrict__ ticket,
@@ -173,33 +176,7 @@ __global__ void __launch_bounds__(256) mgx_time_avg_total_kernel(const MgxTaLayo
       P[0] = full; P[1] = part;
     }
   }
-  __threadfence();
-  __syncthreads();
-  __shared__ uint32_t s_last;
-  if (threadIdx.x == 0) s_last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
-  for (int c = threadIdx.x; c < TW; c += blockDim.x) {   // totals += chunk sums, in chunk order
-    double t = totals[c];
-    for (int ch = 0; ch < nchunks; ch++)
-      t += __longlong_as_double((long long)__hip_atomic_load((const unsigned long long*)(partial + (size_t)ch * TW + c),
-                                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    totals[c] = t;
-  }
-  if (threadIdx.x == 0) {
-    *ticket = 0;
-    if (has_log) {
-      const uint32_t have = log_state[0], room = (uint32_t)log_cap - have, take = (uint32_t)n < room ? (uint32_t)n : room;
-      log_state[0] = have + take;
-      log_state[1] += (uint32_t)n - take;
-    }
-  }
-}
-
-// totals -> snapshot, totals cleared.
-__global__ void __launch_bounds__(256) mgx_time_avg_snapshot_kernel(double* __restrict__ totals, double* __restrict__ snap, int TW) {
-  for (int c = threadIdx.x; c < TW; c += blockDim.x) { snap[c] = totals[c]; totals[c] = 0.0; }
+  mgx_totals_fold(MgxTaKind{}, partial, totals, ticket, gridDim.x, nchunks, TW, log_state, log_cap, has_log, n);
 }
 
 // The accumulators of the listed envs (n on the device, or n_host >= 0) or of the masked envs (list == nullptr) -> 0.

@@ -575,6 +575,39 @@ class BatchedMettaGrid:
         _check(self.L.mgx_pool_draws(self.h, ev.ctypes.data, ep.ctypes.data, int(ev.size), out.ctypes.data))
         return out
 
+    # ---- the snapshot / drain protocol the statistics reducers share ----
+    def _fetch_totals(self, fn, shape, dtype, wait: bool):
+        """One ``mgx_fetch_*`` call: the snapshot requested last as an array, or None (nothing requested, or still in flight)."""
+        out = np.zeros(shape, dtype)
+        ready = C.c_int32(0)
+        _check(fn(self.h, 1 if wait else 0, out.ctypes.data, C.byref(ready)))
+        return out if ready.value else None
+
+    @staticmethod
+    def _drain_totals(request, fetch, lo=None, hi=None):
+        """Everything recorded up to now, synchronously: a snapshot still in flight (requested earlier, not fetched) is merged
+        with a fresh one — sums and counts add, the entries indexed by ``lo`` take the minimum, those by ``hi`` the maximum."""
+        first = fetch(True)                    # None unless a request was pending
+        request()
+        tot = fetch(True)
+        if first is None:
+            return tot
+        merged = first + tot
+        if lo is not None:
+            merged[lo] = np.minimum(first[lo], tot[lo])
+        if hi is not None:
+            merged[hi] = np.maximum(first[hi], tot[hi])
+        return merged
+
+    def _drain_log(self, fn, cap: int, words: int, what: str) -> tuple:
+        """One ``mgx_drain_*_log`` call: (uint32 [n][words] records, dropped count)."""
+        if cap <= 0:
+            raise ValueError(what)
+        raw = np.zeros((cap, words), np.uint32)
+        n, dropped = C.c_int32(0), C.c_int32(0)
+        _check(fn(self.h, raw.ctypes.data, cap, C.byref(n), C.byref(dropped)))
+        return raw[:n.value], dropped.value
+
     def set_map_stats(self, enabled: bool = True) -> None:
         """Per-map episode statistics reduced on the device (needs ``set_episode_stats`` and a pool)."""
         _check(self.L.mgx_set_map_stats(self.h, 1 if enabled else 0))
@@ -584,10 +617,7 @@ class BatchedMettaGrid:
         _check(self.L.mgx_request_map_stats(self.h))
 
     def _fetch_ms_raw(self, wait: bool):
-        out = np.zeros((self.pool_size + 1, 6), np.uint64)
-        ready = C.c_int32(0)
-        _check(self.L.mgx_fetch_map_stats(self.h, 1 if wait else 0, out.ctypes.data, C.byref(ready)))
-        return out if ready.value else None
+        return self._fetch_totals(self.L.mgx_fetch_map_stats, (self.pool_size + 1, 6), np.uint64, wait)
 
     def fetch_map_stats(self, wait: bool = False, raw: bool = False):
         """The snapshot requested last: one dict per pool map plus a last one for episodes without a pool index (a slot's first
@@ -600,15 +630,8 @@ class BatchedMettaGrid:
     def drain_map_stats(self, raw: bool = False):
         """Everything recorded up to now, synchronously; a snapshot still in flight is merged with a fresh one."""
         from .pool_sampling import table_dicts
-        first = self._fetch_ms_raw(True)       # None unless a request was pending
-        self.request_map_stats()
-        t = self._fetch_ms_raw(True)
-        if first is not None:
-            with np.errstate(over="ignore"):
-                merged = first + t             # (two's complement: the q sums add like the counts)
-            merged[:, 4] = np.minimum(first[:, 4], t[:, 4])
-            merged[:, 5] = np.maximum(first[:, 5], t[:, 5])
-            t = merged
+        with np.errstate(over="ignore"):       # (two's complement: the q sums add like the counts)
+            t = self._drain_totals(self.request_map_stats, self._fetch_ms_raw, lo=(slice(None), 4), hi=(slice(None), 5))
         return t if raw else table_dicts(t)
 
     # ---- episode-end statistics (include/mgx.h "Episode-end statistics"; the reference's StatsTracker.on_episode_end) ----
@@ -637,10 +660,7 @@ class BatchedMettaGrid:
         _check(self.L.mgx_request_episode_stats(self.h))
 
     def _fetch_raw(self, wait: bool):
-        out = np.zeros(self._epl["TOTALS_WORDS"], np.float64)
-        ready = C.c_int32(0)
-        _check(self.L.mgx_fetch_episode_stats(self.h, 1 if wait else 0, out.ctypes.data, C.byref(ready)))
-        return out if ready.value else None
+        return self._fetch_totals(self.L.mgx_fetch_episode_stats, self._epl["TOTALS_WORDS"], np.float64, wait)
 
     def fetch_episode_stats(self, wait: bool = False):
         """The snapshot requested last as a dict (see ``episode_totals_dict``), or None while its copy is still in flight."""
@@ -650,16 +670,8 @@ class BatchedMettaGrid:
     def drain_episode_stats(self):
         """Everything recorded up to now, synchronously: a snapshot still in flight (requested earlier, not fetched) is merged
         with a fresh one (sums and counts add, minima / maxima combine)."""
-        first = self._fetch_raw(True)          # None unless a request was pending
-        self.request_episode_stats()
-        tot = self._fetch_raw(True)
-        if first is not None:
-            lo, hi = [2, 5], [3, 6]            # MGX_EPT_RETURN_MIN / LENGTH_MIN, ..._MAX
-            merged = first + tot
-            merged[lo] = np.minimum(first[lo], tot[lo])
-            merged[hi] = np.maximum(first[hi], tot[hi])
-            tot = merged
-        return self.episode_totals_dict(tot)
+        lo, hi = [2, 5], [3, 6]                # MGX_EPT_RETURN_MIN / LENGTH_MIN, ..._MAX
+        return self.episode_totals_dict(self._drain_totals(self.request_episode_stats, self._fetch_raw, lo, hi))
 
     def episode_totals_dict(self, totals: np.ndarray) -> dict:
         """Raw totals -> {"episodes", "return_sum", ..., "game_sum": {name: f64}, "game_count": {name: int}, "agent_sum", "agent_count"}
@@ -680,13 +692,9 @@ class BatchedMettaGrid:
         (f32 [A]), game {name: value}, agent {name: f64 mean over agents} — the reference's infos["game"] / infos["agent"] —
         and, with log_per_agent, per_agent [A] dicts (incl. the "action.invalid_index.<k>" keys without a stat column)."""
         Lw = self._epl
-        cap, W = Lw["LOG_CAPACITY"], Lw["LOG_WORDS"]
-        if cap <= 0:
-            raise ValueError("no episode log: set_episode_stats(log_capacity=...)")
-        raw = np.zeros((cap, W), np.uint32)
-        n, dropped = C.c_int32(0), C.c_int32(0)
-        _check(self.L.mgx_drain_episode_log(self.h, raw.ctypes.data, cap, C.byref(n), C.byref(dropped)))
-        return [self.episode_record_dict(raw[i]) for i in range(n.value)], dropped.value
+        raw, dropped = self._drain_log(self.L.mgx_drain_episode_log, Lw["LOG_CAPACITY"], Lw["LOG_WORDS"],
+                                       "no episode log: set_episode_stats(log_capacity=...)")
+        return [self.episode_record_dict(r) for r in raw], dropped
 
     def episode_record_dict(self, rec: np.ndarray) -> dict:
         Lw = self._epl
@@ -784,10 +792,7 @@ class BatchedMettaGrid:
         _check(self.L.mgx_request_time_averages(self.h))
 
     def _fetch_ta_raw(self, wait: bool):
-        out = np.zeros(self._ta_layout()["TOTALS_WORDS"], np.float64)
-        ready = C.c_int32(0)
-        _check(self.L.mgx_fetch_time_averages(self.h, 1 if wait else 0, out.ctypes.data, C.byref(ready)))
-        return out if ready.value else None
+        return self._fetch_totals(self.L.mgx_fetch_time_averages, self._ta_layout()["TOTALS_WORDS"], np.float64, wait)
 
     def fetch_time_averages(self, wait: bool = False):
         """The snapshot requested last as a dict (see ``time_average_totals_dict``), or None while its copy is in flight."""
@@ -796,10 +801,7 @@ class BatchedMettaGrid:
 
     def drain_time_averages(self) -> dict:
         """Everything finished up to now, synchronously; a snapshot still in flight is added to a fresh one."""
-        first = self._fetch_ta_raw(True)
-        self.request_time_averages()
-        tot = self._fetch_ta_raw(True)
-        return self.time_average_totals_dict(tot if first is None else first + tot)
+        return self.time_average_totals_dict(self._drain_totals(self.request_time_averages, self._fetch_ta_raw))
 
     def time_average_totals_dict(self, totals: np.ndarray) -> dict:
         """Raw totals -> {"episodes", "partial", "sum": {key: f64 sum of the per-episode averages}, "count": {key: episodes
@@ -816,19 +818,16 @@ class BatchedMettaGrid:
         """(list of per-episode dicts, dropped count).  Each dict: env, episode, steps (the env's step at the end), ta_steps
         (steps accumulated), partial, time_averaged_game_stats {key: f64}."""
         Lw = self._ta_layout()
-        cap, W, NG = Lw["LOG_CAPACITY"], Lw["LOG_WORDS"], Lw["NG"]
-        if cap <= 0:
-            raise ValueError("no time-average log: set_time_averages(log_capacity=...)")
-        raw = np.zeros((cap, W), np.uint32)
-        n, dropped = C.c_int32(0), C.c_int32(0)
-        _check(self.L.mgx_drain_time_average_log(self.h, raw.ctypes.data, cap, C.byref(n), C.byref(dropped)))
+        NG = Lw["NG"]
+        raw, dropped = self._drain_log(self.L.mgx_drain_time_average_log, Lw["LOG_CAPACITY"], Lw["LOG_WORDS"],
+                                       "no time-average log: set_time_averages(log_capacity=...)")
         out = []
-        for r in raw[:n.value]:
+        for r in raw:
             avg = np.ascontiguousarray(r[Lw["OFF_AVG"]:Lw["OFF_AVG"] + 2 * NG]).view(np.float64)
             out.append({"env": int(r[0]), "episode": int(r[1]), "steps": int(r[2]), "ta_steps": int(r[3]),
                         "partial": bool(int(r[4]) & self.TA_PARTIAL),
                         "time_averaged_game_stats": self._ta_keys(avg, r[Lw["OFF_SEEN"]:Lw["OFF_SEEN"] + Lw["SEEN_WORDS"]])})
-        return out, dropped.value
+        return out, dropped
 
     # ---- per-policy episode statistics (include/mgx.h "Per-policy episode statistics"; multi_episode/summary.py:38-130) ----
     PSL = ("NS", "A", "P", "SEEN_WORDS", "REC_WORDS", "LOG_WORDS", "HEADER_WORDS", "OFF_REWARD", "OFF_COUNT", "OFF_SUM", "OFF_BITS",
@@ -875,10 +874,7 @@ class BatchedMettaGrid:
         _check(self.L.mgx_request_policy_stats(self.h))
 
     def _fetch_ps_raw(self, wait: bool):
-        out = np.zeros(self._ps_layout()["TOTALS_WORDS"], np.float64)
-        ready = C.c_int32(0)
-        _check(self.L.mgx_fetch_policy_stats(self.h, 1 if wait else 0, out.ctypes.data, C.byref(ready)))
-        return out if ready.value else None
+        return self._fetch_totals(self.L.mgx_fetch_policy_stats, self._ps_layout()["TOTALS_WORDS"], np.float64, wait)
 
     def fetch_policy_stats(self, wait: bool = False):
         """The snapshot requested last as a dict (see ``policy_totals_dict``), or None while its copy is in flight."""
@@ -888,18 +884,10 @@ class BatchedMettaGrid:
     def drain_policy_stats(self) -> dict:
         """Everything finished up to now, synchronously; a snapshot still in flight is merged with a fresh one (sums and
         counts add, minima / maxima combine)."""
-        first = self._fetch_ps_raw(True)
-        self.request_policy_stats()
-        tot = self._fetch_ps_raw(True)
-        if first is not None:
-            Lw = self._psl
-            base = Lw["TOTALS_HEADER"] + Lw["TOTALS_POLICY_WORDS"] * np.arange(Lw["P"])
-            lo, hi = base + 3, base + 4   # MGX_PSP_AVG_REWARD_MIN / _MAX
-            merged = first + tot
-            merged[lo] = np.minimum(first[lo], tot[lo])
-            merged[hi] = np.maximum(first[hi], tot[hi])
-            tot = merged
-        return self.policy_totals_dict(tot)
+        Lw = self._ps_layout()
+        base = Lw["TOTALS_HEADER"] + Lw["TOTALS_POLICY_WORDS"] * np.arange(Lw["P"])
+        lo, hi = base + 3, base + 4            # MGX_PSP_AVG_REWARD_MIN / _MAX
+        return self.policy_totals_dict(self._drain_totals(self.request_policy_stats, self._fetch_ps_raw, lo, hi))
 
     def policy_totals_dict(self, totals: np.ndarray) -> dict:
         """Raw totals -> {"episodes", "policies": [{"episodes", "agent_episodes", "avg_reward_sum", "avg_reward_min",
@@ -921,13 +909,9 @@ class BatchedMettaGrid:
     def drain_policy_log(self):
         """(list of per-episode dicts, dropped count); see ``policy_record_dict``."""
         Lw = self._ps_layout()
-        cap, W = Lw["LOG_CAPACITY"], Lw["LOG_WORDS"]
-        if cap <= 0:
-            raise ValueError("no policy log: set_policy_stats(log_capacity=...)")
-        raw = np.zeros((cap, W), np.uint32)
-        n, dropped = C.c_int32(0), C.c_int32(0)
-        _check(self.L.mgx_drain_policy_log(self.h, raw.ctypes.data, cap, C.byref(n), C.byref(dropped)))
-        return [self.policy_record_dict(raw[i]) for i in range(n.value)], dropped.value
+        raw, dropped = self._drain_log(self.L.mgx_drain_policy_log, Lw["LOG_CAPACITY"], Lw["LOG_WORDS"],
+                                       "no policy log: set_policy_stats(log_capacity=...)")
+        return [self.policy_record_dict(r) for r in raw], dropped
 
     def policy_record_dict(self, rec: np.ndarray) -> dict:
         """One record -> env, episode, steps, flags, reward_sum (f64 [P]), agents (int [P]), avg_rewards ([P] float or None:

@@ -106,7 +106,7 @@ enum { hipEventDisableTiming = 2 };
 static inline void __syncthreads() {}
 static inline void __threadfence() {}
 static inline void __threadfence_system() {}
-enum { hipHostMallocMapped = 2 };
+enum { hipHostMallocDefault = 0, hipHostMallocMapped = 2 };
 static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n); return *p ? hipSuccess : 1; }
 static inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
 static inline hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) { *d = h; return hipSuccess; }

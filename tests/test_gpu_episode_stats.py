@@ -215,6 +215,79 @@ def test_chunked_totals_when_every_env_finishes_at_once():
     assert eng.drain_episode_stats()["episodes"] == 0
 
 
+def _merged(w1: dict, w2: dict) -> dict:
+    """Two windows' totals as one: sums and counts add, minima take min, maxima take max."""
+    out = {}
+    for k, x in w1.items():
+        y = w2[k]
+        if isinstance(x, dict):
+            out[k] = {n: x.get(n, 0) + y.get(n, 0) for n in {**x, **y}}
+        else:
+            out[k] = min(x, y) if k.endswith("_min") else max(x, y) if k.endswith("_max") else x + y
+    return out
+
+
+def test_snapshot_protocol_two_windows():
+    """fetch without a request is None; a request while one is pending changes nothing; the drain behind it is the pending
+    snapshot (window 1) merged with a fresh one (window 2); the totals are then as a cleared snapshot leaves them."""
+    spec = presets.rung2_spec()
+    spec.max_steps = 6
+    spec.episode_truncates = True
+    prog = compile_spec(spec, 32, 32, max_objects=192)
+    E, A, M, stride = 5, prog.num_agents, 5, 1
+    pool = np.stack([prog.class_map(presets.rung2_map(50 + m)) for m in range(M)])
+    seeds = (3 + np.arange(E)).astype(np.uint32)
+    from mettagrid_amd.early_reset import first_integers
+    early = first_integers(seeds, 6)
+    eng = BatchedMettaGrid(prog, pool[np.arange(E) % M], seeds, buffers="host")
+    eng.set_map_pool(pool)
+    eng.set_auto_reset(True, stride, early)
+    eng.set_episode_stats(True, log_capacity=0)
+    assert eng.fetch_episode_stats(wait=False) is None
+    oracles = [op.OracleSim(prog, pool[e % M], int(seeds[e])) for e in range(E)]
+    for o in oracles:
+        o.reinit_buffers()
+    episode, ended = [0] * E, [False] * E
+    rng = np.random.default_rng(1)
+    n_act = len(prog.action_names)
+
+    def step(want):
+        for e in range(E):
+            if ended[e]:
+                episode[e] += 1
+                oracles[e] = op.OracleSim(prog, pool[(e + episode[e] * stride) % M], int(seeds[e]))
+                oracles[e].reinit_buffers()
+                ended[e] = False
+        a = rng.integers(0, n_act, E * A).astype(np.int32)
+        eng.actions[:] = a
+        eng.vibe_actions[:] = 0
+        eng.step()
+        finished = []
+        for e, o in enumerate(oracles):
+            o.step(a[e * A:(e + 1) * A], np.zeros(A, np.int32))
+            s = o.snapshot()
+            early_end = episode[e] == 0 and o.current_step >= early[e]
+            all_term = bool(s["terminals"].all())
+            ended[e] = all_term or bool(s["truncations"].all()) or early_end
+            if ended[e]:
+                finished.append((reference_infos(prog, o), all_term))
+        want.add_step(finished)
+
+    w1, w2 = HostTotals(prog), HostTotals(prog)
+    while w1.n == 0:
+        step(w1)
+    assert 0 < w1.n < E and max(episode) == 0, (w1.n, early)   # some, not all, envs have finished their first episode
+    eng.request_episode_stats()
+    for _ in range(6):
+        step(w2)
+    assert w2.n >= E
+    eng.request_episode_stats()   # the first snapshot is still pending: nothing is taken, the totals keep accumulating
+    _same(eng.drain_episode_stats(), _merged(w1.as_dict(), w2.as_dict()), "two windows")
+    _same(eng.drain_episode_stats(), HostTotals(prog).as_dict(), "cleared")
+    assert eng.fetch_episode_stats(wait=False) is None
+    eng.close()
+
+
 def test_batched_env_returns_infos():
     """MettaGridBatchedEnv.step returns the aggregate of the finished episodes (no host synchronisation: the snapshot
     requested at one step is returned by a later one); summed over the run it accounts for every finished episode, and the

@@ -26,11 +26,12 @@ def _engine(prog, pool, E, early, rows, P, log=None, stride=STRIDE, auto=True, p
     if auto:
         eng.set_map_pool(pool)
         eng.set_auto_reset(True, stride, early)
-    eng.set_episode_stats(True, log_capacity=log or 16 * E, log_per_agent=per_agent)
+    log = 16 * E if log is None else log
+    eng.set_episode_stats(True, log_capacity=log, log_per_agent=per_agent)
     if ta:
-        eng.set_time_averages(True, log_capacity=log or 16 * E)
+        eng.set_time_averages(True, log_capacity=log)
     if rows is not None:
-        eng.set_policy_stats(True, P, rows, log_capacity=log or 16 * E)
+        eng.set_policy_stats(True, P, rows, log_capacity=log)
     return eng, seeds
 
 
@@ -227,6 +228,51 @@ def test_chunked_totals_when_every_env_finishes_at_once():
     assert dropped == 500
     _same_records(recs, fin[:100], "three chunks")
     assert eng.drain_policy_stats()["episodes"] == 0
+    eng.close()
+
+
+def _merged(w1: dict, w2: dict) -> dict:
+    """Two windows' totals as one: sums and counts add, minima take min, maxima take max."""
+    def policy(x, y):
+        out = {k: x[k] + y[k] for k in ("episodes", "agent_episodes", "avg_reward_sum")}
+        out["avg_reward_min"], out["avg_reward_max"] = min(x["avg_reward_min"], y["avg_reward_min"]), max(x["avg_reward_max"], y["avg_reward_max"])
+        for k in ("agent_sum", "agent_count"):
+            out[k] = {n: x[k].get(n, 0) + y[k].get(n, 0) for n in {**x[k], **y[k]}}
+        return out
+    return {"episodes": w1["episodes"] + w2["episodes"], "policies": [policy(x, y) for x, y in zip(w1["policies"], w2["policies"])]}
+
+
+def test_snapshot_protocol_two_windows():
+    """fetch without a request is None; a request while one is pending changes nothing; the drain behind it is the pending
+    snapshot (window 1) merged with a fresh one (window 2); the totals are then as a cleared snapshot leaves them."""
+    prog, pool = _program("rung2", 6)
+    E, A, P = 5, prog.num_agents, 2
+    rows = np.array([[(i + e) % 2 if e % 3 else (i // 4) % 2 for i in range(A)] for e in range(E)], np.uint8)
+    early = first_integers((11 + np.arange(E)).astype(np.uint32), 6)
+    eng, seeds = _engine(prog, pool, E, early, rows, P, log=0)
+    mirror = Mirror(prog, pool, seeds, early, rows, P)
+    rng = np.random.default_rng(1)
+    assert eng.fetch_policy_stats(wait=False) is None
+
+    def step(want):
+        a, v = _random_actions(rng, prog, E)
+        _play(eng, a, v)
+        want.add_step(mirror.step(a, v))
+
+    w1, w2 = PolicyHostTotals(prog.agent_stat_names, P), PolicyHostTotals(prog.agent_stat_names, P)
+    while w1.n == 0:
+        step(w1)
+    assert 0 < w1.n < E and max(mirror.episode) == 0, (w1.n, early)   # some, not all, envs have finished their first episode
+    eng.request_policy_stats()
+    for _ in range(6):
+        step(w2)
+    assert w2.n >= E
+    eng.request_policy_stats()   # the first snapshot is still pending: nothing is taken, the totals keep accumulating
+    _same_totals(eng.drain_policy_stats(), _merged(w1.as_dict(), w2.as_dict()), "two windows")
+    empty = eng.drain_policy_stats()
+    _same_totals(empty, PolicyHostTotals(prog.agent_stat_names, P).as_dict(), "cleared")
+    assert empty["episodes"] == 0 and all(p["avg_reward_min"] == np.inf and p["avg_reward_max"] == -np.inf for p in empty["policies"])
+    assert eng.fetch_policy_stats(wait=False) is None
     eng.close()
 
 

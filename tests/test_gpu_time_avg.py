@@ -37,9 +37,10 @@ def _engine(prog, pool, E, early, log=None, ta=True, stride=STRIDE):
     eng = BatchedMettaGrid(prog, pool[np.arange(E) % M], seeds, buffers="host")
     eng.set_map_pool(pool)
     eng.set_auto_reset(True, stride, early)
-    eng.set_episode_stats(True, log_capacity=log or 5 * E)
+    log = 5 * E if log is None else log
+    eng.set_episode_stats(True, log_capacity=log)
     if ta:
-        eng.set_time_averages(True, log_capacity=log or 5 * E)
+        eng.set_time_averages(True, log_capacity=log)
     return eng, seeds
 
 
@@ -192,6 +193,43 @@ def test_chunked_totals_when_every_env_finishes_at_once():
     assert dropped == 500
     _same_records(recs, fin[:100], "three chunks")
     assert eng.drain_time_averages()["episodes"] == 0
+    eng.close()
+
+
+def test_snapshot_protocol_two_windows():
+    """fetch without a request is None; a request while one is pending changes nothing; the drain behind it is the pending
+    snapshot (window 1) plus a fresh one (window 2); the totals are then as a cleared snapshot leaves them."""
+    prog, pool = _program("rung2", 6)
+    E = 5
+    early = first_integers((11 + np.arange(E)).astype(np.uint32), 6)
+    eng, seeds = _engine(prog, pool, E, early, log=0)
+    mirror = Mirror(prog, pool, seeds, early)
+    rng = np.random.default_rng(1)
+    assert eng.fetch_time_averages(wait=False) is None
+
+    def step(want):
+        a, v = _random_actions(rng, prog, E)
+        eng.actions[:] = a
+        eng.vibe_actions[:] = v
+        eng.step()
+        want.add_step(mirror.step(a, v))
+
+    w1, w2 = HostTotals(prog), HostTotals(prog)
+    while w1.n == 0:
+        step(w1)
+    assert 0 < w1.n < E and max(mirror.episode) == 0, (w1.n, early)   # some, not all, envs have finished their first episode
+    eng.request_time_averages()
+    for _ in range(6):
+        step(w2)
+    assert w2.n >= E
+    eng.request_time_averages()   # the first snapshot is still pending: nothing is taken, the totals keep accumulating
+    a, b = w1.as_dict(), w2.as_dict()
+    merged = {"episodes": a["episodes"] + b["episodes"], "partial": a["partial"] + b["partial"],
+              "sum": {k: a["sum"].get(k, 0.0) + b["sum"].get(k, 0.0) for k in {**a["sum"], **b["sum"]}},
+              "count": {k: a["count"].get(k, 0) + b["count"].get(k, 0) for k in {**a["count"], **b["count"]}}}
+    _same_totals(eng.drain_time_averages(), merged, "two windows")
+    _same_totals(eng.drain_time_averages(), HostTotals(prog).as_dict(), "cleared")
+    assert eng.fetch_time_averages(wait=False) is None
     eng.close()
 
 
