@@ -634,6 +634,18 @@ int mgx_attach_code(mgx_engine* e, int32_t kind, const char* code_object_path);
  * episode length set (max_steps read at run time), 9 = an instance compiled for this program at run time (mgx_attach_code).
  * Diagnostic. */
 int32_t mgx_obs_variant(const mgx_engine* e);
+/* Which instance of the lean world kernel the engine launches: 0 = the generic one (every size and path decision read from
+ * the engine's table at run time), 3 = the instance compiled for the shape of BASELINE.json configs[2] (MgxWorldShapeR3,
+ * mettagrid_amd/gen_presets.py) — chosen at mgx_create only when every field of the shape is equal AND the program runs the
+ * handlers generated for that preset (mgx_handler_variant 3), so never under MGX_NO_GEN; MGX_WORLD_GENERIC=1 at mgx_create
+ * switches it off (the A/B switch on one binary) —, 9 = a code object attached at run time (mgx_attach_code).  Same results.
+ * Diagnostic. */
+int32_t mgx_world_variant(const mgx_engine* e);
+/* The fields of the world kernels' shape (MGX_WORLD_SHAPE_FIELDS, csrc/mgx_world.h, in that order) that mgx_create would
+ * derive for `program` under the current create-time switches: host-only, no device is touched.  Writes at most `capacity`
+ * values to `out` and returns the number of fields, or an MGX_ERR_* code (negative).  What the build() step and the run-time
+ * specialiser compile a MgxWorldShape<...> from. */
+int32_t mgx_world_shape_fields(const int32_t* program, size_t program_words, int32_t* out, int32_t capacity);
 /* How the action dispatch of MettaGrid::_step (mettagrid_c.cpp:966-999) is executed: 0 = one lane per env, agents one
  * after another; 1 = one lane per agent, in rounds ordered by the agents' cell footprints (mgx_act.h) — chosen at
  * mgx_create when every handler an action can reach stays with its actor and target.  Same results. Diagnostic. */

@@ -592,7 +592,7 @@ struct MgxObsArgs {
 };
 // The lean world unit's launcher and limit function by constant-memory slot (mgx_engine::slot).
 static const struct {
-  void (*launch)(bool prog_lds, size_t lds, hipStream_t stream, const MgxDev& d, int prog_words);
+  void (*launch)(bool prog_lds, int variant, size_t lds, hipStream_t stream, const MgxDev& d, int prog_words);
   bool (*set_lds)(size_t lds);
 } g_world_fast[MGX_FAST_SLOTS] = {{mgx_launch_world_fast_s0, mgx_world_fast_set_lds_s0}, {mgx_launch_world_fast_s1, mgx_world_fast_set_lds_s1}};
 // The lean world kernel of a run-time code object: its MgxDev lives in the module's constant memory.
@@ -1029,6 +1029,7 @@ static void report_plan(const mgx_engine* e, size_t program_words) {
           (int)e->prog_in_lds, e->lds_world);
   if (d.X) fprintf(stderr, "[mgx] action-phase handlers on the %s VM\n", d.flat_top ? "register" : "LDS");
   fprintf(stderr, "[mgx] handler code: %s\n", d.gen_prog ? "generated for this program at build()" : "interpreter");
+  if (!d.X && !d.act_par) fprintf(stderr, "[mgx] lean world kernel: %s\n", e->world_variant ? "the instance compiled for this shape" : "generic (shape read at run time)");
   fprintf(stderr, "[mgx] lean dispatch: move targets %s\n", !d.move_fast ? "read by every move" : d.mf_exact ?
           "resolved in the staging pass, trivial actions run ahead (exact dirty bitmap)" : "resolved in the staging pass, trivial actions run ahead (hashed dirty mask)");
   fprintf(stderr, "[mgx] lean dispatch: %s\n", d.duo ? "two agents of an env at a time (disjoint footprints)" : "one agent at a time");
@@ -1910,6 +1911,14 @@ int mgx_attach_code(mgx_engine* e, int32_t kind, const char* path) {
     if (hipModuleGetGlobal(&sym, &n, mod, "g_mgx_dev") != hipSuccess || n != sizeof(MgxDev)) return refuse("no g_mgx_dev symbol of the right size");
     if (hipModuleGetFunction(&j.f0, mod, e->prog_in_lds ? "mgx_jit_world_pl" : "mgx_jit_world_pg") != hipSuccess)
       return refuse(std::string("no ") + (e->prog_in_lds ? "mgx_jit_world_pl" : "mgx_jit_world_pg") + " kernel");
+    {   // a code object compiled for one shape (MGX_JIT_WORLD_SHAPE): every field equal, with the handler id it will run under
+      int ks[1 + MGX_WORLD_SHAPE_NFIELDS] = {}, mine[MGX_WORLD_SHAPE_NFIELDS];
+      if (!read_sym("mgx_jit_world_shape", ks, sizeof ks)) return refuse("no mgx_jit_world_shape symbol");
+      MgxDev t = d;
+      t.gen_prog = (int)info[5];
+      mgx_world_shape_of(t, mine);
+      if (ks[0] != 0 && (ks[0] != MGX_WORLD_SHAPE_NFIELDS || memcmp(ks + 1, mine, sizeof mine) != 0)) return refuse("compiled for another world shape");
+    }
     j.dev_sym = sym; j.epg = (int)info[2]; j.threads = (int)info[3];
     j.mod = mod;
     e->d.gen_prog = (int)info[5];
@@ -2608,7 +2617,7 @@ int mgx_step(mgx_engine* e) {
         mgx_launch_act_fast_s0(e->prog_in_lds, e->lds_act, e->stream, e->d, pw);   // (one constant-memory copy: an opt-in path)
       } else {
         if (e->jit_world.mod) { int jrc = launch_world_jit(e, pw); if (jrc) return jrc; }
-        else g_world_fast[e->slot].launch(e->prog_in_lds, e->lds_world, e->stream, e->d, pw);
+        else g_world_fast[e->slot].launch(e->prog_in_lds, e->world_variant, e->lds_world, e->stream, e->d, pw);
       }
       MGX_MARK(1); MGX_MARK(2); MGX_MARK(3);
     } else if (e->aoe_kernel) {
@@ -3462,6 +3471,21 @@ int mgx_get_step_timing(mgx_engine* e, float* ms_out) {
 }
 
 int32_t mgx_obs_variant(const mgx_engine* e) { return e ? e->obs_variant : 0; }
+int32_t mgx_world_variant(const mgx_engine* e) { return !e || e->d.X || e->d.act_par ? 0 : e->jit_world.mod ? 9 : e->world_variant; }
+int32_t mgx_world_shape_fields(const int32_t* program, size_t program_words, int32_t* out, int32_t capacity) {
+  if (!program || !out || capacity < 0) return fail(MGX_ERR_BAD_ARG, "mgx_world_shape_fields: null argument");
+  if (program_words < MGX_H_WORDS || program[MGX_H_HEIGHT] < 0 || program[MGX_H_WIDTH] < 0 || program[MGX_H_HEIGHT] > 255 || program[MGX_H_WIDTH] > 255)
+    return fail(MGX_ERR_PROGRAM, "mgx_world_shape_fields: not an mgx program");
+  const std::vector<uint16_t> empty_map((size_t)program[MGX_H_HEIGHT] * program[MGX_H_WIDTH] + 1, 0);   // nothing of the shape depends on the maps
+  MgxPlan plan;
+  std::string why;
+  const int rc = mgx_plan(program, program_words, empty_map.data(), 1, mgx_read_switches(), plan, why);
+  if (rc != MGX_OK) return fail(rc, why);
+  int v[MGX_WORLD_SHAPE_NFIELDS];
+  mgx_world_shape_of(plan.d, v);
+  for (int i = 0; i < MGX_WORLD_SHAPE_NFIELDS && i < capacity; i++) out[i] = v[i];
+  return MGX_WORLD_SHAPE_NFIELDS;
+}
 int32_t mgx_act_variant(const mgx_engine* e) { return e ? e->d.act_par : 0; }
 int32_t mgx_handler_variant(const mgx_engine* e) { return e ? e->d.gen_prog : 0; }
 int32_t mgx_world_prog_in_lds(const mgx_engine* e) { return e && e->prog_in_lds ? 1 : 0; }

@@ -106,8 +106,8 @@ inline int mgx_read_cycles(const void* symbol, unsigned long long* out, int rese
 // lean world kernels (mgx_world_fast.hip): one copy per constant-memory slot, the unit is compiled with MGX_SLOT = 0 and 1
 #define MGX_FAST_SLOTS 2
 size_t mgx_world_fast_lds_bytes(int A);   // dynamic LDS of the unit's kernels without the program copy
-void mgx_launch_world_fast_s0(bool prog_lds, size_t lds, hipStream_t stream, const MgxDev& d, int prog_words);
-void mgx_launch_world_fast_s1(bool prog_lds, size_t lds, hipStream_t stream, const MgxDev& d, int prog_words);
+void mgx_launch_world_fast_s0(bool prog_lds, int variant, size_t lds, hipStream_t stream, const MgxDev& d, int prog_words);
+void mgx_launch_world_fast_s1(bool prog_lds, int variant, size_t lds, hipStream_t stream, const MgxDev& d, int prog_words);
 bool mgx_world_fast_set_lds_s0(size_t lds);  // raises the kernels' dynamic LDS limit (MgxLdsLimit)
 bool mgx_world_fast_set_lds_s1(size_t lds);
 // the lane-per-agent action kernels (mgx_act_fast.hip, mgx_act_x.hip; mgx_act.h)

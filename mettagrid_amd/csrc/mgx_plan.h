@@ -22,7 +22,7 @@
 // the engine's lifetime: a later reset that grows the token pool sizes the observation kernel with the same ones.
 struct MgxSwitches {   // (mgx_read_switches: which switch sets or clears each)
   bool verbose, prog_lds, aoe_local, tick_in_aoe, aoe_prog_lds, flat_top, tick_split, rewards_mid, obs_512, obs_preset, act_lean,
-      act_par, act_map, act_replay, duo, coop_passes, move_fast, move_fast_count, shadow, gen, obs_tail;
+      act_par, act_map, act_replay, duo, coop_passes, move_fast, move_fast_count, shadow, gen, obs_tail, world_preset;
 };
 inline MgxSwitches mgx_read_switches() {
   auto on = [](const char* name) { return getenv(name) != nullptr; };
@@ -49,6 +49,7 @@ inline MgxSwitches mgx_read_switches() {
   s.shadow = !on("MGX_NO_SHADOW");                  // no integer bookkeeping
   s.gen = !on("MGX_NO_GEN");                        // handlers on the interpreter
   s.obs_tail = !on("MGX_OBS_FULL_ROWS");            // every observation pass rewrites whole rows (no MgxDev::obs_used)
+  s.world_preset = !on("MGX_WORLD_GENERIC");        // no preset instance of the lean world kernel (the A/B switch on one binary)
 #ifdef MGX_CPU_EMU
   // the sanitizer build runs work-items one by one: no LDS program copies (they need a workgroup barrier), no flush kernel
   // for the integer bookkeeping, no wavefront-cooperative (ballot / readlane) lane-per-agent dispatch
@@ -191,6 +192,7 @@ struct MgxPlan {
   int obs_threads = MGX_OBS_THREADS, obs_ew = MGX_OBS_THREADS / MGX_WAVE;
   size_t lds_obs = 0;
   int obs_variant = 0;   // 0: generic observation kernel; 3 / 5: the instances for the shape of BASELINE.json configs[2]; 9: mgx_attach_code
+  int world_variant = 0; // 0: generic lean world kernel; 3: the instance compiled for the shape of BASELINE.json configs[2] (MgxWorldShapeR3)
   // where reward expressions are evaluated: 1 beside the token-cache phase (no stat operands, lean), 2 during the extended
   // kernel's encode phase (nothing it writes is read), 0 at the kernel's end
   int rmode = 0;
@@ -681,6 +683,10 @@ inline int mgx_plan(const int32_t* P, size_t words, const uint16_t* class_maps, 
   for (int i = 0; i < d.n_obs_values; i++)
     if (mgx_value_any(P, i, mgx_gv_query)) p.obsval = true;
   if (!p.size_obs(sw)) return refuse(MGX_ERR_PROGRAM, MGX_OBS_LDS_REFUSAL);
+  // The lean world kernel's preset instance (mgx_world_fast.hip): every field of its shape equal — gen_prog among them, so a program
+  // on the interpreter (MGX_NO_GEN, other handler tables) never takes it — and the program copy in LDS, the one form it is built in.
+  p.world_variant = 0;
+  if (sw.world_preset && !d.X && !d.act_par && p.prog_in_lds && d.gen_prog == 3 && mgx_world_shape_matches<MgxWorldShapeR3>(d)) p.world_variant = 3;
   return MGX_OK;
 }
 

@@ -177,8 +177,10 @@ __device__ __forceinline__ MgxALds mgx_world_alds(uint8_t* lds, int A, int lane)
   al.prev = al.rc + A * MGX_WORLD_EPG;
 #ifdef MGX_NO_CLS_STAGE
   al.cls = nullptr;
+#define MGX_CLS_STAGED 0
 #else
   al.cls = al.prev + A * MGX_WORLD_EPG;
+#define MGX_CLS_STAGED 1
 #endif
   return al;
 }
@@ -199,11 +201,65 @@ struct MgxValueStack {
   __device__ __forceinline__ float pop() { float v = s0; s0 = s1; s1 = s2; s2 = s3; s3 = s4; s4 = s5; s5 = s6; s6 = s7; n--; return v; }
 };
 
+// Shape policy of the world kernels, in the manner of MgxObsShape (mgx_obs.h): every scalar of the engine's table that the
+// lean kernel reads — map, agents, slots, stat pitches, action count, the planner's path decisions and the LDS offsets behind
+// them — goes through K::field(d).  MgxWorldShapeDyn returns the table's field (any program); MgxWorldShape<...> returns the
+// value of ONE compiled program as a constant, so index products become shifts, divisions by A disappear, the sides a
+// decision rules out are not compiled and nothing of it is live in (or spilled from) scalar registers across the handler
+// code.  Pointers and E stay run-time.  The host launches an instance only for a table equal in every field
+// (mgx_world_shape_matches).  One list names the fields, in template-argument order:
+#define MGX_WORLD_SHAPE_FIELDS(F)                                                                                              \
+  F(H) F(W) F(A) F(S) F(NSP) F(NSW) F(NG) F(NGW) F(SEENW) F(nact) F(max_priority) F(flags) F(hp_res) F(n_move_handlers)          \
+  F(any_on_tick) F(tick_in_aoe) F(flat_top) F(defer_book) F(shadow) F(gen_prog) F(duo) F(tick_split) F(coop_passes) F(move_fast)  \
+  F(mf_lds_off) F(mf_dirty_words) F(mf_exact) F(act_ngset)
+#define MGX_WS_COUNT(f) +1
+#define MGX_WORLD_SHAPE_NFIELDS (0 MGX_WORLD_SHAPE_FIELDS(MGX_WS_COUNT))
+struct MgxWorldShapeDyn {
+  static constexpr bool fixed = false;
+#define MGX_WS_DYN(f) static __host__ __device__ __forceinline__ int f(const MgxDev& d) { return d.f; }
+  MGX_WORLD_SHAPE_FIELDS(MGX_WS_DYN)
+#undef MGX_WS_DYN
+};
+template <int I, int V0, int... Vs> struct MgxPackAt { static constexpr int value = MgxPackAt<I - 1, Vs...>::value; };
+template <int V0, int... Vs> struct MgxPackAt<0, V0, Vs...> { static constexpr int value = V0; };
+template <int... V>
+struct MgxWorldShape {
+  static_assert(sizeof...(V) == MGX_WORLD_SHAPE_NFIELDS, "MgxWorldShape: one value per field of MGX_WORLD_SHAPE_FIELDS");
+  static constexpr bool fixed = true;
+  enum {
+#define MGX_WS_IDX(f) i_##f,
+    MGX_WORLD_SHAPE_FIELDS(MGX_WS_IDX)
+#undef MGX_WS_IDX
+  };
+#define MGX_WS_FIX(f) static __host__ __device__ __forceinline__ constexpr int f(const MgxDev&) { return MgxPackAt<i_##f, V...>::value; }
+  MGX_WORLD_SHAPE_FIELDS(MGX_WS_FIX)
+#undef MGX_WS_FIX
+};
+// the fields of an engine table in the list's order (host: matching, mgx_world_shape_fields, the run-time specialiser)
+inline void mgx_world_shape_of(const MgxDev& d, int* out) {
+  int n = 0;
+#define MGX_WS_GET(f) out[n++] = d.f;
+  MGX_WORLD_SHAPE_FIELDS(MGX_WS_GET)
+#undef MGX_WS_GET
+}
+// does an engine table have this shape?  (host)
+template <class K>
+inline bool mgx_world_shape_matches(const MgxDev& d) {
+  if (!K::fixed) return false;
+  bool same = true;
+#define MGX_WS_CMP(f) same = same && d.f == K::f(d);
+  MGX_WORLD_SHAPE_FIELDS(MGX_WS_CMP)
+#undef MGX_WS_CMP
+  return same;
+}
+
 template <class Env> struct MgxGenR3;   // generated at build(): mgx_handlers_gen.h
 template <class Env> struct MgxGenR4;
 template <class Env> struct MgxGenJ;    // generated at run time for the program at hand (mettagrid_amd/jit.py): MGX_GEN_HEADER
-template <class PP, bool X>
+template <class PP, bool X, class K_ = MgxWorldShapeDyn>
 struct MgxEnvT {  // per-lane view of one env
+  typedef K_ K;   // the shape policy (MgxWorldShapeDyn / MgxWorldShape<...>): every scalar table read below is K::field(d)
+  typedef K_ Shape;
   typedef PP ProgPtr;
 #ifdef MGX_CONST_DEV
   static constexpr const MgxDev& d = g_mgx_dev;
@@ -225,11 +281,11 @@ struct MgxEnvT {  // per-lane view of one env
   // Each set goes to a per-env LDS cell as (position + 1) << 32 | value bits under a 64-bit max; mgx_act_body applies the
   // surviving value when the phase is over.  (The host only selects this kernel when nothing reads those stats mid-phase.)
   __device__ __forceinline__ unsigned long long* act_gset_cells() const {
-    return (unsigned long long*)(mgx_dyn_lds + mgx_world_lds_fixed(d.A, X, d.x_aoe_lds != 0) - MGX_ACT_GSET * MGX_WORLD_EPG * 8);  // (in front of act_lds_extra)
+    return (unsigned long long*)(mgx_dyn_lds + mgx_world_lds_fixed(K::A(d), X, d.x_aoe_lds != 0) - MGX_ACT_GSET * MGX_WORLD_EPG * 8);  // (in front of act_lds_extra)
   }
   __device__ __forceinline__ void act_gstat_set(int id, float v) const {
     int k = 0;
-    while (k < d.act_ngset - 1 && d.act_gset_ids[k] != id) k++;
+    while (k < K::act_ngset(d) - 1 && d.act_gset_ids[k] != id) k++;
     // key: order position, then this lane's set count — game_stats->set is last-write-wins (stats_tracker.hpp), so of two
     // sets by the same agent in one chain (on_use, then on_after_use) the later one must survive, not the larger bit pattern
     const uint32_t seq = act_seq < 255u ? act_seq++ : 255u;
@@ -252,17 +308,17 @@ struct MgxEnvT {  // per-lane view of one env
   __device__ __forceinline__ int envi() const { return (int)(blockIdx.x * MGX_WORLD_EPG) + mgx_world_lane(); }
   __device__ __forceinline__ PP prog() const {
 #ifdef MGX_ACT_TU
-    if constexpr (std::is_same<PP, MgxLdsProg>::value) return (MgxLdsProg)(int32_t*)(mgx_dyn_lds + mgx_world_lds_fixed(d.A, X, d.x_aoe_lds != 0, d.act_lds_extra));
+    if constexpr (std::is_same<PP, MgxLdsProg>::value) return (MgxLdsProg)(int32_t*)(mgx_dyn_lds + mgx_world_lds_fixed(K::A(d), X, d.x_aoe_lds != 0, d.act_lds_extra));
 #else
-    if constexpr (std::is_same<PP, MgxLdsProg>::value) return (MgxLdsProg)(int32_t*)(mgx_dyn_lds + mgx_world_lds_fixed(d.A, X, d.x_aoe_lds != 0));
+    if constexpr (std::is_same<PP, MgxLdsProg>::value) return (MgxLdsProg)(int32_t*)(mgx_dyn_lds + mgx_world_lds_fixed(K::A(d), X, d.x_aoe_lds != 0));
 #endif
     else return d.P;
   }
-  __device__ __forceinline__ MgxALds AL() const { return mgx_world_alds(mgx_dyn_lds, d.A, mgx_world_lane()); }
+  __device__ __forceinline__ MgxALds AL() const { return mgx_world_alds(mgx_dyn_lds, K::A(d), mgx_world_lane()); }
   __device__ __forceinline__ MgxXLds XL() const {  // per-lane scratch of the extended variant
     MgxXLds x;
-    x.def_delta = (int*)(mgx_dyn_lds + mgx_world_xlds_off(d.A) + MGX_VM_WORDS * MGX_WORLD_EPG * 4);
-    x.terr_score = (long long*)(mgx_dyn_lds + mgx_world_xlds_off(d.A) + MGX_VM_WORDS * MGX_WORLD_EPG * 4 + 28 * MGX_WORLD_EPG * 4);
+    x.def_delta = (int*)(mgx_dyn_lds + mgx_world_xlds_off(K::A(d)) + MGX_VM_WORDS * MGX_WORLD_EPG * 4);
+    x.terr_score = (long long*)(mgx_dyn_lds + mgx_world_xlds_off(K::A(d)) + MGX_VM_WORDS * MGX_WORLD_EPG * 4 + 28 * MGX_WORLD_EPG * 4);
     x.lane = mgx_world_lane(); x.stride = MGX_WORLD_EPG;
     return x;
   }
@@ -283,8 +339,8 @@ struct MgxEnvT {  // per-lane view of one env
   __device__ __forceinline__ CP cls(int c) const { return prog() + d.sec[MGX_SEC_CLASSES] + c * MGX_C_WORDS; }
 #endif
 
-  __device__ __forceinline__ size_t so(int slot) const { return (size_t)envi() * d.S + slot; }
-  __device__ __forceinline__ size_t ao(int agent) const { return (size_t)envi() * d.A + agent; }
+  __device__ __forceinline__ size_t so(int slot) const { return (size_t)envi() * K::S(d) + slot; }
+  __device__ __forceinline__ size_t ao(int agent) const { return (size_t)envi() * K::A(d) + agent; }
   __device__ __forceinline__ uint16_t& inv(int slot, int item) const { return d.obj_inv[so(slot) * MGX_INV_PITCH + item]; }
   __device__ __forceinline__ int inv_of(int slot, int item) const { return slot >= 0 ? (int)inv(slot, item) : 0; }
   __device__ __forceinline__ CP cls_of(int slot) const { return cls(d.obj_cls[so(slot)]); }
@@ -304,15 +360,15 @@ struct MgxEnvT {  // per-lane view of one env
   // agent's own cell (it was not displaced) nor the target is in the set; a false positive sends the action down the general
   // path, so results do not depend on the mask size.  Two lanes of an env may mark at once (paired dispatch): LDS atomics.
 #if MGX_HELPERS_ON
-  __device__ __forceinline__ uint8_t* mf_pre() const { return mgx_dyn_lds + d.mf_lds_off; }
-  __device__ __forceinline__ uint32_t* mf_dirty() const { return (uint32_t*)(mf_pre() + ((d.A * MGX_WORLD_EPG + 15) & ~15)); }
+  __device__ __forceinline__ uint8_t* mf_pre() const { return mgx_dyn_lds + K::mf_lds_off(d); }
+  __device__ __forceinline__ uint32_t* mf_dirty() const { return (uint32_t*)(mf_pre() + ((K::A(d) * MGX_WORLD_EPG + 15) & ~15)); }
   __device__ __forceinline__ uint32_t mf_bit(int r, int c) const {
-    const uint32_t cellidx = (uint32_t)(r * d.W + c);
-    return d.mf_exact ? cellidx : (cellidx & (uint32_t)(d.mf_dirty_words * 32 - 1));
+    const uint32_t cellidx = (uint32_t)(r * K::W(d) + c);
+    return K::mf_exact(d) ? cellidx : (cellidx & (uint32_t)(K::mf_dirty_words(d) * 32 - 1));
   }
   __device__ __forceinline__ void mf_mark(int r, int c) const {
     if constexpr (!X) {
-      if (d.move_fast) { const uint32_t b = mf_bit(r, c); atomicOr(mf_dirty() + (b >> 5) * MGX_WORLD_EPG + mgx_world_lane(), 1u << (b & 31)); }
+      if (K::move_fast(d)) { const uint32_t b = mf_bit(r, c); atomicOr(mf_dirty() + (b >> 5) * MGX_WORLD_EPG + mgx_world_lane(), 1u << (b & 31)); }
     }
   }
 #else
@@ -320,37 +376,37 @@ struct MgxEnvT {  // per-lane view of one env
 #endif
 
   // ---- stats (systems/stats_tracker.hpp:69-90) ----
-  __device__ __forceinline__ void astat_touch(int agent, int id) const { d.ag_touched[ao(agent) * d.NSW + (id >> 5)] |= 1u << (id & 31); }
+  __device__ __forceinline__ void astat_touch(int agent, int id) const { d.ag_touched[ao(agent) * K::NSW(d) + (id >> 5)] |= 1u << (id & 31); }
   // add(): every caller adds a strictly positive amount to a key that only ever grows, so "value != 0" already
   // says the key exists; the host ORs that into the touched flags (mgx_get_stats) and the bit RMW is skipped here.
   // Plain read-modify-write on purpose: float atomics execute at the memory side on gfx950 (nothing stays in L2) and
   // 64 lanes adding into 64 different rows is their slowest shape (MI355X_MICROARCH.md "Global float atomics").
   __device__ __forceinline__ void astat_add(int agent, int id, float v) const {
     if (id < 0) return;
-    d.ag_stats[ao(agent) * d.NSP + id] += v;
+    d.ag_stats[ao(agent) * K::NSP(d) + id] += v;
   }
   __device__ __forceinline__ void astat_add_touch(int agent, int id, float v) const {  // for deltas that may be zero or negative
     if (id < 0) return;
-    d.ag_stats[ao(agent) * d.NSP + id] += v;
+    d.ag_stats[ao(agent) * K::NSP(d) + id] += v;
     astat_touch(agent, id);
   }
   __device__ __forceinline__ void astat_set(int agent, int id, float v) const {
     if (id < 0) return;
-    d.ag_stats[ao(agent) * d.NSP + id] = v;
+    d.ag_stats[ao(agent) * K::NSP(d) + id] = v;
     astat_touch(agent, id);
   }
   __device__ __forceinline__ float astat_get(int agent, int id) const {
-    return id < 0 ? 0.f : d.ag_stats[ao(agent) * d.NSP + id];
+    return id < 0 ? 0.f : d.ag_stats[ao(agent) * K::NSP(d) + id];
   }
-  __device__ __forceinline__ void gstat_touch(int id) const { d.game_touched[(size_t)envi() * d.NGW + (id >> 5)] |= 1u << (id & 31); }
+  __device__ __forceinline__ void gstat_touch(int id) const { d.game_touched[(size_t)envi() * K::NGW(d) + (id >> 5)] |= 1u << (id & 31); }
   __device__ __forceinline__ void gstat_set(int id, float v) const {
     if (id < 0) return;
-    d.game_stats[(size_t)envi() * d.NG + id] = v;
+    d.game_stats[(size_t)envi() * K::NG(d) + id] = v;
     gstat_touch(id);
   }
   __device__ __forceinline__ void gstat_add(int id, float v) const {
     if (id < 0) return;
-    d.game_stats[(size_t)envi() * d.NG + id] += v;
+    d.game_stats[(size_t)envi() * K::NG(d) + id] += v;
     gstat_touch(id);
   }
 
@@ -411,13 +467,13 @@ struct MgxEnvT {  // per-lane view of one env
   // from the same round trip as the inventory row).  The three cells it updates are loaded together.
   __device__ MGX_BIG void on_inventory_change(int a, int item, int delta, int amount) const {
     if (a < 0 || delta == 0) return;
-    const size_t sb = ao(a) * d.NSP;
+    const size_t sb = ao(a) * K::NSP(d);
     const int s_flow = (delta > 0 ? d.wk[MGX_S_RES_GAINED_BASE] : d.wk[MGX_S_RES_LOST_BASE]) + item;
     const int s_amt = d.wk[MGX_S_RES_AMOUNT_BASE] + item;
-    const bool died = amount == 0 && delta < 0 && item == d.hp_res;
+    const bool died = amount == 0 && delta < 0 && item == K::hp_res(d);
     const int s_death = d.wk[MGX_S_DEATH];
     const float flow = d.ag_stats[sb + s_flow];
-    uint32_t* tw = &d.ag_touched[ao(a) * d.NSW + (s_amt >> 5)];
+    uint32_t* tw = &d.ag_touched[ao(a) * K::NSW(d) + (s_amt >> 5)];
     const uint32_t tword = *tw;
     const float deaths = d.ag_stats[sb + max(s_death, 0)];
     d.ag_stats[sb + s_flow] = __fadd_rn(flow, (float)(delta > 0 ? delta : -delta));  // add(): value != 0 marks the key
@@ -526,7 +582,7 @@ struct MgxEnvT {  // per-lane view of one env
 #else
   __device__ __forceinline__ int tag_list(int tag) const { return prog()[d.sec[MGX_SEC_TAG_LISTS] + tag]; }
 #endif
-  __device__ __forceinline__ uint16_t* tl_items(int li) const { return d.tl_items + ((size_t)envi() * d.NL + li) * d.S; }
+  __device__ __forceinline__ uint16_t* tl_items(int li) const { return d.tl_items + ((size_t)envi() * d.NL + li) * K::S(d); }
   __device__ __forceinline__ uint16_t& tl_count(int li) const { return d.tl_count[(size_t)envi() * d.NL + li]; }
   // GridObject::add_tag / remove_tag without the lifecycle handlers (core/grid_object.cpp:93-123): bitset + TagIndex.
   // Returns true when the tag set changed; the handler VM (vm_run) then fires on_tag_add / on_tag_remove.
@@ -534,7 +590,7 @@ struct MgxEnvT {  // per-lane view of one env
     if (o < 0 || tag < 0 || tag >= 256 || !d.obj_tags || has_tag(o, tag)) return false;
     d.obj_tags[so(o) * MGX_TAG_WORDS + (tag >> 5)] |= 1u << (tag & 31);
     int li = tag_list(tag);
-    if (li >= 0) { uint16_t n = tl_count(li); if (n < d.S) { tl_items(li)[n] = (uint16_t)o; tl_count(li) = n + 1; } }
+    if (li >= 0) { uint16_t n = tl_count(li); if (n < K::S(d)) { tl_items(li)[n] = (uint16_t)o; tl_count(li) = n + 1; } }
     territory_tags_changed(o);
     return true;
   }
@@ -562,7 +618,7 @@ struct MgxEnvT {  // per-lane view of one env
   }
 
   // ---- query workspace ----
-  __device__ __forceinline__ uint16_t* qbuf(int idx) const { return d.qws + ((size_t)envi() * d.QB + idx) * d.S; }
+  __device__ __forceinline__ uint16_t* qbuf(int idx) const { return d.qws + ((size_t)envi() * d.QB + idx) * K::S(d); }
   __device__ __forceinline__ uint32_t* qvis(int depth) const { return d.qvis + ((size_t)envi() * (d.QD + 1) + depth) * d.SW; }
   enum { QB_EVENT = 0, QB_LOST = 1, QB_KEEP = 2, QB_BASE = 3 };  // then two buffers per nesting level
 
@@ -667,7 +723,7 @@ struct MgxEnvT {  // per-lane view of one env
           for (int k = 0; k < a3; k++)
             for (int dist = 1; dist <= range; dist++) {
               int r = (rc >> 8) + dirs[k * 2] * dist, cc = (rc & 0xFF) + dirs[k * 2 + 1] * dist;
-              if (r < 0 || cc < 0 || r >= d.H || cc >= d.W) break;
+              if (r < 0 || cc < 0 || r >= K::H(d) || cc >= K::W(d)) break;
               int o = (int)cell(r, cc) - 1;
               if (o < 0) continue;
               bool blocker = false;
@@ -696,7 +752,7 @@ struct MgxEnvT {  // per-lane view of one env
         case MGX_GOP_INVENTORY: st.push(entity >= 0 ? (float)inv(entity, a0) : 0.f); break;
         case MGX_GOP_STAT: {
           float v = 0.f;
-          if (a0 == 1) { gstat_touch(a1); v = d.game_stats[(size_t)envi() * d.NG + a1]; }
+          if (a0 == 1) { gstat_touch(a1); v = d.game_stats[(size_t)envi() * K::NG(d) + a1]; }
           else { int a = agent_of(entity); if (a >= 0) { astat_touch(a, a1); v = astat_get(a, a1); } }
           st.push(v);
           break;
@@ -847,7 +903,7 @@ struct MgxEnvT {  // per-lane view of one env
 #endif
 
   // ---- grid (core/grid.hpp:75-113) ----
-  __device__ __forceinline__ uint16_t& cell(int r, int c) const { return d.grid[(size_t)envi() * d.H * d.W + r * d.W + c]; }
+  __device__ __forceinline__ uint16_t& cell(int r, int c) const { return d.grid[(size_t)envi() * K::H(d) * K::W(d) + r * K::W(d) + c]; }
   __device__ void territory_moved(int slot) const {  // TerritoryTracker::notify_source_moved (:187-199)
     if constexpr (X) {
       if (d.NTS == 0) return;
@@ -878,7 +934,7 @@ struct MgxEnvT {  // per-lane view of one env
   // Grid::move_object.  known_empty: the caller saw (r, c) empty and no grid cell has been written since (the acting
   // agent stepping into the cell its own line scan just read) — the target is then not read again.
   __device__ MGX_BIG bool move_object(int slot, int r, int c, bool known_empty = false) const {
-    if (r < 0 || c < 0 || r >= d.H || c >= d.W) return false;
+    if (r < 0 || c < 0 || r >= K::H(d) || c >= K::W(d)) return false;
     if (!known_empty && cell(r, c) != 0) return false;
     const bool own = slot == cur_slot && AL().rc != nullptr;
     const uint16_t rc = own ? AL().rc[cur_agent * MGX_WORLD_EPG + AL().lane] : d.obj_rc[so(slot)];
@@ -904,7 +960,7 @@ struct MgxEnvT {  // per-lane view of one env
       CP C = cls(cls_id);
       if (C[MGX_C_KIND] == MGX_KIND_AGENT) { flag(64u); return -1; }
       uint32_t n = d.num_objs[envi()];
-      if ((int)n >= d.S) { flag(8u); return -1; }
+      if ((int)n >= K::S(d)) { flag(8u); return -1; }
       d.num_objs[envi()] = n + 1;
       const int slot = (int)n;
       d.obj_cls[so(slot)] = (uint16_t)cls_id;
@@ -922,9 +978,9 @@ struct MgxEnvT {  // per-lane view of one env
       for (int t = 0; t < 256 && d.NL > 0; t++) {
         if (!(((uint32_t)C[MGX_C_TAGS + (t >> 5)] >> (t & 31)) & 1u)) continue;
         int li = tag_list(t);
-        if (li >= 0) { uint16_t k = tl_count(li); if (k < d.S) { tl_items(li)[k] = (uint16_t)slot; tl_count(li) = k + 1; } }
+        if (li >= 0) { uint16_t k = tl_count(li); if (k < K::S(d)) { tl_items(li)[k] = (uint16_t)slot; tl_count(li) = k + 1; } }
       }
-      if (C[MGX_C_AOE_COUNT] > 0) { uint16_t k = d.def_count[envi()]; d.def_aoe[(size_t)envi() * d.S + k] = (uint16_t)slot; d.def_count[envi()] = k + 1; }
+      if (C[MGX_C_AOE_COUNT] > 0) { uint16_t k = d.def_count[envi()]; d.def_aoe[(size_t)envi() * K::S(d) + k] = (uint16_t)slot; d.def_count[envi()] = k + 1; }
       return slot;
     }
   }
@@ -937,14 +993,14 @@ struct MgxEnvT {  // per-lane view of one env
         if (n >= d.NF) { flag(8u); continue; }
         size_t q = (size_t)envi() * d.NF + n;
         d.fx_obj[q] = (uint16_t)slot; d.fx_aoe[q] = (uint16_t)a; d.fx_rc[q] = d.obj_rc[so(slot)];
-        for (int ai = 0; ai < d.A; ai++) fx_in(n, ai) &= ~(1u << (n & 31));
+        for (int ai = 0; ai < K::A(d); ai++) fx_in(n, ai) &= ~(1u << (n & 31));
         d.fx_count[envi()] = n + 1;
       } else {
         uint16_t n = d.mb_count[envi()];
         if (n >= d.NM) { flag(8u); continue; }
         size_t q = (size_t)envi() * d.NM + n;
         d.mb_obj[q] = (uint16_t)slot; d.mb_aoe[q] = (uint16_t)a;
-        for (int ai = 0; ai < d.A; ai++) mb_in(n, ai) &= ~(1u << (n & 31));
+        for (int ai = 0; ai < K::A(d); ai++) mb_in(n, ai) &= ~(1u << (n & 31));
         d.mb_count[envi()] = n + 1;
       }
     }
@@ -956,7 +1012,7 @@ struct MgxEnvT {  // per-lane view of one env
       for (int f = 0; f < d.fx_count[envi()]; f++) {
         if (d.fx_obj[fb + f] != (uint16_t)slot) continue;
         PP a = aoe(d.fx_aoe[fb + f]);
-        for (int ai = 0; ai < d.A; ai++) {
+        for (int ai = 0; ai < K::A(d); ai++) {
           uint32_t& w = fx_in(f, ai);
           if ((w >> (f & 31)) & 1u) { w &= ~(1u << (f & 31)); presence(a, d.ag_obj[ao(ai)], -1); }
         }
@@ -968,7 +1024,7 @@ struct MgxEnvT {  // per-lane view of one env
       for (int f = 0; f < d.mb_count[envi()]; f++) {
         if (d.mb_obj[mb + f] != (uint16_t)slot) continue;
         PP a = aoe(d.mb_aoe[mb + f]);
-        for (int ai = 0; ai < d.A; ai++) {
+        for (int ai = 0; ai < K::A(d); ai++) {
           uint32_t& w = mb_in(f, ai);
           if ((w >> (f & 31)) & 1u) { w &= ~(1u << (f & 31)); presence(a, d.ag_obj[ao(ai)], -1); }
         }
@@ -1114,7 +1170,7 @@ struct MgxEnvT {  // per-lane view of one env
         uint16_t arc = d.obj_rc[so(c.actor)], trc = d.obj_rc[so(c.target)];
         int dr = min(max((int)(trc >> 8) - (int)(arc >> 8), -1), 1), dc = min(max((int)(trc & 0xFF) - (int)(arc & 0xFF), -1), 1);
         int nr = (trc >> 8) + dr, nc = (trc & 0xFF) + dc;
-        if (nr < 0 || nc < 0 || nr >= d.H || nc >= d.W || cell(nr, nc) != 0 || !move_object(c.target, nr, nc)) c.mutation_failed = true;
+        if (nr < 0 || nc < 0 || nr >= K::H(d) || nc >= K::W(d) || cell(nr, nc) != 0 || !move_object(c.target, nr, nc)) c.mutation_failed = true;
         break;
       }
       case MGX_MOP_SPAWN_OBJECT: {  // spawn_object_mutation.cpp:10-64
@@ -1136,7 +1192,7 @@ struct MgxEnvT {  // per-lane view of one env
         for (int k = 0; k < a2; k++)
           for (int dist = 1; dist <= range; dist++) {
             int r = (orc >> 8) + dirs[k * 2] * dist, cc = (orc & 0xFF) + dirs[k * 2 + 1] * dist;
-            if (r < 0 || cc < 0 || r >= d.H || cc >= d.W) break;
+            if (r < 0 || cc < 0 || r >= K::H(d) || cc >= K::W(d)) break;
             int ex = (int)cell(r, cc) - 1;
             if (ex >= 0) {
               bool blocker = false;
@@ -1289,7 +1345,7 @@ struct MgxEnvT {  // per-lane view of one env
   // actor = target = the tagged object (core/grid_object.cpp:83-91).
   __device__ __forceinline__ uint32_t* vm_words() const {
 #ifdef MGX_WORLD_IDS
-    return (uint32_t*)(mgx_dyn_lds + mgx_world_xlds_off(d.A)) + mgx_world_lane();
+    return (uint32_t*)(mgx_dyn_lds + mgx_world_xlds_off(K::A(d))) + mgx_world_lane();
 #else
     return nullptr;  // the handler VM only runs in the lane-per-env world kernels
 #endif
@@ -1489,10 +1545,10 @@ struct MgxEnvT {  // per-lane view of one env
   // them: the register VM of the lean variant runs them, frames and contexts in registers)
   __device__ __forceinline__ bool apply_top(int h, MgxCtx& c) const {
 #ifdef MGX_GEN_HANDLERS  // the unit carries straight-line code for one preset's handlers (mgx_handlers_gen.h)
-    if (d.gen_prog == MGX_GEN_ID) return MGX_GEN_HANDLERS<MgxEnvT>::top(*this, h, c);
+    if (K::gen_prog(d) == MGX_GEN_ID) return MGX_GEN_HANDLERS<MgxEnvT>::top(*this, h, c);
 #endif
     if constexpr (X) {
-      if (d.flat_top) return run_handler(h, c);
+      if (K::flat_top(d)) return run_handler(h, c);
       return vm_run(h, 0, 0, 0, c);
     } else {
       return run_handler(h, c);
@@ -1622,7 +1678,7 @@ struct MgxEnvT {  // per-lane view of one env
       PP a = aoe(d.mb_aoe[mb + m]);
       const int src = d.mb_obj[mb + m];
       const long long range = a[MGX_AO_RADIUS];
-      for (int ai = 0; ai < d.A; ai++) {
+      for (int ai = 0; ai < K::A(d); ai++) {
         const int tgt = d.ag_obj[ao(ai)];
         if (!a[MGX_AO_EFFECT_SELF] && src == tgt) continue;
         uint32_t& w = mb_in(m, ai);
@@ -1693,7 +1749,7 @@ struct MgxEnvT {  // per-lane view of one env
   // moved or changed tags), else computed on the spot.
   __device__ __forceinline__ int owner_at(int r, int c, int ti) const {
     if (d.terr_owner && !d.terr_dirty[envi()]) {
-      const uint16_t v = d.terr_owner[((size_t)envi() * d.NT + ti) * (size_t)(d.H * d.W) + r * d.W + c];
+      const uint16_t v = d.terr_owner[((size_t)envi() * d.NT + ti) * (size_t)(K::H(d) * K::W(d)) + r * K::W(d) + c];
       return v == 0xFFFF ? -1 : (int)v;
     }
     return cell_owner(r, c, ti);
@@ -1728,11 +1784,11 @@ struct MgxEnvT {  // per-lane view of one env
     const int dx = (orient == 2 || orient == 4 || orient == 6) ? -1 : (orient == 3 || orient == 5 || orient == 7) ? 1 : 0;
     const int dy = (orient == 0 || orient == 4 || orient == 5) ? -1 : (orient == 1 || orient == 6 || orient == 7) ? 1 : 0;
     PP mh = prog() + d.sec[MGX_SEC_MOVE_HANDLERS];
-    for (int k = 0; k < d.n_move_handlers; k++, mh += MGX_MH_WORDS) {
+    for (int k = 0; k < K::n_move_handlers(d); k++, mh += MGX_MH_WORDS) {
       uint16_t rc = (AL().rc && slot == cur_slot) ? AL().rc[cur_agent * MGX_WORLD_EPG + AL().lane] : d.obj_rc[so(slot)];
       for (int i = 1; i <= mh[MGX_MH_MAX_RANGE]; i++) {
         int r = (rc >> 8) + dy * i, c = (rc & 0xFF) + dx * i;
-        if (r < 0 || c < 0 || r >= d.H || c >= d.W) break;
+        if (r < 0 || c < 0 || r >= K::H(d) || c >= K::W(d)) break;
         int t = (int)cell(r, c) - 1;
         grid_dirty = 0;
         if (t < 0 && !mh[MGX_MH_ACCEPTS_EMPTY]) continue;
@@ -1758,7 +1814,7 @@ struct MgxEnvT {  // per-lane view of one env
     if (kind == MGX_AK_MOVE) ok = do_move(slot, ac[MGX_AC_ARG]);
     else if (kind == MGX_AK_VIBE) d.obj_vibe[so(slot)] = (uint8_t)ac[MGX_AC_ARG];  // actions/change_vibe.hpp:48-57
     MGX_TICK(6);
-    if (d.defer_book) {
+    if (K::defer_book(d)) {
       // Bookkeeping touches only this agent's own counters.  Here: the LDS copies and a result byte (in place of the
       // consumed action id); the HBM side — swm / prev_location write-back and the stat updates — is applied for all
       // agents in one batched pass (bookkeeping_flush), off the serial chain.
@@ -1766,7 +1822,7 @@ struct MgxEnvT {  // per-lane view of one env
       const bool moved = rc != prev;
       if (moved) { AL().swm[li] = 0; AL().prev[li] = rc; }
       else AL().swm[li] += 1;
-      AL().act[(stream * d.A + ai) * MGX_WORLD_EPG + AL().lane] = (int16_t)(1 | (kind << 1) | (ok ? 8 : 0) | (moved ? 16 : 0));
+      AL().act[(stream * K::A(d) + ai) * MGX_WORLD_EPG + AL().lane] = (int16_t)(1 | (kind << 1) | (ok ? 8 : 0) | (moved ? 16 : 0));
       cur_agent = cur_slot = -1;
       return ok;
     }
@@ -1810,8 +1866,8 @@ struct MgxEnvT {  // per-lane view of one env
     d.ag_covrc[ao(ai)] = rc;
     uint16_t sp = d.ag_spawn[ao(ai)];
     int r = rc >> 8, c = rc & 0xFF;
-    int bit = r * d.W + c;
-    uint32_t& w = d.ag_seen[ao(ai) * d.SEENW + (bit >> 5)];
+    int bit = r * K::W(d) + c;
+    uint32_t& w = d.ag_seen[ao(ai) * K::SEENW(d) + (bit >> 5)];
     uint32_t uniq = d.ag_unique[ao(ai)];
     if (!(w & (1u << (bit & 31)))) { w |= 1u << (bit & 31); d.ag_unique[ao(ai)] = ++uniq; }
     astat_set(ai, d.wk[MGX_S_CELL_UNIQUE], (float)uniq);
@@ -1828,8 +1884,8 @@ struct MgxEnvT {  // per-lane view of one env
   // (success or failed), action.failed (+1 per failed call, added one by one like the reference) and
   // max_steps_without_motion (set when a call's incremented counter exceeds it).
   __device__ MGX_BIG void bookkeeping_flush(int a_lo = 0, int a_hi = 1 << 30) const {   // agents [a_lo, min(a_hi, A))
-    const int A = min(d.A, a_hi), lane = AL().lane;
-    const int AS = d.A;   // stride of the vibe-stream result bytes
+    const int A = min(K::A(d), a_hi), lane = AL().lane;
+    const int AS = K::A(d);   // stride of the vibe-stream result bytes
     const int s_max = d.wk[MGX_S_MAX_STEPS_WITHOUT_MOTION], s_failed = d.wk[MGX_S_ACTION_FAILED];
     // the six result counters as scalars (a lane-varying index into d.wk would be a memory load per agent)
     const int w_noop_ok = d.wk[MGX_S_NOOP_SUCCESS], w_noop_no = d.wk[MGX_S_NOOP_SUCCESS + 1];
@@ -1857,7 +1913,7 @@ struct MgxEnvT {  // per-lane view of one env
         id0[q] = stat_of(res0[q]);
         id1[q] = stat_of(res1[q]);
         nfail[q] = ((res0[q] & 9) == 1 ? 1 : 0) + ((res1[q] & 9) == 1 ? 1 : 0);
-        const size_t sb = ao(i) * d.NSP;
+        const size_t sb = ao(i) * K::NSP(d);
         // unconditional loads (a dummy in-range cell when there is nothing to update): no branch between them, so
         // the whole chunk is in flight at once
         swm0[q] = d.ag_swm[ao(i)];
@@ -1865,14 +1921,14 @@ struct MgxEnvT {  // per-lane view of one env
         v1[q] = d.ag_stats[sb + max(id1[q], 0)];
         vf[q] = d.ag_stats[sb + max(s_failed, 0)];
         vm[q] = d.ag_stats[sb + max(s_max, 0)];
-        tw[q] = d.ag_touched[ao(i) * d.NSW + (max(s_max, 0) >> 5)];
+        tw[q] = d.ag_touched[ao(i) * K::NSW(d) + (max(s_max, 0) >> 5)];
       }
 #pragma unroll
       for (int q = 0; q < 8; q++) {
         const int i = i0 + q;
         if (i >= A || !((res0[q] | res1[q]) & 1)) continue;
         const int li = i * MGX_WORLD_EPG + lane;
-        const size_t sb = ao(i) * d.NSP;
+        const size_t sb = ao(i) * K::NSP(d);
         // replay the calls: a call that did not move increments the counter and may raise the max stat
         uint32_t swm = swm0[q];
         float mx = vm[q];
@@ -1888,7 +1944,7 @@ struct MgxEnvT {  // per-lane view of one env
         d.ag_prev[ao(i)] = AL().prev[li];
         if (set_max && s_max >= 0) {
           d.ag_stats[sb + s_max] = mx;
-          d.ag_touched[ao(i) * d.NSW + (s_max >> 5)] = tw[q] | (1u << (s_max & 31));
+          d.ag_touched[ao(i) * K::NSW(d) + (s_max >> 5)] = tw[q] | (1u << (s_max & 31));
         }
         if (id0[q] >= 0) d.ag_stats[sb + id0[q]] = __fadd_rn(v0[q], 1.f);
         if (id1[q] >= 0) d.ag_stats[sb + id1[q]] = __fadd_rn(v1[q], 1.f);
@@ -1901,14 +1957,14 @@ struct MgxEnvT {  // per-lane view of one env
     }
   }
 
-  // d.shadow: bookkeeping_flush + track_coverage_all in ONE pass over the agents, with the counters of the bookkeeping kept
+  // MgxDev::shadow: bookkeeping_flush + track_coverage_all in ONE pass over the agents, with the counters of the bookkeeping kept
   // as integers in the agent's 32-byte ag_cnt record instead of six cells of its stat row (one 128-byte line per agent
   // read and written back every step for +1.f on two of them): two 16-byte loads and stores.  The float cells — and
   // cell.unique_visited / cell.max_distance_from_spawn, which ag_unique / ag_maxdist already hold — are written by
   // mgx_shadow_flush_kernel before anything reads them.  (float)min(count, 2^24) is what count additions of 1.f give.
   __device__ MGX_BIG void tail_shadow(int a_lo = 0, int a_hi = 1 << 30) const {   // agents [a_lo, min(a_hi, A))
-    const int A = min(d.A, a_hi), lane = AL().lane;
-    const int AS = d.A;   // stride of the vibe-stream result bytes
+    const int A = min(K::A(d), a_hi), lane = AL().lane;
+    const int AS = K::A(d);   // stride of the vibe-stream result bytes
     const uint4* __restrict__ cnt = (const uint4*)d.ag_cnt;
     uint4* __restrict__ cnt_w = (uint4*)d.ag_cnt;
     for (int i0 = a_lo; i0 < A; i0 += 8) {
@@ -1933,9 +1989,9 @@ struct MgxEnvT {  // per-lane view of one env
       for (int q = 0; q < 8; q++) {   // second level, only for agents that moved
         const int i = i0 + q;
         if (i < A && rc8[q] != cov8[q]) {
-          const int bit = (rc8[q] >> 8) * d.W + (rc8[q] & 0xFF);
+          const int bit = (rc8[q] >> 8) * K::W(d) + (rc8[q] & 0xFF);
           sp8[q] = d.ag_spawn[ao(i)];
-          w8[q] = d.ag_seen[ao(i) * d.SEENW + (bit >> 5)];
+          w8[q] = d.ag_seen[ao(i) * K::SEENW(d) + (bit >> 5)];
           un8[q] = d.ag_unique[ao(i)];
           md8[q] = d.ag_maxdist[ao(i)];
         }
@@ -1945,10 +2001,10 @@ struct MgxEnvT {  // per-lane view of one env
         const int i = i0 + q;
         if (i < A && rc8[q] != cov8[q]) {   // track_coverage (objects/agent.cpp:49-57): the position changed since the last call
           const int r = rc8[q] >> 8, c = rc8[q] & 0xFF;
-          const int bit = r * d.W + c;
+          const int bit = r * K::W(d) + c;
           d.ag_covrc[ao(i)] = rc8[q];
           if (!(w8[q] & (1u << (bit & 31)))) {
-            d.ag_seen[ao(i) * d.SEENW + (bit >> 5)] = w8[q] | (1u << (bit & 31));
+            d.ag_seen[ao(i) * K::SEENW(d) + (bit >> 5)] = w8[q] | (1u << (bit & 31));
             d.ag_unique[ao(i)] = un8[q] + 1;
           }
           const int dist = abs((int)(sp8[q] >> 8) - r) + abs(c - (int)(sp8[q] & 0xFF));
@@ -1986,7 +2042,7 @@ struct MgxEnvT {  // per-lane view of one env
   // counters, action.failed, max steps without motion), each updated from the result bytes alone, so a load or store of the
   // wavefront is 1 KB of consecutive bytes; then coverage and the swm / prev_location write-back, one agent per lane.
   __device__ MGX_BIG void tail_shadow_flat(int wl, int wenv0) const {
-    const int A = d.A, n_flat = MGX_WORLD_LPW * A;
+    const int A = K::A(d), n_flat = MGX_WORLD_LPW * A;
     const size_t g0 = ((size_t)(blockIdx.x * MGX_WORLD_EPG) + wenv0) * A;
     const MgxALds al = AL();
     auto flat_li = [&](int p) {
@@ -2055,9 +2111,9 @@ struct MgxEnvT {  // per-lane view of one env
         const int p = (t0 + q) * MGX_WAVE + wl;
         if (p < n_flat && rc8[q] != cov8[q]) {
           const size_t g = g0 + p;
-          const int bit = (rc8[q] >> 8) * d.W + (rc8[q] & 0xFF);
+          const int bit = (rc8[q] >> 8) * K::W(d) + (rc8[q] & 0xFF);
           sp8[q] = d.ag_spawn[g];
-          w8[q] = d.ag_seen[g * d.SEENW + (bit >> 5)];
+          w8[q] = d.ag_seen[g * K::SEENW(d) + (bit >> 5)];
           un8[q] = d.ag_unique[g];
           md8[q] = d.ag_maxdist[g];
         }
@@ -2069,10 +2125,10 @@ struct MgxEnvT {  // per-lane view of one env
         const size_t g = g0 + p;
         if (rc8[q] != cov8[q]) {   // track_coverage (objects/agent.cpp:49-57): the position changed since the last call
           const int r = rc8[q] >> 8, c = rc8[q] & 0xFF;
-          const int bit = r * d.W + c;
+          const int bit = r * K::W(d) + c;
           d.ag_covrc[g] = rc8[q];
           if (!(w8[q] & (1u << (bit & 31)))) {
-            d.ag_seen[g * d.SEENW + (bit >> 5)] = w8[q] | (1u << (bit & 31));
+            d.ag_seen[g * K::SEENW(d) + (bit >> 5)] = w8[q] | (1u << (bit & 31));
             d.ag_unique[g] = un8[q] + 1;
           }
           const int dist = abs((int)(sp8[q] >> 8) - r) + abs(c - (int)(sp8[q] & 0xFF));
@@ -2096,7 +2152,7 @@ struct MgxEnvT {  // per-lane view of one env
 
   // bookkeeping_flush for ONE agent (the lane-per-agent kernel, mgx_act.h: every lane flushes its own agent)
   __device__ MGX_BIG void bookkeeping_flush_one(int i) const {
-    const int A = d.A, lane = AL().lane;
+    const int A = K::A(d), lane = AL().lane;
     const int s_max = d.wk[MGX_S_MAX_STEPS_WITHOUT_MOTION], s_failed = d.wk[MGX_S_ACTION_FAILED];
     const int li = i * MGX_WORLD_EPG + lane;
     const uint32_t res0 = (uint32_t)(uint16_t)AL().act[li], res1 = (uint32_t)(uint16_t)AL().act[A * MGX_WORLD_EPG + li];
@@ -2108,7 +2164,7 @@ struct MgxEnvT {  // per-lane view of one env
     };
     const int id0 = stat_of(res0), id1 = stat_of(res1);
     const int nfail = ((res0 & 9) == 1 ? 1 : 0) + ((res1 & 9) == 1 ? 1 : 0);
-    if (d.shadow) {   // the counters as integers in the agent's ag_cnt record (see tail_shadow)
+    if (K::shadow(d)) {   // the counters as integers in the agent's ag_cnt record (see tail_shadow)
       uint32_t swm = d.ag_swm[ao(i)];
       uint4 a = ((const uint4*)d.ag_cnt)[ao(i) * 2], b = ((const uint4*)d.ag_cnt)[ao(i) * 2 + 1];
 #pragma unroll
@@ -2130,12 +2186,12 @@ struct MgxEnvT {  // per-lane view of one env
       ((uint4*)d.ag_cnt)[ao(i) * 2 + 1] = b;
       return;
     }
-    const size_t sb = ao(i) * d.NSP;
+    const size_t sb = ao(i) * K::NSP(d);
     uint32_t swm = d.ag_swm[ao(i)];
     const float v0 = d.ag_stats[sb + max(id0, 0)], v1 = d.ag_stats[sb + max(id1, 0)];
     const float vf = d.ag_stats[sb + max(s_failed, 0)];
     float mx = d.ag_stats[sb + max(s_max, 0)];
-    const uint32_t tw = d.ag_touched[ao(i) * d.NSW + (max(s_max, 0) >> 5)];
+    const uint32_t tw = d.ag_touched[ao(i) * K::NSW(d) + (max(s_max, 0) >> 5)];
     bool set_max = false;
 #pragma unroll
     for (int call = 0; call < 2; call++) {
@@ -2148,7 +2204,7 @@ struct MgxEnvT {  // per-lane view of one env
     d.ag_prev[ao(i)] = AL().prev[li];
     if (set_max && s_max >= 0) {
       d.ag_stats[sb + s_max] = mx;
-      d.ag_touched[ao(i) * d.NSW + (s_max >> 5)] = tw | (1u << (s_max & 31));
+      d.ag_touched[ao(i) * K::NSW(d) + (s_max >> 5)] = tw | (1u << (s_max & 31));
     }
     // (id0 == id1 cannot happen: the primary stream never holds a vibe action, the vibe stream nothing else)
     if (id0 >= 0) d.ag_stats[sb + id0] = __fadd_rn(v0, 1.f);
@@ -2200,7 +2256,7 @@ struct MgxEnvT {  // per-lane view of one env
   // track_coverage of every agent (mettagrid_c.cpp:1054-1056).  Agents are independent here, so the loads of eight
   // of them are issued together.  Both stat keys exist since Agent::init (mgx_init_kernel calls track_coverage).
   __device__ MGX_BIG void track_coverage_all(int a_lo = 0, int a_hi = 1 << 30) const {   // agents [a_lo, min(a_hi, A))
-    const int A = min(d.A, a_hi), lane = AL().lane;
+    const int A = min(K::A(d), a_hi), lane = AL().lane;
     const int su = d.wk[MGX_S_CELL_UNIQUE], sm = d.wk[MGX_S_CELL_MAXDIST];
     for (int i0 = a_lo; i0 < A; i0 += 8) {
       uint16_t rc8[8], cov8[8];
@@ -2216,9 +2272,9 @@ struct MgxEnvT {  // per-lane view of one env
       for (int q = 0; q < 8; q++) {
         const int i = i0 + q;
         if (i < A && rc8[q] != cov8[q]) {
-          const int bit = (rc8[q] >> 8) * d.W + (rc8[q] & 0xFF);
+          const int bit = (rc8[q] >> 8) * K::W(d) + (rc8[q] & 0xFF);
           sp8[q] = d.ag_spawn[ao(i)];
-          w8[q] = d.ag_seen[ao(i) * d.SEENW + (bit >> 5)];
+          w8[q] = d.ag_seen[ao(i) * K::SEENW(d) + (bit >> 5)];
           un8[q] = d.ag_unique[ao(i)];
           md8[q] = d.ag_maxdist[ao(i)];
         }
@@ -2228,18 +2284,18 @@ struct MgxEnvT {  // per-lane view of one env
         const int i = i0 + q;
         if (i < A && rc8[q] != cov8[q]) {
           const int r = rc8[q] >> 8, c = rc8[q] & 0xFF;
-          const int bit = r * d.W + c;
+          const int bit = r * K::W(d) + c;
           d.ag_covrc[ao(i)] = rc8[q];
           uint32_t uniq = un8[q];
           if (!(w8[q] & (1u << (bit & 31)))) {
-            d.ag_seen[ao(i) * d.SEENW + (bit >> 5)] = w8[q] | (1u << (bit & 31));
+            d.ag_seen[ao(i) * K::SEENW(d) + (bit >> 5)] = w8[q] | (1u << (bit & 31));
             d.ag_unique[ao(i)] = ++uniq;
           }
-          if (su >= 0) d.ag_stats[ao(i) * d.NSP + su] = (float)uniq;
+          if (su >= 0) d.ag_stats[ao(i) * K::NSP(d) + su] = (float)uniq;
           const int dist = abs((int)(sp8[q] >> 8) - r) + abs(c - (int)(sp8[q] & 0xFF));
           const uint32_t md = max(md8[q], (uint32_t)dist);
           d.ag_maxdist[ao(i)] = md;
-          if (sm >= 0) d.ag_stats[ao(i) * d.NSP + sm] = (float)md;
+          if (sm >= 0) d.ag_stats[ao(i) * K::NSP(d) + sm] = (float)md;
         }
       }
     }
@@ -2329,28 +2385,29 @@ __device__ __forceinline__ void mgx_shuffle_order(const ENV& e, uint8_t* order, 
 
 // The cell a staged action `a` of an agent standing on `own` ((r << 8) | c) acts on: (r << 8) | c of the cell ahead for a move
 // that stays on the map, -1 otherwise (orientation.hpp:28-48).
-template <class PP>
+template <class K, class PP>
 __device__ __forceinline__ int mgx_move_target(const MgxDev& d, PP acts, int a, uint32_t own) {
-  if (a < 0 || a >= d.nact || acts[a * MGX_AC_WORDS + MGX_AC_KIND] != MGX_AK_MOVE) return -1;
+  if (a < 0 || a >= K::nact(d) || acts[a * MGX_AC_WORDS + MGX_AC_KIND] != MGX_AK_MOVE) return -1;
   const int orient = acts[a * MGX_AC_WORDS + MGX_AC_ARG];
   const int dx = (orient == 2 || orient == 4 || orient == 6) ? -1 : (orient == 3 || orient == 5 || orient == 7) ? 1 : 0;
   const int dy = (orient == 0 || orient == 4 || orient == 5) ? -1 : (orient == 1 || orient == 6 || orient == 7) ? 1 : 0;
   const int r = (int)(own >> 8) + dy, c = (int)(own & 0xFF) + dx;
-  return (r >= 0 && c >= 0 && r < d.H && c < d.W) ? ((r << 8) | c) : -1;
+  return (r >= 0 && c >= 0 && r < K::H(d) && c < K::W(d)) ? ((r << 8) | c) : -1;
 }
 
 // One agent's action of one stream (the body of the dispatch loop, mettagrid_c.cpp:966-999): invalid-index bookkeeping,
 // the stream / kind check, ActionHandler::handle_action and the executed / success rows.
 template <class ENV, class PP>
 __device__ __forceinline__ void mgx_dispatch_one(const ENV& e, const MgxDev& d, PP acts, const MgxALds& al, int ai, int stream, int lane, int repeats) {
-  const int A = d.A;
+  typedef typename ENV::Shape K;
+  const int A = K::A(d);
   int a = al.act[(stream * A + ai) * MGX_WORLD_EPG + lane];
-  if (a < 0 || a >= d.nact) {  // _handle_invalid_action :914-919
+  if (a < 0 || a >= K::nact(d)) {  // _handle_invalid_action :914-919
     a = (stream == 0 ? d.actions : d.vibe_actions)[e.ao(ai)];  // the raw index (the staged copy is saturated to int16)
     for (int rep = 0; rep < repeats; rep++) {
       e.astat_add(ai, d.wk[MGX_S_INVALID_INDEX], 1.f);
       if (a < 0 && a >= -MGX_INVALID_WINDOW) e.astat_add(ai, d.wk[MGX_S_INVALID_NEG_BASE] + a + MGX_INVALID_WINDOW, 1.f);
-      else if (a >= d.nact && a < d.nact + MGX_INVALID_WINDOW) e.astat_add(ai, d.wk[MGX_S_INVALID_POS_BASE] + a - d.nact, 1.f);
+      else if (a >= K::nact(d) && a < K::nact(d) + MGX_INVALID_WINDOW) e.astat_add(ai, d.wk[MGX_S_INVALID_POS_BASE] + a - K::nact(d), 1.f);
       else e.invalid_extra(ai, a);
     }
     d.success[e.ao(ai)] = 0;
@@ -2372,12 +2429,13 @@ __device__ __forceinline__ void mgx_dispatch_one(const ENV& e, const MgxDev& d, 
 // MGX_PH_EVENTS = timestep events + the serial per-agent on_tick loop (part of MGX_PH_ACTIONS' launch unless the dispatch
 // itself ran in mgx_act_kernel).
 enum { MGX_PH_ACTIONS = 1, MGX_PH_AOE = 2, MGX_PH_TAIL = 4, MGX_PH_EVENTS = 8, MGX_PH_ALL = 15 };
-template <class PP, bool X>
+template <class PP, bool X, class K>
 __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* order, MgxXLds xl, MgxALds al, int lane, int env, int phases,
                                                const bool helper = false) {
-  MgxEnvT<PP, X> e(d, P, env);
+  MgxEnvT<PP, X, K> e(d, P, env);
   e.xl = xl;
-  const int A = d.A;
+  const int A = K::A(d);
+  const bool cls_staged = K::fixed ? MGX_CLS_STAGED != 0 : al.cls != nullptr;   // (a constant either way: mgx_world_alds)
   MGX_TICK0();
   if constexpr (!X) phases = MGX_PH_ALL;
   const bool act = (phases & MGX_PH_ACTIONS) != 0;
@@ -2399,7 +2457,7 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
     wl = (int)(threadIdx.x & (MGX_WAVE - 1));
     wenv0 = (int)(threadIdx.x >> 6) * MGX_WORLD_LPW;
     genv0 = (int)(blockIdx.x * MGX_WORLD_EPG) + wenv0;
-    coop = d.coop_passes != 0 && (phases & MGX_PH_ACTIONS) != 0 && genv0 + MGX_WORLD_LPW <= d.E;
+    coop = K::coop_passes(d) != 0 && (phases & MGX_PH_ACTIONS) != 0 && genv0 + MGX_WORLD_LPW <= d.E;
     n_flat = MGX_WORLD_LPW * A;
     g0 = (size_t)genv0 * A;
   }
@@ -2416,7 +2474,7 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
     if (act && !helper) d.step[env] = e.step;
   }
   if constexpr (X) {
-    if (phases == MGX_PH_EVENTS && !(d.any_on_tick && !d.tick_in_aoe)) {  // launched behind mgx_act_kernel: most steps have no event due
+    if (phases == MGX_PH_EVENTS && !(K::any_on_tick(d) && !K::tick_in_aoe(d))) {  // launched behind mgx_act_kernel: most steps have no event due
       const uint32_t k = d.next_event[env];
       if (k >= (uint32_t)d.n_schedule || (uint32_t)d.P[d.sec[MGX_SEC_SCHEDULE] + k * MGX_SC_WORDS + MGX_SC_TIMESTEP] > e.step) return;
     }
@@ -2441,7 +2499,7 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
 
   // ---- stage every agent's own state + both action streams in LDS.  The loads of one chunk are independent, so
   // they are all in flight together instead of one HBM round trip per agent inside the serial loop below. ----
-  const bool want_stepprev = (d.flags & MGX_G_LAST_ACTION_MOVE) != 0;
+  const bool want_stepprev = (K::flags(d) & MGX_G_LAST_ACTION_MOVE) != 0;
   if (coop) {   // eight trips of the flat run at a time: every load is one to four whole lines
     for (int t0 = 0; t0 * MGX_WAVE < n_flat; t0 += 8) {
       uint16_t slot8[8], prev8[8], rc8[8], cls8[8];
@@ -2464,7 +2522,7 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
         if (p < n_flat) {
           const int li = flat_li(p);
           al.slot[li] = slot8[q]; al.rc[li] = rc8[q]; al.prev[li] = prev8[q]; al.swm[li] = swm8[q];
-          if (al.cls) al.cls[li] = cls8[q];
+          if (cls_staged) al.cls[li] = cls8[q];
           al.act[li] = mgx_sat16(a8[q]); al.act[A * MGX_WORLD_EPG + li] = mgx_sat16(v8[q]);
           if (want_stepprev) d.ag_stepprev[g0 + p] = rc8[q];  // mettagrid_c.cpp:929-931
           order[li] = (uint8_t)(li / MGX_WORLD_EPG);
@@ -2493,7 +2551,7 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
       if (i < a_hi) {
         int li = i * MGX_WORLD_EPG + lane;
         al.slot[li] = slot8[q]; al.rc[li] = rc8[q]; al.prev[li] = prev8[q]; al.swm[li] = swm8[q];
-        if (al.cls) al.cls[li] = cls8[q];
+        if (cls_staged) al.cls[li] = cls8[q];
         al.act[li] = mgx_sat16(a8[q]); al.act[A * MGX_WORLD_EPG + li] = mgx_sat16(v8[q]);
         if (want_stepprev && act) d.ag_stepprev[e.ao(i)] = rc8[q];  // mettagrid_c.cpp:929-931
         order[li] = (uint8_t)i;
@@ -2510,13 +2568,13 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
   bool mf = false;
 #if MGX_HELPERS_ON
   if constexpr (HELP) {
-    mf = d.move_fast != 0 && d.duo != 0 && act;
+    mf = K::move_fast(d) != 0 && K::duo(d) != 0 && act;
     if (mf) {
       uint8_t* pre = e.mf_pre();
       uint32_t* dirty = e.mf_dirty();
       if (!helper)
-        for (int w = 0; w < d.mf_dirty_words; w++) dirty[w * MGX_WORLD_EPG + lane] = 0u;
-      const size_t HW = (size_t)d.H * d.W;
+        for (int w = 0; w < K::mf_dirty_words(d); w++) dirty[w * MGX_WORLD_EPG + lane] = 0u;
+      const size_t HW = (size_t)K::H(d) * K::W(d);
       const int n_el = coop ? n_flat : a_hi;
       for (int i0 = coop ? 0 : a_lo; i0 < (coop ? (n_flat + MGX_WAVE - 1) / MGX_WAVE : a_hi); i0 += 8) {
         int li8[8];
@@ -2532,15 +2590,15 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
             if (coop) env8[q] = (size_t)(genv0 + ew);
             li8[q] = li;
             const int a = al.act[li];
-            const int kind = (a < 0 || a >= d.nact) ? 3 : min((int)acts[a * MGX_AC_WORDS + MGX_AC_KIND], 3);
-            const int t = mgx_move_target(d, acts, a, al.rc[li]);
+            const int kind = (a < 0 || a >= K::nact(d)) ? 3 : min((int)acts[a * MGX_AC_WORDS + MGX_AC_KIND], 3);
+            const int t = mgx_move_target<K>(d, acts, a, al.rc[li]);
             kd8[q] = (uint32_t)(kind << 2);
             if (kind == MGX_AK_MOVE) kd8[q] |= ((uint32_t)acts[a * MGX_AC_WORDS + MGX_AC_ARG] & 7u) << 4 | (t < 0 ? 0x80u : 0u);
-            if (t >= 0) cv8[q] = d.grid[env8[q] * HW + (size_t)((t >> 8) * d.W + (t & 0xFF))];
+            if (t >= 0) cv8[q] = d.grid[env8[q] * HW + (size_t)((t >> 8) * K::W(d) + (t & 0xFF))];
           }
         }
 #pragma unroll
-        for (int q = 0; q < 8; q++) cls8[q] = cv8[q] ? (uint32_t)d.obj_cls[env8[q] * d.S + (cv8[q] - 1u)] : 0u;   // level 2
+        for (int q = 0; q < 8; q++) cls8[q] = cv8[q] ? (uint32_t)d.obj_cls[env8[q] * K::S(d) + (cv8[q] - 1u)] : 0u;   // level 2
 #pragma unroll
         for (int q = 0; q < 8; q++)
           if (li8[q] >= 0) {   // cell ahead (0 empty, 1 no on_use, 2 on_use) | kind << 2 (3: general path) | orientation << 4 | off the map << 7
@@ -2556,13 +2614,13 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __builtin_amdgcn_wave_barrier();
   }
-  const bool split_tick = HELP && d.tick_split != 0;   // the agents' on_tick handlers stay with their agent: the pair shares them
+  const bool split_tick = HELP && K::tick_split(d) != 0;   // the agents' on_tick handlers stay with their agent: the pair shares them
   if (!helper && act) mgx_shuffle_order(e, order, lane, A);
   // Action dispatch (mettagrid_c.cpp:966-999).  The reference loops over priority levels max..0 and, inside each,
   // over the primary then the vibe stream.  Every real action handler has priority 0 and the only thing the
   // higher (empty) levels do is repeat the invalid-index bookkeeping, so one pass per stream with the invalid-index
   // stats added (max_priority + 1) times is equivalent — the stat keys involved are touched by nothing else.
-  const int repeats = d.max_priority + 1;
+  const int repeats = K::max_priority(d) + 1;
   MGX_TICK(1);
   // MgxDev::duo (MGX_WORLD_HELPERS): the env's own lane runs the next agent a of the order and its helper lane the agent b
   // behind it IN THE SAME TRIP when their cell footprints {own cell, cell ahead} are disjoint — then nothing a's action
@@ -2574,7 +2632,7 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
   bool duo = false;
 #if MGX_HELPERS_ON
   if constexpr (HELP) {
-    duo = d.duo != 0 && act;
+    duo = K::duo(d) != 0 && act;
     if (duo) {
       e.duo_on = true;
       if (!helper) {
@@ -2592,7 +2650,7 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
       // its own bookkeeping and nothing reads either before the stream ends, so the order of the agents cannot be observed
       // — one straight pass per lane over its half of the agents (this lane's and its helper's), without the trip loop's
       // pairing, fences and the call into handle_action (measured: 6 000 cycles per trip for one store).
-      if (stream == 1 && d.defer_book && coop) {
+      if (stream == 1 && K::defer_book(d) && coop) {
         // ... and over the flat run when the wavefront walks it together.  An invalid index needs the stat rows of its env's
         // own lanes (MgxEnvT works on the lane's env): the flat pass marks it (-1: the raw index is read again from HBM), and
         // only when the wavefront has one the envs' lanes walk their agents for the marked entries.  Their bookkeeping touches
@@ -2604,9 +2662,9 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
           int ew;
           const int li = flat_li(p, &ew), ri = A * MGX_WORLD_EPG + li;
           const int a = al.act[ri];
-          if (a < 0 || a >= d.nact) { al.act[ri] = -1; invalid = true; continue; }
+          if (a < 0 || a >= K::nact(d)) { al.act[ri] = -1; invalid = true; continue; }
           if (acts[a * MGX_AC_WORDS + MGX_AC_KIND] != MGX_AK_VIBE) { al.act[ri] = 0; continue; }
-          d.obj_vibe[(size_t)(genv0 + ew) * d.S + al.slot[li]] = (uint8_t)acts[a * MGX_AC_WORDS + MGX_AC_ARG];
+          d.obj_vibe[(size_t)(genv0 + ew) * K::S(d) + al.slot[li]] = (uint8_t)acts[a * MGX_AC_WORDS + MGX_AC_ARG];
           const uint16_t rc = al.rc[li], prev = al.prev[li];
           const bool moved = rc != prev;
           if (moved) { al.swm[li] = 0; al.prev[li] = rc; }
@@ -2625,11 +2683,11 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
         MGX_TICK(3);
         continue;
       }
-      if (stream == 1 && d.defer_book) {
+      if (stream == 1 && K::defer_book(d)) {
         for (int i = a_lo; i < a_hi; i++) {
           const int li = i * MGX_WORLD_EPG + lane, ri = (A + i) * MGX_WORLD_EPG + lane;
           const int a = al.act[ri];
-          if (a < 0 || a >= d.nact) { mgx_dispatch_one(e, d, acts, al, i, 1, lane, repeats); continue; }   // invalid index: the general path
+          if (a < 0 || a >= K::nact(d)) { mgx_dispatch_one(e, d, acts, al, i, 1, lane, repeats); continue; }   // invalid index: the general path
           if (acts[a * MGX_AC_WORDS + MGX_AC_KIND] != MGX_AK_VIBE) { al.act[ri] = 0; continue; }           // wrong stream: no call
           d.obj_vibe[e.so(al.slot[li])] = (uint8_t)acts[a * MGX_AC_WORDS + MGX_AC_ARG];
           const uint16_t rc = al.rc[li], prev = al.prev[li];   // handle_action's bookkeeping (action_handler.hpp:78-105), deferred form
@@ -2665,13 +2723,14 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
           // registers.  Under this kernel's register pressure a table field used inside the loop is re-read there by a vector
           // load, and a load behind the run's stores waits for every one of them (measured: one store round trip per
           // consumed agent, slower than the trip loop it replaces).  The loop itself issues LDS accesses and stores only.
-          int mW = d.W, mHW = d.H * d.W, mA = A, mS = d.S, mFl = d.move_fast, mMask = d.mf_exact ? -1 : d.mf_dirty_words * 32 - 1;
+          int mW = K::W(d), mHW = K::H(d) * K::W(d), mA = A, mS = K::S(d), mFl = K::move_fast(d), mMask = K::mf_exact(d) ? -1 : K::mf_dirty_words(d) * 32 - 1;
           const int alds0 = (A * MGX_WORLD_EPG + 15) & ~15;   // (mgx_world_alds)
           int oSwm = alds0, oAct = alds0 + A * MGX_WORLD_EPG * 4, oSlot = alds0 + A * MGX_WORLD_EPG * 8;
-          int oPre = d.mf_lds_off;
+          int oPre = K::mf_lds_off(d);
           uint16_t* gGrid = d.grid; uint16_t* gObjRc = d.obj_rc; uint16_t* gAgRc = d.ag_rc;
           int32_t* gEx = d.executed; uint8_t* gSu = d.success;
-          asm volatile("" : "+s"(mW), "+s"(mHW), "+s"(mA), "+s"(mS), "+s"(mFl), "+s"(mMask), "+s"(oSwm), "+s"(oAct), "+s"(oSlot), "+s"(oPre));
+          if constexpr (!K::fixed)   // (a fixed shape: immediates, nothing to pin)
+            asm volatile("" : "+s"(mW), "+s"(mHW), "+s"(mA), "+s"(mS), "+s"(mFl), "+s"(mMask), "+s"(oSwm), "+s"(oAct), "+s"(oSlot), "+s"(oPre));
           asm volatile("" : "+s"(gGrid), "+s"(gObjRc), "+s"(gAgRc), "+s"(gEx), "+s"(gSu));
           if (!helper) {
             const int oRc = oSlot + mA * MGX_WORLD_EPG * 2, oPrev = oRc + mA * MGX_WORLD_EPG * 2;
@@ -2753,12 +2812,12 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
             const uint32_t own = al.rc[ai * MGX_WORLD_EPG + lane];
             uint32_t tgt = own;
             const int a = al.act[ai * MGX_WORLD_EPG + lane];
-            if (a >= 0 && a < d.nact && acts[a * MGX_AC_WORDS + MGX_AC_KIND] == MGX_AK_MOVE && d.n_move_handlers > 0) {
+            if (a >= 0 && a < K::nact(d) && acts[a * MGX_AC_WORDS + MGX_AC_KIND] == MGX_AK_MOVE && K::n_move_handlers(d) > 0) {
               const int orient = acts[a * MGX_AC_WORDS + MGX_AC_ARG];  // orientation.hpp:28-48
               const int dx = (orient == 2 || orient == 4 || orient == 6) ? -1 : (orient == 3 || orient == 5 || orient == 7) ? 1 : 0;
               const int dy = (orient == 0 || orient == 4 || orient == 5) ? -1 : (orient == 1 || orient == 6 || orient == 7) ? 1 : 0;
               const int r = (int)(own >> 8) + dy, c = (int)(own & 0xFF) + dx;
-              if (r >= 0 && c >= 0 && r < d.H && c < d.W) tgt = (uint32_t)((r << 8) | c);
+              if (r >= 0 && c >= 0 && r < K::H(d) && c < K::W(d)) tgt = (uint32_t)((r << 8) | c);
             }
             F = (own << 16) | tgt;
           }
@@ -2807,7 +2866,7 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
     if (duo) {   // the surviving game-stat sets (mgx_act.h mgx_act_apply_gsets)
       if (!helper) {
         unsigned long long* cells = e.act_gset_cells();
-        for (int k = 0; k < d.act_ngset; k++) {
+        for (int k = 0; k < K::act_ngset(d); k++) {
           const unsigned long long w = cells[k * MGX_WORLD_EPG + lane];
           if (w) e.gstat_set(d.act_gset_ids[k], __uint_as_float((uint32_t)w));
         }
@@ -2820,11 +2879,11 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
   if constexpr (X) {
     if (evt && d.n_schedule > 0) e.process_events();  // mettagrid_c.cpp:1009-1011
   }
-  if (d.any_on_tick && evt && !d.tick_in_aoe && !split_tick) {
+  if (K::any_on_tick(d) && evt && !K::tick_in_aoe(d) && !split_tick) {
     for (int i = 0; i < A; i++) {  // per-agent on_tick (mettagrid_c.cpp:1019-1024); slot and class come from LDS
       const int li = i * MGX_WORLD_EPG + lane;
       const int slot = al.slot[li];
-      const int h = (al.cls ? e.cls(al.cls[li]) : e.cls_of(slot))[MGX_C_ON_TICK];
+      const int h = (cls_staged ? e.cls(al.cls[li]) : e.cls_of(slot))[MGX_C_ON_TICK];
       if (h >= 0) {
         MgxCtx c = mgx_ctx(slot, slot);
         e.apply_top(h, c);
@@ -2841,7 +2900,7 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
     if (d.NM > 0) e.apply_mobile();  // :1038
     if (d.def_aoe) {                 // AOETracker::flush_deferred :1042
       int n = d.def_count[env];
-      for (int k = 0; k < n; k++) e.register_aoes(d.def_aoe[(size_t)env * d.S + k]);
+      for (int k = 0; k < n; k++) e.register_aoes(d.def_aoe[(size_t)env * K::S(d) + k]);
       d.def_count[env] = 0;
     }
    }
@@ -2856,11 +2915,11 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
     __builtin_amdgcn_wave_barrier();
   }
   if constexpr (HELP) {
-    if (d.any_on_tick && evt && split_tick) {
+    if (K::any_on_tick(d) && evt && split_tick) {
       for (int i = a_lo; i < a_hi; i++) {  // per-agent on_tick (mettagrid_c.cpp:1019-1024), each lane of the pair its half
         const int li = i * MGX_WORLD_EPG + lane;
         const int slot = al.slot[li];
-        const int h = (al.cls ? e.cls(al.cls[li]) : e.cls_of(slot))[MGX_C_ON_TICK];
+        const int h = (cls_staged ? e.cls(al.cls[li]) : e.cls_of(slot))[MGX_C_ON_TICK];
         if (h >= 0) {
           MgxCtx c = mgx_ctx(slot, slot);
           e.apply_top(h, c);
@@ -2870,12 +2929,12 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
   }
   MGX_TICK(4);
 #if MGX_HELPERS_ON
-  if (!X && d.shadow == 3 && coop) e.tail_shadow_flat(wl, wenv0);
+  if (!X && K::shadow(d) == 3 && coop) e.tail_shadow_flat(wl, wenv0);
   else
 #endif
-  if (!X && d.shadow == 3 && act) e.tail_shadow(a_lo, a_hi);   // (d.shadow implies d.defer_book)
+  if (!X && K::shadow(d) == 3 && act) e.tail_shadow(a_lo, a_hi);   // (shadow implies defer_book)
   else {
-    if (d.defer_book && act) e.bookkeeping_flush(a_lo, a_hi);
+    if (K::defer_book(d) && act) e.bookkeeping_flush(a_lo, a_hi);
     if (phases & MGX_PH_TAIL) e.track_coverage_all(a_lo, a_hi);
   }
   MGX_TICK(5);
@@ -2883,7 +2942,7 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
 
 // PROG_LDS: the program blob is first copied into LDS (16-byte coalesced loads) and every table lookup of the
 // handler VM becomes a ds_read.
-template <bool PROG_LDS, bool X>
+template <bool PROG_LDS, bool X, class K = MgxWorldShapeDyn>
 __device__ __forceinline__ void mgx_world_entry(const MgxDev& d, int prog_words, int phases = MGX_PH_ALL) {
   uint8_t* order = mgx_dyn_lds;
   const int lane = mgx_world_lane();
@@ -2893,8 +2952,8 @@ __device__ __forceinline__ void mgx_world_entry(const MgxDev& d, int prog_words,
   MgxXLds xl;
   xl.lane = lane;
   xl.stride = MGX_WORLD_EPG;
-  const MgxALds al = mgx_world_alds(mgx_dyn_lds, d.A, lane);
-  int off = ((d.A * MGX_WORLD_EPG + 15) & ~15) + ((mgx_world_alds_bytes(d.A) + 15) & ~15);
+  const MgxALds al = mgx_world_alds(mgx_dyn_lds, K::A(d), lane);
+  int off = ((K::A(d) * MGX_WORLD_EPG + 15) & ~15) + ((mgx_world_alds_bytes(K::A(d)) + 15) & ~15);
   if (X) {
     off += MGX_VM_WORDS * MGX_WORLD_EPG * 4;
     xl.def_delta = (int*)(mgx_dyn_lds + off);   // (both only exist — and are only touched — with the in-kernel AoE phase)
@@ -2914,10 +2973,10 @@ __device__ __forceinline__ void mgx_world_entry(const MgxDev& d, int prog_words,
     for (int i = threadIdx.x; i < prog_words / 4; i += blockDim.x) dst[i] = src[i];
     __syncthreads();
     if ((!active && !helper) || env >= d.E) return;
-    mgx_world_body<MgxLdsProg, X>(d, (MgxLdsProg)lprog, order, xl, al, lane, env, phases, helper);
+    mgx_world_body<MgxLdsProg, X, K>(d, (MgxLdsProg)lprog, order, xl, al, lane, env, phases, helper);
   } else {
     if ((!active && !helper) || env >= d.E) return;
-    mgx_world_body<MgxGlobalProg, X>(d, d.P, order, xl, al, lane, env, phases, helper);
+    mgx_world_body<MgxGlobalProg, X, K>(d, d.P, order, xl, al, lane, env, phases, helper);
   }
 }
 

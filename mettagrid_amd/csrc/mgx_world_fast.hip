@@ -32,6 +32,7 @@
 #include "mgx_device.h"
 #include "mgx_world.h"
 #include "mgx_host.h"
+#include "mgx_presets_gen.h"   // MgxWorldShapeR3: the preset's shape (mettagrid_amd/gen_presets.py, written at build())
 
 #ifdef MGX_WORLD_WPE
 #define MGX_WPE_ATTR __attribute__((amdgpu_waves_per_eu(MGX_WORLD_WPE, MGX_WORLD_WPE)))
@@ -47,11 +48,27 @@ template <bool PROG_LDS>
 __global__ void __launch_bounds__(MGX_WORLD_THREADS) MGX_WPE_ATTR mgx_world_kernel_fast(int prog_words) {
   mgx_world_entry<PROG_LDS, false>(g_mgx_dev, prog_words);
 }
+// The instance compiled for ONE shape (MgxWorldShape, mgx_world.h): every scalar of the table is a constant.  Only the form
+// with the program copy in LDS is built — the one the preset launches; each instance takes minutes to compile.  Not in the
+// sanitizer build (its planner never chooses it) nor in a unit without the preset's generated handlers.
+#if defined(MGX_GEN_HANDLERS) && !defined(MGX_CPU_EMU)
+#define MGX_WORLD_PRESET_INSTANCE 1
+#endif
+#ifdef MGX_WORLD_PRESET_INSTANCE
+template <class K>
+__global__ void __launch_bounds__(MGX_WORLD_THREADS) MGX_WPE_ATTR mgx_world_kernel_fast_shape(int prog_words) {
+  mgx_world_entry<true, false, K>(g_mgx_dev, prog_words);
+}
+#endif
 }  // namespace
 
 static MgxLdsLimit g_lds_limit;
 bool MGX_CAT(mgx_world_fast_set_lds_s, MGX_SLOT)(size_t lds) {
-  return g_lds_limit.raise_current({(const void*)mgx_world_kernel_fast<true>, (const void*)mgx_world_kernel_fast<false>}, lds);
+  return g_lds_limit.raise_current({(const void*)mgx_world_kernel_fast<true>, (const void*)mgx_world_kernel_fast<false>,
+#ifdef MGX_WORLD_PRESET_INSTANCE
+                                    (const void*)mgx_world_kernel_fast_shape<MgxWorldShapeR3>,
+#endif
+                                   }, lds);
 }
 
 #if MGX_SLOT == 0
@@ -59,9 +76,16 @@ size_t mgx_world_fast_lds_bytes(int A) { return (size_t)mgx_world_lds_fixed(A, f
 #endif
 
 static MgxConstDev g_const_dev;   // keeps this slot's g_mgx_dev equal to the launching engine's MgxDev
-void MGX_CAT(mgx_launch_world_fast_s, MGX_SLOT)(bool prog_lds, size_t lds, hipStream_t stream, const MgxDev& d, int prog_words) {
+// variant: MgxPlan::world_variant — 3 asks for the preset's instance; the table is compared with its shape once more here, field
+// by field (it may have changed since mgx_create: mgx_attach_code), and anything else runs the generic kernels.
+void MGX_CAT(mgx_launch_world_fast_s, MGX_SLOT)(bool prog_lds, int variant, size_t lds, hipStream_t stream, const MgxDev& d, int prog_words) {
   const auto lock = g_const_dev.upload(&g_mgx_dev, d, stream, __func__);
   dim3 grid((d.E + MGX_WORLD_EPG - 1) / MGX_WORLD_EPG), block(MGX_WORLD_THREADS);
+#ifdef MGX_WORLD_PRESET_INSTANCE
+  if (variant == 3 && prog_lds && mgx_world_shape_matches<MgxWorldShapeR3>(d))
+    hipLaunchKernelGGL((mgx_world_kernel_fast_shape<MgxWorldShapeR3>), grid, block, lds, stream, prog_words);
+  else
+#endif
   if (prog_lds) hipLaunchKernelGGL((mgx_world_kernel_fast<true>), grid, block, lds, stream, prog_words);
   else hipLaunchKernelGGL((mgx_world_kernel_fast<false>), grid, block, lds, stream, prog_words);
 }

@@ -202,10 +202,12 @@ def load_lib():
         L.mgx_unpack_rows.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     for name in ("mgx_num_envs", "mgx_num_agents", "mgx_num_tokens", "mgx_obs_variant", "mgx_act_variant", "mgx_handler_variant",
                  "mgx_world_prog_in_lds", "mgx_is_extended", "mgx_dispatch_pairs", "mgx_integer_bookkeeping",
-                 "mgx_create_paths", "mgx_move_fast"):
+                 "mgx_create_paths", "mgx_move_fast", "mgx_world_variant"):
         getattr(L, name).argtypes = [vp]
         getattr(L, name).restype = i32
     L.mgx_move_fast_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.mgx_world_shape_fields.argtypes = [vp, C.c_size_t, vp, i32]
+    L.mgx_world_shape_fields.restype = i32
     L.mgx_state_bytes.argtypes = [vp]
     L.mgx_state_bytes.restype = i64
     L.mgx_env_state_layout.argtypes = [vp, C.c_size_t, vp, i32, C.POINTER(EnvStateInfo)]
@@ -1438,6 +1440,13 @@ class BatchedMettaGrid:
         """0: generic observation kernel; 3: the instance compiled for the shape of BASELINE.json configs[2] (gen_presets.py);
         5: that shape with an episode length read at run time; 9: an instance compiled for this program at run time (jit.py)."""
         return int(self.L.mgx_obs_variant(self.h))
+
+    @property
+    def world_variant(self) -> int:
+        """0: generic lean world kernel (shape read at run time); 3: the instance compiled for the shape of BASELINE.json
+        configs[2] (gen_presets.py; never with MGX_NO_GEN or MGX_WORLD_GENERIC set at creation); 9: a code object compiled for
+        this program at run time (jit.py)."""
+        return int(self.L.mgx_world_variant(self.h))
 
     @property
     def handler_variant(self) -> int:

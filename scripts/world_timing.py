@@ -38,7 +38,7 @@ lib.mgx_debug_world_cycles(out, 0)
 names = ["stage agents", "shuffle", "stream0 (move/noop)", "stream1 (vibe)", "on_tick", "coverage", "  do_move (in streams)", "  action bookkeeping",
          "resolve move targets"]
 waves = (E + 63) // 64
-print(f"move_fast {eng.move_fast}")
+print(f"move_fast {eng.move_fast}  world_variant {eng.world_variant}")
 for k, nm in enumerate(names):
     print(f"{nm:28s} {out[k] / steps / waves:12.0f} cycles / wave / step")
 # event counts of the primary stream (MGX_COUNT), first wavefront of every workgroup (32 envs) like the cycle totals
