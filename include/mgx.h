@@ -613,7 +613,33 @@ int mgx_pack_result(const uint32_t* scratch, int64_t n_rows, int64_t* total_toke
 int mgx_unpack_rows(const uint8_t* packed, const uint16_t* counts, int64_t n_rows, int32_t n_tokens, uint8_t* rows, uint32_t* scratch,
                     void* hip_stream);
 
-/* Code specialised for THIS engine's program at run time.  The build specialises two kernels for the benchmark presets (the
+/* ---- Dense-policy front end: Linear over u8 observation rows ----------------------------------------------
+ * What the reference's trainable baselines do first (python/src/mettagrid/policy/stateless.py:29,42, lstm.py:31-37,73-84,
+ * puffer_default.py:57,65: `observations.view(B, -1).float() / 255.0` into Linear(3T, hidden)), without the float copy of the
+ * observations: a u8 value is exact in bfloat16, so the rows go to the matrix cores as they are.  Engine-independent like
+ * mgx_pack_rows: raw DEVICE pointers and a hipStream_t (as void*); everything is enqueued on that stream.
+ *   forward:  y[n][h] = fl(fl(scale * sum_k x[n][k] * W[h][k]) + bias[h]), sums in float32 in an unspecified order.
+ *     x u8 [n_rows][k] at a row stride of x_stride bytes (>= k), any alignment (dword loads where base and stride are
+ *     4-aligned, bytewise otherwise; no byte past the k bytes of a row is read).  W = w_hi (terms = 1) or w_hi + w_lo
+ *     (terms = 2), each bfloat16 [h][k] contiguous in torch's Linear layout, k not padded.  bias float32 [h] or NULL.
+ *     y [n_rows][h] at a row stride of y_stride ELEMENTS (>= h); y_dtype 1 = float32, 2 = bfloat16 = the float32 result
+ *     rounded to nearest even.
+ *   wgrad:  dw[h][k] = scale * sum_n dy[n][h] * x[n][k], float32 [h][k] contiguous.  dy [n_rows][h] contiguous, dy_dtype
+ *     1 = float32 or 2 = bfloat16.  terms = 2 with float32 dy: every dy is used as hi + lo, hi = bf16(dy), lo = bf16(dy - hi)
+ *     (round to nearest even); otherwise as bf16(dy).  Every chunk of mgx_byte_linear_chunk_rows() rows is reduced into a
+ *     float32 partial [h][k] in `scratch` (device memory of mgx_byte_linear_scratch_bytes(n_rows, k, h) bytes), then the
+ *     partials are added in chunk order: no atomics, the same input gives the same bits on every call.
+ * 1 <= k <= 65535; h a multiple of 16, 16 <= h <= 4096; terms 1 or 2; n_rows >= 0, and n_rows = 0 enqueues nothing (dw is
+ * then not written).  Anything else, a NULL or misaligned pointer included, is MGX_ERR_BAD_ARG before anything is
+ * enqueued; MGX_ERR_PROGRAM if the kernels' LDS did not fit (it does not depend on the shape).  No reference counterpart. */
+int mgx_byte_linear_forward(const uint8_t* x, int64_t n_rows, int32_t k, int64_t x_stride, const void* w_hi, const void* w_lo, int32_t terms,
+                            const float* bias, float scale, void* y, int32_t y_dtype, int64_t y_stride, int32_t h, void* hip_stream);
+int mgx_byte_linear_wgrad(const uint8_t* x, int64_t n_rows, int32_t k, int64_t x_stride, const void* dy, int32_t dy_dtype, int32_t h,
+                          int32_t terms, float scale, float* dw, void* scratch, void* hip_stream);
+int64_t mgx_byte_linear_scratch_bytes(int64_t n_rows, int32_t k, int32_t h);
+int32_t mgx_byte_linear_chunk_rows(void);
+
+/* Code specialised for THIS engine's program at run time. The build specialises two kernels for the benchmark presets (the
  * lean world kernel with straight-line handler code, the observation kernel with the shape as compile-time constants:
  * mgx_handler_variant / mgx_obs_variant 3, 4, 5); for any other program the host can generate the same two units
  * (csrc/mgx_jit_world.hip, csrc/mgx_jit_obs.hip; mettagrid_amd/jit.py drives hipcc --genco into a cache) and hand the code

@@ -200,6 +200,13 @@ def load_lib():
         L.mgx_pack_rows.argtypes = [vp, i64, i32, vp, vp, i64, vp, vp]
         L.mgx_pack_result.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i32), vp]
         L.mgx_unpack_rows.argtypes = [vp, vp, i64, i32, vp, vp, vp]
+    if hasattr(L, "mgx_byte_linear_forward"):   # (absent from the CPU sanitizer build: no MFMA stand-in)
+        L.mgx_byte_linear_forward.argtypes = [vp, i64, i32, i64, vp, vp, i32, vp, C.c_float, vp, i32, i64, i32, vp]
+        L.mgx_byte_linear_wgrad.argtypes = [vp, i64, i32, i64, vp, i32, i32, i32, C.c_float, vp, vp, vp]
+        L.mgx_byte_linear_scratch_bytes.argtypes = [i64, i32, i32]
+        L.mgx_byte_linear_scratch_bytes.restype = i64
+        L.mgx_byte_linear_chunk_rows.argtypes = []
+        L.mgx_byte_linear_chunk_rows.restype = i32
     for name in ("mgx_num_envs", "mgx_num_agents", "mgx_num_tokens", "mgx_obs_variant", "mgx_act_variant", "mgx_handler_variant",
                  "mgx_world_prog_in_lds", "mgx_is_extended", "mgx_dispatch_pairs", "mgx_integer_bookkeeping",
                  "mgx_create_paths", "mgx_move_fast", "mgx_world_variant"):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Developer builds for A/B measurements: build/libmgx_<name>.so with extra compiler flags for chosen units.
-# Usage: scripts/build_variant.sh <name> <unit: engine|fast|x|aoe|decode|box|actf|actx|bag|render|all> "<extra flags>"; run with MGX_LIB=build/libmgx_<name>.so
+# Usage: scripts/build_variant.sh <name> <unit: engine|fast|x|aoe|decode|box|actf|actx|bag|render|linear|all> "<extra flags>"; run with MGX_LIB=build/libmgx_<name>.so
 set -e
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 C="$ROOT/mettagrid_amd/csrc"
@@ -21,6 +21,7 @@ hipcc $F $(x actx) -c $C/mgx_act_x.hip -o $O/ax.o &
 hipcc $F -c $C/mgx_pack.hip -o $O/p.o &
 hipcc $F $(x bag) -c $C/mgx_token_bag.hip -o $O/tb.o &
 hipcc $F $(x render) -c $C/mgx_render.hip -o $O/rn.o &
+hipcc $F $(x linear) -c $C/mgx_byte_linear.hip -o $O/bl.o &
 for job in $(jobs -p); do wait $job; done
 mkdir -p $ROOT/build
 hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/build/libmgx_$NAME.so $O/*.o
