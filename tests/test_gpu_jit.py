@@ -1,7 +1,6 @@
 """GPU: run-time specialisation (mettagrid_amd/jit.py + mgx_attach_code): for programs the build did not specialise, the world
 kernel with generated handler code and the observation kernel with the shape folded in are compiled on the spot, attached,
 and must reproduce the oracle bit for bit."""
-import glob
 import json
 import os
 
@@ -9,10 +8,9 @@ import numpy as np
 import pytest
 
 import helpers as hp
+import jit_cases as jc
 import oracle_py as op
-import ref_tree
-from mettagrid_amd import from_reference, jit
-from mettagrid_amd.compiler import compile_spec
+from mettagrid_amd import jit
 from mettagrid_amd.engine import BatchedMettaGrid
 
 pytestmark = pytest.mark.gpu
@@ -22,23 +20,25 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 def _programs():
     """(name, program, class maps [E]) of three lean programs that are not build-time presets: the reference's arena and
     navigation configs (fixtures of its own converter) and the handler-VM torture scenario."""
-    out = []
-    for name in ("arena", "navigation"):
-        doc = json.load(open(os.path.join(HERE, "golden", f"ref_{name}.json")))
-        cfg = ref_tree.load(doc["config"])
-        prog = from_reference.compile_reference_config(cfg, len(doc["map"]), len(doc["map"][0]))
-        out.append((name, prog, np.stack([prog.class_map(doc["map"])] * 6)))
-    spec_f, map_f, _, _ = hp.SCENARIOS["torture"]
-    maps = [map_f(s) for s in range(6)]
-    prog = compile_spec(spec_f(), *maps[0].shape)
-    out.append(("torture", prog, np.stack([prog.class_map(m) for m in maps])))
+    out = [(name, prog, np.stack([prog.class_map(grid)] * 6)) for name, prog, grid in jc.reference_programs()]
+    torture = jc.case("torture")   # (built in one place: what start_all() compiles is what runs here)
+    out.append(("torture", torture.prog, jc.class_maps(torture, range(6))))
     return out
 
 
-def test_specialised_kernels_match_the_oracle(tmp_path, monkeypatch):
-    monkeypatch.setenv("MGX_JIT_CACHE", str(tmp_path))
+@pytest.fixture(autouse=True)
+def shared_cache():
+    """One cache and one round of compiles per test process, shared with tests/test_gpu_jit_matrix.py and
+    tests/test_gpu_jit_paths.py (jit_cases.start_all: every code object of the session side by side; what is still compiling
+    when the process ends is stopped there)."""
+    jc.start_all()
+    with jc.cache_env():
+        yield
+
+
+def test_specialised_kernels_match_the_oracle():
     progs = _programs()
-    jobs = [jit.start(p, True) for _, p, _ in progs]      # all compiles side by side (the world unit takes a minute or two)
+    jobs = [jit.start(p, True) for _, p, _ in progs]      # (joins the compiles start_all() began, or finds their objects)
     for js in jobs:
         assert sorted(j.kind for j in js) == ["obs", "world"]
         for j in js:
@@ -74,8 +74,7 @@ def test_specialised_kernels_match_the_oracle(tmp_path, monkeypatch):
         eng.close(); plain.close()
 
 
-def test_code_object_of_another_program_is_refused(tmp_path, monkeypatch):
-    monkeypatch.setenv("MGX_JIT_CACHE", str(tmp_path))
+def test_code_object_of_another_program_is_refused():
     (_, p_arena, cms_arena), (_, p_nav, cms_nav), _ = _programs()
     jobs = jit.start(p_arena, True, kinds=("obs",))
     assert jobs[0].wait(600) and jobs[0].error is None
@@ -87,19 +86,13 @@ def test_code_object_of_another_program_is_refused(tmp_path, monkeypatch):
     eng.close()
 
 
-def test_extended_dispatch_kernel_specialised_at_run_time(tmp_path, monkeypatch):
+def test_extended_dispatch_kernel_specialised_at_run_time():
     """An extended program that is not the rung-4 preset (its chests mark a game stat): the lane-per-agent dispatch kernel is
     compiled with this program's handlers as straight-line code (csrc/mgx_jit_act_x.hip), attached, and must reproduce the
     oracle and the interpreter-driven kernel."""
     from mettagrid_amd import presets
-    from mettagrid_amd import spec as S
     from mettagrid_amd.mapgen import random_map
-    monkeypatch.setenv("MGX_JIT_CACHE", str(tmp_path))
-    spec = presets.rung4_spec(obs_tokens=400)
-    spec.objects["chest"].on_use = S.Handler([S.ResourceFilter(S.ACTOR, "ore", 2)],
-                                             [S.ResourceTransfer(S.ACTOR, S.TARGET, "ore", -2),
-                                              S.SetStat("chest.ore", S.InventoryValue("ore"), scope="game", entity=S.TARGET)], "deposit2")
-    prog = compile_spec(spec, 20, 20, max_objects=presets.RUNG4_MAX_OBJECTS)
+    (_, prog), (_, chains) = jc.extended_programs()   # (built in one place: what start_all() compiles is what runs here)
     objs = {"wall": 8, "extractor": 6, "chest": 4, "healer_red": 1, "healer_blue": 1, "healer_green": 1, "healer_yellow": 1,
             "flag_red": 1, "flag_blue": 1, "flag_green": 1, "flag_yellow": 1, "hub": 1, "wire": 3}
     E = 6
@@ -109,7 +102,6 @@ def test_extended_dispatch_kernel_specialised_at_run_time(tmp_path, monkeypatch)
     # the reference's handler-chain config (fixture of its own converter: AoE, an event, a materialized query) compiles beside it
     doc = json.load(open(os.path.join(HERE, "golden", "ref_chains.json")))
     zc = np.load(os.path.join(HERE, "golden", "ref_chains.npz"))
-    chains = from_reference.compile_reference_config(ref_tree.load(doc["config"]), len(doc["map"]), len(doc["map"][0]))
     pending = jit.start(prog, True) + jit.start(chains, True)
     for j in pending:
         assert j.wait(900) and j.error is None, j.error
