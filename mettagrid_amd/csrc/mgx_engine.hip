@@ -23,7 +23,7 @@
 #include "mgx_plan.h"       // mgx_create's host-only half: validation and every create-time decision
 #include "mgx_env_state.h"  // what an env's state is (the one list of its arrays) and the save / load kernel
 #include "mgx_replay.h"     // change log of the watched envs (mgx_set_replay)
-#include "mgx_mapgen.h"     // the random map builder on the device (mgx_set_map_generator)
+#include "mgx_mapgen_plan.h"  // the map builders on the device (mgx_mapgen.h) and the host-only half of mgx_set_map_*generator
 #include "mgx_step_stats.h" // chosen stats of every env / agent read out behind every step (mgx_set_step_stats)
 #include "mgx_time_avg.h"   // time-averaged game stats of every episode (mgx_set_time_averages)
 #include "mgx_policy_stats.h"  // per-policy episode statistics (mgx_set_policy_stats)
@@ -445,13 +445,8 @@ struct mgx_engine : MgxPlan {   // the plan mgx_create made (d, paths, LDS layou
   uint8_t* d_gs_mask = nullptr;     // [E] inside the block behind gs.used
   // device map generator (mgx_set_map_generator; csrc/mgx_mapgen.h): the recipe and the base seeds belong to the slot, never
   // to a saved env state
-  MgxMapGen gen{};                  // device pointers into d_gen_recipe + the shape
-  MgxMapScene gen_scene{};          // ... of the scene recipe (gen_is_scene; an engine holds one recipe of either kind)
-  bool gen_is_scene = false;
-  MgxMapMaze gen_maze{};            // ... of the maze recipe (gen_is_maze)
-  bool gen_is_maze = false;
-  bool gen_on = false;              // (false: mgx_step and the restarts enqueue nothing for it)
-  size_t gen_lds = 0;               // dynamic LDS of mgx_mapgen_kernel: the inner array (scene: map, indices, symbols)
+  MgxMapRecipe gen{};               // the kind (MGX_GEN_OFF: none) and its kernel's argument: device pointers into d_gen_recipe + the shape
+  size_t gen_lds = 0;               // dynamic LDS of the kind's kernel: the inner array (scene: map, indices, symbols)
   void* d_gen_recipe = nullptr;     // inner (scene: symbols) | rename | rename_off
   uint32_t* d_gen_base = nullptr;   // [E] map seed base of each slot
   uint32_t* d_gen_seed = nullptr;   // [E] seed of the map each env's most recent generated restart built
@@ -1441,7 +1436,7 @@ int mgx_set_auto_reset(mgx_engine* e, int32_t enabled, int32_t pool_stride, cons
   if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_auto_reset: null engine");
   HIP_TRY(hipSetDevice(e->device));
   if (!enabled) { e->auto_reset = false; return MGX_OK; }
-  if (e->n_pool <= 0 && !e->gen_on) return fail(MGX_ERR_BAD_ARG, "mgx_set_auto_reset: no map pool (mgx_set_map_pool)");
+  if (e->n_pool <= 0 && !e->gen.kind) return fail(MGX_ERR_BAD_ARG, "mgx_set_auto_reset: no map pool (mgx_set_map_pool)");
   const MgxDev& d = e->d;
   int rc = MGX_OK;
   if (!e->d_next_mask) {
@@ -1484,68 +1479,48 @@ int mgx_get_episodes(mgx_engine* e, uint32_t* episodes, int32_t* map_index) {
 static void free_map_generator(mgx_engine* e) {
   if (e->d_gen_recipe) (void)hipFree(e->d_gen_recipe);
   e->d_gen_recipe = nullptr;
-  e->gen = MgxMapGen{};
-  e->gen_scene = MgxMapScene{};
-  e->gen_is_scene = false;
-  e->gen_maze = MgxMapMaze{};
-  e->gen_is_maze = false;
-  e->gen_on = false;
+  e->gen = MgxMapRecipe{};
   e->gen_lds = 0;
 }
 static int raise_mapgen_lds(mgx_engine* e, size_t bytes) {
   static MgxLdsLimit limit;
   return raise_lds(limit, {(const void*)mgx_mapgen_kernel, (const void*)mgx_mapscene_kernel, (const void*)mgx_maze_kernel}, e, bytes);
 }
-// The kernel of the recipe that is set: map k of `grid`-strided n (or *n_dev) maps (mgx_mapgen_kernel's arguments).
+// The kernel of the recipe that is set: map k of `grid`-strided n (or *n_dev) maps (mgx_mapgen_run's arguments).
 static int launch_mapgen(mgx_engine* e, unsigned grid, const uint32_t* seeds, const uint32_t* base, const uint32_t* episodes,
                          const int32_t* env_list, const uint32_t* n_dev, int n, uint16_t* out, uint32_t* cur_seed) {
-  if (e->gen_is_maze)
-    hipLaunchKernelGGL(mgx_maze_kernel, dim3(grid), dim3(MGX_WAVE), e->gen_lds, e->stream, e->gen_maze, seeds, base, episodes, env_list, n_dev,
-                       n, out, cur_seed);
-  else if (e->gen_is_scene)
-    hipLaunchKernelGGL(mgx_mapscene_kernel, dim3(grid), dim3(MGX_WAVE), e->gen_lds, e->stream, e->gen_scene, seeds, base, episodes, env_list,
-                       n_dev, n, out, cur_seed);
-  else
-    hipLaunchKernelGGL(mgx_mapgen_kernel, dim3(grid), dim3(MGX_WAVE), e->gen_lds, e->stream, e->gen, seeds, base, episodes, env_list, n_dev,
-                       n, out, cur_seed);
+#define MGX_LAUNCH_MAPGEN(kernel, recipe) \
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(MGX_WAVE), e->gen_lds, e->stream, recipe, seeds, base, episodes, env_list, n_dev, n, out, cur_seed)
+  switch (e->gen.kind) {
+    case MGX_GEN_RANDOM: MGX_LAUNCH_MAPGEN(mgx_mapgen_kernel, e->gen.random); break;
+    case MGX_GEN_SCENE: MGX_LAUNCH_MAPGEN(mgx_mapscene_kernel, e->gen.scene); break;
+    case MGX_GEN_MAZE: MGX_LAUNCH_MAPGEN(mgx_maze_kernel, e->gen.maze); break;
+    default: return fail(MGX_ERR_BAD_ARG, "map generator: not set (mgx_set_map_generator)");
+  }
+#undef MGX_LAUNCH_MAPGEN
   HIP_TRY(hipGetLastError());
   return MGX_OK;
 }
 // The listed envs' maps into dmaps (restart_masked): seeds one per list entry, or base[env] + episodes[env].
 static int launch_mapgen_envs(mgx_engine* e, const MgxList& l, const uint32_t* dseeds_packed) {
-  if (!e->gen_on || !l.list) return fail(MGX_ERR_BAD_ARG, "map generator: not set (mgx_set_map_generator)");
+  if (!e->gen.kind || !l.list) return fail(MGX_ERR_BAD_ARG, "map generator: not set (mgx_set_map_generator)");
   return launch_mapgen(e, list_grid(e, l, 128, 2048), dseeds_packed, (const uint32_t*)e->d_gen_base, (const uint32_t*)e->d_episodes, l.list,
                        l.n_host >= 0 ? (const uint32_t*)nullptr : l.n, l.n_host >= 0 ? l.n_host : 0, e->dmaps, e->d_gen_seed);
 }
 
-// What both recipe kinds share once a recipe is accepted: the LDS limit (MGX_MAPGEN_LDS_BYTES test hook), the capacity checks
-// on ONE generated map, the per-slot seed arrays and the upload of `host` (the recipe blob) with the base seeds.  The old
-// recipe is freed only when nothing can fail any more; on return e->d_gen_recipe is the new blob and gen_on is still false.
-static int accept_map_recipe(mgx_engine* e, const char* who, const std::vector<uint16_t>& one, size_t lds, const std::string& lds_what,
-                             const std::vector<uint8_t>& host, const uint32_t* map_seed_base) {
+// The setters' common end, with the plan `p` of a planner entry (csrc/mgx_mapgen_plan.h).  What needs the engine happens
+// here: the capacity checks on the ONE representative map, the kernels' LDS limit, the per-slot seed arrays and the upload of
+// the recipe blob with the base seeds.  The old recipe is freed only when nothing can fail any more; the new one is on (its
+// three pointers into the uploaded blob) only when everything has landed.
+static int accept_map_recipe(mgx_engine* e, const char* who, const MgxMapPlan& p, const uint32_t* map_seed_base) {
   const MgxDev& d = e->d;
-  int rc = validate_maps(e, one.data(), 1, nullptr, who);
-  if (rc) return rc;
-  size_t lds_max = MGX_MAPGEN_LDS_MAX;
-  // Test hook: a map of at most 255 x 255 cells needs 127 KB, so no program reaches the real limit; the tests of this refusal
-  // lower it with MGX_MAPGEN_LDS_BYTES (a decimal byte count, only ever lowering).  Anything else in the variable is an error.
-  if (const char* s = getenv("MGX_MAPGEN_LDS_BYTES")) {
-    char* end = nullptr;
-    const unsigned long long v = strtoull(s, &end, 10);
-    if (end == s || *end || *s < '0' || *s > '9')
-      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": MGX_MAPGEN_LDS_BYTES = '" + s + "' is not a decimal byte count");
-    lds_max = std::min<size_t>(lds_max, (size_t)v);
-  }
-  if (lds > lds_max)
-    return fail(MGX_ERR_PROGRAM, std::string(who) + ": " + lds_what + " needs " + std::to_string(lds) +
-                                     " B of LDS, the generator's workgroup has " + std::to_string(lds_max));
-  rc = fit_maps(e, one.data(), 0, 1, nullptr, who);
-  if (rc) return rc;
-  rc = raise_mapgen_lds(e, lds);
+  int rc = validate_maps(e, p.one.data(), 1, nullptr, who);   // (kept as defence behind the planner's own check: fit_maps indexes by these ids)
+  if (!rc) rc = fit_maps(e, p.one.data(), 0, 1, nullptr, who);
+  if (!rc) rc = raise_mapgen_lds(e, p.lds);
   if (rc) return rc;
   // accepted: replace the recipe
   void* blob = nullptr;
-  HIP_TRY(hipMalloc(&blob, host.size()));
+  HIP_TRY(hipMalloc(&blob, p.blob.size()));
   if (!e->d_gen_base) {
     rc = e->alloc(&e->d_gen_base, (size_t)d.E);
     if (!rc) rc = e->alloc(&e->d_gen_seed, (size_t)d.E);
@@ -1558,127 +1533,33 @@ static int accept_map_recipe(mgx_engine* e, const char* who, const std::vector<u
   HIP_TRY(hipStreamSynchronize(e->stream));
   free_map_generator(e);
   e->d_gen_recipe = blob;
-  HIP_TRY(hipMemcpyAsync(blob, host.data(), host.size(), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(blob, p.blob.data(), p.blob.size(), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(e->d_gen_base, map_seed_base, (size_t)d.E * 4, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(e->d_gen_seed, map_seed_base, (size_t)d.E * 4, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));   // `host` is the caller's local
-  e->gen_lds = lds;
+  HIP_TRY(hipStreamSynchronize(e->stream));   // the plan is the caller's local
+  e->gen_lds = p.lds;
+  e->gen = p.recipe;
+  e->gen.point_into(blob, p.off_rename, p.off_off);
   return MGX_OK;
 }
-// rename / rename_off of either recipe kind: shape, ascending offsets, class ids.
-static int check_rename_tables(const mgx_engine* e, const char* who, const uint16_t* rename, const int32_t* rename_off, int32_t n_teams) {
-  const int nc = e->prog[MGX_H_NUM_CLASSES];
-  if (n_teams < 0 || n_teams > MGX_MAPGEN_MAX_TEAMS || (n_teams > 0 && (!rename || !rename_off)) || (n_teams > 0 && rename_off[0] != 0))
-    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": bad rename tables");
-  for (int t = 0; t < n_teams; t++)
-    if (rename_off[t + 1] < rename_off[t]) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": rename offsets must ascend");
-  const int n_rename = n_teams > 0 ? rename_off[n_teams] : 0;
-  for (int k = 0; k < n_rename; k++)
-    if (rename[k] > nc)
-      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": class map holds id " + std::to_string(rename[k]) + " but the program has " +
-                                       std::to_string(nc) + " classes");
-  return MGX_OK;
-}
-// The recipe blob: cells | rename | rename_off, 16-byte aligned parts.
-struct MgxRecipeBlob { std::vector<uint8_t> host; size_t off_rename, off_off; };
-static MgxRecipeBlob pack_map_recipe(const uint16_t* cells, size_t n_cells, const uint16_t* rename, const int32_t* rename_off, int32_t n_teams) {
-  const int n_rename = n_teams > 0 ? rename_off[n_teams] : 0;
-  MgxRecipeBlob b;
-  b.off_rename = (n_cells * 2 + 15) & ~(size_t)15;
-  b.off_off = (b.off_rename + (size_t)n_rename * 2 + 15) & ~(size_t)15;
-  b.host.assign(b.off_off + ((size_t)n_teams + 1) * 4, 0);
-  if (n_cells) memcpy(b.host.data(), cells, n_cells * 2);
-  if (n_rename) memcpy(b.host.data() + b.off_rename, rename, (size_t)n_rename * 2);
-  if (n_teams) memcpy(b.host.data() + b.off_off, rename_off, ((size_t)n_teams + 1) * 4);
-  return b;
-}
+static MgxMapWorld map_world(const mgx_engine* e) { return {e->d.H, e->d.W, e->prog[MGX_H_NUM_CLASSES], getenv("MGX_MAPGEN_LDS_BYTES")}; }
 
 int mgx_set_map_generator(mgx_engine* e, const uint16_t* inner, int32_t n_inner, int32_t border_width, int32_t border_code,
                           const uint16_t* rename, const int32_t* rename_off, int32_t n_teams, const uint32_t* map_seed_base) {
   if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_map_generator: null engine");
   HIP_TRY(hipSetDevice(e->device));
-  const MgxDev& d = e->d;
   if (!inner) {   // off: the recipe goes, the base seeds stay allocated with the engine
-    if (e->gen_on && e->auto_reset && e->n_pool <= 0)   // (finished envs would be rebuilt from their stale dmaps)
+    if (e->gen.kind && e->auto_reset && e->n_pool <= 0)   // (finished envs would be rebuilt from their stale dmaps)
       return fail(MGX_ERR_BAD_ARG, "mgx_set_map_generator: the generator is the map source of auto-reset; switch that off first (mgx_set_auto_reset)");
     HIP_TRY(hipStreamSynchronize(e->stream));
     free_map_generator(e);
     return MGX_OK;
   }
-  const char* who = "mgx_set_map_generator";
-  const int nc = e->prog[MGX_H_NUM_CLASSES];
-  const int ih = d.H - 2 * border_width, iw = d.W - 2 * border_width;
-  if (!map_seed_base || border_width < 0 || ih <= 0 || iw <= 0 || n_inner != ih * iw)
-    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": the inner array must hold (H - 2 * border_width) * (W - 2 * border_width) = " +
-                                     std::to_string(ih > 0 && iw > 0 ? ih * iw : 0) + " cells of the program's " + std::to_string(d.H) + " x " +
-                                     std::to_string(d.W) + " map, and base seeds must be given");
-  int rc = check_rename_tables(e, who, rename, rename_off, n_teams);
-  if (rc) return rc;
-  if (border_code < 0 || border_code > nc)
-    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": class map holds id " + std::to_string(border_code) + " but the program has " +
-                                     std::to_string(nc) + " classes");
-  // ONE generated map stands for all of them: a shuffle keeps the multiset of cells and the renaming hands out the same
-  // classes in another order, so the class ids, the AoE / territory source counts and the bound of the observation token
-  // pool are the same for every seed.  The unshuffled recipe is such a map.
-  std::vector<uint16_t> one((size_t)d.H * d.W, (uint16_t)border_code);
-  {
-    std::vector<int> seen((size_t)std::max(n_teams, 1), 0);
-    for (int i = 0; i < n_inner; i++) {
-      uint16_t v = inner[i];
-      if (v >= MGX_MAPGEN_TEAM0) {
-        const int t = v - MGX_MAPGEN_TEAM0;
-        if (t >= n_teams) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": an inner cell names team " + std::to_string(t) + " of " + std::to_string(n_teams));
-        const int k = seen[t]++;
-        if (k >= rename_off[t + 1] - rename_off[t])
-          return fail(MGX_ERR_BAD_ARG, std::string(who) + ": more cells of team " + std::to_string(t) + " than entries in its rename table");
-        v = rename[rename_off[t] + k];
-      }
-      one[(size_t)(i / iw + border_width) * d.W + (i % iw + border_width)] = v;
-    }
-  }
-  const size_t lds = ((size_t)n_inner * 2 + 15) & ~(size_t)15;
-  const MgxRecipeBlob blob_host = pack_map_recipe(inner, (size_t)n_inner, rename, rename_off, n_teams);
-  rc = accept_map_recipe(e, who, one, lds, "the inner area of " + std::to_string(n_inner) + " cells", blob_host.host, map_seed_base);
-  if (rc) return rc;
-  const uint8_t* blob = (const uint8_t*)e->d_gen_recipe;
-  const size_t off_rename = blob_host.off_rename, off_off = blob_host.off_off;
-  MgxMapGen& g = e->gen;
-  g.inner = (const uint16_t*)blob;
-  g.rename = (const uint16_t*)((const uint8_t*)blob + off_rename);
-  g.rename_off = (const int32_t*)((const uint8_t*)blob + off_off);
-  g.n_inner = n_inner; g.ih = ih; g.iw = iw; g.border = border_width; g.H = d.H; g.W = d.W; g.n_teams = n_teams;
-  g.border_code = (uint32_t)border_code;
-  e->gen_on = true;
-  return MGX_OK;
-}
-
-// The room grid of MapGen.prepare_grid (mapgen.py:305-315), in 64 bits: rows x cols for n_inst rooms, adding up to the program's map.
-static int check_room_grid(const mgx_engine* e, const char* who, int rh, int rw, int n_inst, int rows, int cols, int b, int ibw) {
-  const MgxDev& d = e->d;
-  int want_rows = 1;
-  while ((long long)want_rows * want_rows < n_inst) want_rows++;
-  const int want_cols = (n_inst + want_rows - 1) / want_rows;
-  const long long wantH = (long long)rows * rh + (long long)(rows - 1) * ibw + 2LL * b, wantW = (long long)cols * rw + (long long)(cols - 1) * ibw + 2LL * b;
-  if (rows != want_rows || cols != want_cols || wantH != d.H || wantW != d.W)
-    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": " + std::to_string(n_inst) + " instances are a grid of " + std::to_string(want_rows) + " x " +
-                                     std::to_string(want_cols) + " rooms, and rooms, instance borders and the outer border must add up to the program's " +
-                                     std::to_string(d.H) + " x " + std::to_string(d.W) + " map (they give " + std::to_string(wantH) + " x " +
-                                     std::to_string(wantW) + ")");
-  return MGX_OK;
-}
-// The representative map of a scene or maze recipe: its team cells renamed in row-major order over the whole map.
-static int rename_one_map(const char* who, std::vector<uint16_t>& one, const uint16_t* rename, const int32_t* rename_off, int32_t n_teams) {
-  std::vector<int> seen((size_t)std::max(n_teams, 1), 0);
-  for (uint16_t& v : one) {   // row-major over the whole map
-    if (v < MGX_MAPGEN_TEAM0) continue;
-    const int t = v - MGX_MAPGEN_TEAM0;
-    if (t >= n_teams) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": a symbol names team " + std::to_string(t) + " of " + std::to_string(n_teams));
-    const int k = seen[t]++;
-    if (k >= rename_off[t + 1] - rename_off[t])
-      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": more cells of team " + std::to_string(t) + " than entries in its rename table");
-    v = rename[rename_off[t] + k];
-  }
-  return MGX_OK;
+  MgxMapPlan p;
+  std::string why;
+  const int rc = mgx_plan_map_random(map_world(e), inner, n_inner, border_width, border_code, rename, rename_off, n_teams, map_seed_base, p, why);
+  if (rc) return fail(rc, why);
+  return accept_map_recipe(e, "mgx_set_map_generator", p, map_seed_base);
 }
 
 int mgx_set_map_scene_generator(mgx_engine* e, int32_t room_height, int32_t room_width, int32_t n_inst, int32_t rows, int32_t cols,
@@ -1687,53 +1568,12 @@ int mgx_set_map_scene_generator(mgx_engine* e, int32_t room_height, int32_t room
                                 const int32_t* rename_off, int32_t n_teams, const uint32_t* map_seed_base) {
   if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_map_scene_generator: null engine");
   HIP_TRY(hipSetDevice(e->device));
-  const MgxDev& d = e->d;
-  const char* who = "mgx_set_map_scene_generator";
-  const int nc = e->prog[MGX_H_NUM_CLASSES];
-  const int rh = room_height, rw = room_width, b = border_width, ibw = instance_border_width;
-  if (!map_seed_base || rh <= 0 || rw <= 0 || rh > d.H || rw > d.W || b < 0 || ibw < 0 || ibw > 0xFFFF || n_inst < 1 || rows < 1 || cols < 1 || n_sym < 0 ||
-      (n_sym > 0 && !symbols))
-    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": null / negative argument, or base seeds not given");
-  int rc = check_room_grid(e, who, rh, rw, n_inst, rows, cols, b, ibw);
-  if (rc) return rc;
-  const int area = rh * rw;
-  if (n_sym > area)
-    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": " + std::to_string(n_sym) + " symbols do not fit the " + std::to_string(area) + " cells of a room");
-  rc = check_rename_tables(e, who, rename, rename_off, n_teams);
-  if (rc) return rc;
-  for (int code : {border_code, instance_border_code})
-    if (code < 0 || code > nc)
-      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": class map holds id " + std::to_string(code) + " but the program has " + std::to_string(nc) +
-                                       " classes");
-  // ONE generated map stands for all of them: every symbol is always placed, so all maps of a recipe hold the same multiset
-  // of cells and the renaming hands out the same classes in another order.  The unshuffled recipe (symbol k of an instance on
-  // cell k of its room) is such a map.
-  std::vector<uint16_t> one((size_t)d.H * d.W, (uint16_t)border_code);
-  const int ph = rh + ibw, pw = rw + ibw;
-  for (int r = 0; r < d.H - 2 * b; r++)
-    for (int c = 0; c < d.W - 2 * b; c++)
-      one[(size_t)(r + b) * d.W + c + b] = (n_inst > 1 && (r % ph >= rh || c % pw >= rw)) ? (uint16_t)instance_border_code : (uint16_t)0;
-  for (int k = 0; k < n_inst; k++)
-    for (int i = 0; i < n_sym; i++)
-      one[(size_t)(b + (k / cols) * ph + i / rw) * d.W + b + (k % cols) * pw + i % rw] = symbols[(size_t)k * n_sym + i];
-  rc = rename_one_map(who, one, rename, rename_off, n_teams);
-  if (rc) return rc;
-  const size_t lds = MGX_MAPSCENE_LDS_BYTES((size_t)d.H * d.W, area, n_sym);
-  const MgxRecipeBlob blob_host = pack_map_recipe(symbols, (size_t)n_inst * n_sym, rename, rename_off, n_teams);
-  rc = accept_map_recipe(e, who, one, lds, "the map of " + std::to_string(d.H * d.W) + " cells with a room of " + std::to_string(area) + " and " +
-                                               std::to_string(n_sym) + " symbols", blob_host.host, map_seed_base);
-  if (rc) return rc;
-  const uint8_t* blob = (const uint8_t*)e->d_gen_recipe;
-  MgxMapScene& g = e->gen_scene;
-  g.symbols = (const uint16_t*)blob;
-  g.rename = (const uint16_t*)(blob + blob_host.off_rename);
-  g.rename_off = (const int32_t*)(blob + blob_host.off_off);
-  g.n_sym = n_sym; g.rh = rh; g.rw = rw; g.n_inst = n_inst; g.rows = rows; g.cols = cols; g.border = b; g.ibw = ibw; g.H = d.H; g.W = d.W;
-  g.n_teams = n_teams; g.first_on_root = first_on_root ? 1 : 0;
-  g.border_code = (uint32_t)border_code; g.iborder_code = (uint32_t)instance_border_code;
-  e->gen_is_scene = true;
-  e->gen_on = true;
-  return MGX_OK;
+  MgxMapPlan p;
+  std::string why;
+  const int rc = mgx_plan_map_rooms(map_world(e), nullptr, room_height, room_width, n_inst, rows, cols, border_width, instance_border_width,
+                                    border_code, instance_border_code, first_on_root, symbols, n_sym, rename, rename_off, n_teams, map_seed_base, p, why);
+  if (rc) return fail(rc, why);
+  return accept_map_recipe(e, "mgx_set_map_scene_generator", p, map_seed_base);
 }
 
 int mgx_set_map_maze_generator(mgx_engine* e, int32_t room_height, int32_t room_width, int32_t n_inst, int32_t rows, int32_t cols,
@@ -1743,89 +1583,18 @@ int mgx_set_map_maze_generator(mgx_engine* e, int32_t room_height, int32_t room_
                                const int32_t* rename_off, int32_t n_teams, const uint32_t* map_seed_base) {
   if (!e) return fail(MGX_ERR_BAD_ARG, "mgx_set_map_maze_generator: null engine");
   HIP_TRY(hipSetDevice(e->device));
-  const MgxDev& d = e->d;
-  const char* who = "mgx_set_map_maze_generator";
-  const int nc = e->prog[MGX_H_NUM_CLASSES];
-  const int rh = room_height, rw = room_width, b = border_width, ibw = instance_border_width;
-  if (!map_seed_base || rh <= 0 || rw <= 0 || rh > d.H || rw > d.W || b < 0 || ibw < 0 || ibw > 0xFFFF || n_inst < 1 || rows < 1 || cols < 1 || n_sym < 0 ||
-      (n_sym > 0 && !symbols) || (key_offset != 0 && key_offset != 1))
-    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": null / negative argument, a key offset other than 0 or 1, or base seeds not given");
-  if (algorithm != MGX_MAZE_KRUSKAL && algorithm != MGX_MAZE_DFS)
-    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": algorithm " + std::to_string(algorithm) + " is neither kruskal (0) nor dfs (1)");
-  int rc = check_room_grid(e, who, rh, rw, n_inst, rows, cols, b, ibw);
-  if (rc) return rc;
-  // MazeGrid (mapgen/scenes/maze.py): the clamped sizes, the maze cells of a room and the walls between neighbouring cells
-  // (a wall as wide as the room's longer side or wider leaves one maze cell whatever its width: clamped, so that sums stay small)
-  const int rs = std::max(1, std::min(room_size, std::min(rw, rh))), ws = std::min(std::max(1, wall_size), std::max(rw, rh));
-  const int p = rs + ws, mcols = (rw + ws) / p, mrows = (rh + ws) / p;
-  const int cells = mcols * mrows, n_walls = mcols * (mrows - 1) + (mcols - 1) * mrows, area = rh * rw;
-  if (mcols < 1 || mrows < 1 || n_walls > 0xFFFF)
-    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": a room of " + std::to_string(rh) + " x " + std::to_string(rw) + " holds " + std::to_string(mrows) +
-                                     " x " + std::to_string(mcols) + " maze cells");
-  rc = check_rename_tables(e, who, rename, rename_off, n_teams);
-  if (rc) return rc;
-  for (int code : {border_code, instance_border_code, wall_code})
-    if (code < 0 || code > nc)
-      return fail(MGX_ERR_BAD_ARG, std::string(who) + ": class map holds id " + std::to_string(code) + " but the program has " + std::to_string(nc) +
-                                       " classes");
-  if (wall_code == 0) return fail(MGX_ERR_BAD_ARG, std::string(who) + ": the wall code is 0 (empty)");
-  // ONE generated map stands for all of them: every maze of a recipe is a spanning tree of the same maze cells, so all hold
-  // the same number of wall and empty cells, and every symbol is always placed.  The representative is a comb maze (every
-  // wall between vertical neighbours open, between horizontal neighbours in the top row only) with symbol q of an instance
-  // on the q-th empty cell of its room.
-  std::vector<uint16_t> room((size_t)area);
-  for (int i = 0; i < area; i++) {
-    const int x = i % rw, y = i / rw;
-    const bool strip = (x % p >= rs && x / p < mcols - 1) || (y % p >= rs && y / p < mrows - 1);
-    const bool cell = x % p < rs && x / p < mcols && y % p < rs && y / p < mrows;
-    const bool open_down = x % p < rs && x / p < mcols && y % p >= rs && y / p < mrows - 1;
-    const bool open_right = y < rs && x % p >= rs && x / p < mcols - 1;
-    const bool wall = algorithm == MGX_MAZE_KRUSKAL ? (strip && !open_down && !open_right) : !(cell || open_down || open_right);
-    room[(size_t)i] = wall ? (uint16_t)wall_code : (uint16_t)0;
-  }
-  std::vector<int> empties;
-  for (int i = 0; i < area; i++)
-    if (!room[(size_t)i]) empties.push_back(i);
-  const int n_empty = (int)empties.size();
-  if (n_sym > n_empty)
-    return fail(MGX_ERR_BAD_ARG, std::string(who) + ": " + std::to_string(n_sym) + " symbols do not fit the " + std::to_string(n_empty) +
-                                     " empty cells of a room's maze");
-  std::vector<uint16_t> one((size_t)d.H * d.W, (uint16_t)border_code);
-  const int ph = rh + ibw, pw = rw + ibw;
-  for (int r = 0; r < d.H - 2 * b; r++)
-    for (int c = 0; c < d.W - 2 * b; c++)
-      one[(size_t)(r + b) * d.W + c + b] = (n_inst > 1 && (r % ph >= rh || c % pw >= rw)) ? (uint16_t)instance_border_code : (uint16_t)0;
-  for (int k = 0; k < n_inst; k++) {
-    uint16_t* at = one.data() + (size_t)(b + (k / cols) * ph) * d.W + b + (k % cols) * pw;
-    for (int i = 0; i < area; i++) at[(size_t)(i / rw) * d.W + i % rw] = room[(size_t)i];
-    for (int q = 0; q < n_sym; q++) at[(size_t)(empties[(size_t)q] / rw) * d.W + empties[(size_t)q] % rw] = symbols[(size_t)k * n_sym + q];
-  }
-  rc = rename_one_map(who, one, rename, rename_off, n_teams);
-  if (rc) return rc;
-  const int n_work = std::max(n_walls, cells);
-  const size_t lds = MGX_MAZE_LDS_BYTES((size_t)d.H * d.W, n_work, cells, area, n_sym);
-  const MgxRecipeBlob blob_host = pack_map_recipe(symbols, (size_t)n_inst * n_sym, rename, rename_off, n_teams);
-  rc = accept_map_recipe(e, who, one, lds, "the map of " + std::to_string(d.H * d.W) + " cells with a room of " + std::to_string(area) + ", " +
-                                               std::to_string(cells) + " maze cells, " + std::to_string(n_walls) + " walls and " +
-                                               std::to_string(n_sym) + " symbols", blob_host.host, map_seed_base);
-  if (rc) return rc;
-  const uint8_t* blob = (const uint8_t*)e->d_gen_recipe;
-  MgxMapMaze& g = e->gen_maze;
-  g.symbols = (const uint16_t*)blob;
-  g.rename = (const uint16_t*)(blob + blob_host.off_rename);
-  g.rename_off = (const int32_t*)(blob + blob_host.off_off);
-  g.n_sym = n_sym; g.rh = rh; g.rw = rw; g.n_inst = n_inst; g.rows = rows; g.cols = cols; g.border = b; g.ibw = ibw; g.H = d.H; g.W = d.W;
-  g.n_teams = n_teams; g.first_on_root = first_on_root ? 1 : 0; g.key_offset = key_offset;
-  g.algorithm = algorithm; g.rs = rs; g.ws = ws; g.mcols = mcols; g.mrows = mrows; g.n_walls = n_walls; g.n_work = n_work;
-  g.border_code = (uint32_t)border_code; g.iborder_code = (uint32_t)instance_border_code; g.wall_code = (uint32_t)wall_code;
-  e->gen_is_maze = true;
-  e->gen_on = true;
-  return MGX_OK;
+  const MgxMazeArgs mz = {algorithm, room_size, wall_size, wall_code, key_offset};
+  MgxMapPlan p;
+  std::string why;
+  const int rc = mgx_plan_map_rooms(map_world(e), &mz, room_height, room_width, n_inst, rows, cols, border_width, instance_border_width,
+                                    border_code, instance_border_code, first_on_root, symbols, n_sym, rename, rename_off, n_teams, map_seed_base, p, why);
+  if (rc) return fail(rc, why);
+  return accept_map_recipe(e, "mgx_set_map_maze_generator", p, map_seed_base);
 }
 
 int mgx_generate_maps(mgx_engine* e, const uint32_t* map_seeds, int32_t n, uint16_t* out, int32_t out_is_device) {
   if (!e || !map_seeds || !out || n <= 0) return fail(MGX_ERR_BAD_ARG, "mgx_generate_maps: null/empty argument");
-  if (!e->gen_on) return fail(MGX_ERR_BAD_ARG, "mgx_generate_maps: no map generator (mgx_set_map_generator)");
+  if (!e->gen.kind) return fail(MGX_ERR_BAD_ARG, "mgx_generate_maps: no map generator (mgx_set_map_generator)");
   HIP_TRY(hipSetDevice(e->device));
   const size_t HW = (size_t)e->d.H * e->d.W, seed_bytes = ((size_t)n * 4 + 15) & ~(size_t)15;
   int rc = stage(e, seed_bytes + (out_is_device ? 0 : (size_t)n * HW * 2));
@@ -1842,7 +1611,7 @@ int mgx_generate_maps(mgx_engine* e, const uint32_t* map_seeds, int32_t n, uint1
 
 int mgx_reset_envs_generated(mgx_engine* e, const uint8_t* env_mask, const uint32_t* map_seeds, const uint32_t* seeds) {
   if (!e || !env_mask) return fail(MGX_ERR_BAD_ARG, "mgx_reset_envs_generated: null argument");
-  if (!e->gen_on) return fail(MGX_ERR_BAD_ARG, "mgx_reset_envs_generated: no map generator (mgx_set_map_generator)");
+  if (!e->gen.kind) return fail(MGX_ERR_BAD_ARG, "mgx_reset_envs_generated: no map generator (mgx_set_map_generator)");
   HIP_TRY(hipSetDevice(e->device));
   return reset_from_host(e, env_mask, {map_seeds, nullptr}, {seeds, e->dseeds}, nullptr, false, true, 0);
 }
@@ -2600,7 +2369,7 @@ int mgx_step(mgx_engine* e) {
       l.list = e->d_done_list; l.n = e->d_done_n;
       // map source: the pool when there is one, else the generator (mgx_set_auto_reset refuses an engine with neither)
       const bool pool = e->n_pool > 0;
-      int rrc = restart_masked(e, e->d_next_mask, pool, true, l, !pool && e->gen_on);
+      int rrc = restart_masked(e, e->d_next_mask, pool, true, l, !pool && e->gen.kind);
       if (rrc) return rrc;
     }
   }

@@ -53,16 +53,39 @@ struct MgxMapGen {
   const int32_t* rename_off;   // [n_teams + 1]
   int n_inner, ih, iw, border, H, W, n_teams;
   uint32_t border_code;
+  __host__ __device__ size_t cells() const { return (size_t)H * W; }
 };
 
-struct MgxMapScene {
+// The frame of a scene map (and of the planner's representative maps), before anything is placed: the outer wall of `border` cells, n_inst rooms of rh x rw in a
+// grid of rows x cols, ibw apart, the fill between them (n_inst > 1) and the empty rooms.  The kernels fill and scatter by
+// these functions, and the host planner (csrc/mgx_mapgen_plan.h) builds its representative map by them.
+struct MgxYX { int y, x; };
+struct MgxMapFrame {
+  int H, W, border, ibw, rh, rw, n_inst, rows, cols;
+  uint32_t border_code, iborder_code;   // outer wall; fill between the rooms
+  __host__ __device__ __forceinline__ MgxYX pitch() const { return {rh + ibw, rw + ibw}; }
+  __host__ __device__ __forceinline__ MgxYX origin(int k) const {   // of room k, row-major (scenes/room_grid.py:71-76)
+    return {border + (k / cols) * pitch().y, border + (k % cols) * pitch().x};
+  }
+  __host__ __device__ __forceinline__ uint32_t cell(int y, int x) const {   // of the whole map
+    const int ph = pitch().y, pw = pitch().x, r = y - border, c = x - border;
+    if (r < 0 || r >= H - 2 * border || c < 0 || c >= W - 2 * border) return border_code;
+    return (n_inst > 1 && (r % ph >= rh || c % pw >= rw)) ? iborder_code : 0u;
+  }
+  __host__ __device__ size_t cells() const { return (size_t)H * W; }
+};
+
+struct MgxMapScene : MgxMapFrame {
   const uint16_t* symbols;     // [n_inst][n_sym] the unshuffled symbols of each instance: class index + 1, TEAM0 + t
   const uint16_t* rename;      // as MgxMapGen's; the cells of a team are counted over the whole map
   const int32_t* rename_off;   // [n_teams + 1]
-  int n_sym, rh, rw, n_inst, rows, cols, border, ibw, H, W, n_teams, first_on_root;
-  uint32_t border_code, iborder_code;   // outer wall; fill between the rooms (n_inst > 1)
+  int n_sym, n_teams, first_on_root;
 };
 
+// Written out in full, with its own frame fill in mgx_maze_one and its own launch body: this kernel's code is kept as it was.
+// Its depth-first walk is sensitive to the compiler's block placement: the three forms of this struct and of mgx_maze_one that
+// went through MgxMapFrame / mgx_mapgen_run and were measured ran the dfs recipes 0.5 - 3 % slower
+// (profiles/mapgen_plan/timing.txt, "not adopted").
 struct MgxMapMaze {
   const uint16_t* symbols;     // [n_inst][n_sym] as MgxMapScene's
   const uint16_t* rename;
@@ -76,6 +99,13 @@ struct MgxMapMaze {
 };
 #define MGX_MAZE_KRUSKAL 0
 #define MGX_MAZE_DFS 1
+
+// LDS of the scene kernel: the map [H * W], the index array [rh * rw], the symbols [n_sym], u16 each.
+#define MGX_MAPSCENE_LDS_BYTES(HW, area, n_sym) ((((size_t)(HW) + (size_t)(area) + (size_t)(n_sym)) * 2 + 15) & ~(size_t)15)
+// LDS of the maze kernel, u16 each: the map [H * W], the wall permutation or the walk's stack [n_work], the component label or
+// the visited flag of every maze cell [cells], the room's empty cells [rh * rw], the symbols [n_sym].
+#define MGX_MAZE_LDS_BYTES(HW, n_work, cells, area, n_sym) \
+  ((((size_t)(HW) + (size_t)(n_work) + (size_t)(cells) + (size_t)(area) + (size_t)(n_sym)) * 2 + 15) & ~(size_t)15)
 
 #ifndef MGX_CPU_EMU
 struct MgxU128 { unsigned long long hi, lo; };
@@ -241,46 +271,30 @@ __device__ __forceinline__ void mgx_mapgen_multipliers(MgxU128& mulA, MgxU128& m
     }
 }
 
-// Map k of the launch: seed = seeds[k] when given, else base[env] + episodes[env] (mod 2^32); destination out + k * H * W
-// (env_list == nullptr: the maps alone) or out + env_list[k] * H * W (the envs' own maps).  n_dev: the list length when only
-// the device knows it (auto-reset), else n.  cur_seed [E] (listed form): the seed each env's map was made from.
-__global__ void __launch_bounds__(MGX_WAVE) mgx_mapgen_kernel(MgxMapGen g, const uint32_t* __restrict__ seeds, const uint32_t* __restrict__ base,
-                                                              const uint32_t* __restrict__ episodes, const int32_t* __restrict__ env_list,
-                                                              const uint32_t* __restrict__ n_dev, int n, uint16_t* __restrict__ out,
-                                                              uint32_t* __restrict__ cur_seed) {
-  extern __shared__ uint16_t mgx_mapgen_lds[];
-  const int lane = threadIdx.x;
-  MgxU128 mulA, mulG;
-  mgx_mapgen_multipliers(mulA, mulG);
-  const int count = n_dev ? (int)*n_dev : n;
-  const size_t HW = (size_t)g.H * g.W;
-  for (int k = blockIdx.x; k < count; k += gridDim.x) {
-    const int env = env_list ? env_list[k] : k;
-    const uint32_t seed = seeds ? seeds[k] : base[env] + episodes[env];
-    if (cur_seed && lane == 0) cur_seed[env] = seed;
-    mgx_mapgen_one(g, seed, mulA, mulG, mgx_mapgen_lds, out + (size_t)env * HW);
-  }
+// The frame of a scene or maze map into `map` (LDS, H * W u16): border, fill and empty rooms.
+__device__ __forceinline__ void mgx_mapgen_fill_frame(const MgxMapFrame& f, uint16_t* map) {
+  const int HW = f.H * f.W;
+  for (int i = threadIdx.x; i < HW; i += MGX_WAVE) map[i] = (uint16_t)f.cell(i / f.W, i % f.W);
+}
+// The end of a scene or maze map: the rename over the whole map -> dst [H][W].
+__device__ __forceinline__ void mgx_mapgen_finish(const MgxMapScene& g, uint16_t* map, uint16_t* __restrict__ dst) {
+  const int HW = g.H * g.W;
+  __syncthreads();
+  mgx_mapgen_rename(map, HW, g.rename, g.rename_off, g.n_teams);
+  __syncthreads();
+  for (int i = threadIdx.x; i < HW; i += MGX_WAVE) dst[i] = map[i];
+  __syncthreads();   // (the next map of this wavefront refills `map`)
 }
 
-// LDS of the scene kernel: the map [H * W], the index array [rh * rw], the symbols [n_sym], u16 each.
-#define MGX_MAPSCENE_LDS_BYTES(HW, area, n_sym) ((((size_t)(HW) + (size_t)(area) + (size_t)(n_sym)) * 2 + 15) & ~(size_t)15)
-
-// One map of the scene recipe: border, fill and empty rooms in `map` (LDS, H * W u16), then per instance the two shuffles on
-// one stream and the scatter into its room, then the rename over the whole map -> dst [H][W].  Called by all 64 lanes.
-__device__ __forceinline__ void mgx_mapscene_one(const MgxMapScene& g, uint32_t seed, MgxU128 mulA, MgxU128 mulG, uint16_t* map,
-                                                 uint16_t* __restrict__ dst) {
+// One map of the scene recipe: the frame in `map` (LDS, H * W u16), then per instance the two shuffles on one stream and the
+// scatter into its room, then the rename over the whole map -> dst [H][W].  Called by all 64 lanes.
+__device__ __forceinline__ void mgx_mapgen_one(const MgxMapScene& g, uint32_t seed, MgxU128 mulA, MgxU128 mulG, uint16_t* map,
+                                               uint16_t* __restrict__ dst) {
   const int lane = threadIdx.x;
   const int HW = g.H * g.W, area = g.rh * g.rw, n_sym = g.n_sym;
   uint16_t* idx = map + HW;
   uint16_t* sym = idx + area;
-  const int ph = g.rh + g.ibw, pw = g.rw + g.ibw;   // room pitch
-  const int inh = g.H - 2 * g.border, inw = g.W - 2 * g.border;
-  for (int i = lane; i < HW; i += MGX_WAVE) {
-    const int r = i / g.W - g.border, c = i % g.W - g.border;
-    uint32_t v = g.border_code;
-    if (r >= 0 && r < inh && c >= 0 && c < inw) v = (g.n_inst > 1 && (r % ph >= g.rh || c % pw >= g.rw)) ? g.iborder_code : 0u;
-    map[i] = (uint16_t)v;
-  }
+  mgx_mapgen_fill_frame(g, map);
   for (int k = 0; k < g.n_inst && n_sym > 0; k++) {
     __syncthreads();   // (the map is filled / the scatter of the instance before has read idx and sym)
     for (int i = lane; i < n_sym; i += MGX_WAVE) sym[i] = g.symbols[(size_t)k * n_sym + i];
@@ -292,44 +306,16 @@ __device__ __forceinline__ void mgx_mapscene_one(const MgxMapScene& g, uint32_t 
     d.shuffle(sym, n_sym, mulA, mulG);
     d.shuffle(idx, area, mulA, mulG);
     __syncthreads();
-    const int y0 = g.border + (k / g.cols) * ph, x0 = g.border + (k % g.cols) * pw;
+    const MgxYX o = g.origin(k);
     for (int t = lane; t < n_sym; t += MGX_WAVE) {   // (distinct targets: idx is a permutation, n_sym <= area)
       const int v = idx[t];
-      map[(y0 + v / g.rw) * g.W + x0 + v % g.rw] = sym[t];
+      map[(o.y + v / g.rw) * g.W + o.x + v % g.rw] = sym[t];
     }
   }
-  __syncthreads();
-  mgx_mapgen_rename(map, HW, g.rename, g.rename_off, g.n_teams);
-  __syncthreads();
-  for (int i = lane; i < HW; i += MGX_WAVE) dst[i] = map[i];
-  __syncthreads();   // (the next map of this wavefront refills `map`)
-}
-
-// mgx_mapgen_kernel for the scene recipe: the same launch arguments.
-__global__ void __launch_bounds__(MGX_WAVE) mgx_mapscene_kernel(MgxMapScene g, const uint32_t* __restrict__ seeds, const uint32_t* __restrict__ base,
-                                                                const uint32_t* __restrict__ episodes, const int32_t* __restrict__ env_list,
-                                                                const uint32_t* __restrict__ n_dev, int n, uint16_t* __restrict__ out,
-                                                                uint32_t* __restrict__ cur_seed) {
-  extern __shared__ uint16_t mgx_mapgen_lds[];
-  const int lane = threadIdx.x;
-  MgxU128 mulA, mulG;
-  mgx_mapgen_multipliers(mulA, mulG);
-  const int count = n_dev ? (int)*n_dev : n;
-  const size_t HW = (size_t)g.H * g.W;
-  for (int k = blockIdx.x; k < count; k += gridDim.x) {
-    const int env = env_list ? env_list[k] : k;
-    const uint32_t seed = seeds ? seeds[k] : base[env] + episodes[env];
-    if (cur_seed && lane == 0) cur_seed[env] = seed;
-    mgx_mapscene_one(g, seed, mulA, mulG, mgx_mapgen_lds, out + (size_t)env * HW);
-  }
+  mgx_mapgen_finish(g, map, dst);
 }
 
 // ---- the third recipe kind: MapGen with a Maze instance scene and a Random child (mgx_set_map_maze_generator) ----
-// LDS of the maze kernel, u16 each: the map [H * W], the wall permutation or the walk's stack [n_work], the component label or
-// the visited flag of every maze cell [cells], the room's empty cells [rh * rw], the symbols [n_sym].
-#define MGX_MAZE_LDS_BYTES(HW, n_work, cells, area, n_sym) \
-  ((((size_t)(HW) + (size_t)(n_work) + (size_t)(cells) + (size_t)(area) + (size_t)(n_sym)) * 2 + 15) & ~(size_t)15)
-
 // A value every lane read from the same LDS address, as a scalar: the maze's control flow is wavefront-uniform.
 __device__ __forceinline__ int mgx_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
@@ -477,6 +463,38 @@ __device__ __forceinline__ void mgx_maze_one(const MgxMapMaze& g, uint32_t seed,
   __syncthreads();   // (the next map of this wavefront refills `map`)
 }
 
+// ---- the launch: one body for the random and the scene recipe; the maze kernel keeps its own ----
+// Map k of the launch: seed = seeds[k] when given, else base[env] + episodes[env] (mod 2^32); destination out + k * H * W
+// (env_list == nullptr: the maps alone) or out + env_list[k] * H * W (the envs' own maps).  n_dev: the list length when only
+// the device knows it (auto-reset), else n.  cur_seed [E] (listed form): the seed each env's map was made from.
+template <class Recipe>
+__device__ __forceinline__ void mgx_mapgen_run(const Recipe& g, const uint32_t* __restrict__ seeds, const uint32_t* __restrict__ base,
+                                               const uint32_t* __restrict__ episodes, const int32_t* __restrict__ env_list,
+                                               const uint32_t* __restrict__ n_dev, int n, uint16_t* __restrict__ out,
+                                               uint32_t* __restrict__ cur_seed) {
+  extern __shared__ uint16_t mgx_mapgen_lds[];
+  const int lane = threadIdx.x;
+  MgxU128 mulA, mulG;
+  mgx_mapgen_multipliers(mulA, mulG);
+  const int count = n_dev ? (int)*n_dev : n;
+  const size_t HW = g.cells();
+  for (int k = blockIdx.x; k < count; k += gridDim.x) {
+    const int env = env_list ? env_list[k] : k;
+    const uint32_t seed = seeds ? seeds[k] : base[env] + episodes[env];
+    if (cur_seed && lane == 0) cur_seed[env] = seed;
+    mgx_mapgen_one(g, seed, mulA, mulG, mgx_mapgen_lds, out + (size_t)env * HW);
+  }
+}
+#define MGX_MAPGEN_ARGS                                                                                                          \
+  const uint32_t *__restrict__ seeds, const uint32_t *__restrict__ base, const uint32_t *__restrict__ episodes,                  \
+      const int32_t *__restrict__ env_list, const uint32_t *__restrict__ n_dev, int n, uint16_t *__restrict__ out, uint32_t *__restrict__ cur_seed
+__global__ void __launch_bounds__(MGX_WAVE) mgx_mapgen_kernel(MgxMapGen g, MGX_MAPGEN_ARGS) {
+  mgx_mapgen_run(g, seeds, base, episodes, env_list, n_dev, n, out, cur_seed);
+}
+__global__ void __launch_bounds__(MGX_WAVE) mgx_mapscene_kernel(MgxMapScene g, MGX_MAPGEN_ARGS) {
+  mgx_mapgen_run(g, seeds, base, episodes, env_list, n_dev, n, out, cur_seed);
+}
+#undef MGX_MAPGEN_ARGS
 // mgx_mapgen_kernel for the maze recipe: the same launch arguments.
 __global__ void __launch_bounds__(MGX_WAVE) mgx_maze_kernel(MgxMapMaze g, const uint32_t* __restrict__ seeds, const uint32_t* __restrict__ base,
                                                             const uint32_t* __restrict__ episodes, const int32_t* __restrict__ env_list,

@@ -496,27 +496,20 @@ class BatchedMettaGrid:
         off = np.ascontiguousarray(low.rename_off, dtype=np.int32)
         base = np.ascontiguousarray(np.broadcast_to(np.asarray(map_seed_base, dtype=np.uint32), (self.E,)))
         n_teams = int(off.size) - 1
+        tables = (rename.ctypes.data if rename.size else None, off.ctypes.data if n_teams > 0 else None, n_teams, base.ctypes.data)
+        if not hasattr(low, "symbols"):   # a mapgen.LoweredMap
+            inner = np.ascontiguousarray(low.inner, dtype=np.uint16)
+            _check(self.L.mgx_set_map_generator(self.h, inner.ctypes.data, int(inner.size), int(low.border_width), int(low.border_code), *tables))
+            return
+        sym = np.ascontiguousarray(low.symbols, dtype=np.uint16)
+        rooms = [int(v) for v in (low.room_height, low.room_width, low.n_inst, low.rows, low.cols, low.border_width, low.instance_border_width,
+                                  low.border_code, low.instance_border_code)]
+        tail = (sym.ctypes.data if sym.size else None, int(low.n_sym), *tables)
         if hasattr(low, "algorithm"):   # a mapgen.LoweredMaze
-            sym = np.ascontiguousarray(low.symbols, dtype=np.uint16)
-            _check(self.L.mgx_set_map_maze_generator(
-                self.h, int(low.room_height), int(low.room_width), int(low.n_inst), int(low.rows), int(low.cols), int(low.border_width),
-                int(low.instance_border_width), int(low.border_code), int(low.instance_border_code), int(low.algorithm),
-                int(low.room_size), int(low.wall_size), int(low.wall_code), int(bool(low.first_on_root)), int(low.key_offset),
-                sym.ctypes.data if sym.size else None, int(low.n_sym), rename.ctypes.data if rename.size else None,
-                off.ctypes.data if n_teams > 0 else None, n_teams, base.ctypes.data))
-            return
-        if hasattr(low, "symbols"):   # a mapgen.LoweredScene
-            sym = np.ascontiguousarray(low.symbols, dtype=np.uint16)
-            _check(self.L.mgx_set_map_scene_generator(
-                self.h, int(low.room_height), int(low.room_width), int(low.n_inst), int(low.rows), int(low.cols), int(low.border_width),
-                int(low.instance_border_width), int(low.border_code), int(low.instance_border_code), int(bool(low.first_on_root)),
-                sym.ctypes.data if sym.size else None, int(low.n_sym), rename.ctypes.data if rename.size else None,
-                off.ctypes.data if n_teams > 0 else None, n_teams, base.ctypes.data))
-            return
-        inner = np.ascontiguousarray(low.inner, dtype=np.uint16)
-        _check(self.L.mgx_set_map_generator(self.h, inner.ctypes.data, int(inner.size), int(low.border_width), int(low.border_code),
-                                            rename.ctypes.data if rename.size else None, off.ctypes.data if n_teams > 0 else None,
-                                            n_teams, base.ctypes.data))
+            _check(self.L.mgx_set_map_maze_generator(self.h, *rooms, int(low.algorithm), int(low.room_size), int(low.wall_size), int(low.wall_code),
+                                                     int(bool(low.first_on_root)), int(low.key_offset), *tail))
+        else:                           # a mapgen.LoweredScene
+            _check(self.L.mgx_set_map_scene_generator(self.h, *rooms, int(bool(low.first_on_root)), *tail))
 
     def generate_maps(self, map_seeds, out=None):
         """The generator's maps for ``map_seeds`` (uint32 [n]) -> uint16 [n, H, W]; no env is touched.  ``out``: a contiguous

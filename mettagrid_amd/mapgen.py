@@ -440,33 +440,21 @@ def _maze_key(rule, k: int):
     return None if (k == 0 and rule.first_on_root) else (k + rule.key_offset,)
 
 
-class LoweredMaze:
-    """What ``MazeGenSpec.lower`` makes: the arguments of ``mgx_set_map_maze_generator``."""
+class LoweredMaze(LoweredScene):
+    """What ``MazeGenSpec.lower`` makes: the arguments of ``mgx_set_map_maze_generator``, a ``LoweredScene``'s and the maze's own."""
 
     def __init__(self, height, width, room_height, room_width, n_inst, rows, cols, border_width, instance_border_width, border_code,
                  instance_border_code, first_on_root, key_offset, algorithm, room_size, wall_size, wall_code, n_empty, symbols, rename,
                  rename_off):
-        self.height, self.width, self.room_height, self.room_width = height, width, room_height, room_width
-        self.n_inst, self.rows, self.cols = n_inst, rows, cols
-        self.border_width, self.instance_border_width = border_width, instance_border_width
-        self.border_code, self.instance_border_code = border_code, instance_border_code   # class index + 1, 0 = empty
+        super().__init__(height, width, room_height, room_width, n_inst, rows, cols, border_width, instance_border_width, border_code,
+                         instance_border_code, first_on_root, symbols, rename, rename_off)
         # the key rule: the Maze scene of instance k draws from default_rng(seed) when k == 0 and first_on_root, else from spawn
         # key (k + key_offset,); its Random child from that key with one more word 0
-        self.first_on_root, self.key_offset = first_on_root, key_offset
+        self.key_offset = key_offset
         self.algorithm = algorithm                               # index into MAZE_ALGORITHMS
         self.room_size, self.wall_size = room_size, wall_size    # as configured; maze_geometry clamps them
         self.wall_code = wall_code                               # class index + 1 of "wall"
         self.n_empty = n_empty                                   # empty cells of every room's maze: a constant of the recipe
-        self.symbols = symbols                                   # uint16 [n_inst][n_sym], as LoweredScene's
-        self.rename, self.rename_off = rename, rename_off
-
-    @property
-    def n_sym(self) -> int:
-        return self.symbols.shape[1]
-
-    @property
-    def n_teams(self) -> int:
-        return len(self.rename_off) - 1
 
     def maze_key(self, k: int):
         return _maze_key(self, k)

@@ -5,7 +5,8 @@ metadata entry must be equal.  For host-only refactors of a unit that also holds
 
   F="--offload-arch=gfx950 -O3 -std=c++17 -I include -I mettagrid_amd/csrc --cuda-device-only -S"
   hipcc $F mettagrid_amd/csrc/mgx_engine.hip -o new.s        (and the same at the parent commit -> parent.s)
-  scripts/cmp_device_asm.py parent.s new.s
+  scripts/cmp_device_asm.py parent.s new.s [--skip NAME ...]
+--skip NAME: leave the functions whose symbol contains NAME out of the comparison (kernels the change means to touch).
 """
 import re
 import sys
@@ -48,9 +49,17 @@ def parse(path: str):
 
 
 def main() -> int:
-    (b0, m0), (b1, m1) = parse(sys.argv[1]), parse(sys.argv[2])
+    args, skip, paths = sys.argv[1:], [], []
+    while args:
+        a = args.pop(0)
+        if a == "--skip":
+            skip.append(args.pop(0))
+        else:
+            paths.append(a)
+    (b0, m0), (b1, m1) = parse(paths[0]), parse(paths[1])
     same = True
     for what, x, y in (("function bodies", b0, b1), ("kernel metadata entries", m0, m1)):
+        x, y = ({k: v for k, v in t.items() if not any(n in k for n in skip)} for t in (x, y))
         diff = sorted(k for k in x if k in y and x[k] != y[k])
         print(f"{what}: {len(x)} / {len(y)}, only in the first {sorted(set(x) - set(y))}, only in the second {sorted(set(y) - set(x))}, "
               f"{len(diff)} differ {diff[:4]}")
