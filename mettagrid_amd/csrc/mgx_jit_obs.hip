@@ -21,7 +21,7 @@ extern "C" __constant__ long long mgx_jit_obs_info[24] = {0x4D47584A49544F31ll /
 #define MGX_JIT_OBS_ARGS                                                                                                                    \
   MgxDev d, int pool_tokens, int pool_prefix, const uint8_t *env_mask, int blk_start, int blk_words_arg, int rewards_early_arg, void *box_out, \
       const float *box_scale, int box_C, int box_dtype, const int32_t *env_list, const uint32_t *env_list_n, int stat_passes
-extern "C" __global__ void __launch_bounds__(MGX_OBS_THREADS) mgx_jit_obs_r(MGX_JIT_OBS_ARGS) {   // the step: observations + rewards
+extern "C" __global__ void __launch_bounds__(MGX_OBS_THREADS, MGX_OBS_STEP_WAVES) mgx_jit_obs_r(MGX_JIT_OBS_ARGS) {   // the step: observations + rewards (bound: as the preset instance, mgx_obs.h)
   mgx_obs_run<true, false, true, MGX_OBS_THREADS, MGX_OBS_THREADS / MGX_WAVE, MgxObsShapeJ, false>(
       d, pool_tokens, pool_prefix, env_mask, blk_start, blk_words_arg, rewards_early_arg, box_out, box_scale, box_C, box_dtype, env_list, env_list_n,
       stat_passes);

@@ -274,8 +274,15 @@ static __device__ __forceinline__ void mgx_obs_run(const MgxDev& d, int pool_tok
     __syncthreads();   // the next env's staging overwrites this one's LDS
   }
 }
+// Wavefronts per SIMD the compiler is asked to leave room for (the second launch bound).  The step's lean instances compiled
+// for one shape run eight workgroups of four wavefronts per CU on their 20 KB of LDS, and at 41 vector registers nothing had to
+// say so; told, the compiler budgets its scalar registers for eight as well (78 instead of 95, DESIGN.md §4 "Round 10") and
+// the kernel is 4 % shorter.  Every other instance keeps the default: the generic and extended ones hold their shape in
+// scalar registers they already spill, the instances without rewards walk a list and need 86 vector registers.
+#define MGX_OBS_STEP_WAVES 8
+template <bool WITH_REWARDS, bool X, class K> constexpr int mgx_obs_min_waves() { return WITH_REWARDS && !X && K::fixed ? MGX_OBS_STEP_WAVES : 1; }
 template <bool WITH_REWARDS, bool X, bool PL, int NTH = MGX_OBS_THREADS, int EW = NTH / MGX_WAVE, class K = MgxObsShapeDyn, bool BOX = false>
-__global__ void __launch_bounds__(NTH) mgx_obs_kernel(MgxDev d, int pool_tokens, int pool_prefix, const uint8_t* env_mask,
+__global__ void __launch_bounds__(NTH, (mgx_obs_min_waves<WITH_REWARDS, X, K>())) mgx_obs_kernel(MgxDev d, int pool_tokens, int pool_prefix, const uint8_t* env_mask,
                                                                   int blk_start, int blk_words_arg, int rewards_early_arg,
                                                                   void* box_out, const float* box_scale, int box_C, int box_dtype,
                                                                   const int32_t* env_list, const uint32_t* env_list_n, int stat_passes) {
