@@ -639,6 +639,46 @@ int mgx_byte_linear_wgrad(const uint8_t* x, int64_t n_rows, int32_t k, int64_t x
 int64_t mgx_byte_linear_scratch_bytes(int64_t n_rows, int32_t k, int32_t h);
 int32_t mgx_byte_linear_chunk_rows(void);
 
+/* ---- Policy output side: actions, log-probabilities and entropy from logits ------------------------------
+ * What the reference's policies do last (python/src/mettagrid/policy/lstm.py:232, stateless.py:98, token_encoder.py:149,
+ * puffer_default.py:107, pufferlib.py:73: `Categorical(logits=logits).sample()` / pufferlib's `sample_logits(logits)`) and what
+ * a trainer re-evaluates with a gradient (`log_prob(actions)`, `entropy()`), each as ONE read of the logits.  Engine-independent
+ * like mgx_byte_linear_*: raw DEVICE pointers and a hipStream_t (as void*); everything is enqueued on that stream.
+ *   logits [n_rows][n_actions], dtype 1 = float32 or 2 = bfloat16, unit stride along the actions, row_stride ELEMENTS (>=
+ *   n_actions) between rows, any alignment the dtype allows.  t = inv_temperature (float32, > 0, finite).  Per row, every step
+ *   in float32 (exp / log within 2 ulp, sums of n_actions terms in index order or as a wave prefix scan):
+ *     z_a = fl(t l_a)   m = max z   pt_a = exp(z_a - m)   S = sum pt_a   p_a = pt_a / S   logp_a = z_a - m - log S
+ *     H = log S - (sum pt_a (z_a - m)) / S, a term with pt_a = 0 contributing exactly 0: masked actions (l_a = -inf) are legal.
+ *   A BAD row has no finite entry, or a NaN or +inf: it gets action 0 and NaN logprob / entropy / lse and adds 1 to *bad_rows
+ *   (uint32, device memory, may be NULL; one atomic add per workgroup at most; the caller clears it).
+ * mgx_sample_actions (no gradient): logits is indexed by i in [0, n_rows), every output by r = rows[i] (rows: int64 [n_rows]
+ *   device memory, or NULL = the identity): a policy that owns some agent rows writes straight into the joint tensors.  The
+ *   caller keeps every rows[i] inside the outputs; they are not checked.  actions int32, logprob / entropy float32 (each may be
+ *   NULL).  mode 0 samples: u = (x0 >> 8) 2^-24 in [0, 1), x0 the first word of Philox4x32-10 with key (seed lo, seed hi) and
+ *   counter (r lo, r hi, step lo, step hi) — a row's draw depends on (seed, step, r) alone, not on n_rows, the launch or how
+ *   rows are split between calls — and the action is the smallest a with c_a > u c_{A-1}, c the running sum of pt in index
+ *   order; if rounding leaves none, the last a with pt_a > 0.  An action with pt_a = 0 is never returned.  mode 1 is greedy:
+ *   the lowest index among the maxima of z, no random number.
+ * mgx_action_logprob: logprob[i] = logp_{actions[i]}, entropy[i] = H, lse[i] = m + log S (entropy, lse may be NULL); actions
+ *   int32 [n_rows]; an action outside [0, n_actions) makes the row bad.
+ * mgx_action_logprob_backward: with p_a = exp(z_a - lse) and H recomputed from logits and lse (nothing of size
+ *   [n_rows][n_actions] is kept between the two calls),
+ *     d_logits[i][a] = t (d_logprob[i] ([a = actions[i]] - p_a) - d_entropy[i] p_a (logp_a + H)),
+ *   exactly 0 where l_a = -inf; d_logprob / d_entropy float32 [n_rows], either may be NULL = zeros; d_logits
+ *   [n_rows][n_actions] at d_row_stride elements, d_dtype 1 = float32 or 2 = bfloat16 (rounded to nearest even).
+ * 1 <= n_actions <= 4096; 0 <= n_rows <= 2^25, and n_rows = 0 enqueues nothing.  Anything else — a NULL or misaligned pointer,
+ * a stride < n_actions, t <= 0 or not finite, an unknown dtype or mode — is MGX_ERR_BAD_ARG before anything is enqueued.
+ * Rows back to back with n_actions <= 64 take the lane-per-row kernels, every other shape a wavefront per row.
+ * No reference counterpart. */
+int mgx_sample_actions(const void* logits, int32_t dtype, int64_t n_rows, int32_t n_actions, int64_t row_stride, const int64_t* rows,
+                       float inv_temperature, int32_t mode, uint64_t seed, uint64_t step, int32_t* actions, float* logprob, float* entropy,
+                       uint32_t* bad_rows, void* hip_stream);
+int mgx_action_logprob(const void* logits, int32_t dtype, int64_t n_rows, int32_t n_actions, int64_t row_stride, const int32_t* actions,
+                       float inv_temperature, float* logprob, float* entropy, float* lse, uint32_t* bad_rows, void* hip_stream);
+int mgx_action_logprob_backward(const void* logits, int32_t dtype, int64_t n_rows, int32_t n_actions, int64_t row_stride,
+                                const int32_t* actions, float inv_temperature, const float* lse, const float* d_logprob,
+                                const float* d_entropy, void* d_logits, int32_t d_dtype, int64_t d_row_stride, void* hip_stream);
+
 /* Code specialised for THIS engine's program at run time. The build specialises two kernels for the benchmark presets (the
  * lean world kernel with straight-line handler code, the observation kernel with the shape as compile-time constants:
  * mgx_handler_variant / mgx_obs_variant 3, 4, 5); for any other program the host can generate the same two units

@@ -207,6 +207,11 @@ def load_lib():
         L.mgx_byte_linear_scratch_bytes.restype = i64
         L.mgx_byte_linear_chunk_rows.argtypes = []
         L.mgx_byte_linear_chunk_rows.restype = i32
+    if hasattr(L, "mgx_sample_actions"):        # (absent from the CPU sanitizer build: wavefront-cooperative kernels)
+        u64 = C.c_uint64
+        L.mgx_sample_actions.argtypes = [vp, i32, i64, i32, i64, vp, C.c_float, i32, u64, u64, vp, vp, vp, vp, vp]
+        L.mgx_action_logprob.argtypes = [vp, i32, i64, i32, i64, vp, C.c_float, vp, vp, vp, vp, vp]
+        L.mgx_action_logprob_backward.argtypes = [vp, i32, i64, i32, i64, vp, C.c_float, vp, vp, vp, vp, i32, i64, vp]
     for name in ("mgx_num_envs", "mgx_num_agents", "mgx_num_tokens", "mgx_obs_variant", "mgx_act_variant", "mgx_handler_variant",
                  "mgx_world_prog_in_lds", "mgx_is_extended", "mgx_dispatch_pairs", "mgx_integer_bookkeeping",
                  "mgx_create_paths", "mgx_move_fast", "mgx_world_variant"):

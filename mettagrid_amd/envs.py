@@ -722,6 +722,17 @@ class MettaGridBatchedEnv:
         self._policy_table[lst] = r if r.ndim == 2 else np.broadcast_to(r, (len(lst), len(r)))
         self._policy_ids = None
 
+    def action_sampler(self, seed: int = 0):
+        """A ``sampling.ActionSampler`` for this env's joint actions: ``E * A`` rows of
+        ``transport_action_n`` logits on the engine's device.  Its ``actions`` tensor (1-D int32, the shape of the engine's
+        action buffer) is what ``step`` takes on its one-kernel path: ``env.step(s.sample(logits)[0])``.  Needs device
+        buffers and a ``reset()``."""
+        if self._kind != "device":
+            raise ValueError("action_sampler needs device buffers")
+        from .sampling import ActionSampler
+        eng = self.engine
+        return ActionSampler(self.E * self.prog.num_agents, self.transport_action_n, seed=seed, device=eng.obs.device)
+
     def check_actions(self, wait: bool = True) -> None:
         """Raise the reference's ValueError for a joint action id the device-side decode found out of range
         (mettagrid_puffer_env.py:336-360).  ``step`` calls this with ``wait=False`` (no synchronisation: an error surfaces at
