@@ -733,7 +733,9 @@ int32_t mgx_dispatch_pairs(const mgx_engine* e);
 /* Non-zero: the lean lane-per-env kernel resolves every agent's move target in its staging pass and runs consecutive
  * trivial actions of an env's order (noop, move off the map / into an empty cell / into an object without on_use) without a
  * load (MgxDev::move_fast, csrc/mgx_world.h) — chosen at mgx_create for programs whose move handlers have the reference's
- * default shape and that dispatch pairs; 0 under env MGX_NO_MOVE_FAST.  Same results.  Diagnostic. */
+ * default shape and that dispatch pairs; 0 under env MGX_NO_MOVE_FAST.  Bit 2 is set under env MGX_MF_SERIAL_BOOK: the run
+ * takes one agent at a time with its bookkeeping inside the loop instead of the pipelined form (generic kernel only; the
+ * A/B switch of the two forms on one binary).  Same results.  Diagnostic. */
 int32_t mgx_move_fast(const mgx_engine* e);
 /* With env MGX_MOVE_FAST_COUNT set at mgx_create: out[0] = actions the run-ahead consumed, out[1] = resolved entries found
  * stale (the action then took the general path), summed over all envs and steps so far.  Synchronises the engine's stream.

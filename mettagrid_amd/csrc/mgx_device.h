@@ -57,11 +57,16 @@ struct MgxDev {
                           //    target) and the lean lane-per-env kernel resolves every agent's move target in its staging pass
                           //    and runs consecutive trivial actions of an env's order without a load (mgx_world.h, "run-ahead";
                           //    0 under env MGX_NO_MOVE_FAST).  bit 1: there is no use-target handler: an occupied cell always fails.
+                          //    bit 2 (env MGX_MF_SERIAL_BOOK): the run-ahead's first form — one agent at a time, its bookkeeping
+                          //    inside the loop — instead of the pipelined one; such a table matches no preset shape.
                           //    Engine configuration like coop_passes: it changes speed only
   int mf_lds_off;         // ... byte offset of its LDS behind everything else of the kernel: resolved actions u8[A][64] (cell ahead: 0 empty,
                           //    1 an object whose class has no on_use, 2 one with | kind << 2 | orientation << 4 | off the map << 7) | dirty cells of the tick u32[mf_dirty_words][64]
   int mf_dirty_words;     // words per env of the dirty set: an exact bitmap of the map (mf_exact) or a hashed mask (a power of two)
   int mf_exact;
+  int act_kinds;          // the action table packed for the shape policy (mgx_world.h mgx_act_kind / mgx_act_arg; mgx_plan.h): kinds at two
+  int act_args_lo;        //    bits per action | arguments of actions 0-7 and
+  int act_args_hi;        //    8-15 at four bits each; all three -1 when the table does not fit (more than 16 actions, an argument above 15)
   uint32_t* mf_count;     // [E][2] run-ahead actions | stale entries sent down the general path, summed over the steps; nullptr
                           //    unless env MGX_MOVE_FAST_COUNT asks for them (tests)
   int act_ngset;          // game-scope stats the action-phase handlers SET (StatsMutation): applied in agent order at the end

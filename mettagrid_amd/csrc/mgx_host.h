@@ -94,10 +94,10 @@ struct MgxConstDev {
 };
 
 #ifdef MGX_WORLD_TIMING  // instrumented developer builds only (scripts/*_timing.py): a unit's mgx_dbg_cycles, optionally cleared
-inline int mgx_read_cycles(const void* symbol, unsigned long long* out, int reset) {
+inline int mgx_read_cycles(const void* symbol, unsigned long long* out, int reset, int n = 16) {   // n <= 16 counters
   (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out, symbol, sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(symbol, z, sizeof z); }
+  (void)hipMemcpyFromSymbol(out, symbol, sizeof(unsigned long long) * n);
+  if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(symbol, z, sizeof(unsigned long long) * n); }
   return 0;
 }
 #endif

@@ -22,7 +22,7 @@
 // the engine's lifetime: a later reset that grows the token pool sizes the observation kernel with the same ones.
 struct MgxSwitches {   // (mgx_read_switches: which switch sets or clears each)
   bool verbose, prog_lds, aoe_local, tick_in_aoe, aoe_prog_lds, flat_top, tick_split, rewards_mid, obs_512, obs_preset, act_lean,
-      act_par, act_map, act_replay, duo, coop_passes, move_fast, move_fast_count, shadow, gen, obs_tail, world_preset;
+      act_par, act_map, act_replay, duo, coop_passes, move_fast, move_fast_count, mf_serial_book, shadow, gen, obs_tail, world_preset;
 };
 inline MgxSwitches mgx_read_switches() {
   auto on = [](const char* name) { return getenv(name) != nullptr; };
@@ -46,6 +46,7 @@ inline MgxSwitches mgx_read_switches() {
   s.coop_passes = !on("MGX_WORLD_PASSES_PER_ENV");  // the lean kernel's batched per-agent passes one lane per env
   s.move_fast = !on("MGX_NO_MOVE_FAST");            // the lean kernel resolves no move target up front: every action takes the trip loop
   s.move_fast_count = on("MGX_MOVE_FAST_COUNT");    // ... and counts run-ahead actions and stale entries per env (tests)
+  s.mf_serial_book = on("MGX_MF_SERIAL_BOOK");      // ... with the run-ahead's first form: one agent at a time, bookkeeping inside (the A/B switch)
   s.shadow = !on("MGX_NO_SHADOW");                  // no integer bookkeeping
   s.gen = !on("MGX_NO_GEN");                        // handlers on the interpreter
   s.obs_tail = !on("MGX_OBS_FULL_ROWS");            // every observation pass rewrites whole rows (no MgxDev::obs_used)
@@ -646,7 +647,21 @@ inline int mgx_plan(const int32_t* P, size_t words, const uint16_t* class_maps, 
           p.lds_world += pre + (size_t)4 * words * MGX_WORLD_EPG;
         }
       }
-      d.move_fast = mf ? (nm == 1 ? 3 : 1) : 0;
+      d.move_fast = mf ? (nm == 1 ? 3 : 1) | (sw.mf_serial_book ? 4 : 0) : 0;
+    }
+    {  // MgxDev::act_kinds / act_args_lo / act_args_hi: the action table as three words, for shapes compiled into a kernel
+      const int32_t* ac = P + d.sec[MGX_SEC_ACTIONS];
+      bool fits = d.nact <= 16;
+      uint32_t kinds = 0, lo = 0, hi = 0;
+      for (int a = 0; fits && a < d.nact; a++) {
+        const int kind = ac[a * MGX_AC_WORDS + MGX_AC_KIND], arg = ac[a * MGX_AC_WORDS + MGX_AC_ARG];
+        if (kind < 0 || kind > 2 || arg < 0 || arg > 15) { fits = false; break; }
+        kinds |= (uint32_t)kind << (2 * a);
+        (a < 8 ? lo : hi) |= (uint32_t)arg << (4 * (a & 7));
+      }
+      d.act_kinds = fits ? (int)kinds : -1;
+      d.act_args_lo = fits ? (int)lo : -1;
+      d.act_args_hi = fits ? (int)hi : -1;
     }
     // game-stat SETs are applied in agent order through per-env cells (the paired dispatch too)
     const std::vector<int>& sets = par ? gset : duo ? act_sets : std::vector<int>();

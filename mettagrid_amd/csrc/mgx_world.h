@@ -77,10 +77,19 @@ MGX_DBG_LINKAGE __device__ unsigned long long mgx_dbg_cycles[16];
 #define MGX_TICK(k) do { unsigned long long _n = clock64(); if (threadIdx.x == 0) atomicAdd(&mgx_dbg_cycles[k], _n - _t); _t = _n; } while (0)
 #define MGX_TICK0() unsigned long long _t = clock64()
 #define MGX_COUNT(k, n) atomicAdd(&mgx_dbg_cycles[k], (unsigned long long)(n))   // plain event counts beside the cycle totals
+// The primary stream of the lean kernel, split per wavefront and step (mgx_world_body): [0] inside the run-ahead loop, [1] the
+// fence, wave barrier and exchange of q behind it, [2] footprint exchange + mgx_dispatch_one + the pair's fence of the
+// general-path trips, [3] iterations of the run-ahead loop (the wavefront's: the maximum over its lanes, summed over the
+// trips).  The spans are kept in registers and added once per step; what is left of the stream's total is everything else.
+MGX_DBG_LINKAGE __device__ unsigned long long mgx_dbg_run[4];
+#define MGX_RUN_T0() (_rt = clock64())
+#define MGX_RUN_T(k) do { unsigned long long _n = clock64(); _rs[k] += (uint32_t)(_n - _rt); _rt = _n; } while (0)
 #else
 #define MGX_TICK(k)
 #define MGX_TICK0()
 #define MGX_COUNT(k, n)
+#define MGX_RUN_T0()
+#define MGX_RUN_T(k)
 #endif
 
 // MGX_BIG: inlining policy of the large interpreter functions.  The lean world kernel is built in its own translation
@@ -211,7 +220,7 @@ struct MgxValueStack {
 #define MGX_WORLD_SHAPE_FIELDS(F)                                                                                              \
   F(H) F(W) F(A) F(S) F(NSP) F(NSW) F(NG) F(NGW) F(SEENW) F(nact) F(max_priority) F(flags) F(hp_res) F(n_move_handlers)          \
   F(any_on_tick) F(tick_in_aoe) F(flat_top) F(defer_book) F(shadow) F(gen_prog) F(duo) F(tick_split) F(coop_passes) F(move_fast)  \
-  F(mf_lds_off) F(mf_dirty_words) F(mf_exact) F(act_ngset)
+  F(mf_lds_off) F(mf_dirty_words) F(mf_exact) F(act_ngset) F(act_kinds) F(act_args_lo) F(act_args_hi)
 #define MGX_WS_COUNT(f) +1
 #define MGX_WORLD_SHAPE_NFIELDS (0 MGX_WORLD_SHAPE_FIELDS(MGX_WS_COUNT))
 struct MgxWorldShapeDyn {
@@ -251,6 +260,22 @@ inline bool mgx_world_shape_matches(const MgxDev& d) {
   MGX_WORLD_SHAPE_FIELDS(MGX_WS_CMP)
 #undef MGX_WS_CMP
   return same;
+}
+
+// The action table (MGX_SEC_ACTIONS: kind, argument) as constants of the shape.  The planner packs it into three fields when it
+// fits — up to 16 actions, kinds 0..2 at two bits each in act_kinds, arguments 0..15 at four bits each in act_args_lo (actions
+// 0-7) and act_args_hi (8-15); a table that does not fit has all three -1 (no valid table packs to that: kind 3 does not exist)
+// — so for a fixed shape a per-lane lookup is a shift and a mask instead of a table read.  The run-time shape reads the table.
+template <class K, class PP>
+__device__ __forceinline__ int mgx_act_kind(const MgxDev& d, PP acts, int a) {
+  if (K::fixed && K::act_kinds(d) != -1) return (int)(((uint32_t)K::act_kinds(d) >> (2 * a)) & 3u);
+  return acts[a * MGX_AC_WORDS + MGX_AC_KIND];
+}
+template <class K, class PP>
+__device__ __forceinline__ int mgx_act_arg(const MgxDev& d, PP acts, int a) {
+  if (K::fixed && K::act_kinds(d) != -1)
+    return (int)(((uint32_t)(a < 8 ? K::act_args_lo(d) : K::act_args_hi(d)) >> (4 * (a & 7))) & 15u);
+  return acts[a * MGX_AC_WORDS + MGX_AC_ARG];
 }
 
 template <class Env> struct MgxGenR3;   // generated at build(): mgx_handlers_gen.h
@@ -1803,16 +1828,16 @@ struct MgxEnvT {  // per-lane view of one env
     return false;
   }
   __device__ MGX_BIG bool handle_action(int ai, int action, int stream) const {  // actions/action_handler.hpp:78-105
-    PP ac = prog() + d.sec[MGX_SEC_ACTIONS] + action * MGX_AC_WORDS;
-    int kind = ac[MGX_AC_KIND];
+    PP acts = prog() + d.sec[MGX_SEC_ACTIONS];
+    int kind = mgx_act_kind<K>(d, acts, action);
     const int li = ai * MGX_WORLD_EPG + AL().lane;
     int slot = AL().slot ? (int)AL().slot[li] : (int)d.ag_obj[ao(ai)];
     cur_agent = ai;
     cur_slot = slot;
     bool ok = true;
     MGX_TICK0();
-    if (kind == MGX_AK_MOVE) ok = do_move(slot, ac[MGX_AC_ARG]);
-    else if (kind == MGX_AK_VIBE) d.obj_vibe[so(slot)] = (uint8_t)ac[MGX_AC_ARG];  // actions/change_vibe.hpp:48-57
+    if (kind == MGX_AK_MOVE) ok = do_move(slot, mgx_act_arg<K>(d, acts, action));
+    else if (kind == MGX_AK_VIBE) d.obj_vibe[so(slot)] = (uint8_t)mgx_act_arg<K>(d, acts, action);  // actions/change_vibe.hpp:48-57
     MGX_TICK(6);
     if (K::defer_book(d)) {
       // Bookkeeping touches only this agent's own counters.  Here: the LDS copies and a result byte (in place of the
@@ -2387,8 +2412,8 @@ __device__ __forceinline__ void mgx_shuffle_order(const ENV& e, uint8_t* order, 
 // that stays on the map, -1 otherwise (orientation.hpp:28-48).
 template <class K, class PP>
 __device__ __forceinline__ int mgx_move_target(const MgxDev& d, PP acts, int a, uint32_t own) {
-  if (a < 0 || a >= K::nact(d) || acts[a * MGX_AC_WORDS + MGX_AC_KIND] != MGX_AK_MOVE) return -1;
-  const int orient = acts[a * MGX_AC_WORDS + MGX_AC_ARG];
+  if (a < 0 || a >= K::nact(d) || mgx_act_kind<K>(d, acts, a) != MGX_AK_MOVE) return -1;
+  const int orient = mgx_act_arg<K>(d, acts, a);
   const int dx = (orient == 2 || orient == 4 || orient == 6) ? -1 : (orient == 3 || orient == 5 || orient == 7) ? 1 : 0;
   const int dy = (orient == 0 || orient == 4 || orient == 5) ? -1 : (orient == 1 || orient == 6 || orient == 7) ? 1 : 0;
   const int r = (int)(own >> 8) + dy, c = (int)(own & 0xFF) + dx;
@@ -2414,7 +2439,7 @@ __device__ __forceinline__ void mgx_dispatch_one(const ENV& e, const MgxDev& d, 
     al.act[(stream * A + ai) * MGX_WORLD_EPG + lane] = 0;  // no handle_action call: empty result byte
     return;
   }
-  const bool is_vibe = acts[a * MGX_AC_WORDS + MGX_AC_KIND] == MGX_AK_VIBE;
+  const bool is_vibe = mgx_act_kind<K>(d, acts, a) == MGX_AK_VIBE;
   if (is_vibe != (stream == 1)) { al.act[(stream * A + ai) * MGX_WORLD_EPG + lane] = 0; return; }
   if (e.handle_action(ai, a, stream)) {
     d.executed[e.ao(ai)] = a;
@@ -2566,6 +2591,11 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
   // instead of two dependent round trips at the head of every move of the ordered loop.  Each lane resolves the elements it
   // staged itself (its own LDS writes: program order).  The dirty set of the tick starts empty.
   bool mf = false;
+  // Which form of the run-ahead loop an instance holds is a compile-time matter: the pipelined one where the shape is fixed
+  // (the preset's instance, run-time specialised kernels) unless that shape says otherwise (MgxDev::move_fast bit 2, env
+  // MGX_MF_SERIAL_BOOK), the first form — one agent at a time, bookkeeping inside — in the run-time-shape kernels.  Those stand at
+  // 254 VGPRs; with the pipelined loop they spill vector registers to scratch, with both loops behind a run-time test more.
+  const bool mf_serial = K::fixed ? (K::move_fast(d) & 4) != 0 : true;
 #if MGX_HELPERS_ON
   if constexpr (HELP) {
     mf = K::move_fast(d) != 0 && K::duo(d) != 0 && act;
@@ -2590,10 +2620,10 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
             if (coop) env8[q] = (size_t)(genv0 + ew);
             li8[q] = li;
             const int a = al.act[li];
-            const int kind = (a < 0 || a >= K::nact(d)) ? 3 : min((int)acts[a * MGX_AC_WORDS + MGX_AC_KIND], 3);
+            const int kind = (a < 0 || a >= K::nact(d)) ? 3 : min(mgx_act_kind<K>(d, acts, a), 3);
             const int t = mgx_move_target<K>(d, acts, a, al.rc[li]);
             kd8[q] = (uint32_t)(kind << 2);
-            if (kind == MGX_AK_MOVE) kd8[q] |= ((uint32_t)acts[a * MGX_AC_WORDS + MGX_AC_ARG] & 7u) << 4 | (t < 0 ? 0x80u : 0u);
+            if (kind == MGX_AK_MOVE) kd8[q] |= ((uint32_t)mgx_act_arg<K>(d, acts, a) & 7u) << 4 | (t < 0 ? 0x80u : 0u);
             if (t >= 0) cv8[q] = d.grid[env8[q] * HW + (size_t)((t >> 8) * K::W(d) + (t & 0xFF))];
           }
         }
@@ -2663,8 +2693,8 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
           const int li = flat_li(p, &ew), ri = A * MGX_WORLD_EPG + li;
           const int a = al.act[ri];
           if (a < 0 || a >= K::nact(d)) { al.act[ri] = -1; invalid = true; continue; }
-          if (acts[a * MGX_AC_WORDS + MGX_AC_KIND] != MGX_AK_VIBE) { al.act[ri] = 0; continue; }
-          d.obj_vibe[(size_t)(genv0 + ew) * K::S(d) + al.slot[li]] = (uint8_t)acts[a * MGX_AC_WORDS + MGX_AC_ARG];
+          if (mgx_act_kind<K>(d, acts, a) != MGX_AK_VIBE) { al.act[ri] = 0; continue; }
+          d.obj_vibe[(size_t)(genv0 + ew) * K::S(d) + al.slot[li]] = (uint8_t)mgx_act_arg<K>(d, acts, a);
           const uint16_t rc = al.rc[li], prev = al.prev[li];
           const bool moved = rc != prev;
           if (moved) { al.swm[li] = 0; al.prev[li] = rc; }
@@ -2688,8 +2718,8 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
           const int li = i * MGX_WORLD_EPG + lane, ri = (A + i) * MGX_WORLD_EPG + lane;
           const int a = al.act[ri];
           if (a < 0 || a >= K::nact(d)) { mgx_dispatch_one(e, d, acts, al, i, 1, lane, repeats); continue; }   // invalid index: the general path
-          if (acts[a * MGX_AC_WORDS + MGX_AC_KIND] != MGX_AK_VIBE) { al.act[ri] = 0; continue; }           // wrong stream: no call
-          d.obj_vibe[e.so(al.slot[li])] = (uint8_t)acts[a * MGX_AC_WORDS + MGX_AC_ARG];
+          if (mgx_act_kind<K>(d, acts, a) != MGX_AK_VIBE) { al.act[ri] = 0; continue; }           // wrong stream: no call
+          d.obj_vibe[e.so(al.slot[li])] = (uint8_t)mgx_act_arg<K>(d, acts, a);
           const uint16_t rc = al.rc[li], prev = al.prev[li];   // handle_action's bookkeeping (action_handler.hpp:78-105), deferred form
           const bool moved = rc != prev;
           if (moved) { al.swm[li] = 0; al.prev[li] = rc; }
@@ -2706,6 +2736,8 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
     uint32_t mf_ran = 0, mf_stale = 0;   // (MgxDev::mf_count)
 #ifdef MGX_WORLD_TIMING
     uint32_t mf_slow = 0;
+    uint32_t _rs[3] = {0u, 0u, 0u}, _rit = 0, _rn = 0;   // (mgx_dbg_run)
+    unsigned long long _rt = 0;
 #endif
     for (;;) {
 #if MGX_HELPERS_ON
@@ -2732,11 +2764,91 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
           if constexpr (!K::fixed)   // (a fixed shape: immediates, nothing to pin)
             asm volatile("" : "+s"(mW), "+s"(mHW), "+s"(mA), "+s"(mS), "+s"(mFl), "+s"(mMask), "+s"(oSwm), "+s"(oAct), "+s"(oSlot), "+s"(oPre));
           asm volatile("" : "+s"(gGrid), "+s"(gObjRc), "+s"(gAgRc), "+s"(gEx), "+s"(gSu));
+          MGX_RUN_T0();
           if (!helper) {
             const int oRc = oSlot + mA * MGX_WORLD_EPG * 2, oPrev = oRc + mA * MGX_WORLD_EPG * 2;
             const int oDirty = oPre + ((mA * MGX_WORLD_EPG + 15) & ~15);
             auto dirty_word = [&](uint32_t b) { return (uint32_t*)(mgx_dyn_lds + oDirty) + (b >> 5) * MGX_WORLD_EPG + lane; };
+            if (!mf_serial) {
+              // The pipelined form.  Nothing the run does for agent q changes what agent q + 1 brings to its turn except the
+              // dirty set: a relocate moves the acting agent's own object only, swaps and removals happen on the general path,
+              // which ends the run.  So while agent q is processed the lane already holds position q + 1's resolved byte,
+              // position, prev_location and slot and position q + 2's agent index (clamped to the last position), and an
+              // iteration issues all its LDS loads — that record, and q's own two dirty words — together behind one wait.  The
+              // general path between two runs may swap or relocate anything: every trip loads its first record afresh.
+              // The loop keeps what the serial order can observe (grid, positions and their mirrors — the swap mutation reads
+              // obj_rc from memory — dirty marks, prev_location) and leaves ONE outcome byte per consumed agent in place of
+              // the resolved byte: 3 (no cell-ahead code) | kind << 2 | ok << 4 | moved << 5.  The rest of handle_action's
+              // bookkeeping is written by the flat pass behind the stream (mf_book below); the staged id stays for it.
+              uint8_t* preb = mgx_dyn_lds + oPre;
+              const uint16_t* rcb = (const uint16_t*)(mgx_dyn_lds + oRc);
+              const uint16_t* prevb = (const uint16_t*)(mgx_dyn_lds + oPrev);
+              const uint16_t* slotb = (const uint16_t*)(mgx_dyn_lds + oSlot);
+              // carried from one iteration to the next, packed (the kernel is at its register limit): LDS cell of this agent and
+              // of the next; position | prev_location << 16; resolved byte | slot << 8
+              int li = order[min(q, mA - 1) * MGX_WORLD_EPG + lane] * MGX_WORLD_EPG + lane;   // (q == A: an env that is through waits for the others)
+              int li1 = order[min(q + 1, mA - 1) * MGX_WORLD_EPG + lane] * MGX_WORLD_EPG + lane;
+              uint32_t rp = (uint32_t)rcb[li] | (uint32_t)prevb[li] << 16, ws = (uint32_t)preb[li] | (uint32_t)slotb[li] << 8;
+              while (q < mA) {
+#ifdef MGX_WORLD_TIMING
+                _rn++;
+#endif
+                const uint32_t w = ws & 0xFFu, slot = ws >> 8, prev = rp >> 16;   // cell ahead (2 bits) | kind << 2 | orientation << 4 | off the map << 7
+                uint32_t rc = rp & 0xFFFFu;
+                const int ai = li / MGX_WORLD_EPG;
+                const int kind = (int)((w >> 2) & 3u);
+                const int r0 = (int)(rc >> 8), c0 = (int)(rc & 0xFF);
+                const int orient = (int)((w >> 4) & 7u);   // orientation.hpp:28-48
+                const bool ahead = kind == MGX_AK_MOVE && !(w & 0x80u);   // (else both words are the own cell's)
+                // (dx + 1, dy + 1 of the eight orientations, two bits each: no branches in front of the dirty words' addresses)
+                const int dx = ahead ? (int)((0x8885u >> (orient * 2)) & 3u) - 1 : 0, dy = ahead ? (int)((0xa058u >> (orient * 2)) & 3u) - 1 : 0;
+                const int r = r0 + dy, c = c0 + dx;
+                // (an agent a swap displaced since the staging pass may have its resolved cell off the map: its own cell is dirty
+                // and ends the run below, the word read for the other one only has to exist)
+                const uint32_t b0 = (uint32_t)(r0 * mW + c0) & (uint32_t)mMask, b1 = min((uint32_t)(r * mW + c), (uint32_t)(mHW - 1)) & (uint32_t)mMask;
+                // every LDS load of the iteration: the two dirty words of this agent (behind the marks of the one before: LDS
+                // runs a wavefront's accesses in order), the next agent's record, the agent index behind it ...
+                uint32_t d0 = *dirty_word(b0), d1 = *dirty_word(b1);
+                uint32_t ai2 = order[min(q + 2, mA - 1) * MGX_WORLD_EPG + lane];
+                uint32_t w1 = preb[li1], rc1 = rcb[li1], prev1 = prevb[li1], slot1 = slotb[li1];
+                // ... issued together and waited for ONCE, here: left alone the compiler sinks each load into the branch that
+                // uses it, one round trip behind the other
+                asm volatile("" : "+v"(d0), "+v"(d1), "+v"(ai2), "+v"(w1), "+v"(rc1), "+v"(prev1), "+v"(slot1));
+                if (kind == 3) break;   // invalid index (or a kind of action this path does not know): the general path
+                uint32_t out = 3u | (uint32_t)(kind << 2);   // (a wrong-stream id: no call, nothing else)
+                if (kind != MGX_AK_VIBE) {
+                  bool ok = true;
+                  if (kind == MGX_AK_MOVE) {
+                    if ((d0 >> (b0 & 31)) & 1u) { mf_stale++; break; }   // displaced by a swap
+                    if (w & 0x80u) ok = false;   // off the map: every handler's line scan ends at once
+                    else {
+                      if ((d1 >> (b1 & 31)) & 1u) { mf_stale++; break; }
+                      if ((w & 3u) == 0u) {   // empty: the relocate handler = Grid::move_object of the agent's own object
+                        const uint16_t nrc = (uint16_t)((r << 8) | c);
+                        uint16_t* g = gGrid + (size_t)env * mHW;
+                        g[r * mW + c] = (uint16_t)(slot + 1u);
+                        g[r0 * mW + c0] = 0;
+                        gObjRc[(size_t)env * mS + slot] = nrc;
+                        gAgRc[(size_t)env * mA + ai] = nrc;
+                        ((uint16_t*)(mgx_dyn_lds + oRc))[li] = nrc; rc = nrc;
+                        atomicOr(dirty_word(b0), 1u << (b0 & 31)); atomicOr(dirty_word(b1), 1u << (b1 & 31));
+                      } else if ((w & 3u) == 1u || (mFl & 2)) ok = false;   // nothing to use
+                      else break;   // an on_use handler chain
+                    }
+                  }
+                  const bool moved = rc != prev;   // at the agent's own turn, as handle_action evaluates it
+                  if (moved) ((uint16_t*)(mgx_dyn_lds + oPrev))[li] = (uint16_t)rc;
+                  out |= (ok ? 16u : 0u) | (moved ? 32u : 0u);
+                }
+                preb[li] = (uint8_t)out;
+                q++;
+                li = li1; li1 = (int)ai2 * MGX_WORLD_EPG + lane; rp = rc1 | prev1 << 16; ws = w1 | slot1 << 8;
+              }
+            } else
             while (q < mA) {
+#ifdef MGX_WORLD_TIMING
+              _rn++;
+#endif
               const int ai = order[q * MGX_WORLD_EPG + lane], li = ai * MGX_WORLD_EPG + lane;
               const uint32_t w = mgx_dyn_lds[oPre + li];   // cell ahead (2 bits) | kind << 2 | orientation << 4 | off the map << 7
               const int kind = (int)((w >> 2) & 3u);
@@ -2784,6 +2896,7 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
             }
             mf_ran += (uint32_t)(q - q0);
           }
+          MGX_RUN_T(0);
           // the helper lane may read cells the run wrote (its agent's cell ahead): visible before the pair's actions
           if (__ballot(q != q0) != 0ull) {
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -2791,6 +2904,12 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
           }
           const int qo = __shfl_xor(q, 32);
           if (helper) q = qo;
+          MGX_RUN_T(1);
+#ifdef MGX_WORLD_TIMING
+          for (int o = 32; o > 0; o >>= 1) _rn = max(_rn, (uint32_t)__shfl_xor((int)_rn, o));
+          _rit += _rn; _rn = 0;
+          MGX_RUN_T0();
+#endif
         }
       }
 #endif
@@ -2812,8 +2931,8 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
             const uint32_t own = al.rc[ai * MGX_WORLD_EPG + lane];
             uint32_t tgt = own;
             const int a = al.act[ai * MGX_WORLD_EPG + lane];
-            if (a >= 0 && a < K::nact(d) && acts[a * MGX_AC_WORDS + MGX_AC_KIND] == MGX_AK_MOVE && K::n_move_handlers(d) > 0) {
-              const int orient = acts[a * MGX_AC_WORDS + MGX_AC_ARG];  // orientation.hpp:28-48
+            if (a >= 0 && a < K::nact(d) && mgx_act_kind<K>(d, acts, a) == MGX_AK_MOVE && K::n_move_handlers(d) > 0) {
+              const int orient = mgx_act_arg<K>(d, acts, a);  // orientation.hpp:28-48
               const int dx = (orient == 2 || orient == 4 || orient == 6) ? -1 : (orient == 3 || orient == 5 || orient == 7) ? 1 : 0;
               const int dy = (orient == 0 || orient == 4 || orient == 5) ? -1 : (orient == 1 || orient == 6 || orient == 7) ? 1 : 0;
               const int r = (int)(own >> 8) + dy, c = (int)(own & 0xFF) + dx;
@@ -2844,9 +2963,35 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
       }
 #endif
       q += adv;
+#ifdef MGX_WORLD_TIMING
+      if (mf && stream == 0) MGX_RUN_T(2);
+#endif
     }
 #if MGX_HELPERS_ON
     if constexpr (HELP) {
+      // mf_book: the bookkeeping the pipelined run-ahead left out, for every agent it consumed (outcome byte: low bits 3), off
+      // the serial chain — steps_without_motion, the result byte in place of the staged id, executed / success.  It touches
+      // the agent's own records only, which nothing reads before the stream ends; agents of the general path wrote theirs in
+      // handle_action / mgx_dispatch_one.  Over the wavefront's flat run (consecutive bytes of executed / success per store)
+      // or each lane of a pair its half of the agents — the split the vibe pass behind it uses, lane for lane.
+      if (mf && stream == 0 && !mf_serial) {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the outcome bytes, written by the envs' own lanes
+        __builtin_amdgcn_wave_barrier();
+        const uint8_t* pre = e.mf_pre();
+        auto book = [&](int li, size_t g) {
+          const uint32_t o = pre[li];
+          if ((o & 3u) != 3u) return;
+          const int kind = (int)((o >> 2) & 3u);
+          if (kind == MGX_AK_VIBE) { al.act[li] = 0; return; }   // wrong stream: empty result byte
+          const int a = al.act[li];
+          if (o & 32u) al.swm[li] = 0;
+          else al.swm[li] += 1;
+          al.act[li] = (int16_t)(1 | (kind << 1) | ((o & 16u) ? 8 : 0) | ((o & 32u) ? 16 : 0));
+          if (o & 16u) { d.executed[g] = a; d.success[g] = 1; }
+        };
+        if (coop) for (int p = wl; p < n_flat; p += MGX_WAVE) book(flat_li(p), g0 + p);
+        else for (int i = a_lo; i < a_hi; i++) book(i * MGX_WORLD_EPG + lane, e.ao(i));
+      }
       if (mf && stream == 0 && !helper) {
         if (d.mf_count) { d.mf_count[2 * (size_t)env] += mf_ran; d.mf_count[2 * (size_t)env + 1] += mf_stale; }
       }
@@ -2857,6 +3002,8 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
       uint32_t c0 = mf_ran, c1 = mf_slow, c2 = mf_stale;
       for (int o = 32; o > 0; o >>= 1) { c0 += __shfl_xor((int)c0, o); c1 += __shfl_xor((int)c1, o); c2 += __shfl_xor((int)c2, o); }
       if (threadIdx.x == 0) { MGX_COUNT(10, c0); MGX_COUNT(11, c1); MGX_COUNT(12, c2); }
+      if (threadIdx.x == 0 && mf)
+        for (int k = 0; k < 4; k++) atomicAdd(&mgx_dbg_run[k], (unsigned long long)(k < 3 ? _rs[k] : _rit));
     }
 #endif
     MGX_TICK(2 + stream);

@@ -65,7 +65,19 @@ def preset_shapes() -> dict:
 # MGX_WORLD_SHAPE_FIELDS of csrc/mgx_world.h, in its order (tests/test_world_shape_fields.py keeps the two equal)
 WORLD_FIELDS = ("H", "W", "A", "S", "NSP", "NSW", "NG", "NGW", "SEENW", "nact", "max_priority", "flags", "hp_res", "n_move_handlers",
                 "any_on_tick", "tick_in_aoe", "flat_top", "defer_book", "shadow", "gen_prog", "duo", "tick_split", "coop_passes",
-                "move_fast", "mf_lds_off", "mf_dirty_words", "mf_exact", "act_ngset")
+                "move_fast", "mf_lds_off", "mf_dirty_words", "mf_exact", "act_ngset", "act_kinds", "act_args_lo", "act_args_hi")
+
+
+def act_kind(fields, a: int) -> int:
+    """Kind of action ``a`` from the packed action table of a world shape (csrc/mgx_world.h mgx_act_kind)."""
+    by = dict(zip(WORLD_FIELDS, fields))
+    return ((by["act_kinds"] & 0xFFFFFFFF) >> (2 * a)) & 3
+
+
+def act_arg(fields, a: int) -> int:
+    """... and its argument (mgx_act_arg): actions 0-7 in act_args_lo, 8-15 in act_args_hi, four bits each."""
+    by = dict(zip(WORLD_FIELDS, fields))
+    return ((by["act_args_lo" if a < 8 else "act_args_hi"] & 0xFFFFFFFF) >> (4 * (a & 7))) & 15
 
 _WORLD_RE = re.compile(r"^typedef MgxWorldShape\w*(?:<([-0-9, ]+)>)? MgxWorldShapeR3;", re.M)
 

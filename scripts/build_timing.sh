@@ -20,6 +20,7 @@ hipcc $F -c $C/mgx_pack.hip -o $O/pk.o &
 hipcc $F -c $C/mgx_token_bag.hip -o $O/tb.o &
 hipcc $F -c $C/mgx_render.hip -o $O/rn.o &
 hipcc $F -c $C/mgx_byte_linear.hip -o $O/bl.o &
+hipcc $F -c $C/mgx_sample.hip -o $O/sm.o &
 for job in $(jobs -p); do wait $job; done
 hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/mettagrid_amd/libmgx_timing.so $O/*.o
 echo built libmgx_timing.so

@@ -29,6 +29,7 @@ for t in range(5 + steps):
     if t == 5:
         eng.sync()
         lib.mgx_debug_world_cycles(out, 1)
+        lib.mgx_debug_world_run_cycles((C.c_ulonglong * 4)(), 1)
         lib.mgx_debug_obs_cycles(out2, 1)
     with torch.cuda.stream(ext):
         eng.actions.copy_(pa[t % 8]); eng.vibe_actions.copy_(pv[t % 8])
@@ -46,6 +47,14 @@ print(f"{'stream0 trips':28s} {out[9] / steps / waves:12.2f} / wave / step")
 print(f"{'run-ahead actions':28s} {out[10] / steps / waves / 32:12.2f} / env / step   (of {A} agents)")
 print(f"{'general-path dispatches':28s} {out[11] / steps / waves / 32:12.2f} / env / step")
 print(f"{'  of them stale entries':28s} {out[12] / steps / waves / 32:12.3f} / env / step")
+# the primary stream split (mgx_dbg_run): the run-ahead loop, the fence behind it, the general-path trips, the rest
+run = (C.c_ulonglong * 4)()
+lib.mgx_debug_world_run_cycles(run, 0)
+a, b, c = (run[k] / steps / waves for k in range(3))
+s0 = out[2] / steps / waves
+for nm, v in [("(a) run-ahead loop", a), ("(b) fence + barrier behind it", b), ("(c) footprints + dispatch_one", c), ("(d) rest", s0 - a - b - c)]:
+    print(f"  {nm:26s} {v:12.0f} cycles / wave / step   {100 * v / max(s0, 1):5.1f} % of stream0")
+print(f"{'run-ahead loop iterations':28s} {run[3] / steps / waves:12.2f} / wave / step   (maximum over the lanes, summed over the trips)")
 lib.mgx_debug_obs_cycles(out2, 0)
 print("observation kernel, thread 0 of every workgroup:")
 for k, nm in [(8, "stage grid/agents"), (9, "object token cache"), (10, "first observer"), (11, "encode 4 agents"),
