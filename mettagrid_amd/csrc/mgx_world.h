@@ -81,15 +81,22 @@ MGX_DBG_LINKAGE __device__ unsigned long long mgx_dbg_cycles[16];
 // fence, wave barrier and exchange of q behind it, [2] footprint exchange + mgx_dispatch_one + the pair's fence of the
 // general-path trips, [3] iterations of the run-ahead loop (the wavefront's: the maximum over its lanes, summed over the
 // trips).  The spans are kept in registers and added once per step; what is left of the stream's total is everything else.
-MGX_DBG_LINKAGE __device__ unsigned long long mgx_dbg_run[4];
+// (c) itself, per general-path trip: [4] footprint exchange and pairing, up to the call of mgx_dispatch_one, [5] the call up to
+// the first lane's entry of apply_top (the grid read, the empty / usable decision), [6] from there to the last lane's return from
+// apply_top, [7] the rest of the call and the pair's fence; [2] is their sum.  [8..12] calls made inside stream 0's dispatches,
+// summed over the wavefront's lanes: inv_row, cls_of, agent_of, inv() reads, on_inventory_change (each starts a round trip);
+// [13] trips in which a lane entered apply_top.
+MGX_DBG_LINKAGE __device__ unsigned long long mgx_dbg_run[16];
 #define MGX_RUN_T0() (_rt = clock64())
 #define MGX_RUN_T(k) do { unsigned long long _n = clock64(); _rs[k] += (uint32_t)(_n - _rt); _rt = _n; } while (0)
+#define MGX_DBG_N(field, add) (field += (add))
 #else
 #define MGX_TICK(k)
 #define MGX_TICK0()
 #define MGX_COUNT(k, n)
 #define MGX_RUN_T0()
 #define MGX_RUN_T(k)
+#define MGX_DBG_N(field, add)
 #endif
 
 // MGX_BIG: inlining policy of the large interpreter functions.  The lean world kernel is built in its own translation
@@ -278,14 +285,53 @@ __device__ __forceinline__ int mgx_act_arg(const MgxDev& d, PP acts, int a) {
   return acts[a * MGX_AC_WORDS + MGX_AC_ARG];
 }
 
+// One object's whole inventory row in registers: two independent 16-byte loads instead of one dependent load per
+// resource a limit group or modifier list touches.
+struct MgxInvRow {
+  uint32_t w[MGX_INV_PITCH / 2];
+  __device__ __forceinline__ uint32_t pair(int i) const {  // w[i] for a run-time i without indexing the array
+    uint32_t a = (i & 1) ? w[1] : w[0], b = (i & 1) ? w[3] : w[2], c = (i & 1) ? w[5] : w[4], e = (i & 1) ? w[7] : w[6];
+    uint32_t ab = (i & 2) ? b : a, ce = (i & 2) ? e : c;
+    return (i & 4) ? ce : ab;
+  }
+  __device__ __forceinline__ int get(int item) const { uint32_t v = pair(item >> 1); return (int)((item & 1) ? v >> 16 : v & 0xFFFFu); }
+  template <int K> __device__ __forceinline__ int at() const { return (int)((K & 1) ? w[K >> 1] >> 16 : w[K >> 1] & 0xFFFFu); }
+  __device__ __forceinline__ void set(int item, int v) {  // run-time item, again without indexing the array
+    const int i = item >> 1;
+    const uint32_t old = pair(i);
+    const uint32_t nw = (item & 1) ? ((old & 0xFFFFu) | ((uint32_t)v << 16)) : ((old & 0xFFFF0000u) | ((uint32_t)v & 0xFFFFu));
+#pragma unroll
+    for (int q = 0; q < MGX_INV_PITCH / 2; q++) w[q] = (i == q) ? nw : w[q];
+  }
+};
+
+// The dispatch records of the fixed-shape lean instances (MgxEnvT::REC): what a general-path move reads of its two objects —
+// the acting agent's and the one in the cell ahead — held in registers from do_move's loads to the end of its handler chain:
+// class id | agent index << 16 | vibe << 24, the iteration-order word and the inventory row.  slot is MGX_REC_NONE outside
+// do_move, which no object slot equals, so every accessor then reads memory.  The other instances carry nothing (empty base).
+#define MGX_REC_NONE (-100)
+struct MgxObjRec {
+  int slot;
+  uint32_t meta;
+  unsigned long long ord;
+  MgxInvRow row;
+};
+template <bool ON> struct MgxDispatchRecs {};
+template <> struct MgxDispatchRecs<true> {
+  mutable MgxObjRec ra, rt;   // actor, target
+};
+
 template <class Env> struct MgxGenR3;   // generated at build(): mgx_handlers_gen.h
 template <class Env> struct MgxGenR4;
 template <class Env> struct MgxGenJ;    // generated at run time for the program at hand (mettagrid_amd/jit.py): MGX_GEN_HEADER
 template <class PP, bool X, class K_ = MgxWorldShapeDyn>
-struct MgxEnvT {  // per-lane view of one env
+struct MgxEnvT : MgxDispatchRecs<!X && K_::fixed && MGX_HELPERS_ON != 0> {  // per-lane view of one env
   typedef K_ K;   // the shape policy (MgxWorldShapeDyn / MgxWorldShape<...>): every scalar table read below is K::field(d)
   typedef K_ Shape;
   typedef PP ProgPtr;
+  // The dispatch records (MgxDispatchRecs) exist in the fixed-shape lean instances only: the preset's and the run-time
+  // specialised kernels.  The run-time-shape kernels stand at their register limit and keep plain memory accesses.
+  static constexpr bool REC = !X && K_::fixed && MGX_HELPERS_ON != 0;
 #ifdef MGX_CONST_DEV
   static constexpr const MgxDev& d = g_mgx_dev;
 #else
@@ -298,6 +344,10 @@ struct MgxEnvT {  // per-lane view of one env
   MgxALds al_;
   mutable int cur_agent, cur_slot;  // agent whose action is being executed (LDS write-through of its position)
   mutable int grid_dirty;           // a grid cell was written since do_move last looked at the move target
+#ifdef MGX_WORLD_TIMING   // (mgx_dbg_run [5..12]) this lane's first entry of / last return from apply_top in the trip, against dbg_t0; call counts
+  mutable unsigned long long dbg_t0 = 0;
+  mutable uint32_t dbg_in = ~0u, dbg_out = 0u, dbg_n0 = 0u, dbg_n1 = 0u, dbg_n2 = 0u;   // inv_row | cls_of << 16, agent_of | inv() << 16, on_inventory_change
+#endif
 #if defined(MGX_ACT_TU) || MGX_HELPERS_ON
   int act_pos = 0;  // this lane's place in the order the reference walks the agents in (shuffled order / agent index)
   bool duo_on = false;   // (MGX_HELPERS_ON) two lanes of this env dispatch agents side by side: shared per-env words need care
@@ -324,7 +374,7 @@ struct MgxEnvT {  // per-lane view of one env
   __device__ MgxEnvT(const MgxDev& dd, PP prog, int e) : d(dd), P_(prog), env_(e), step(0), cur_agent(-1), cur_slot(-1), grid_dirty(1) {
 #endif
     al_.slot = nullptr; al_.rc = nullptr; al_.prev = nullptr; al_.swm = nullptr; al_.act = nullptr; al_.cls = nullptr; al_.lane = 0; al_.A = 0;
-    xl.def_delta = nullptr; xl.terr_score = nullptr; xl.lane = 0; xl.stride = MGX_WAVE; }
+    xl.def_delta = nullptr; xl.terr_score = nullptr; xl.lane = 0; xl.stride = MGX_WAVE; rec_drop(); }
   // MGX_WORLD_IDS (the lane-per-env world kernel's own translation unit): env index, program base and the LDS agent
   // staging are recomputed from the work-item ids and constant memory wherever they are needed.  As members they
   // live in the kernel's stack frame, and an out-of-line handler function has to re-load them through `this` after
@@ -366,13 +416,139 @@ struct MgxEnvT {  // per-lane view of one env
 
   __device__ __forceinline__ size_t so(int slot) const { return (size_t)envi() * K::S(d) + slot; }
   __device__ __forceinline__ size_t ao(int agent) const { return (size_t)envi() * K::A(d) + agent; }
-  __device__ __forceinline__ uint16_t& inv(int slot, int item) const { return d.obj_inv[so(slot) * MGX_INV_PITCH + item]; }
-  __device__ __forceinline__ int inv_of(int slot, int item) const { return slot >= 0 ? (int)inv(slot, item) : 0; }
-  __device__ __forceinline__ CP cls_of(int slot) const { return cls(d.obj_cls[so(slot)]); }
+  // ---- dispatch records (REC): which record holds `slot`, 1 the actor's, 2 the target's, 0 neither (read memory).  The
+  // generated handlers pass c.actor / c.target themselves, the very values do_move puts into the records in front of the
+  // handler chain, so inside the chain these tests fold when the code is compiled and no memory path is left; everywhere
+  // else both slots are MGX_REC_NONE and only the memory path is.  Writes are write-through: the store is issued at once and the record updated, memory is
+  // never stale and nothing is flushed.  Positions (obj_rc, ag_rc, the LDS copy) are not part of a record. ----
+  __device__ __forceinline__ void rec_drop() const {
+    if constexpr (REC) this->ra.slot = this->rt.slot = MGX_REC_NONE;
+  }
+  __device__ __forceinline__ int rec_of(int slot) const {
+    if constexpr (REC) return slot == this->ra.slot ? 1 : slot == this->rt.slot ? 2 : 0;
+    else return 0;
+  }
+  // the six loads of one object's record, issued together (the caller waits for them once: rec_pin)
+  __device__ __forceinline__ MgxObjRec rec_load(int slot) const {
+    MgxObjRec r;
+    const uint4* p = (const uint4*)(d.obj_inv + so(slot) * MGX_INV_PITCH);
+    const uint4 lo = p[0], hi = p[1];
+    const uint32_t c = d.obj_cls[so(slot)], a = d.obj_agent[so(slot)], v = d.obj_vibe[so(slot)];
+    r.ord = d.obj_order[so(slot)];
+    r.slot = slot;
+    r.meta = c | a << 16 | v << 24;
+    r.row.w[0] = lo.x; r.row.w[1] = lo.y; r.row.w[2] = lo.z; r.row.w[3] = lo.w; r.row.w[4] = hi.x; r.row.w[5] = hi.y; r.row.w[6] = hi.z; r.row.w[7] = hi.w;
+    return r;
+  }
+  // Left alone the compiler sinks each load of a record into the branch that first uses it, one round trip behind the other:
+  // an empty asm that names the loaded values keeps them in front of the first branch, behind ONE wait.
+  static __device__ __forceinline__ void rec_pin(MgxObjRec& r) {
+#if MGX_HELPERS_ON
+    asm volatile("" : "+v"(r.meta), "+v"(r.ord), "+v"(r.row.w[0]), "+v"(r.row.w[1]), "+v"(r.row.w[2]), "+v"(r.row.w[3]), "+v"(r.row.w[4]),
+                 "+v"(r.row.w[5]), "+v"(r.row.w[6]), "+v"(r.row.w[7]));
+#endif
+  }
+  static __device__ __forceinline__ void rec_pin(MgxObjRec& r, uint32_t& with) {   // ... and one more value of the same wait
+#if MGX_HELPERS_ON
+    asm volatile("" : "+v"(r.meta), "+v"(r.ord), "+v"(r.row.w[0]), "+v"(r.row.w[1]), "+v"(r.row.w[2]), "+v"(r.row.w[3]), "+v"(r.row.w[4]),
+                 "+v"(r.row.w[5]), "+v"(r.row.w[6]), "+v"(r.row.w[7]), "+v"(with));
+#endif
+  }
+  // Reads and updates of the two records by VALUE, both records named in every expression: a store or load whose address is
+  // chosen between them at run time would keep the whole per-lane view in scratch memory instead of registers.
+  __device__ __forceinline__ uint32_t rec_meta(int w) const { const uint32_t t = this->rt.meta, a = this->ra.meta; return w == 2 ? t : a; }
+  __device__ __forceinline__ void rec_meta_put(int w, uint32_t m) const {
+    const uint32_t t = this->rt.meta, a = this->ra.meta;
+    this->rt.meta = w == 2 ? m : t; this->ra.meta = w == 1 ? m : a;
+  }
+  __device__ __forceinline__ unsigned long long rec_ord(int w) const { const unsigned long long t = this->rt.ord, a = this->ra.ord; return w == 2 ? t : a; }
+  __device__ __forceinline__ void rec_ord_put(int w, unsigned long long o) const {
+    const unsigned long long t = this->rt.ord, a = this->ra.ord;
+    this->rt.ord = w == 2 ? o : t; this->ra.ord = w == 1 ? o : a;
+  }
+  __device__ __forceinline__ MgxInvRow rec_row(int w) const {
+    MgxInvRow r;
+#pragma unroll
+    for (int q = 0; q < MGX_INV_PITCH / 2; q++) { const uint32_t t = this->rt.row.w[q], a = this->ra.row.w[q]; r.w[q] = w == 2 ? t : a; }
+    return r;
+  }
+  __device__ __forceinline__ void rec_row_put(int w, int item, int v) const {
+    MgxInvRow r = rec_row(w);
+    r.set(item, v);
+#pragma unroll
+    for (int q = 0; q < MGX_INV_PITCH / 2; q++) {
+      const uint32_t t = this->rt.row.w[q], a = this->ra.row.w[q];
+      this->rt.row.w[q] = w == 2 ? r.w[q] : t; this->ra.row.w[q] = w == 1 ? r.w[q] : a;
+    }
+  }
+  __device__ __forceinline__ uint16_t& inv(int slot, int item) const { MGX_DBG_N(dbg_n1, 1u << 16); return d.obj_inv[so(slot) * MGX_INV_PITCH + item]; }
+  __device__ __forceinline__ int inv_get(int slot, int item) const {  // inv() as a value
+    if constexpr (REC) {
+      const int w = rec_of(slot);
+      if (w) return rec_row(w).get(item);
+    }
+    return (int)inv(slot, item);
+  }
+  __device__ __forceinline__ void inv_put(int slot, int item, int v) const {
+    d.obj_inv[so(slot) * MGX_INV_PITCH + item] = (uint16_t)v;
+    if constexpr (REC) {
+      const int w = rec_of(slot);
+      if (w) rec_row_put(w, item, v);
+    }
+  }
+  __device__ __forceinline__ int inv_of(int slot, int item) const {
+    if constexpr (!REC) return slot >= 0 ? (int)inv(slot, item) : 0;
+    else return slot >= 0 ? inv_get(slot, item) : 0;
+  }
+  __device__ __forceinline__ int cls_id_of(int slot) const {
+    if constexpr (REC) {
+      const int w = rec_of(slot);
+      if (w) return (int)(rec_meta(w) & 0xFFFFu);
+    }
+    MGX_DBG_N(dbg_n0, 1u << 16);
+    return d.obj_cls[so(slot)];
+  }
+  __device__ __forceinline__ CP cls_of(int slot) const {
+    if constexpr (!REC) { MGX_DBG_N(dbg_n0, 1u << 16); return cls(d.obj_cls[so(slot)]); }
+    else return cls(cls_id_of(slot));
+  }
   __device__ __forceinline__ int agent_of(int slot) const {
     if (slot < 0) return -1;
+    if constexpr (REC) {
+      const int w = rec_of(slot);
+      if (w) { const int a = (int)((rec_meta(w) >> 16) & 0xFFu); return a == MGX_NO_AGENT ? -1 : a; }
+    }
+    MGX_DBG_N(dbg_n1, 1u);
     int a = d.obj_agent[so(slot)];
     return a == MGX_NO_AGENT ? -1 : a;
+  }
+  __device__ __forceinline__ int vibe_of(int slot) const {
+    if constexpr (REC) {
+      const int w = rec_of(slot);
+      if (w) return (int)(rec_meta(w) >> 24);
+    }
+    return (int)d.obj_vibe[so(slot)];
+  }
+  __device__ __forceinline__ void vibe_put(int slot, int v) const {
+    d.obj_vibe[so(slot)] = (uint8_t)v;
+    if constexpr (REC) {
+      const int w = rec_of(slot);
+      if (w) rec_meta_put(w, (rec_meta(w) & 0x00FFFFFFu) | (uint32_t)(v & 0xFF) << 24);
+    }
+  }
+  __device__ __forceinline__ unsigned long long ord_of(int slot) const {
+    if constexpr (REC) {
+      const int w = rec_of(slot);
+      if (w) return rec_ord(w);
+    }
+    return d.obj_order[so(slot)];
+  }
+  __device__ __forceinline__ void ord_put(int slot, unsigned long long ord) const {
+    d.obj_order[so(slot)] = ord;
+    if constexpr (REC) {
+      const int w = rec_of(slot);
+      if (w) rec_ord_put(w, ord);
+    }
   }
 #if MGX_HELPERS_ON
   __device__ __forceinline__ void flag(uint32_t bit) const { atomicOr(&d.err[envi()], bit); }   // (two lanes of an env may flag at once)
@@ -436,26 +612,13 @@ struct MgxEnvT {  // per-lane view of one env
   }
 
   // ---- inventory (cpp/src/mettagrid/objects/inventory.cpp) ----
-  // One object's whole inventory row in registers: two independent 16-byte loads instead of one dependent load per
-  // resource a limit group or modifier list touches.
-  struct InvRow {
-    uint32_t w[MGX_INV_PITCH / 2];
-    __device__ __forceinline__ uint32_t pair(int i) const {  // w[i] for a run-time i without indexing the array
-      uint32_t a = (i & 1) ? w[1] : w[0], b = (i & 1) ? w[3] : w[2], c = (i & 1) ? w[5] : w[4], e = (i & 1) ? w[7] : w[6];
-      uint32_t ab = (i & 2) ? b : a, ce = (i & 2) ? e : c;
-      return (i & 4) ? ce : ab;
-    }
-    __device__ __forceinline__ int get(int item) const { uint32_t v = pair(item >> 1); return (int)((item & 1) ? v >> 16 : v & 0xFFFFu); }
-    template <int K> __device__ __forceinline__ int at() const { return (int)((K & 1) ? w[K >> 1] >> 16 : w[K >> 1] & 0xFFFFu); }
-    __device__ __forceinline__ void set(int item, int v) {  // run-time item, again without indexing the array
-      const int i = item >> 1;
-      const uint32_t old = pair(i);
-      const uint32_t nw = (item & 1) ? ((old & 0xFFFFu) | ((uint32_t)v << 16)) : ((old & 0xFFFF0000u) | ((uint32_t)v & 0xFFFFu));
-#pragma unroll
-      for (int q = 0; q < MGX_INV_PITCH / 2; q++) w[q] = (i == q) ? nw : w[q];
-    }
-  };
+  typedef MgxInvRow InvRow;
   __device__ __forceinline__ InvRow inv_row(int slot) const {
+    if constexpr (REC) {
+      const int w = rec_of(slot);
+      if (w) return rec_row(w);
+    }
+    MGX_DBG_N(dbg_n0, 1u);
     const uint4* p = (const uint4*)(d.obj_inv + so(slot) * MGX_INV_PITCH);
     const uint4 lo = p[0], hi = p[1];
     InvRow r;
@@ -492,6 +655,7 @@ struct MgxEnvT {  // per-lane view of one env
   // from the same round trip as the inventory row).  The three cells it updates are loaded together.
   __device__ MGX_BIG void on_inventory_change(int a, int item, int delta, int amount) const {
     if (a < 0 || delta == 0) return;
+    MGX_DBG_N(dbg_n2, 1u);
     const size_t sb = ao(a) * K::NSP(d);
     const int s_flow = (delta > 0 ? d.wk[MGX_S_RES_GAINED_BASE] : d.wk[MGX_S_RES_LOST_BASE]) + item;
     const int s_amt = d.wk[MGX_S_RES_AMOUNT_BASE] + item;
@@ -511,10 +675,14 @@ struct MgxEnvT {  // per-lane view of one env
   template <int DEPTH>
   __device__ MGX_BIG int inv_update(int slot, int item, int delta, bool ignore_limits = false, bool notify = true) const {
     // class, inventory row and iteration order of the object: independent loads, one round trip
-    const uint16_t cls_id = d.obj_cls[so(slot)];
+    // (REC, an object of the dispatch: its record, no load at all)
+    uint16_t cls_id;
+    unsigned long long ord;
+    uint8_t ag;
+    if constexpr (REC) { cls_id = (uint16_t)cls_id_of(slot); ord = ord_of(slot); ag = (uint8_t)agent_of(slot); }   // (-1 -> 0xFF = MGX_NO_AGENT)
+    else { cls_id = d.obj_cls[so(slot)]; }
     const InvRow row = inv_row(slot);
-    unsigned long long ord = d.obj_order[so(slot)];
-    const uint8_t ag = d.obj_agent[so(slot)];
+    if constexpr (!REC) { ord = d.obj_order[so(slot)]; ag = d.obj_agent[so(slot)]; }
     CP C = cls(cls_id);
     int initial = row.get(item);
     int new_amount = initial + delta;
@@ -532,15 +700,18 @@ struct MgxEnvT {  // per-lane view of one env
     if (clamped != initial) {
       if (initial == 0) {  // new node goes to the list head (libstdc++ _M_insert_bucket_begin; mettagrid_amd/umap.py)
         ord = (ord << 4) | (unsigned long long)item;
-        d.obj_order[so(slot)] = ord;
+        if constexpr (REC) ord_put(slot, ord);
+        else d.obj_order[so(slot)] = ord;
       } else if (clamped == 0) {  // erase keeps the order of the rest
         int p = 0;
         while (p < 16 && ((ord >> (4 * p)) & 0xF) != (unsigned long long)item) p++;
         unsigned long long low = p ? (ord & ((1ull << (4 * p)) - 1ull)) : 0ull;
         unsigned long long high = p >= 15 ? 0ull : (ord >> (4 * (p + 1)));
-        d.obj_order[so(slot)] = low | (high << (4 * p)) | (0xFull << 60);
+        if constexpr (REC) ord_put(slot, low | (high << (4 * p)) | (0xFull << 60));
+        else d.obj_order[so(slot)] = low | (high << (4 * p)) | (0xFull << 60);
       }
-      inv(slot, item) = (uint16_t)clamped;
+      if constexpr (REC) inv_put(slot, item, clamped);
+      else d.obj_inv[so(slot) * MGX_INV_PITCH + item] = (uint16_t)clamped;
     }
     int dl = clamped - initial;
     if (notify && dl != 0) on_inventory_change(ag == MGX_NO_AGENT ? -1 : (int)ag, item, dl, clamped);
@@ -561,7 +732,7 @@ struct MgxEnvT {  // per-lane view of one env
       PP drop = prog() + d.sec[MGX_SEC_DROP_ORDER] + L[MGX_L_DROP_START];
       for (int k = 0; k < L[MGX_L_DROP_COUNT]; k++) {
         int item = drop[k];
-        int to_drop = min((int)inv(slot, item), excess);
+        int to_drop = min(REC ? inv_get(slot, item) : (int)inv(slot, item), excess);
         if (to_drop > 0) {
           inv_update<DEPTH>(slot, item, -to_drop);
           const InvRow row = inv_row(slot);
@@ -572,7 +743,7 @@ struct MgxEnvT {  // per-lane view of one env
     }
   }
   __device__ MGX_BIG int free_space(int slot, int item) const {  // inventory.cpp:97-110
-    const uint16_t cls_id = d.obj_cls[so(slot)];
+    const uint16_t cls_id = REC ? (uint16_t)cls_id_of(slot) : d.obj_cls[so(slot)];
     const InvRow row = inv_row(slot);
     PP L = limit_of(cls(cls_id), item);
     if (!L) return 65535 - row.get(item);
@@ -581,7 +752,7 @@ struct MgxEnvT {  // per-lane view of one env
   }
   __device__ MGX_BIG int transfer(int src, int dst, int item, int delta) const {  // objects/has_inventory.cpp:76-108
     if (delta <= 0) return 0;
-    int give = min((int)inv(src, item), delta);
+    int give = min(REC ? inv_get(src, item) : (int)inv(src, item), delta);
     int amount = min(give, free_space(dst, item));
     inv_update<1>(src, item, -amount);
     inv_update<1>(dst, item, amount);
@@ -774,7 +945,7 @@ struct MgxEnvT {  // per-lane view of one env
     for (int i = 0; i < count; i++, code += MGX_GV_WORDS) {
       int a0 = code[MGX_GV_A0], a1 = code[MGX_GV_A1], a2 = code[MGX_GV_A2];
       switch (code[MGX_GV_OP]) {
-        case MGX_GOP_INVENTORY: st.push(entity >= 0 ? (float)inv(entity, a0) : 0.f); break;
+        case MGX_GOP_INVENTORY: st.push(entity >= 0 ? (REC ? (float)inv_get(entity, a0) : (float)inv(entity, a0)) : 0.f); break;
         case MGX_GOP_STAT: {
           float v = 0.f;
           if (a0 == 1) { gstat_touch(a1); v = d.game_stats[(size_t)envi() * K::NG(d) + a1]; }
@@ -840,7 +1011,7 @@ struct MgxEnvT {  // per-lane view of one env
   template <int QD>
   __device__ MGX_BIG bool atom_v(int op, int a0, int a1, int a2, const MgxCtx& c, int depth) const {
     switch (op) {
-      case MGX_FOP_VIBE: { int e = resolve(c, a0); return e != MGX_SLOT_NONE && (e >= 0 ? (int)d.obj_vibe[so(e)] : 0) == a1; }
+      case MGX_FOP_VIBE: { int e = resolve(c, a0); return e != MGX_SLOT_NONE && (e >= 0 ? (REC ? vibe_of(e) : (int)d.obj_vibe[so(e)]) : 0) == a1; }
       case MGX_FOP_RESOURCE: { int e = resolve(c, a0); return e != MGX_SLOT_NONE && inv_of(e, a1) >= a2; }
       case MGX_FOP_SHARED_TAG: {
         PP mask = prog() + d.sec[MGX_SEC_WORDLIST] + a0;
@@ -1101,7 +1272,7 @@ struct MgxEnvT {  // per-lane view of one env
       case MGX_MOP_RESOURCE_TRANSFER: {  // resource_mutation.hpp:60-98
         int s = resolve(c, a0), t = resolve(c, a1);
         if (s < 0 || t < 0) break;
-        int amount = a3 < 0 ? (int)inv(s, a2) : a3;
+        int amount = a3 < 0 ? (REC ? inv_get(s, a2) : (int)inv(s, a2)) : a3;
         int moved = transfer(s, t, a2, amount);
         int sa = agent_of(s);
         if (moved > 0 && sa >= 0) astat_add(sa, d.wk[MGX_S_RES_DEPOSITED_BASE] + a2, (float)moved);
@@ -1116,21 +1287,21 @@ struct MgxEnvT {  // per-lane view of one env
         int e = resolve(c, a0);
         if (e < 0) break;
         if (a2 == 0) {
-          unsigned long long ord = d.obj_order[so(e)];  // iterate a copy, as the reference does
+          unsigned long long ord = REC ? ord_of(e) : d.obj_order[so(e)];  // iterate a copy, as the reference does
           for (int k = 0; k < 16; k++) {
             int item = (int)((ord >> (4 * k)) & 0xF);
             if (item == 0xF) break;
-            inv_update<1>(e, item, -(int)inv(e, item));
+            inv_update<1>(e, item, REC ? -inv_get(e, item) : -(int)inv(e, item));
           }
         } else {
           PP ids = prog() + d.sec[MGX_SEC_WORDLIST] + a1;
-          for (int i = 0; i < a2; i++) inv_update<1>(e, ids[i], -(int)inv(e, ids[i]));
+          for (int i = 0; i < a2; i++) inv_update<1>(e, ids[i], REC ? -inv_get(e, ids[i]) : -(int)inv(e, ids[i]));
         }
         break;
       }
       case MGX_MOP_ATTACK: {  // attack_mutation.hpp:20-38
         if (c.actor < 0 || c.target < 0) break;
-        int weapon = inv(c.actor, a0), armor = inv(c.target, a1);
+        int weapon = REC ? inv_get(c.actor, a0) : (int)inv(c.actor, a0), armor = REC ? inv_get(c.target, a1) : (int)inv(c.target, a1);
         int dmg = max(0, (weapon * a3) / 100 - armor);
         if (dmg > 0) inv_update<1>(c.target, a2, -dmg);
         break;
@@ -1148,7 +1319,7 @@ struct MgxEnvT {  // per-lane view of one env
         else { int a = agent_of(e); if (a >= 0) astat_set(a, a2, v); }
         break;
       }
-      case MGX_MOP_CHANGE_VIBE: { int e = resolve(c, a0); if (e >= 0) d.obj_vibe[so(e)] = (uint8_t)a1; break; }
+      case MGX_MOP_CHANGE_VIBE: { int e = resolve(c, a0); if (e >= 0) { if constexpr (REC) vibe_put(e, a1); else d.obj_vibe[so(e)] = (uint8_t)a1; } break; }
       case MGX_MOP_RELOCATE:  // relocate_mutation.hpp: agents only
         if (c.actor >= 0 && (c.actor == cur_slot || agent_of(c.actor) >= 0))
           move_object(c.actor, c.target_r, c.target_c, c.target == MGX_SLOT_NONE && !grid_dirty);
@@ -1170,7 +1341,7 @@ struct MgxEnvT {  // per-lane view of one env
         astat_add(xa, d.wk[MGX_S_SWAP], 1.f);
         break;
       }
-      default: flag(4u); break;
+      default: flag(4u); rec_drop(); break;   // (an operation the records do not cover: back to memory)
     }
   }
   __device__ MGX_BIG void mutate_ext(PP m, MgxCtx& c) const {
@@ -1809,6 +1980,50 @@ struct MgxEnvT {  // per-lane view of one env
     const int dx = (orient == 2 || orient == 4 || orient == 6) ? -1 : (orient == 3 || orient == 5 || orient == 7) ? 1 : 0;
     const int dy = (orient == 0 || orient == 4 || orient == 5) ? -1 : (orient == 1 || orient == 6 || orient == 7) ? 1 : 0;
     PP mh = prog() + d.sec[MGX_SEC_MOVE_HANDLERS];
+    // REC, a move-handler table of the default move's shape (MgxDev::move_fast: [0] relocates into an empty cell ahead, a leaf
+    // with that one filter, optionally [1] uses the target when there is one, both one cell ahead): straight-line, with the
+    // dispatch records.  The acting agent's six loads are issued with the grid read and waited for together; the six of the
+    // object in the cell ahead behind it, one more wait.  Both records stay until the handler chain is over: every write of
+    // the chain to one of their fields goes through the write-through accessors, and under the paired dispatch the two lanes
+    // of an env have disjoint footprints {own cell, cell ahead}, so their records are of different objects and neither lane
+    // writes what the other holds.  What an earlier trip stored is ordered before these loads by the fence that closes every
+    // trip.  Handler [0] on an occupied cell fails on its filter with no side effect and is not called; on an empty cell it is
+    // Grid::move_object of the agent's own object (as in the run-ahead) and needs no record.  The cell is read once.
+    if constexpr (REC) {
+      if (K::move_fast(d) != 0) {
+        const uint16_t rc = AL().rc[cur_agent * MGX_WORLD_EPG + AL().lane];   // (handle_action: slot == cur_slot)
+        const int r = (rc >> 8) + dy, c = (rc & 0xFF) + dx;
+        if (r < 0 || c < 0 || r >= K::H(d) || c >= K::W(d)) return false;
+        MgxObjRec an = rec_load(slot);
+        uint32_t cv = cell(r, c);
+        rec_pin(an, cv);
+        const int t = (int)cv - 1;
+#ifdef MGX_WORLD_TIMING
+        if (dbg_in == ~0u) dbg_in = (uint32_t)(clock64() - dbg_t0);
+#endif
+        bool applied = false;
+        if (t < 0) {
+          grid_dirty = 0;
+          move_object(slot, r, c, true);
+          applied = true;
+        } else if (K::n_move_handlers(d) > 1) {
+          __builtin_assume(t != slot);
+          MgxObjRec tn = rec_load(t);
+          rec_pin(tn);
+          this->ra = an; this->rt = tn;
+          MgxCtx ctx = mgx_ctx(slot, t);
+          ctx.target_r = r; ctx.target_c = c; ctx.move_direction = orient;
+          grid_dirty = 0;
+          applied = apply_top(mh[MGX_MH_WORDS + MGX_MH_HANDLER], ctx);
+          rec_drop();
+        }
+#ifdef MGX_WORLD_TIMING
+        dbg_out = (uint32_t)(clock64() - dbg_t0);
+#endif
+        grid_dirty = 1;
+        return applied;
+      }
+    }
     for (int k = 0; k < K::n_move_handlers(d); k++, mh += MGX_MH_WORDS) {
       uint16_t rc = (AL().rc && slot == cur_slot) ? AL().rc[cur_agent * MGX_WORLD_EPG + AL().lane] : d.obj_rc[so(slot)];
       for (int i = 1; i <= mh[MGX_MH_MAX_RANGE]; i++) {
@@ -1819,7 +2034,13 @@ struct MgxEnvT {  // per-lane view of one env
         if (t < 0 && !mh[MGX_MH_ACCEPTS_EMPTY]) continue;
         MgxCtx ctx = mgx_ctx(slot, t);
         ctx.target_r = r; ctx.target_c = c; ctx.move_direction = orient;
+#ifdef MGX_WORLD_TIMING
+        if (dbg_in == ~0u) dbg_in = (uint32_t)(clock64() - dbg_t0);
+#endif
         const bool applied = apply_top(mh[MGX_MH_HANDLER], ctx);
+#ifdef MGX_WORLD_TIMING
+        dbg_out = (uint32_t)(clock64() - dbg_t0);
+#endif
         grid_dirty = 1;  // the "target seen empty" shortcut is only valid inside this handler chain
         if (applied) return true;
         break;
@@ -2736,8 +2957,9 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
     uint32_t mf_ran = 0, mf_stale = 0;   // (MgxDev::mf_count)
 #ifdef MGX_WORLD_TIMING
     uint32_t mf_slow = 0;
-    uint32_t _rs[3] = {0u, 0u, 0u}, _rit = 0, _rn = 0;   // (mgx_dbg_run)
+    uint32_t _rs[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, _rit = 0, _rn = 0, _rtop = 0;   // (mgx_dbg_run; [3] unused)
     unsigned long long _rt = 0;
+    if (stream == 0) e.dbg_n0 = e.dbg_n1 = e.dbg_n2 = 0u;
 #endif
     for (;;) {
 #if MGX_HELPERS_ON
@@ -2952,8 +3174,20 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
 #endif
 #ifdef MGX_WORLD_TIMING
       if (stream == 0 && run) mf_slow++;   // actions through the general path
+      if (mf && stream == 0) { MGX_RUN_T(4); e.dbg_t0 = _rt; e.dbg_in = ~0u; e.dbg_out = 0u; }
 #endif
       if (run) mgx_dispatch_one(e, d, acts, al, order[k * MGX_WORLD_EPG + lane], stream, lane, repeats);
+#ifdef MGX_WORLD_TIMING
+      if (mf && stream == 0) {   // the wavefront's spans: first entry and last return over its lanes (taken behind the end stamp)
+        const unsigned long long _n = clock64();
+        uint32_t tin = e.dbg_in, tout = e.dbg_out;
+        for (int o = 32; o > 0; o >>= 1) { tin = min(tin, (uint32_t)__shfl_xor((int)tin, o)); tout = max(tout, (uint32_t)__shfl_xor((int)tout, o)); }
+        const uint32_t all = (uint32_t)(_n - _rt);
+        if (tin == ~0u) _rs[5] += all;
+        else { _rs[5] += tin; _rs[6] += tout - tin; _rs[7] += all - tout; _rtop++; }
+        MGX_RUN_T0();
+      }
+#endif
 #if MGX_HELPERS_ON
       if constexpr (HELP) {
         if (duo) {   // what the pair wrote is visible to both before the next trip's footprints and actions
@@ -2964,7 +3198,7 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
 #endif
       q += adv;
 #ifdef MGX_WORLD_TIMING
-      if (mf && stream == 0) MGX_RUN_T(2);
+      if (mf && stream == 0) MGX_RUN_T(7);
 #endif
     }
 #if MGX_HELPERS_ON
@@ -3002,8 +3236,15 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
       uint32_t c0 = mf_ran, c1 = mf_slow, c2 = mf_stale;
       for (int o = 32; o > 0; o >>= 1) { c0 += __shfl_xor((int)c0, o); c1 += __shfl_xor((int)c1, o); c2 += __shfl_xor((int)c2, o); }
       if (threadIdx.x == 0) { MGX_COUNT(10, c0); MGX_COUNT(11, c1); MGX_COUNT(12, c2); }
-      if (threadIdx.x == 0 && mf)
-        for (int k = 0; k < 4; k++) atomicAdd(&mgx_dbg_run[k], (unsigned long long)(k < 3 ? _rs[k] : _rit));
+      uint32_t n8[5] = {e.dbg_n0 & 0xFFFFu, e.dbg_n0 >> 16, e.dbg_n1 & 0xFFFFu, e.dbg_n1 >> 16, e.dbg_n2};
+      for (int k = 0; k < 5; k++)
+        for (int o = 32; o > 0; o >>= 1) n8[k] += (uint32_t)__shfl_xor((int)n8[k], o);
+      if (threadIdx.x == 0 && mf) {
+        _rs[2] = _rs[4] + _rs[5] + _rs[6] + _rs[7];
+        for (int k = 0; k < 8; k++) atomicAdd(&mgx_dbg_run[k], (unsigned long long)(k != 3 ? _rs[k] : _rit));
+        for (int k = 0; k < 5; k++) atomicAdd(&mgx_dbg_run[8 + k], (unsigned long long)n8[k]);
+        atomicAdd(&mgx_dbg_run[13], (unsigned long long)_rtop);
+      }
     }
 #endif
     MGX_TICK(2 + stream);

@@ -92,6 +92,6 @@ void MGX_CAT(mgx_launch_world_fast_s, MGX_SLOT)(bool prog_lds, int variant, size
 
 #if defined(MGX_WORLD_TIMING) && MGX_SLOT == 0  // instrumented developer build only (scripts/world_timing.py); not part of the ABI
 extern "C" int mgx_debug_world_cycles(unsigned long long* out, int reset) { return mgx_read_cycles(&mgx_dbg_cycles, out, reset); }
-// ... and the primary stream's split (mgx_dbg_run, mgx_world.h): out[4]
-extern "C" int mgx_debug_world_run_cycles(unsigned long long* out, int reset) { return mgx_read_cycles(&mgx_dbg_run, out, reset, 4); }
+// ... and the primary stream's split (mgx_dbg_run, mgx_world.h): out[16]
+extern "C" int mgx_debug_world_run_cycles(unsigned long long* out, int reset) { return mgx_read_cycles(&mgx_dbg_run, out, reset, 16); }
 #endif

@@ -29,7 +29,7 @@ for t in range(5 + steps):
     if t == 5:
         eng.sync()
         lib.mgx_debug_world_cycles(out, 1)
-        lib.mgx_debug_world_run_cycles((C.c_ulonglong * 4)(), 1)
+        lib.mgx_debug_world_run_cycles((C.c_ulonglong * 16)(), 1)
         lib.mgx_debug_obs_cycles(out2, 1)
     with torch.cuda.stream(ext):
         eng.actions.copy_(pa[t % 8]); eng.vibe_actions.copy_(pv[t % 8])
@@ -48,13 +48,23 @@ print(f"{'run-ahead actions':28s} {out[10] / steps / waves / 32:12.2f} / env / s
 print(f"{'general-path dispatches':28s} {out[11] / steps / waves / 32:12.2f} / env / step")
 print(f"{'  of them stale entries':28s} {out[12] / steps / waves / 32:12.3f} / env / step")
 # the primary stream split (mgx_dbg_run): the run-ahead loop, the fence behind it, the general-path trips, the rest
-run = (C.c_ulonglong * 4)()
+run = (C.c_ulonglong * 16)()
 lib.mgx_debug_world_run_cycles(run, 0)
 a, b, c = (run[k] / steps / waves for k in range(3))
 s0 = out[2] / steps / waves
 for nm, v in [("(a) run-ahead loop", a), ("(b) fence + barrier behind it", b), ("(c) footprints + dispatch_one", c), ("(d) rest", s0 - a - b - c)]:
     print(f"  {nm:26s} {v:12.0f} cycles / wave / step   {100 * v / max(s0, 1):5.1f} % of stream0")
+# (c) per general-path trip: up to the call, up to the first lane's entry of apply_top, to the last lane's return, the rest + the fence
+for k, nm in [(4, "(c1) footprints + pairing"), (5, "(c2) dispatch, to apply_top"), (6, "(c3) inside apply_top"), (7, "(c4) rest + pair's fence")]:
+    v = run[k] / steps / waves
+    print(f"    {nm:28s} {v:10.0f} cycles / wave / step   {100 * v / max(c, 1):5.1f} % of (c)")
 print(f"{'run-ahead loop iterations':28s} {run[3] / steps / waves:12.2f} / wave / step   (maximum over the lanes, summed over the trips)")
+print(f"{'trips that enter apply_top':28s} {run[13] / steps / waves:12.2f} / wave / step")
+# calls inside stream 0's dispatches, each the start of a round trip: per general-path dispatch (and per env and step)
+# (memory-path calls only: an instance with dispatch records answers these from registers for the dispatch's two objects)
+disp = max(out[11], 1)
+for k, nm in [(8, "inv_row"), (9, "cls_of"), (10, "agent_of"), (11, "inv() reads"), (12, "on_inventory_change")]:
+    print(f"  {nm + ' calls':26s} {run[k] / disp:12.2f} / general-path dispatch   {run[k] / steps / waves / 32:8.3f} / env / step")
 lib.mgx_debug_obs_cycles(out2, 0)
 print("observation kernel, thread 0 of every workgroup:")
 for k, nm in [(8, "stage grid/agents"), (9, "object token cache"), (10, "first observer"), (11, "encode 4 agents"),
