@@ -784,8 +784,13 @@ MAX_OBJECTS["map_max_few"] = MAP_FEW_OBJECTS
 
 
 def scenario(name: str) -> tuple:
-    """The SCENARIOS or LIMIT_SCENARIOS entry of ``name``."""
-    return SCENARIOS[name] if name in SCENARIOS else LIMIT_SCENARIOS[name]
+    """The SCENARIOS, LIMIT_SCENARIOS or aoe_cases.AOE_SCENARIOS entry of ``name``."""
+    if name in SCENARIOS:
+        return SCENARIOS[name]
+    if name in LIMIT_SCENARIOS:
+        return LIMIT_SCENARIOS[name]
+    from aoe_cases import AOE_SCENARIOS   # (imports this module)
+    return AOE_SCENARIOS[name]
 
 
 class ParityRun:

@@ -1,7 +1,7 @@
 """Every code path mgx_create chooses (mgx_create_paths / BatchedMettaGrid.paths), on both sides, against the oracle.
 
-1. Coverage table: the paths every scenario of helpers.SCENARIOS and helpers.LIMIT_SCENARIOS takes by default are pinned
-   (EXPECTED), and every bit is seen set and clear across the table — a refactor that moves a scenario off a path, or a
+1. Coverage table: the paths every scenario of helpers.SCENARIOS, helpers.LIMIT_SCENARIOS and aoe_cases.AOE_SCENARIOS
+   takes by default are pinned (EXPECTED), and every bit is seen set and clear across the table — a refactor that moves a scenario off a path, or a
    new path no scenario reaches, fails here.  Bits only an environment switch can flip are listed in FORCED_ONLY.
 2. Forced fallbacks: each switch of mgx_create, on scenarios whose default takes the fast side; the bit must flip, then
    the run is compared with the oracle after every step (E = 70: envs across the 32-env wavefront and the 64-env
@@ -10,6 +10,7 @@
 import pytest
 
 import helpers as hp
+from aoe_cases import AOE_SCENARIOS
 from mettagrid_amd.engine import PATH_BITS
 
 pytestmark = pytest.mark.gpu
@@ -52,6 +53,11 @@ EXPECTED = {
     'nest4_x': ['X', 'act_map', 'act_par', 'flat_top', 'prog_lds', 'rewards_mid', 'shadow', 'x_aoe_lds'],
     'nest6_x': ['X', 'prog_lds', 'rewards_mid', 'x_aoe_lds'],
     'query3': ['X', 'act_map', 'act_par', 'flat_top', 'prog_lds', 'rewards_ext', 'shadow', 'x_aoe_lds'],
+    'aoe_words': ['X', 'aoe_local', 'aoe_prog_lds', 'prog_lds', 'rewards_ext'],
+    'aoe_chunks': ['X', 'aoe_local', 'aoe_prog_lds', 'prog_lds', 'rewards_ext'],
+    'aoe_chunks_wide': ['X', 'aoe_local', 'aoe_prog_lds', 'cov_in_aoe', 'flat_top', 'obs_512', 'prog_lds', 'rewards_mid', 'tick_in_aoe'],
+    'aoe_ops': ['X', 'aoe_local', 'cov_in_aoe', 'prog_lds', 'rewards_ext', 'tick_in_aoe'],
+    'aoe_stats': ['X', 'aoe_local', 'cov_in_aoe', 'prog_lds', 'rewards_ext', 'tick_in_aoe'],
 }
 
 # switch -> (value, the bit it clears, scenarios whose default has that bit set)
@@ -77,7 +83,7 @@ def default_paths(name: str) -> dict:
 
 
 def test_coverage_table():
-    names = list(hp.SCENARIOS) + list(hp.LIMIT_SCENARIOS)
+    names = list(hp.SCENARIOS) + list(hp.LIMIT_SCENARIOS) + list(AOE_SCENARIOS)
     table = {n: default_paths(n) for n in names}
     got = {n: sorted(b for b, on in p.items() if on) for n, p in table.items()}
     listing = "\n".join(f"    {n!r}: {got[n]}," for n in names)
