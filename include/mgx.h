@@ -745,7 +745,8 @@ int mgx_move_fast_counts(mgx_engine* e, uint64_t* out);
  * action.failed, status.max_steps_without_motion; bit 0) and the two coverage stats (objects/agent.cpp:49-57; bit 1, lean
  * lane-per-env dispatch only) are kept as integers beside the agents' stat rows and written into them before anything reads
  * them (mgx_get_stats, the episode records, mgx_state_digests) — chosen at mgx_create when no game value or mutation of the
- * program touches those stats.  0, 1 or 3.  Same results.  Diagnostic. */
+ * program touches those stats.  0, 1 or 3.  Same results.  Diagnostic.  (Both rules and the result byte a call leaves for the
+ * batched pass are stated once, in csrc/mgx_agent_rules.h.) */
 int32_t mgx_integer_bookkeeping(const mgx_engine* e);
 /* Every code path mgx_create chose for this program, one bit per choice (MGX_PATH_*); the environment switch named beside
  * a bit forces its fallback side.  Same results on either side of every bit.  Diagnostic: reading it changes nothing. */

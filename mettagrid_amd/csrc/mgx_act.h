@@ -210,20 +210,15 @@ __device__ __forceinline__ void mgx_act_body(const MgxDev& d, PP P, uint8_t* ord
     const unsigned long long tq0 = clock64();
 #endif
     if (stream == 0) {
-      uint32_t own = 0, tgt = 0;
+      uint32_t own = 0;
+      int ahead = -1;   // the cell a move acts on (mgx_agent_rules.h)
       if (pending) {
         own = al.rc[ai * MGX_WORLD_EPG + envl];
-        tgt = own;
         const int a = al.act[ai * MGX_WORLD_EPG + envl];
-        if (a >= 0 && a < d.nact && acts[a * MGX_AC_WORDS + MGX_AC_KIND] == MGX_AK_MOVE && d.n_move_handlers > 0) {
-          const int orient = acts[a * MGX_AC_WORDS + MGX_AC_ARG];  // orientation.hpp:28-48
-          const int dx = (orient == 2 || orient == 4 || orient == 6) ? -1 : (orient == 3 || orient == 5 || orient == 7) ? 1 : 0;
-          const int dy = (orient == 0 || orient == 4 || orient == 5) ? -1 : (orient == 1 || orient == 6 || orient == 7) ? 1 : 0;
-          const int r = (int)(own >> 8) + dy, c = (int)(own & 0xFF) + dx;
-          if (r >= 0 && c >= 0 && r < d.H && c < d.W) tgt = (uint32_t)((r << 8) | c);
-        }
+        if (a >= 0 && a < d.nact && acts[a * MGX_AC_WORDS + MGX_AC_KIND] == MGX_AK_MOVE && d.n_move_handlers > 0)
+          ahead = mgx_cell_ahead(own, acts[a * MGX_AC_WORDS + MGX_AC_ARG], d.H, d.W);
       }
-      const uint32_t F = (own << 16) | tgt;
+      const uint32_t F = mgx_footprint(own, ahead), tgt = mgx_fp_target(F);
 #ifdef MGX_ACT_STRICT  // (debug) one agent per round, in order: the dispatch of the lane-per-env kernels
       if ((pend & seg & ((1ull << wl) - 1ull)) != 0ull) clear = false;
 #endif
@@ -262,10 +257,10 @@ __device__ __forceinline__ void mgx_act_body(const MgxDev& d, PP P, uint8_t* ord
           }
 #pragma unroll
           for (int k = 0; k < 17; k++) {
-            const bool there = ok[k] && (fj[k] >> 16) == rc17[k];   // an earlier pending agent stands on that cell
+            const bool there = ok[k] && mgx_fp_own(fj[k]) == rc17[k];   // an earlier pending agent stands on that cell
             if (k == 0) { if (there) clear = false; }                                            // tgt == oj
-            else if (k <= 8) { if (there && (fj[k] & 0xFFFFu) == own) { clear = false; hit = true; } }   // own == tj
-            else { if (there && (fj[k] & 0xFFFFu) == tgt) clear = false; }                      // tgt == tj
+            else if (k <= 8) { if (there && mgx_fp_target(fj[k]) == own) { clear = false; hit = true; } }   // own == tj
+            else { if (there && mgx_fp_target(fj[k]) == tgt) clear = false; }                      // tgt == tj
           }
         }
       } else
@@ -273,7 +268,7 @@ __device__ __forceinline__ void mgx_act_body(const MgxDev& d, PP P, uint8_t* ord
         const int j = __builtin_ctzll(m);
         m &= m - 1;
         const uint32_t Fj = (uint32_t)__builtin_amdgcn_readlane((int)F, j);
-        const uint32_t oj = Fj >> 16, tj = Fj & 0xFFFFu;
+        const uint32_t oj = mgx_fp_own(Fj), tj = mgx_fp_target(Fj);
         if (j < wl && ((seg >> j) & 1ull)) {
           if (own == tj) hit = true;
           if (own == tj || tgt == oj || tgt == tj) clear = false;

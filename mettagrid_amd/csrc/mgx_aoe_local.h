@@ -518,17 +518,12 @@ struct MgxLocalAgent {
     const uint16_t rc = (uint16_t)((r << 8) | c);
     if (rc == d.ag_covrc[ao]) return;  // unchanged position: both stats already hold their values
     d.ag_covrc[ao] = rc;
-    const uint16_t sp = d.ag_spawn[ao];
-    const int bit = r * d.W + c;
-    uint32_t& w = d.ag_seen[ao * d.SEENW + (bit >> 5)];
-    uint32_t uniq = d.ag_unique[ao];
-    const uint32_t md0 = d.ag_maxdist[ao];
-    if (!(w & (1u << (bit & 31)))) { w |= 1u << (bit & 31); d.ag_unique[ao] = ++uniq; }
-    sset(d.wk[MGX_S_CELL_UNIQUE], (float)uniq, true);
-    const int dist = abs((int)(sp >> 8) - r) + abs(c - (int)(sp & 0xFF));
-    const uint32_t md = max(md0, (uint32_t)dist);
-    d.ag_maxdist[ao] = md;
-    sset(d.wk[MGX_S_CELL_MAXDIST], (float)md, true);
+    uint32_t& w = d.ag_seen[ao * d.SEENW + (mgx_cov_bit(rc, d.W) >> 5)];
+    const MgxCoverage cv = mgx_coverage(rc, d.ag_spawn[ao], d.W, w, d.ag_unique[ao], d.ag_maxdist[ao]);
+    if (cv.fresh) { w = cv.seen; d.ag_unique[ao] = cv.unique; }
+    sset(d.wk[MGX_S_CELL_UNIQUE], (float)cv.unique, true);
+    d.ag_maxdist[ao] = cv.maxdist;
+    sset(d.wk[MGX_S_CELL_MAXDIST], (float)cv.maxdist, true);
   }
   // ---- write back what changed ----
   __device__ __forceinline__ void store() {

@@ -37,7 +37,8 @@ struct MgxDev {
   int hot_lo;             // first program word of the LDS copy (extended world kernel: sections LIMITS .. TERR_CONTROLS; their
                           // sec[] entries are relative to it in that kernel's copy of this table)
   int x_aoe_lds;          // 1: the extended world kernel runs the AoE phase itself and keeps its scratch in LDS
-  int defer_book;         // 1: per-action bookkeeping stats are applied in one batched pass at the end of the tick
+  int defer_book;         // 1: per-action bookkeeping stats are applied in one batched pass at the end of the tick, replayed from
+                          //    the result byte each call leaves in place of its action id (mgx_agent_rules.h mgx_result_byte)
   int shadow;             // bit 0: ... and into the integer record ag_cnt instead of the agents' stat rows; the float cells are
                           // written from it (mgx_shadow_flush_kernel) before anything reads them.  bit 1: the two coverage stats
                           // likewise (from ag_unique / ag_maxdist; lean lane-per-env dispatch).  0, 1 (lane-per-agent dispatch) or 3
@@ -60,8 +61,8 @@ struct MgxDev {
                           //    bit 2 (env MGX_MF_SERIAL_BOOK): the run-ahead's first form — one agent at a time, its bookkeeping
                           //    inside the loop — instead of the pipelined one; such a table matches no preset shape.
                           //    Engine configuration like coop_passes: it changes speed only
-  int mf_lds_off;         // ... byte offset of its LDS behind everything else of the kernel: resolved actions u8[A][64] (cell ahead: 0 empty,
-                          //    1 an object whose class has no on_use, 2 one with | kind << 2 | orientation << 4 | off the map << 7) | dirty cells of the tick u32[mf_dirty_words][64]
+  int mf_lds_off;         // ... byte offset of its LDS behind everything else of the kernel: resolved actions u8[A][64] (mgx_agent_rules.h
+                          //    mgx_resolved_byte; the pipelined loop leaves mgx_outcome_byte there) | dirty cells of the tick u32[mf_dirty_words][64]
   int mf_dirty_words;     // words per env of the dirty set: an exact bitmap of the map (mf_exact) or a hashed mask (a power of two)
   int mf_exact;
   int act_kinds;          // the action table packed for the shape policy (mgx_world.h mgx_act_kind / mgx_act_arg; mgx_plan.h): kinds at two
@@ -104,7 +105,8 @@ struct MgxDev {
   float* ag_invn;         // ... and how often (0 = free pair)
   uint32_t* ag_swm;       // [E][A] steps_without_motion
   uint32_t* ag_cnt;       // [E][A][8] (32-byte records) noop ok/failed, move ok/failed, change_vibe ok/failed, action.failed,
-                          // max steps without motion — what the per-action bookkeeping counts, as integers (d.shadow)
+                          // max steps without motion — what the per-action bookkeeping counts, as integers (d.shadow;
+                          // mgx_agent_rules.h mgx_replay_cnt_lo / _hi)
   uint32_t* ag_maxdist;   // [E][A]
   uint32_t* ag_unique;    // [E][A]
   uint32_t* ag_seen;      // [E][A][SEENW]

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "mgx_device.h"
+#include "mgx_agent_rules.h"
 
 // Each translation unit instantiates these templates under its own set of build switches (MGX_WORLD_IDS,
 // MGX_BIG, MGX_OUTLINE ...): on the GPU every unit is its own code object, but the single host binary of the
@@ -1977,8 +1978,7 @@ struct MgxEnvT : MgxDispatchRecs<!X && K_::fixed && MGX_HELPERS_ON != 0> {  // p
 
   // ---- actions ----
   __device__ MGX_BIG bool do_move(int slot, int orient) const {  // actions/move.hpp:81-115, orientation.hpp:28-48
-    const int dx = (orient == 2 || orient == 4 || orient == 6) ? -1 : (orient == 3 || orient == 5 || orient == 7) ? 1 : 0;
-    const int dy = (orient == 0 || orient == 4 || orient == 5) ? -1 : (orient == 1 || orient == 6 || orient == 7) ? 1 : 0;
+    const int dx = mgx_orient_dx(orient), dy = mgx_orient_dy(orient);
     PP mh = prog() + d.sec[MGX_SEC_MOVE_HANDLERS];
     // REC, a move-handler table of the default move's shape (MgxDev::move_fast: [0] relocates into an empty cell ahead, a leaf
     // with that one filter, optionally [1] uses the target when there is one, both one cell ahead): straight-line, with the
@@ -2064,11 +2064,10 @@ struct MgxEnvT : MgxDispatchRecs<!X && K_::fixed && MGX_HELPERS_ON != 0> {  // p
       // Bookkeeping touches only this agent's own counters.  Here: the LDS copies and a result byte (in place of the
       // consumed action id); the HBM side — swm / prev_location write-back and the stat updates — is applied for all
       // agents in one batched pass (bookkeeping_flush), off the serial chain.
-      const uint16_t rc = AL().rc[li], prev = AL().prev[li];
-      const bool moved = rc != prev;
-      if (moved) { AL().swm[li] = 0; AL().prev[li] = rc; }
-      else AL().swm[li] += 1;
-      AL().act[(stream * K::A(d) + ai) * MGX_WORLD_EPG + AL().lane] = (int16_t)(1 | (kind << 1) | (ok ? 8 : 0) | (moved ? 16 : 0));
+      const MgxBookStep b = mgx_book_step(AL().rc[li], AL().prev[li], AL().swm[li]);
+      AL().swm[li] = b.swm;
+      if (b.moved) AL().prev[li] = (uint16_t)b.prev;
+      AL().act[(stream * K::A(d) + ai) * MGX_WORLD_EPG + AL().lane] = mgx_result_byte(kind, ok, b.moved);
       cur_agent = cur_slot = -1;
       return ok;
     }
@@ -2110,17 +2109,30 @@ struct MgxEnvT : MgxDispatchRecs<!X && K_::fixed && MGX_HELPERS_ON != 0> {  // p
     // values they already hold (keys exist since Agent::init): nothing to do.
     if (rc == d.ag_covrc[ao(ai)]) return;
     d.ag_covrc[ao(ai)] = rc;
-    uint16_t sp = d.ag_spawn[ao(ai)];
-    int r = rc >> 8, c = rc & 0xFF;
-    int bit = r * K::W(d) + c;
-    uint32_t& w = d.ag_seen[ao(ai) * K::SEENW(d) + (bit >> 5)];
-    uint32_t uniq = d.ag_unique[ao(ai)];
-    if (!(w & (1u << (bit & 31)))) { w |= 1u << (bit & 31); d.ag_unique[ao(ai)] = ++uniq; }
-    astat_set(ai, d.wk[MGX_S_CELL_UNIQUE], (float)uniq);
-    int dist = abs((int)(sp >> 8) - r) + abs(c - (int)(sp & 0xFF));
-    uint32_t md = max(d.ag_maxdist[ao(ai)], (uint32_t)dist);
-    d.ag_maxdist[ao(ai)] = md;
-    astat_set(ai, d.wk[MGX_S_CELL_MAXDIST], (float)md);
+    uint32_t& w = d.ag_seen[ao(ai) * K::SEENW(d) + (mgx_cov_bit(rc, K::W(d)) >> 5)];
+    const MgxCoverage cv = mgx_coverage(rc, d.ag_spawn[ao(ai)], K::W(d), w, d.ag_unique[ao(ai)], d.ag_maxdist[ao(ai)]);
+    if (cv.fresh) { w = cv.seen; d.ag_unique[ao(ai)] = cv.unique; }
+    astat_set(ai, d.wk[MGX_S_CELL_UNIQUE], (float)cv.unique);
+    d.ag_maxdist[ao(ai)] = cv.maxdist;
+    astat_set(ai, d.wk[MGX_S_CELL_MAXDIST], (float)cv.maxdist);
+  }
+  // track_coverage in the batched passes, agent g of [E][A] on a new cell: second-level loads; update (su / sm: stat cells or -1)
+  __device__ __forceinline__ void cov_load(size_t g, uint32_t rc, uint16_t& sp, uint32_t& w, uint32_t& un, uint32_t& md) const {
+    sp = d.ag_spawn[g];
+    w = d.ag_seen[g * K::SEENW(d) + (mgx_cov_bit(rc, K::W(d)) >> 5)];
+    un = d.ag_unique[g];
+    md = d.ag_maxdist[g];
+  }
+  __device__ __forceinline__ void cov_apply(size_t g, uint16_t rc, uint16_t sp, uint32_t w, uint32_t un, uint32_t md, int su = -1, int sm = -1) const {
+    const MgxCoverage cv = mgx_coverage(rc, sp, K::W(d), w, un, md);
+    d.ag_covrc[g] = rc;
+    if (cv.fresh) {
+      d.ag_seen[g * K::SEENW(d) + (mgx_cov_bit(rc, K::W(d)) >> 5)] = cv.seen;
+      d.ag_unique[g] = cv.unique;
+    }
+    if (cv.maxdist != md) d.ag_maxdist[g] = cv.maxdist;
+    if (su >= 0) d.ag_stats[g * K::NSP(d) + su] = (float)cv.unique;
+    if (sm >= 0) d.ag_stats[g * K::NSP(d) + sm] = (float)cv.maxdist;
   }
 
   // ---- std::mt19937 + libstdc++ uniform_int_distribution / shuffle ----
@@ -2148,17 +2160,10 @@ struct MgxEnvT : MgxDispatchRecs<!X && K_::fixed && MGX_HELPERS_ON != 0> {  // p
         res0[q] = (uint32_t)(uint16_t)AL().act[li];
         res1[q] = (uint32_t)(uint16_t)AL().act[AS * MGX_WORLD_EPG + li];
         if (i0 + q >= A) res0[q] = res1[q] = 0;
-        // result bytes have bit 0 set; an action id that was never handled (invalid / wrong stream) is cleared by the caller
-        auto stat_of = [&](uint32_t r) {
-          const int kind = (r >> 1) & 3;
-          const bool ok = (r & 8) != 0;
-          const int id = kind == MGX_AK_NOOP ? (ok ? w_noop_ok : w_noop_no) : kind == MGX_AK_MOVE ? (ok ? w_move_ok : w_move_no)
-                                                                                                    : (ok ? w_vibe_ok : w_vibe_no);
-          return (r & 1) ? id : -1;
-        };
-        id0[q] = stat_of(res0[q]);
-        id1[q] = stat_of(res1[q]);
-        nfail[q] = ((res0[q] & 9) == 1 ? 1 : 0) + ((res1[q] & 9) == 1 ? 1 : 0);
+        // (an action id that was never handled — invalid / wrong stream — is cleared by the caller: no call)
+        id0[q] = mgx_rb_stat(res0[q], w_noop_ok, w_noop_no, w_move_ok, w_move_no, w_vibe_ok, w_vibe_no);
+        id1[q] = mgx_rb_stat(res1[q], w_noop_ok, w_noop_no, w_move_ok, w_move_no, w_vibe_ok, w_vibe_no);
+        nfail[q] = (mgx_rb_failed(res0[q]) ? 1 : 0) + (mgx_rb_failed(res1[q]) ? 1 : 0);
         const size_t sb = ao(i) * K::NSP(d);
         // unconditional loads (a dummy in-range cell when there is nothing to update): no branch between them, so
         // the whole chunk is in flight at once
@@ -2172,20 +2177,15 @@ struct MgxEnvT : MgxDispatchRecs<!X && K_::fixed && MGX_HELPERS_ON != 0> {  // p
 #pragma unroll
       for (int q = 0; q < 8; q++) {
         const int i = i0 + q;
-        if (i >= A || !((res0[q] | res1[q]) & 1)) continue;
+        if (i >= A || !mgx_rb_called(res0[q] | res1[q])) continue;
         const int li = i * MGX_WORLD_EPG + lane;
         const size_t sb = ao(i) * K::NSP(d);
         // replay the calls: a call that did not move increments the counter and may raise the max stat
         uint32_t swm = swm0[q];
         float mx = vm[q];
         bool set_max = false;
-#pragma unroll
-        for (int call = 0; call < 2; call++) {
-          const uint32_t r = call ? res1[q] : res0[q];
-          if (!(r & 1)) continue;
-          if (r & 16) swm = 0;
-          else { swm += 1; if ((float)swm > mx) { mx = (float)swm; set_max = true; } }
-        }
+        mgx_replay_max(res0[q], swm, mx, set_max);
+        mgx_replay_max(res1[q], swm, mx, set_max);
         d.ag_swm[ao(i)] = swm;
         d.ag_prev[ao(i)] = AL().prev[li];
         if (set_max && s_max >= 0) {
@@ -2234,46 +2234,18 @@ struct MgxEnvT : MgxDispatchRecs<!X && K_::fixed && MGX_HELPERS_ON != 0> {  // p
 #pragma unroll
       for (int q = 0; q < 8; q++) {   // second level, only for agents that moved
         const int i = i0 + q;
-        if (i < A && rc8[q] != cov8[q]) {
-          const int bit = (rc8[q] >> 8) * K::W(d) + (rc8[q] & 0xFF);
-          sp8[q] = d.ag_spawn[ao(i)];
-          w8[q] = d.ag_seen[ao(i) * K::SEENW(d) + (bit >> 5)];
-          un8[q] = d.ag_unique[ao(i)];
-          md8[q] = d.ag_maxdist[ao(i)];
-        }
+        if (i < A && rc8[q] != cov8[q]) cov_load(ao(i), rc8[q], sp8[q], w8[q], un8[q], md8[q]);
       }
 #pragma unroll
       for (int q = 0; q < 8; q++) {
         const int i = i0 + q;
-        if (i < A && rc8[q] != cov8[q]) {   // track_coverage (objects/agent.cpp:49-57): the position changed since the last call
-          const int r = rc8[q] >> 8, c = rc8[q] & 0xFF;
-          const int bit = r * K::W(d) + c;
-          d.ag_covrc[ao(i)] = rc8[q];
-          if (!(w8[q] & (1u << (bit & 31)))) {
-            d.ag_seen[ao(i) * K::SEENW(d) + (bit >> 5)] = w8[q] | (1u << (bit & 31));
-            d.ag_unique[ao(i)] = un8[q] + 1;
-          }
-          const int dist = abs((int)(sp8[q] >> 8) - r) + abs(c - (int)(sp8[q] & 0xFF));
-          if ((uint32_t)dist > md8[q]) d.ag_maxdist[ao(i)] = (uint32_t)dist;
-        }
-        if (i >= A || !((res0[q] | res1[q]) & 1)) continue;
+        if (i < A && rc8[q] != cov8[q]) cov_apply(ao(i), rc8[q], sp8[q], w8[q], un8[q], md8[q]);   // the position changed since the last call
+        if (i >= A || !mgx_rb_called(res0[q] | res1[q])) continue;
         const int li = i * MGX_WORLD_EPG + lane;
-        // replay the calls (actions/action_handler.hpp:78-105): result bytes have bit 0 set, bit 3 = success, bit 4 = moved
+        // replay the tick's two calls (actions/action_handler.hpp:78-105)
         uint32_t swm = swm0[q];
-        uint4 a = c0[q], b = c1[q];
-#pragma unroll
-        for (int call = 0; call < 2; call++) {
-          const uint32_t r = call ? res1[q] : res0[q];
-          if (!(r & 1)) continue;
-          if (r & 16) swm = 0;
-          else { swm += 1; b.w = max(b.w, swm); }
-          const int kind = (r >> 1) & 3;
-          const uint32_t ok = (r >> 3) & 1u, no = ok ^ 1u;
-          if (kind == MGX_AK_NOOP) { a.x += ok; a.y += no; }
-          else if (kind == MGX_AK_MOVE) { a.z += ok; a.w += no; }
-          else { b.x += ok; b.y += no; }
-          b.z += no;
-        }
+        uint4 a = mgx_replay_cnt_lo(mgx_replay_cnt_lo(c0[q], res0[q]), res1[q]);
+        uint4 b = mgx_replay_cnt_hi(mgx_replay_cnt_hi(c1[q], res0[q], swm), res1[q], swm);
         d.ag_swm[ao(i)] = swm;
         d.ag_prev[ao(i)] = AL().prev[li];
         cnt_w[ao(i) * 2] = a;
@@ -2312,29 +2284,12 @@ struct MgxEnvT : MgxDispatchRecs<!X && K_::fixed && MGX_HELPERS_ON != 0> {  // p
       }
 #pragma unroll
       for (int q = 0; q < 8; q++) {
-        if (!((res0[q] | res1[q]) & 1)) continue;
+        if (!mgx_rb_called(res0[q] | res1[q])) continue;
         const int u = (t0 + q) * MGX_WAVE + wl;
-        const bool second = (u & 1) != 0;
-        // replay the calls (actions/action_handler.hpp:78-105): result bytes have bit 0 set, bit 3 = success, bit 4 = moved
+        // replay the tick's two calls (actions/action_handler.hpp:78-105) into this lane's half
         uint32_t swm = swm0[q];
-        uint4 h = c[q];
-#pragma unroll
-        for (int call = 0; call < 2; call++) {
-          const uint32_t r = call ? res1[q] : res0[q];
-          if (!(r & 1)) continue;
-          const int kind = (r >> 1) & 3;
-          const uint32_t ok = (r >> 3) & 1u, no = ok ^ 1u;
-          if (second) {
-            if (r & 16) swm = 0;
-            else { swm += 1; h.w = max(h.w, swm); }
-            if (kind != MGX_AK_NOOP && kind != MGX_AK_MOVE) { h.x += ok; h.y += no; }
-            h.z += no;
-          } else {
-            if (kind == MGX_AK_NOOP) { h.x += ok; h.y += no; }
-            else if (kind == MGX_AK_MOVE) { h.z += ok; h.w += no; }
-          }
-        }
-        cnt_w[u] = h;
+        cnt_w[u] = (u & 1) != 0 ? mgx_replay_cnt_hi(mgx_replay_cnt_hi(c[q], res0[q], swm), res1[q], swm)
+                                : mgx_replay_cnt_lo(mgx_replay_cnt_lo(c[q], res0[q]), res1[q]);
       }
     }
     for (int t0 = 0; t0 * MGX_WAVE < n_flat; t0 += 8) {
@@ -2355,41 +2310,16 @@ struct MgxEnvT : MgxDispatchRecs<!X && K_::fixed && MGX_HELPERS_ON != 0> {  // p
 #pragma unroll
       for (int q = 0; q < 8; q++) {   // second level, only for agents that moved
         const int p = (t0 + q) * MGX_WAVE + wl;
-        if (p < n_flat && rc8[q] != cov8[q]) {
-          const size_t g = g0 + p;
-          const int bit = (rc8[q] >> 8) * K::W(d) + (rc8[q] & 0xFF);
-          sp8[q] = d.ag_spawn[g];
-          w8[q] = d.ag_seen[g * K::SEENW(d) + (bit >> 5)];
-          un8[q] = d.ag_unique[g];
-          md8[q] = d.ag_maxdist[g];
-        }
+        if (p < n_flat && rc8[q] != cov8[q]) cov_load(g0 + p, rc8[q], sp8[q], w8[q], un8[q], md8[q]);
       }
 #pragma unroll
       for (int q = 0; q < 8; q++) {
         const int p = (t0 + q) * MGX_WAVE + wl;
         if (p >= n_flat) continue;
         const size_t g = g0 + p;
-        if (rc8[q] != cov8[q]) {   // track_coverage (objects/agent.cpp:49-57): the position changed since the last call
-          const int r = rc8[q] >> 8, c = rc8[q] & 0xFF;
-          const int bit = r * K::W(d) + c;
-          d.ag_covrc[g] = rc8[q];
-          if (!(w8[q] & (1u << (bit & 31)))) {
-            d.ag_seen[g * K::SEENW(d) + (bit >> 5)] = w8[q] | (1u << (bit & 31));
-            d.ag_unique[g] = un8[q] + 1;
-          }
-          const int dist = abs((int)(sp8[q] >> 8) - r) + abs(c - (int)(sp8[q] & 0xFF));
-          if ((uint32_t)dist > md8[q]) d.ag_maxdist[g] = (uint32_t)dist;
-        }
-        if (!((res0[q] | res1[q]) & 1)) continue;
-        uint32_t swm = swm0[q];
-#pragma unroll
-        for (int call = 0; call < 2; call++) {
-          const uint32_t r = call ? res1[q] : res0[q];
-          if (!(r & 1)) continue;
-          if (r & 16) swm = 0;
-          else swm += 1;
-        }
-        d.ag_swm[g] = swm;
+        if (rc8[q] != cov8[q]) cov_apply(g, rc8[q], sp8[q], w8[q], un8[q], md8[q]);   // the position changed since the last call
+        if (!mgx_rb_called(res0[q] | res1[q])) continue;
+        d.ag_swm[g] = mgx_replay_swm(mgx_replay_swm(swm0[q], res0[q]), res1[q]);
         d.ag_prev[g] = al.prev[flat_li(p)];
       }
     }
@@ -2402,36 +2332,23 @@ struct MgxEnvT : MgxDispatchRecs<!X && K_::fixed && MGX_HELPERS_ON != 0> {  // p
     const int s_max = d.wk[MGX_S_MAX_STEPS_WITHOUT_MOTION], s_failed = d.wk[MGX_S_ACTION_FAILED];
     const int li = i * MGX_WORLD_EPG + lane;
     const uint32_t res0 = (uint32_t)(uint16_t)AL().act[li], res1 = (uint32_t)(uint16_t)AL().act[A * MGX_WORLD_EPG + li];
-    if (!((res0 | res1) & 1)) return;
-    auto stat_of = [&](uint32_t r) {
-      const int kind = (r >> 1) & 3;
-      const int base = kind == MGX_AK_NOOP ? MGX_S_NOOP_SUCCESS : kind == MGX_AK_MOVE ? MGX_S_MOVE_SUCCESS : MGX_S_VIBE_SUCCESS;
-      return (r & 1) ? d.wk[base + ((r & 8) ? 0 : 1)] : -1;
+    if (!mgx_rb_called(res0 | res1)) return;
+    auto stat_of = [&](uint32_t r) {   // (a lane-varying index into d.wk: one agent per lane, one load)
+      const int k = mgx_rb_stat(r, MGX_S_NOOP_SUCCESS, MGX_S_NOOP_SUCCESS + 1, MGX_S_MOVE_SUCCESS, MGX_S_MOVE_SUCCESS + 1,
+                                MGX_S_VIBE_SUCCESS, MGX_S_VIBE_SUCCESS + 1);
+      return k >= 0 ? d.wk[k] : -1;
     };
     const int id0 = stat_of(res0), id1 = stat_of(res1);
-    const int nfail = ((res0 & 9) == 1 ? 1 : 0) + ((res1 & 9) == 1 ? 1 : 0);
     if (K::shadow(d)) {   // the counters as integers in the agent's ag_cnt record (see tail_shadow)
       uint32_t swm = d.ag_swm[ao(i)];
-      uint4 a = ((const uint4*)d.ag_cnt)[ao(i) * 2], b = ((const uint4*)d.ag_cnt)[ao(i) * 2 + 1];
-#pragma unroll
-      for (int call = 0; call < 2; call++) {
-        const uint32_t r = call ? res1 : res0;
-        if (!(r & 1)) continue;
-        if (r & 16) swm = 0;
-        else { swm += 1; b.w = max(b.w, swm); }
-        const int kind = (r >> 1) & 3;
-        const uint32_t ok = (r >> 3) & 1u, no = ok ^ 1u;
-        if (kind == MGX_AK_NOOP) { a.x += ok; a.y += no; }
-        else if (kind == MGX_AK_MOVE) { a.z += ok; a.w += no; }
-        else { b.x += ok; b.y += no; }
-        b.z += no;
-      }
+      const uint4 a = ((const uint4*)d.ag_cnt)[ao(i) * 2], b = ((const uint4*)d.ag_cnt)[ao(i) * 2 + 1];
+      ((uint4*)d.ag_cnt)[ao(i) * 2] = mgx_replay_cnt_lo(mgx_replay_cnt_lo(a, res0), res1);
+      ((uint4*)d.ag_cnt)[ao(i) * 2 + 1] = mgx_replay_cnt_hi(mgx_replay_cnt_hi(b, res0, swm), res1, swm);
       d.ag_swm[ao(i)] = swm;
       d.ag_prev[ao(i)] = AL().prev[li];
-      ((uint4*)d.ag_cnt)[ao(i) * 2] = a;
-      ((uint4*)d.ag_cnt)[ao(i) * 2 + 1] = b;
       return;
     }
+    const int nfail = (mgx_rb_failed(res0) ? 1 : 0) + (mgx_rb_failed(res1) ? 1 : 0);
     const size_t sb = ao(i) * K::NSP(d);
     uint32_t swm = d.ag_swm[ao(i)];
     const float v0 = d.ag_stats[sb + max(id0, 0)], v1 = d.ag_stats[sb + max(id1, 0)];
@@ -2439,13 +2356,8 @@ struct MgxEnvT : MgxDispatchRecs<!X && K_::fixed && MGX_HELPERS_ON != 0> {  // p
     float mx = d.ag_stats[sb + max(s_max, 0)];
     const uint32_t tw = d.ag_touched[ao(i) * K::NSW(d) + (max(s_max, 0) >> 5)];
     bool set_max = false;
-#pragma unroll
-    for (int call = 0; call < 2; call++) {
-      const uint32_t r = call ? res1 : res0;
-      if (!(r & 1)) continue;
-      if (r & 16) swm = 0;
-      else { swm += 1; if ((float)swm > mx) { mx = (float)swm; set_max = true; } }
-    }
+    mgx_replay_max(res0, swm, mx, set_max);
+    mgx_replay_max(res1, swm, mx, set_max);
     d.ag_swm[ao(i)] = swm;
     d.ag_prev[ao(i)] = AL().prev[li];
     if (set_max && s_max >= 0) {
@@ -2517,32 +2429,12 @@ struct MgxEnvT : MgxDispatchRecs<!X && K_::fixed && MGX_HELPERS_ON != 0> {  // p
 #pragma unroll
       for (int q = 0; q < 8; q++) {
         const int i = i0 + q;
-        if (i < A && rc8[q] != cov8[q]) {
-          const int bit = (rc8[q] >> 8) * K::W(d) + (rc8[q] & 0xFF);
-          sp8[q] = d.ag_spawn[ao(i)];
-          w8[q] = d.ag_seen[ao(i) * K::SEENW(d) + (bit >> 5)];
-          un8[q] = d.ag_unique[ao(i)];
-          md8[q] = d.ag_maxdist[ao(i)];
-        }
+        if (i < A && rc8[q] != cov8[q]) cov_load(ao(i), rc8[q], sp8[q], w8[q], un8[q], md8[q]);
       }
 #pragma unroll
       for (int q = 0; q < 8; q++) {
         const int i = i0 + q;
-        if (i < A && rc8[q] != cov8[q]) {
-          const int r = rc8[q] >> 8, c = rc8[q] & 0xFF;
-          const int bit = r * K::W(d) + c;
-          d.ag_covrc[ao(i)] = rc8[q];
-          uint32_t uniq = un8[q];
-          if (!(w8[q] & (1u << (bit & 31)))) {
-            d.ag_seen[ao(i) * K::SEENW(d) + (bit >> 5)] = w8[q] | (1u << (bit & 31));
-            d.ag_unique[ao(i)] = ++uniq;
-          }
-          if (su >= 0) d.ag_stats[ao(i) * K::NSP(d) + su] = (float)uniq;
-          const int dist = abs((int)(sp8[q] >> 8) - r) + abs(c - (int)(sp8[q] & 0xFF));
-          const uint32_t md = max(md8[q], (uint32_t)dist);
-          d.ag_maxdist[ao(i)] = md;
-          if (sm >= 0) d.ag_stats[ao(i) * K::NSP(d) + sm] = (float)md;
-        }
+        if (i < A && rc8[q] != cov8[q]) cov_apply(ao(i), rc8[q], sp8[q], w8[q], un8[q], md8[q], su, sm);
       }
     }
   }
@@ -2634,11 +2526,7 @@ __device__ __forceinline__ void mgx_shuffle_order(const ENV& e, uint8_t* order, 
 template <class K, class PP>
 __device__ __forceinline__ int mgx_move_target(const MgxDev& d, PP acts, int a, uint32_t own) {
   if (a < 0 || a >= K::nact(d) || mgx_act_kind<K>(d, acts, a) != MGX_AK_MOVE) return -1;
-  const int orient = mgx_act_arg<K>(d, acts, a);
-  const int dx = (orient == 2 || orient == 4 || orient == 6) ? -1 : (orient == 3 || orient == 5 || orient == 7) ? 1 : 0;
-  const int dy = (orient == 0 || orient == 4 || orient == 5) ? -1 : (orient == 1 || orient == 6 || orient == 7) ? 1 : 0;
-  const int r = (int)(own >> 8) + dy, c = (int)(own & 0xFF) + dx;
-  return (r >= 0 && c >= 0 && r < K::H(d) && c < K::W(d)) ? ((r << 8) | c) : -1;
+  return mgx_cell_ahead(own, mgx_act_arg<K>(d, acts, a), K::H(d), K::W(d));
 }
 
 // One agent's action of one stream (the body of the dispatch loop, mettagrid_c.cpp:966-999): invalid-index bookkeeping,
@@ -2841,10 +2729,9 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
             if (coop) env8[q] = (size_t)(genv0 + ew);
             li8[q] = li;
             const int a = al.act[li];
-            const int kind = (a < 0 || a >= K::nact(d)) ? 3 : min(mgx_act_kind<K>(d, acts, a), 3);
+            const int kind = (a < 0 || a >= K::nact(d)) ? MGX_PRE_GENERAL : min(mgx_act_kind<K>(d, acts, a), MGX_PRE_GENERAL);
             const int t = mgx_move_target<K>(d, acts, a, al.rc[li]);
-            kd8[q] = (uint32_t)(kind << 2);
-            if (kind == MGX_AK_MOVE) kd8[q] |= ((uint32_t)mgx_act_arg<K>(d, acts, a) & 7u) << 4 | (t < 0 ? 0x80u : 0u);
+            kd8[q] = kind == MGX_AK_MOVE ? mgx_resolved_byte(kind, mgx_act_arg<K>(d, acts, a), t < 0) : mgx_resolved_byte(kind, 0, false);
             if (t >= 0) cv8[q] = d.grid[env8[q] * HW + (size_t)((t >> 8) * K::W(d) + (t & 0xFF))];
           }
         }
@@ -2852,9 +2739,9 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
         for (int q = 0; q < 8; q++) cls8[q] = cv8[q] ? (uint32_t)d.obj_cls[env8[q] * K::S(d) + (cv8[q] - 1u)] : 0u;   // level 2
 #pragma unroll
         for (int q = 0; q < 8; q++)
-          if (li8[q] >= 0) {   // cell ahead (0 empty, 1 no on_use, 2 on_use) | kind << 2 (3: general path) | orientation << 4 | off the map << 7
+          if (li8[q] >= 0) {   // the resolved byte (mgx_agent_rules.h)
             const int h = cv8[q] ? e.cls((int)cls8[q])[MGX_C_ON_USE] : -1;
-            pre[li8[q]] = (uint8_t)((cv8[q] == 0u ? 0u : h < 0 ? 1u : 2u) | kd8[q]);
+            pre[li8[q]] = (uint8_t)mgx_pre_with_cell(kd8[q], cv8[q] != 0u, h >= 0);
           }
       }
     }
@@ -2916,11 +2803,10 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
           if (a < 0 || a >= K::nact(d)) { al.act[ri] = -1; invalid = true; continue; }
           if (mgx_act_kind<K>(d, acts, a) != MGX_AK_VIBE) { al.act[ri] = 0; continue; }
           d.obj_vibe[(size_t)(genv0 + ew) * K::S(d) + al.slot[li]] = (uint8_t)mgx_act_arg<K>(d, acts, a);
-          const uint16_t rc = al.rc[li], prev = al.prev[li];
-          const bool moved = rc != prev;
-          if (moved) { al.swm[li] = 0; al.prev[li] = rc; }
-          else al.swm[li] += 1;
-          al.act[ri] = (int16_t)(1 | (MGX_AK_VIBE << 1) | 8 | (moved ? 16 : 0));
+          const MgxBookStep b = mgx_book_step(al.rc[li], al.prev[li], al.swm[li]);
+          al.swm[li] = b.swm;
+          if (b.moved) al.prev[li] = (uint16_t)b.prev;
+          al.act[ri] = mgx_result_byte(MGX_AK_VIBE, true, b.moved);
           d.executed[g0 + p] = a;
           d.success[g0 + p] = 1;
         }
@@ -2941,11 +2827,10 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
           if (a < 0 || a >= K::nact(d)) { mgx_dispatch_one(e, d, acts, al, i, 1, lane, repeats); continue; }   // invalid index: the general path
           if (mgx_act_kind<K>(d, acts, a) != MGX_AK_VIBE) { al.act[ri] = 0; continue; }           // wrong stream: no call
           d.obj_vibe[e.so(al.slot[li])] = (uint8_t)mgx_act_arg<K>(d, acts, a);
-          const uint16_t rc = al.rc[li], prev = al.prev[li];   // handle_action's bookkeeping (action_handler.hpp:78-105), deferred form
-          const bool moved = rc != prev;
-          if (moved) { al.swm[li] = 0; al.prev[li] = rc; }
-          else al.swm[li] += 1;
-          al.act[ri] = (int16_t)(1 | (MGX_AK_VIBE << 1) | 8 | (moved ? 16 : 0));
+          const MgxBookStep b = mgx_book_step(al.rc[li], al.prev[li], al.swm[li]);   // handle_action's bookkeeping, deferred form
+          al.swm[li] = b.swm;
+          if (b.moved) al.prev[li] = (uint16_t)b.prev;
+          al.act[ri] = mgx_result_byte(MGX_AK_VIBE, true, b.moved);
           d.executed[e.ao(i)] = a;
           d.success[e.ao(i)] = 1;
         }
@@ -3000,7 +2885,7 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
               // general path between two runs may swap or relocate anything: every trip loads its first record afresh.
               // The loop keeps what the serial order can observe (grid, positions and their mirrors — the swap mutation reads
               // obj_rc from memory — dirty marks, prev_location) and leaves ONE outcome byte per consumed agent in place of
-              // the resolved byte: 3 (no cell-ahead code) | kind << 2 | ok << 4 | moved << 5.  The rest of handle_action's
+              // the resolved byte (mgx_outcome_byte: kind, ok, moved).  The rest of handle_action's
               // bookkeeping is written by the flat pass behind the stream (mf_book below); the staged id stays for it.
               uint8_t* preb = mgx_dyn_lds + oPre;
               const uint16_t* rcb = (const uint16_t*)(mgx_dyn_lds + oRc);
@@ -3015,15 +2900,14 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
 #ifdef MGX_WORLD_TIMING
                 _rn++;
 #endif
-                const uint32_t w = ws & 0xFFu, slot = ws >> 8, prev = rp >> 16;   // cell ahead (2 bits) | kind << 2 | orientation << 4 | off the map << 7
+                const uint32_t w = ws & 0xFFu, slot = ws >> 8, prev = rp >> 16;   // w: the resolved byte
                 uint32_t rc = rp & 0xFFFFu;
                 const int ai = li / MGX_WORLD_EPG;
-                const int kind = (int)((w >> 2) & 3u);
+                const int kind = mgx_pre_kind(w);
                 const int r0 = (int)(rc >> 8), c0 = (int)(rc & 0xFF);
-                const int orient = (int)((w >> 4) & 7u);   // orientation.hpp:28-48
-                const bool ahead = kind == MGX_AK_MOVE && !(w & 0x80u);   // (else both words are the own cell's)
-                // (dx + 1, dy + 1 of the eight orientations, two bits each: no branches in front of the dirty words' addresses)
-                const int dx = ahead ? (int)((0x8885u >> (orient * 2)) & 3u) - 1 : 0, dy = ahead ? (int)((0xa058u >> (orient * 2)) & 3u) - 1 : 0;
+                const int orient = mgx_pre_orient(w);
+                const bool ahead = kind == MGX_AK_MOVE && !mgx_pre_off_map(w);   // (else both words are the own cell's)
+                const int dx = ahead ? mgx_orient_dx_packed(orient) : 0, dy = ahead ? mgx_orient_dy_packed(orient) : 0;
                 const int r = r0 + dy, c = c0 + dx;
                 // (an agent a swap displaced since the staging pass may have its resolved cell off the map: its own cell is dirty
                 // and ends the run below, the word read for the other one only has to exist)
@@ -3036,16 +2920,16 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
                 // ... issued together and waited for ONCE, here: left alone the compiler sinks each load into the branch that
                 // uses it, one round trip behind the other
                 asm volatile("" : "+v"(d0), "+v"(d1), "+v"(ai2), "+v"(w1), "+v"(rc1), "+v"(prev1), "+v"(slot1));
-                if (kind == 3) break;   // invalid index (or a kind of action this path does not know): the general path
-                uint32_t out = 3u | (uint32_t)(kind << 2);   // (a wrong-stream id: no call, nothing else)
+                if (kind == MGX_PRE_GENERAL) break;   // invalid index (or a kind of action this path does not know): the general path
+                uint32_t out = mgx_outcome_byte(kind, false, false);   // (a wrong-stream id: no call, nothing else)
                 if (kind != MGX_AK_VIBE) {
                   bool ok = true;
                   if (kind == MGX_AK_MOVE) {
                     if ((d0 >> (b0 & 31)) & 1u) { mf_stale++; break; }   // displaced by a swap
-                    if (w & 0x80u) ok = false;   // off the map: every handler's line scan ends at once
+                    if (mgx_pre_off_map(w)) ok = false;   // off the map: every handler's line scan ends at once
                     else {
                       if ((d1 >> (b1 & 31)) & 1u) { mf_stale++; break; }
-                      if ((w & 3u) == 0u) {   // empty: the relocate handler = Grid::move_object of the agent's own object
+                      if (mgx_pre_cell(w) == MGX_PRE_EMPTY) {   // empty: the relocate handler = Grid::move_object of the agent's own object
                         const uint16_t nrc = (uint16_t)((r << 8) | c);
                         uint16_t* g = gGrid + (size_t)env * mHW;
                         g[r * mW + c] = (uint16_t)(slot + 1u);
@@ -3054,13 +2938,13 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
                         gAgRc[(size_t)env * mA + ai] = nrc;
                         ((uint16_t*)(mgx_dyn_lds + oRc))[li] = nrc; rc = nrc;
                         atomicOr(dirty_word(b0), 1u << (b0 & 31)); atomicOr(dirty_word(b1), 1u << (b1 & 31));
-                      } else if ((w & 3u) == 1u || (mFl & 2)) ok = false;   // nothing to use
+                      } else if (mgx_pre_cell(w) == MGX_PRE_NO_USE || (mFl & 2)) ok = false;   // nothing to use
                       else break;   // an on_use handler chain
                     }
                   }
-                  const bool moved = rc != prev;   // at the agent's own turn, as handle_action evaluates it
+                  const bool moved = mgx_book_step(rc, prev, 0u).moved;   // at the agent's own turn, as handle_action evaluates it
                   if (moved) ((uint16_t*)(mgx_dyn_lds + oPrev))[li] = (uint16_t)rc;
-                  out |= (ok ? 16u : 0u) | (moved ? 32u : 0u);
+                  out = mgx_outcome_byte(kind, ok, moved);
                 }
                 preb[li] = (uint8_t)out;
                 q++;
@@ -3072,9 +2956,9 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
               _rn++;
 #endif
               const int ai = order[q * MGX_WORLD_EPG + lane], li = ai * MGX_WORLD_EPG + lane;
-              const uint32_t w = mgx_dyn_lds[oPre + li];   // cell ahead (2 bits) | kind << 2 | orientation << 4 | off the map << 7
-              const int kind = (int)((w >> 2) & 3u);
-              if (kind == 3) break;   // invalid index (or a kind of action this path does not know): the general path
+              const uint32_t w = mgx_dyn_lds[oPre + li];   // the resolved byte
+              const int kind = mgx_pre_kind(w);
+              if (kind == MGX_PRE_GENERAL) break;   // invalid index (or a kind of action this path does not know): the general path
               int16_t* actp = (int16_t*)(mgx_dyn_lds + oAct) + li;
               if (kind == MGX_AK_VIBE) { *actp = 0; q++; continue; }   // wrong stream: no call, empty result byte
               uint16_t* rcp = (uint16_t*)(mgx_dyn_lds + oRc) + li;
@@ -3084,15 +2968,13 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
                 const int r0 = (int)(rc >> 8), c0 = (int)(rc & 0xFF);
                 const uint32_t b0 = (uint32_t)(r0 * mW + c0) & (uint32_t)mMask;
                 if ((*dirty_word(b0) >> (b0 & 31)) & 1u) { mf_stale++; break; }   // displaced by a swap
-                if (w & 0x80u) ok = false;   // off the map: every handler's line scan ends at once
+                if (mgx_pre_off_map(w)) ok = false;   // off the map: every handler's line scan ends at once
                 else {
-                  const int orient = (int)((w >> 4) & 7u);   // orientation.hpp:28-48
-                  const int dx = (orient == 2 || orient == 4 || orient == 6) ? -1 : (orient == 3 || orient == 5 || orient == 7) ? 1 : 0;
-                  const int dy = (orient == 0 || orient == 4 || orient == 5) ? -1 : (orient == 1 || orient == 6 || orient == 7) ? 1 : 0;
-                  const int r = r0 + dy, c = c0 + dx;
+                  const int orient = mgx_pre_orient(w);
+                  const int r = r0 + mgx_orient_dy(orient), c = c0 + mgx_orient_dx(orient);
                   const uint32_t b1 = (uint32_t)(r * mW + c) & (uint32_t)mMask;
                   if ((*dirty_word(b1) >> (b1 & 31)) & 1u) { mf_stale++; break; }
-                  if ((w & 3u) == 0u) {   // empty: the relocate handler = Grid::move_object of the agent's own object
+                  if (mgx_pre_cell(w) == MGX_PRE_EMPTY) {   // empty: the relocate handler = Grid::move_object of the agent's own object
                     const uint32_t slot = ((uint16_t*)(mgx_dyn_lds + oSlot))[li];
                     const uint16_t nrc = (uint16_t)((r << 8) | c);
                     uint16_t* g = gGrid + (size_t)env * mHW;
@@ -3102,17 +2984,17 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
                     gAgRc[(size_t)env * mA + ai] = nrc;
                     *rcp = nrc; rc = nrc;
                     atomicOr(dirty_word(b0), 1u << (b0 & 31)); atomicOr(dirty_word(b1), 1u << (b1 & 31));
-                  } else if ((w & 3u) == 1u || (mFl & 2)) ok = false;   // nothing to use
+                  } else if (mgx_pre_cell(w) == MGX_PRE_NO_USE || (mFl & 2)) ok = false;   // nothing to use
                   else break;   // an on_use handler chain
                 }
               }
               const int a = *actp;
               uint16_t* prevp = (uint16_t*)(mgx_dyn_lds + oPrev) + li;   // handle_action's bookkeeping, deferred form
               uint32_t* swmp = (uint32_t*)(mgx_dyn_lds + oSwm) + li;
-              const bool moved = rc != *prevp;
-              if (moved) { *swmp = 0; *prevp = (uint16_t)rc; }
-              else *swmp += 1;
-              *actp = (int16_t)(1 | (kind << 1) | (ok ? 8 : 0) | (moved ? 16 : 0));
+              const MgxBookStep b = mgx_book_step(rc, *prevp, *swmp);
+              *swmp = b.swm;
+              if (b.moved) *prevp = (uint16_t)b.prev;
+              *actp = mgx_result_byte(kind, ok, b.moved);
               if (ok) { gEx[(size_t)env * mA + ai] = a; gSu[(size_t)env * mA + ai] = 1; }
               q++;
             }
@@ -3147,25 +3029,15 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
         if (duo) {
           const bool has_b = q + 1 < A;
           k = min(q + (helper ? 1 : 0), A - 1);
-          uint32_t F = 0xFFFFFFFFu;   // own cell << 16 | cell ahead (= own cell when the action is no move)
+          uint32_t F = 0xFFFFFFFFu;   // mgx_footprint: own cell << 16 | cell ahead (= own cell when the action is no move)
           if (more && stream == 0) {
             const int ai = order[k * MGX_WORLD_EPG + lane];
             const uint32_t own = al.rc[ai * MGX_WORLD_EPG + lane];
-            uint32_t tgt = own;
             const int a = al.act[ai * MGX_WORLD_EPG + lane];
-            if (a >= 0 && a < K::nact(d) && mgx_act_kind<K>(d, acts, a) == MGX_AK_MOVE && K::n_move_handlers(d) > 0) {
-              const int orient = mgx_act_arg<K>(d, acts, a);  // orientation.hpp:28-48
-              const int dx = (orient == 2 || orient == 4 || orient == 6) ? -1 : (orient == 3 || orient == 5 || orient == 7) ? 1 : 0;
-              const int dy = (orient == 0 || orient == 4 || orient == 5) ? -1 : (orient == 1 || orient == 6 || orient == 7) ? 1 : 0;
-              const int r = (int)(own >> 8) + dy, c = (int)(own & 0xFF) + dx;
-              if (r >= 0 && c >= 0 && r < K::H(d) && c < K::W(d)) tgt = (uint32_t)((r << 8) | c);
-            }
-            F = (own << 16) | tgt;
+            F = mgx_footprint(own, K::n_move_handlers(d) > 0 ? mgx_move_target<K>(d, acts, a, own) : -1);
           }
           const uint32_t Fo = (uint32_t)__shfl_xor((int)F, 32);
-          const uint32_t Fa = helper ? Fo : F, Fb = helper ? F : Fo;
-          const bool disjoint = (Fa >> 16) != (Fb & 0xFFFFu) && (Fa & 0xFFFFu) != (Fb >> 16) && (Fa & 0xFFFFu) != (Fb & 0xFFFFu);
-          const bool indep = has_b && (stream == 1 || disjoint);
+          const bool indep = has_b && (stream == 1 || mgx_fp_disjoint(helper ? Fo : F, helper ? F : Fo));
           run = more && (!helper || indep);
           adv = indep ? 2 : 1;
           e.act_pos = k;
@@ -3203,7 +3075,7 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
     }
 #if MGX_HELPERS_ON
     if constexpr (HELP) {
-      // mf_book: the bookkeeping the pipelined run-ahead left out, for every agent it consumed (outcome byte: low bits 3), off
+      // mf_book: the bookkeeping the pipelined run-ahead left out, for every agent it consumed (mgx_is_outcome), off
       // the serial chain — steps_without_motion, the result byte in place of the staged id, executed / success.  It touches
       // the agent's own records only, which nothing reads before the stream ends; agents of the general path wrote theirs in
       // handle_action / mgx_dispatch_one.  Over the wavefront's flat run (consecutive bytes of executed / success per store)
@@ -3214,14 +3086,13 @@ __device__ __forceinline__ void mgx_world_body(const MgxDev& d, PP P, uint8_t* o
         const uint8_t* pre = e.mf_pre();
         auto book = [&](int li, size_t g) {
           const uint32_t o = pre[li];
-          if ((o & 3u) != 3u) return;
-          const int kind = (int)((o >> 2) & 3u);
+          if (!mgx_is_outcome(o)) return;
+          const int kind = mgx_pre_kind(o);
           if (kind == MGX_AK_VIBE) { al.act[li] = 0; return; }   // wrong stream: empty result byte
           const int a = al.act[li];
-          if (o & 32u) al.swm[li] = 0;
-          else al.swm[li] += 1;
-          al.act[li] = (int16_t)(1 | (kind << 1) | ((o & 16u) ? 8 : 0) | ((o & 32u) ? 16 : 0));
-          if (o & 16u) { d.executed[g] = a; d.success[g] = 1; }
+          al.swm[li] = mgx_swm_step(al.swm[li], mgx_out_moved(o));
+          al.act[li] = mgx_result_byte(kind, mgx_out_ok(o), mgx_out_moved(o));
+          if (mgx_out_ok(o)) { d.executed[g] = a; d.success[g] = 1; }
         };
         if (coop) for (int p = wl; p < n_flat; p += MGX_WAVE) book(flat_li(p), g0 + p);
         else for (int i = a_lo; i < a_hi; i++) book(i * MGX_WORLD_EPG + lane, e.ao(i));
